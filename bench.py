@@ -130,6 +130,44 @@ def _p50(xs):
     return 1e3 * float(np.median(xs))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+STEP_FIELDS = {"bm25": ("doc", "score", "n"), "dense": ("doc", "score", "chunk", "n"),
+               "rerank": ("doc", "score", "orig", "chunk", "n", "rows")}
+
+
+def host_outputs(out):
+    """The tensors of one step ({stage: tuple}) -> {"<stage>_<field>": host array}: float32 stays float32, everything else
+    (float64 scores; int32 documents, rows and counts, exact in float64) becomes float64.  The slots of a list past its
+    query's count n are not results: their -inf scores are written as 0 (indices there are -1 already), so every value is
+    finite."""
+    arrays = {}
+    for stage, ts in out.items():
+        fields = dict(zip(STEP_FIELDS[stage], ts))
+        n = fields["n"].cpu().numpy()
+        for field, t in fields.items():
+            if t is None:
+                continue
+            a = t.cpu().numpy()
+            if a.ndim == 2 and a.dtype.kind == "f":
+                a = np.where(np.arange(a.shape[1])[None, :] >= n[:, None], 0, a).astype(a.dtype)
+            arrays[f"{stage}_{field}"] = a if a.dtype == np.float32 else a.astype(np.float64)
+    return arrays
+
+
+def write_outputs(arrays, path, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes every array as <path>/<name>.npy, plus query_index.npy: the queries (first axis) kept.  All queries when the
+    files fit in `limit` bytes, else a fixed seeded sample of them, the same queries in every array."""
+    n_q = max(a.shape[0] for a in arrays.values())
+    per_query = 8 + sum(a.nbytes // max(1, a.shape[0]) for a in arrays.values())
+    fit = (limit - 256 * (len(arrays) + 1)) // per_query                      # (256 B: an .npy header, at most)
+    keep = np.arange(n_q) if fit >= n_q else np.sort(np.random.default_rng(seed).permutation(n_q)[:max(1, fit)])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "query_index.npy"), keep.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a[keep[keep < a.shape[0]]])
+    return len(keep)
+
+
 def cpu_baseline(args, shard, terms, qvec, dev):
     """The CPU restatements of the path (oracle/) timed on this box's host cores, as BASELINE.md section 2 lays it out:
       port        C + OpenMP: BM25 over ALL postings, dense cosine / max-pool / top-k over ALL chunk rows, + the rerank / fuse
@@ -504,7 +542,12 @@ def main():
                     help="dense / hybrid workloads: bf16 = batched candidates (<= 128 queries per step: one bf16 sweep; more: "
                          "the tiled matrix-core GEMM, 1024 queries per pass) + exact f32 rescoring "
                          "(BASELINE configs[4] shape: use --workload dense --queries-per-step 1024)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<stage>_<field>.npy (float32 / float64; at most 64 MB "
+                         "in all: a fixed seeded sample of the queries beyond that, listed in DIR/query_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "bm25":
         args.chunks = 0
 
@@ -657,6 +700,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        kept = write_outputs(host_outputs(out), args.dump_outputs)
+        log(f"outputs of the last timed step ({kept} queries) written to {args.dump_outputs}")
 
     # single-query latency (p50), same path with a batch of one
     lat = []

@@ -22,14 +22,17 @@ MAX_BOOST, MAX_DECAY = 0.1, 0.05  # reranker_api.py:317-318
 
 
 def cosine_f32(q, E):
-    """cosine_similarity(q[1,D], E[n,D])[0] as scikit-learn computes it for float32 input."""
+    """cosine_similarity(q[1,D], E[n,D])[0] as scikit-learn computes it for float32 input.  The products are one einsum
+    dot per row, not a BLAS matrix-vector product: a row's cosine is then the same bits whatever matrix it sits in (BLAS
+    blocks and threads by the matrix shape and the host's cores, so a shard's or a 32-row batch's rows can differ from the
+    whole matrix' in the last bit)."""
     q = np.asarray(q, np.float32).reshape(1, -1)
-    E = np.asarray(E, np.float32)
+    E = np.ascontiguousarray(E, np.float32)
     qn = np.sqrt(np.einsum("ij,ij->i", q, q)).astype(np.float32)
     qn[qn == 0.0] = 1.0
     en = np.sqrt(np.einsum("ij,ij->i", E, E)).astype(np.float32)
     en[en == 0.0] = 1.0
-    return ((E / en[:, None]) @ (q / qn[:, None])[0]).astype(np.float32)
+    return np.einsum("ij,j->i", E / en[:, None], (q / qn[:, None])[0]).astype(np.float32)
 
 
 def normalise(sims):

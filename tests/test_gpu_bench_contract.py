@@ -58,3 +58,26 @@ def test_exact_f32_line_reports_the_matrix_core_roofline():
     assert d["dtype"].startswith("f32 (dense cosine)") and "cpu_baseline" not in d and "variant_bf16_candidates" not in d
     r = d["roofline"]
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and r["peak"] == 157.3 and 0 < r["frac"] < 1
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the arrays the last timed step returned, float32 / float64, every value finite (BM25 lists shorter than
+    k1 are padded: those slots' scores are written as 0), at most 64 MB, identical in two runs with
+    the same arguments (the inputs are seeded); --steps is the number of timed steps (one pass of each kernel per step)."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = _run("--steps", "2", "--no-cpu-baseline", "--no-variants", "--dump-outputs", str(tmp_path / name))
+        assert d["steps"] == 2 and d["roofline"]["launches"] == 2 and d["roofline"]["bm25_taat"]["launches"] == 2
+        assert d["outputs_sane"] is True
+        runs.append({p.stem: np.load(p) for p in sorted((tmp_path / name).glob("*.npy"))})
+    a, b = runs
+    assert sorted(a) == sorted(["query_index", "bm25_doc", "bm25_score", "bm25_n", "dense_doc", "dense_score", "dense_chunk",
+                                "dense_n", "rerank_doc", "rerank_score", "rerank_orig", "rerank_chunk", "rerank_n", "rerank_rows"])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    assert np.array_equal(a["query_index"], np.arange(256))
+    assert a["bm25_doc"].shape == (256, 1000) and a["dense_doc"].shape == (256, 100) and a["rerank_doc"].shape == (256, 1000)
+    assert a["dense_score"].dtype == np.float32 and a["bm25_score"].dtype == np.float64 and np.all(a["dense_n"] == 100)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all(), k
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k

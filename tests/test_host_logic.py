@@ -518,3 +518,50 @@ def test_emitted_rows_suffice_for_the_exact_top_k():
             first = rows[np.argmax(exact[rows])]
             assert emitted[first]
         assert emitted.sum() < 40 * k                          # (the filter filters: a few rows per candidate)
+
+
+def test_bench_dump_writes_every_query_or_one_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 file per returned array, every value finite (the -inf scores of the
+    slots past a query's count are written as 0); every query when the files fit in the limit, else the same seeded sample
+    of queries in every array (a stage with fewer rows keeps the sampled queries it has)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    idx = lambda q, k: torch.randint(-1, 1 << 30, (q, k), generator=g, dtype=torch.int32)
+    cnt = lambda q, k: torch.randint(0, k + 1, (q,), generator=g, dtype=torch.int32)
+    pad = lambda s, n: s.masked_fill(torch.arange(s.shape[1])[None, :] >= n[:, None], float("-inf"))   # as the engine pads
+    nb, nd, nr = cnt(400, 10), cnt(400, 5), cnt(100, 10)
+    out = {"bm25": (idx(400, 10), pad(torch.rand(400, 10, generator=g, dtype=torch.float64), nb), nb),
+           "dense": (idx(400, 5), pad(torch.rand(400, 5, generator=g), nd), None, nd),
+           "rerank": (idx(100, 10), pad(torch.rand(100, 10, generator=g, dtype=torch.float64), nr),
+                      torch.rand(100, 10, generator=g, dtype=torch.float64), idx(100, 10), nr, cnt(100, 10))}
+    arrays = bench.host_outputs(out)
+    assert sorted(arrays) == sorted(["bm25_doc", "bm25_score", "bm25_n", "dense_doc", "dense_score", "dense_n", "rerank_doc",
+                                     "rerank_score", "rerank_orig", "rerank_chunk", "rerank_n", "rerank_rows"])
+    assert arrays["dense_score"].dtype == np.float32 and all(a.dtype == np.float64 for k, a in arrays.items() if k != "dense_score")
+    assert np.array_equal(arrays["bm25_doc"], out["bm25"][0].numpy()) and np.array_equal(arrays["rerank_rows"], out["rerank"][5].numpy())
+    assert all(np.isfinite(a).all() for a in arrays.values())
+    for stage, n in (("bm25", nb), ("dense", nd), ("rerank", nr)):
+        got, exp = arrays[f"{stage}_score"], out[stage][1].numpy()
+        inside = np.arange(exp.shape[1])[None, :] < n.numpy()[:, None]
+        assert np.array_equal(got[inside], exp[inside]) and np.all(got[~inside] == 0), stage
+
+    assert bench.write_outputs(arrays, str(tmp_path / "all")) == 400
+    assert np.array_equal(np.load(tmp_path / "all" / "query_index.npy"), np.arange(400))
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a), name
+
+    limit = 20000
+    kept = [bench.write_outputs(arrays, str(tmp_path / d), limit=limit) for d in ("a", "b")]
+    assert kept[0] == kept[1] and 1 <= kept[0] < 400
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= limit
+    q = np.load(tmp_path / "a" / "query_index.npy")
+    assert len(q) == kept[0] and np.all(np.diff(q) > 0) and np.array_equal(q, np.load(tmp_path / "b" / "query_index.npy"))
+    q = q.astype(np.int64)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert np.array_equal(got, a[q[q < len(a)]]) and np.array_equal(got, np.load(tmp_path / "b" / f"{name}.npy")), name

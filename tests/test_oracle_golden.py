@@ -59,6 +59,20 @@ def test_cosine_matches_sklearn_float32():
     assert abs(float(got[123]) - float(z["single_123"])) < 1e-6
 
 
+def test_cosine_of_a_row_does_not_depend_on_the_matrix_it_sits_in():
+    """The sharded oracle must equal the unsharded one and the 32-row batches of the pandas-shaped chain the whole-matrix
+    restatement, bit for bit, on every host: a row's cosine is the same in the whole matrix, in row blocks of any size and
+    alone."""
+    rng = np.random.default_rng(5)
+    E = rng.standard_normal((4200, 768)).astype(np.float32)
+    q = rng.standard_normal(768).astype(np.float32) * 3
+    whole = rerank_ref.cosine_f32(q, E)
+    for blk in (1, 32, 1337, 2100):
+        parts = np.concatenate([rerank_ref.cosine_f32(q, E[s:s + blk]) for s in range(0, len(E), blk)])
+        assert np.array_equal(parts, whole), blk
+    assert np.array_equal(rerank_ref.cosine_f32(q, E[1::3]), whole[1::3])
+
+
 def test_oracle_dense_matches_reference_on_unit_rows():
     """cosine_unit.npz (reference get_new_similarity on unit-norm rows, 40 queries): the oracle's per-chunk cosines,
     per-document maxima and ranking restate it."""
