@@ -35,9 +35,11 @@ int msr_enc_layernorm(const float* x, const int32_t* ids, const float* table, co
 /* Self-attention of short sequences.  qkv is [n_tok][3][n_heads][64] (the Wqkv product); sequence b owns tokens
  * [seq_off[b], seq_off[b+1]) (<= 128 each).  Rotary embedding (rotate-half form) with inv_freq[32] applied to q and k,
  * scores q.k / 8, keys farther than `window` positions away masked out (window <= 0: none), softmax, times v.
- * max_len: an upper bound of the sequence lengths the caller vouches for (<= 128; 0 = no better bound than 128): up to 32
- * a WAVE serves a (sequence, head) pair instead of a workgroup (a batch of queries: 1536 pairs of 8 tokens); a sequence
- * longer than the bound gets NaNs.  out is [n_tok][n_heads * 64]. */
+ * max_len: an upper bound of the sequence lengths the caller vouches for (<= 128; 0 = no better bound than 128).  It picks
+ * a length class: 1..8, 9..16 and 17..32 are served by one WAVE per (sequence, head) pair instead of a workgroup (a batch
+ * of queries: 1536 pairs of 8 tokens), 0 and 33..128 by a workgroup per pair.  A sequence longer than its class (8, 16,
+ * 32 or 128 tokens; not max_len itself) gets NaN in all of its rows, in every class; nothing past the class bound is read
+ * and the other sequences' rows are unaffected.  out is [n_tok][n_heads * 64]. */
 int msr_enc_attention(const float* qkv, const int32_t* seq_off, int32_t n_seq, int32_t n_heads, const float* inv_freq,
                       int32_t window, int32_t max_len, float* out, void* stream);
 

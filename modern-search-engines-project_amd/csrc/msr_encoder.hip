@@ -62,6 +62,13 @@ __global__ __launch_bounds__(MAX_SEQ) void enc_attention_kernel(const float* __r
     const int b = blockIdx.x, h = blockIdx.y, t = threadIdx.x;
     const int t0 = seq_off[b], S = seq_off[b + 1] - t0;
     const int stride = 3 * n_heads * HEAD_DIM;
+    if (S > MAX_SEQ) {                                           // longer than Ks / Vs: NaN rows, read nothing (S is block-uniform)
+        float* o = out + (int64_t)t0 * (n_heads * HEAD_DIM) + h * HEAD_DIM;
+        for (int r = t; r < S; r += MAX_SEQ)
+#pragma unroll
+            for (int j = 0; j < HEAD_DIM; ++j) o[(int64_t)r * (n_heads * HEAD_DIM) + j] = __builtin_nanf("");
+        return;
+    }
     float q[HEAD_DIM];
 #pragma unroll
     for (int j = 0; j < HEAD_DIM; ++j) q[j] = 0.f;
@@ -242,7 +249,8 @@ extern "C" int msr_enc_attention(const float* qkv, const int32_t* seq_off, int32
     if (!qkv || !seq_off || !inv_freq || !out || n_seq < 0 || n_heads < 1 || n_heads > 64 || max_len > MAX_SEQ)
         return msr_fail_global(MSR_ERR_INVALID, "msr_enc_attention: bad argument");
     if (n_seq == 0) return MSR_OK;
-    // (sequence lengths are on the device; the caller guarantees <= max_len (<= 128) tokens per sequence, encoder.py checks it)
+    // (sequence lengths are on the device; the caller vouches for <= max_len (<= 128) tokens per sequence, encoder.py checks
+    // it; a sequence longer than its kernel's bound -- 8 / 16 / 32 / 128 -- gets NaN rows in every kernel)
     const unsigned pairs = (unsigned)n_seq * (unsigned)n_heads;
     hipStream_t st = (hipStream_t)stream;
     if (max_len >= 1 && max_len <= 8)

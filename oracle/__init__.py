@@ -10,5 +10,6 @@ Pinning status: every function below is checked in `tests/test_oracle_golden.py`
 (`tests/golden/make_goldens.py`).  The one routine with no reference code to execute is
 `dense_ref.quick_search` (retriever.py is missing from the reference snapshot): its
 arithmetic (cosine, max-pool) is pinned through `rerank_ref.cosine_f32`, its top-k/tie rule is the
-build's definition -> "parity unpinned" for that function's selection semantics.
+build's definition -> "parity unpinned" for that function's selection semantics.  `encoder_ref` (the query
+encoder in float64) has no fixture: it is pinned to transformers' ModernBertModel run in float64, in the same test file.
 """

@@ -316,3 +316,125 @@ def test_vectorised_idf_equals_the_scalar_formula():
         got = idf_real(N, df)
         exp = np.array([build_ref.idf_real(N, int(c)) for c in df], np.float32)
         assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), exp.view(np.uint32)), N
+
+
+# ------------------------------------------------------------------ query encoder restatement (oracle/encoder_ref.py)
+# transformers' ModernBertModel run in float64 on the CPU is the reference the restatement is pinned to.  It is not all
+# float64: it takes cos / sin of the rotary angle in float32 (modeling_modernbert.py:160-161) and its softmax casts the
+# scores to float32 (:180).  Each perturbs a row of attention output by about one float32 rounding unit u = 2**-24 of
+# |v|, and mean pooling averages those perturbations over the tokens; the bar per pooled vector is therefore
+# u * max|pooled vector|.  Measured (4 layers, the cases below): at most 0.07 of it; the window one token off: 4000 -
+# 15000 times it.
+U32 = 2.0 ** -24
+
+
+@pytest.fixture(scope="module")
+def modernbert_f64():
+    torch = pytest.importorskip("torch")
+    from transformers import ModernBertConfig, ModernBertModel
+    torch.manual_seed(11)
+    # 4 layers: global (theta 160000, no attn_norm), local, local (theta 10000, +-64 window), global with attn_norm
+    cfg = ModernBertConfig(num_hidden_layers=4, reference_compile=False, attn_implementation="eager")
+    hf = ModernBertModel(cfg).eval()
+    with torch.no_grad():                                     # LayerNorm weights away from 1, as the GPU fixture does
+        for n, p in hf.named_parameters():
+            if n.endswith("norm.weight"):
+                p.add_(0.2 * torch.randn_like(p))
+    return hf.double(), {k: v for k, v in hf.state_dict().items()}
+
+
+def _hf_pooled_f64(hf, seqs, pad_id=50283):
+    """transformers on one padded batch + sentence-transformers mean pooling (Pooling: sum(h * mask) / sum(mask))."""
+    import torch
+    L = max(len(s) for s in seqs)
+    ids = torch.full((len(seqs), L), pad_id, dtype=torch.long)
+    mask = torch.zeros((len(seqs), L), dtype=torch.long)
+    for i, s in enumerate(seqs):
+        ids[i, :len(s)] = torch.tensor(s)
+        mask[i, :len(s)] = 1
+    with torch.no_grad():
+        h = hf(input_ids=ids, attention_mask=mask).last_hidden_state
+    m = mask.unsqueeze(-1).bool()
+    return torch.where(m, h, 0.0).sum(1) / m.sum(1).clamp(min=1)
+
+
+def _row_excess(got, ref):
+    """max over the pooled vectors of |got - ref| / (u * max|ref|): <= 1 passes the bar."""
+    import torch
+    return float(((got - ref).abs().amax(1) / (U32 * ref.abs().amax(1))).max())
+
+
+# Padded batches: in float64 transformers turns a padded row whose +-64 window holds no real token into NaN (its mask is
+# finfo(float64).min, -inf once the softmax casts to float32), and in the next layer that NaN key poisons every row of the
+# sequence.  So a padded batch here keeps every sequence within 64 tokens of the longest one in the batch.
+ENCODER_PIN_CASES = [[1], [8], [65], [128], [2, 9, 17, 33, 66], [128, 64, 100, 70, 65]]
+
+
+@pytest.mark.parametrize("lens", ENCODER_PIN_CASES, ids=lambda l: "x".join(map(str, l)))
+def test_encoder_restatement_matches_transformers_float64(modernbert_f64, lens):
+    from oracle import encoder_ref
+    hf, w = modernbert_f64
+    rng = np.random.default_rng(sum(lens))
+    seqs = [rng.integers(0, 50000, size=n).tolist() for n in lens]
+    ref = _hf_pooled_f64(hf, seqs)
+    got = encoder_ref.forward(w, seqs)
+    assert got.shape == (len(seqs), 768)
+    assert _row_excess(got, ref) <= 1.0
+    if max(lens) > 65:          # negative controls: the local window one token too narrow or too wide is seen
+        for win in (63, 65):
+            assert _row_excess(encoder_ref.forward(w, seqs, window=win), ref) > 100, win
+    elif max(lens) == 65:       # (65 tokens: window 65 is no window at all; 63 drops the keys at distance 64)
+        assert _row_excess(encoder_ref.forward(w, seqs, window=63), ref) > 100
+
+
+def test_encoder_restatement_positions_restart_in_every_sequence(modernbert_f64):
+    """Rotary embedding is relative: positions that run on across a pack change the scores only through the float32
+    rounding of the angle t * inv_freq, which grows with t.  At offsets of ~2000 tokens (the bench's 256 x 8 pack) that
+    rounding is visible above the bar (measured: 3.2 times it, 0.05 with positions restarting)."""
+    from oracle import encoder_ref
+    hf, w = modernbert_f64
+    rng = np.random.default_rng(7)
+    seqs = [rng.integers(0, 50000, size=n).tolist() for n in [128] * 16 + [66, 9]]
+    import torch
+    ref = torch.cat([_hf_pooled_f64(hf, [s]) for s in seqs])
+    assert _row_excess(encoder_ref.forward(w, seqs), ref) <= 1.0
+    assert _row_excess(encoder_ref.forward(w, seqs, run_on_positions=True), ref) > 2.0
+
+
+@pytest.mark.parametrize("S", [128, 66, 65, 1])
+def test_attention_window_edge_closed_form(S):
+    """inv_freq = 0 and q = 0: every score is 0 and attention is the plain mean of the kept keys' v.  With v[k][0] = k,
+    out[t][0] is the mean of the positions k with |k - t| <= 64; window 0: of all positions."""
+    from oracle import encoder_ref
+    rng = np.random.default_rng(S)
+    for n_heads in (1, 3):
+        qkv = rng.standard_normal((2 * S, 3, n_heads, 64))
+        qkv[:, 0] = 0.0
+        qkv[:, 2, :, 0] = np.concatenate([np.arange(S), np.arange(S)])[:, None]
+        off = [0, S, S, 2 * S]                                # two sequences and an empty one: positions restart
+        for window in (64, 0, 3):
+            got = encoder_ref.attention(qkv, off, n_heads, np.zeros(32, np.float32), window).numpy()
+            got = got.reshape(2 * S, n_heads, 64)[:, :, 0]
+            for t in range(S):
+                ks = [k for k in range(S) if window <= 0 or abs(k - t) <= window]
+                want = sum(ks) / len(ks)
+                assert np.abs(got[t] - want).max() <= 1e-12 * max(want, 1) and np.abs(got[S + t] - want).max() <= 1e-12 * max(want, 1)
+
+
+def test_encoder_restatement_pointwise_forms():
+    """geglu, layernorm (with and without the lookup) and mean pooling against the torch ops they restate."""
+    torch = pytest.importorskip("torch")
+    from oracle import encoder_ref
+    g = torch.Generator().manual_seed(3)
+    u = torch.randn(5, 16, generator=g, dtype=torch.float64) * 4
+    assert torch.allclose(encoder_ref.geglu(u), torch.nn.functional.gelu(u[:, :8]) * u[:, 8:], rtol=0, atol=1e-14)
+    x = torch.randn(7, 1024, generator=g, dtype=torch.float64) * 3 + 1
+    w = torch.randn(1024, generator=g, dtype=torch.float64)
+    want = torch.nn.functional.layer_norm(x, (1024,), w, None, 1e-5)
+    assert torch.allclose(encoder_ref.layernorm(x, w), want, rtol=0, atol=1e-12)
+    assert torch.allclose(encoder_ref.layernorm_lookup([6, 0, 6], x, w), want[[6, 0, 6]], rtol=0, atol=1e-12)
+    h = torch.randn(6, 4, generator=g, dtype=torch.float64)
+    pool = encoder_ref.mean_pool(h, [0, 0, 2, 6], normalize=True)
+    assert torch.equal(pool[0], torch.zeros(4, dtype=torch.float64))
+    assert torch.allclose(pool[1:], torch.nn.functional.normalize(torch.stack([h[:2].mean(0), h[2:].mean(0)]), dim=1))
+    assert encoder_ref.positions([0, 3, 3, 5]).tolist() == [0, 1, 2, 0, 1]
