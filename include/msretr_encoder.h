@@ -6,9 +6,10 @@
  * are fetched by NAME there; here they come from a local directory (or are random for tests), see
  * modern-search-engines-project_amd/encoder.py.
  *
- * For a query (<= 128 tokens) the whole forward pass is hand-written HIP behind the entry points below: the four matrix
- * products of a layer (msr_enc_linear, exact-f32 matrix cores, weights streamed once) and everything between them;
- * encoder.py hands larger batches' products to the library GEMM (hipBLASLt), which wins there.  All tensors are float32, row-major, device
+ * The whole forward pass is hand-written HIP behind the entry points below: the four matrix products of a layer
+ * (msr_enc_linear, exact-f32 matrix cores; weights streamed once for a query, 64 x 48 token tiles for batches) and
+ * everything between them.  Queries (<= 128 tokens) take msr_enc_attention, document chunks (up to 8192 tokens, the
+ * index side) msr_enc_attention_long; no product goes to a library GEMM.  All tensors are float32, row-major, device
  * pointers owned by the caller; functions are stateless (no engine handle), enqueue on `stream`, never synchronise, and
  * return 0 or a negative msr_status (msr_last_error(NULL) holds the text).
  *
@@ -42,6 +43,16 @@ int msr_enc_layernorm(const float* x, const int32_t* ids, const float* table, co
  * and the other sequences' rows are unaffected.  out is [n_tok][n_heads * 64]. */
 int msr_enc_attention(const float* qkv, const int32_t* seq_off, int32_t n_seq, int32_t n_heads, const float* inv_freq,
                       int32_t window, int32_t max_len, float* out, void* stream);
+
+/* msr_enc_attention for sequences of up to 8192 tokens (ModernBERT's max_position_embeddings): same arguments, layouts,
+ * rotary embedding, window and arithmetic contract.  Flash-style: K / V streamed through LDS in 64-key tiles, online
+ * softmax in f32, both products on v_mfma_f32_16x16x4_f32; a windowed call (window > 0) visits only the key tiles within
+ * the window of each 64-row query tile.  max_len: the bound the caller vouches for (<= 8192; 0 = 8192); it sizes the
+ * grid, so a batch of mixed lengths is one call.  A sequence longer than max_len gets NaN in all of its rows, nothing of
+ * it is read and the other sequences' rows are unaffected.  qkv and out 16-byte aligned.  max_len > 8192 or a bad
+ * argument: MSR_ERR_INVALID. */
+int msr_enc_attention_long(const float* qkv, const int32_t* seq_off, int32_t n_seq, int32_t n_heads, const float* inv_freq,
+                           int32_t window, int32_t max_len, float* out, void* stream);
 
 /* y[m][j] = gelu(u[m][j]) * u[m][half + j], j < half (exact erf GELU). */
 int msr_enc_geglu(const float* u, float* y, int64_t n_rows, int32_t half, void* stream);

@@ -29,6 +29,7 @@ UNITS = {
     "msr_gemm_f32.hip": [],
     "msr_build.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
+    "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]

@@ -1,10 +1,11 @@
 // Query encoder, the parts between the matrix products (include/msretr_encoder.h).
 //
 // The reference encodes the query with a sentence-transformers ModernBERT-base bi-encoder
-// (reranker/reranker_api.py:137-139,355).  Its GEMMs are plain library GEMMs (hipBLASLt via torch); the kernels here
-// are the rest of the forward pass for the shapes a query has -- a few tokens to a few thousand tokens in total,
+// (reranker/reranker_api.py:137-139,355).  Its matrix products are msr_enc_linear (csrc/msr_enc_linear.hip); the kernels
+// here are the rest of the forward pass for the shapes a query has -- a few tokens to a few thousand tokens in total,
 // sequences of at most 128 tokens: LayerNorm (with the embedding lookup fused in), rotary embedding + attention per
-// (sequence, head), GeGLU, masked mean pooling.  All float32.
+// (sequence, head), GeGLU, masked mean pooling.  All float32.  Document chunks (longer sequences) take the attention of
+// csrc/msr_enc_attention_long.hip; the other kernels here serve them unchanged.
 #include <math.h>
 
 #include "../../include/msretr.h"

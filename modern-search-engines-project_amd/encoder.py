@@ -11,7 +11,9 @@ For a query (<= 128 tokens in all) the whole forward pass is hand-written HIP be
 include/msretr_encoder.h: the matrix products (msr_enc_linear: skinny products on the exact-f32 matrix cores, each weight
 read once) and everything between them -- embedding lookup + LayerNorm, LayerNorm, rotary embedding + attention, GeGLU,
 masked mean pooling; torch owns the buffers and the hipGraph.  Batches take the same kernels (a tile shape of
-msr_enc_linear for many tokens, the wave-per-(sequence, head) form of the attention for short sequences).  There is no CPU
+msr_enc_linear for many tokens, the wave-per-(sequence, head) form of the attention for short sequences).  Document chunks
+(encode_chunks: up to 8192 tokens per sequence, the index side) run the same layer loop eagerly, without graph capture,
+with the attention of msr_enc_attention_long (K / V tiles streamed through LDS, online softmax).  There is no CPU
 fallback: without the library the class raises.  Parity: tests/test_gpu_encoder.py compares the output with transformers' ModernBertModel (the reference's
 dependency) on the same random weights.
 """
@@ -27,6 +29,8 @@ from . import _abi
 HIDDEN, HEADS, LAYERS, INTER, VOCAB = 768, 12, 22, 1152, 50368
 GLOBAL_EVERY, LOCAL_WINDOW, THETA_GLOBAL, THETA_LOCAL, EPS = 3, 128, 160000.0, 10000.0, 1e-5
 MAX_SEQ = 128                                               # msr_enc_attention: tokens per sequence
+MAX_SEQ_LONG = 8192                                         # msr_enc_attention_long: ModernBERT max_position_embeddings
+BATCH_TOKENS = 32768                                        # encode_chunks: tokens per forward pass (u, qkv ~300 MB each)
 
 
 def _ptr(t):
@@ -62,6 +66,7 @@ class QueryEncoder:
             raise _abi.MsrError(-101, "QueryEncoder needs a GPU: the encoder kernels have no CPU fallback")
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.tokenizer, self.normalize = tokenizer, bool(normalize)
+        self.max_seq_length = None                           # sentence_bert_config.json (encode_chunks truncates to it)
         self.use_graphs, self._graphs = bool(use_graphs), {}
         strip = lambda k: k[len("model."):] if k.startswith("model.") else k
         self.w = {strip(k): v.to(device=self.device, dtype=torch.float32).contiguous() for k, v in weights.items()}
@@ -88,7 +93,13 @@ class QueryEncoder:
         if os.path.exists(mj):
             with open(mj, encoding="utf-8") as f:
                 normalize = any("Normalize" in str(m.get("type", "")) for m in json.load(f))
-        return QueryEncoder(weights, device=device, tokenizer=tok, normalize=normalize)
+        enc = QueryEncoder(weights, device=device, tokenizer=tok, normalize=normalize)
+        sb = os.path.join(path, "sentence_bert_config.json")
+        if os.path.exists(sb):
+            with open(sb, encoding="utf-8") as f:
+                m = json.load(f).get("max_seq_length")
+            enc.max_seq_length = int(m) if m else None
+        return enc
 
     # ------------------------------------------------------------------ forward
     def _check(self, rc):
@@ -172,7 +183,55 @@ class QueryEncoder:
                                             int(n_in), self._stream()))
         return y
 
-    def _forward(self, ids, seq_off, n_seq, n_tok, normalize, out, max_len=MAX_SEQ):
+    def _truncate(self, seq):
+        """sentence-transformers truncation to max_seq_length: a sequence wrapped in [CLS] ... [SEP] keeps both (the
+        tokenizer truncates the text between them), any other sequence keeps its first max_seq_length tokens."""
+        m = self.max_seq_length
+        if m is None or len(seq) <= m:
+            return seq
+        tok = self.tokenizer
+        cls, sep = (tok.token_to_id("[CLS]"), tok.token_to_id("[SEP]")) if tok is not None else (None, None)
+        if cls is not None and sep is not None and m >= 2 and seq[0] == cls and seq[-1] == sep:
+            return seq[:m - 1] + [sep]
+        return seq[:m]
+
+    def encode_chunks(self, seqs, normalize=True, out=None, row0=0, batch_tokens=BATCH_TOKENS):
+        """Document side (indexer/indexer.py:157-172, `encode(window_texts, normalize_embeddings=True)`): token-id sequences
+        of up to 8192 tokens -> out[row0 + i] = the pooled embedding of seqs[i] (float32 device tensor [C, 768], allocated
+        when out is None; returned).  Sequences are packed back to back and run in eager forward passes of at most
+        `batch_tokens` tokens (one longer sequence goes alone), attention through msr_enc_attention_long.  Truncation as in
+        sentence-transformers: to max_seq_length when the model directory names one, otherwise none, and a sequence of
+        more than 8192 tokens is refused."""
+        seqs = [self._truncate([int(t) for t in s]) for s in seqs]
+        if any(len(s) > MAX_SEQ_LONG for s in seqs):
+            raise ValueError(f"a sequence has more than {MAX_SEQ_LONG} tokens (ModernBERT max_position_embeddings)")
+        if any(t < 0 or t >= VOCAB for s in seqs for t in s):
+            raise ValueError("token id outside the vocabulary")
+        if out is None:
+            out = torch.zeros((row0 + len(seqs), HIDDEN), dtype=torch.float32, device=self.device)
+        if (out.dtype != torch.float32 or out.device != self.device or out.dim() != 2 or out.shape[1] != HIDDEN
+                or not out.is_contiguous() or row0 < 0 or row0 + len(seqs) > out.shape[0]):
+            raise ValueError("out must be a contiguous float32 [C, 768] tensor on the encoder's device with room for the rows")
+        i = 0
+        while i < len(seqs):
+            j, n_tok = i, 0
+            while j < len(seqs) and (j == i or n_tok + len(seqs[j]) <= batch_tokens):
+                n_tok += len(seqs[j])
+                j += 1
+            batch = seqs[i:j]
+            dst = out[row0 + i: row0 + j]
+            if n_tok == 0:
+                dst.zero_()
+            else:
+                off = np.zeros(len(batch) + 1, np.int32)
+                off[1:] = np.cumsum([len(s) for s in batch])
+                ids = torch.tensor([t for s in batch for t in s], dtype=torch.int32).to(self.device)
+                self._forward(ids, torch.from_numpy(off).to(self.device), len(batch), n_tok, bool(normalize), dst,
+                              max(len(s) for s in batch), long=True)
+            i = j
+        return out
+
+    def _forward(self, ids, seq_off, n_seq, n_tok, normalize, out, max_len=MAX_SEQ, long=False):
         w, st = self.w, self._stream
         h = self._ln(None, w["embeddings.norm.weight"], ids=ids)                      # lookup + LayerNorm
         new = lambda cols: torch.empty((n_tok, cols), dtype=torch.float32, device=self.device)
@@ -182,8 +241,9 @@ class QueryEncoder:
             glob = l % GLOBAL_EVERY == 0
             x = h if l == 0 else self._ln(h, w[p + "attn_norm.weight"])               # layer 0 has no attn_norm
             self._linear(x, w[p + "attn.Wqkv.weight"], qkv)
-            self._check(self.lib.msr_enc_attention(_ptr(qkv), _ptr(seq_off), n_seq, HEADS, _ptr(self.inv_freq[glob]),
-                                                   0 if glob else LOCAL_WINDOW // 2, int(max_len), _ptr(att), st()))
+            attention = self.lib.msr_enc_attention_long if long else self.lib.msr_enc_attention
+            self._check(attention(_ptr(qkv), _ptr(seq_off), n_seq, HEADS, _ptr(self.inv_freq[glob]),
+                                  0 if glob else LOCAL_WINDOW // 2, int(max_len), _ptr(att), st()))
             if l == 0:
                 h = self._linear(att, w[p + "attn.Wo.weight"], new(HIDDEN), resid=h)  # (x is h in layer 0: keep it intact)
             else:

@@ -30,7 +30,7 @@ def stats(stats_csv, trace_csv, out):
     ours = [r for r in rows if any(k in r["Name"] for k in ("dense_scan", "dense_ksplit", "build_qimage", "thr_compact", "rescore", "bm25_taat", "sel_", "rerank_", "best_chunk",
                                                              "prep_queries", "merge_kernel", "interleave", "row_inv_norm",
                                                              "fill_chunk_doc", "gemm_", "build_qimg", "qmat_kernel", "batch_margin",
-                                                             "unit_bf16", "pad_inv", "rescore", "f16_", "build_qimg1"))]
+                                                             "unit_bf16", "pad_inv", "rescore", "f16_", "build_qimg1", "enc_"))]
     lines = ["| kernel | calls | avg us | min us | max us | total ms |", "|---|---|---|---|---|---|"]
     for r in sorted(ours, key=lambda r: -float(r["TotalDurationNs"])):
         lines.append(f"| {short(r['Name'])} | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['MinNs']) / 1e3:.1f} | "
