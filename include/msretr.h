@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 3
+#define MSR_ABI_VERSION 4         /* 4: msr_unbind, msr_merge_postings */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -123,6 +123,13 @@ int msr_row_image_state(const msr_engine* e);
  * arrays are not included. */
 int64_t msr_owned_bytes(const msr_engine* e);
 
+/* Drop every binding: postings, chunks, document metadata and domain tables, the tables and copies built at bind, the scratch
+ * sized by the corpus, and a pending msr_dense_topk_begin (its msr_dense_topk_end then fails).  Afterwards the engine is as
+ * created: every query call returns MSR_ERR_NOT_BOUND, and the next msr_bind_postings / msr_bind_chunks pair may have any
+ * n_docs (a larger corpus after an index update).  The caller makes sure no enqueued work still uses the old binding
+ * (synchronise the stream first); the arrays it bound may be freed once this returns. */
+int msr_unbind(msr_engine* e);
+
 /* Per-document metadata the rerank stage needs: url_group[n_docs] i32 = id of the document's URL with
  * the query string removed, or -1 when the document is not in urlsDB.   reranker_api.py:38-47 */
 int msr_bind_doc_meta(msr_engine* e, const int32_t* url_group, int64_t n_docs, void* stream);
@@ -185,7 +192,9 @@ int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, int32_t k, 
  *     bound - (half the filter's measured error margin) cannot be in the global top-k and are dropped before the candidate lists and the exact rescoring.  Output
  *     as msr_dense_topk, except that out_n[q] may be < k: the shard returns every document it can contribute to the global
  *     top-k (merge the shards' lists with msr_merge_topk_payload as usual; the merged list is the unsharded one, bit for bit).
- * One begin may be pending per engine; the matching end must follow with the same n_queries and k. */
+ * One begin may be pending per engine; the matching end must follow with the same n_queries and k.  An msr_unbind between
+ * them (an index update) cancels the begin: the end then fails (MSR_ERR_NOT_BOUND while no chunks are bound) and launches
+ * nothing. */
 int msr_dense_split_max(const msr_engine* e, int32_t k);
 int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t k_part, float* out_part,
                          void* stream);
@@ -341,6 +350,22 @@ int msr_merge_topk_payload(msr_engine* e, const int32_t* in_doc, const void* in_
  * return after the counting phase and leave term_off untouched), then again.  All arrays are device pointers. */
 int msr_build_postings(const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int32_t n_terms, int64_t* term_off,
                        int32_t* post_doc, int32_t* post_tf, int64_t capacity, int64_t* n_postings, void* stream);
+
+/* Merge of two CSR-by-term posting tables (index update: the postings of newly indexed documents, B, join those of a built
+ * index, A; OFFLINE and handle-less like msr_build_postings: allocates its workspace and synchronises).  Each side:
+ * x_term_off[x_terms + 1] i64, x_doc / x_tf i32 (documents strictly ascending inside a term), x_map[x_docs] i32 = the side's
+ * dense document index -> the merged one, strictly increasing, in [0, n_docs); a_map NULL = identity (A's documents keep
+ * their indices).  n_terms >= a_terms, b_terms: the merged vocabulary (term t >= x_terms has no posting on that side).
+ * Writes term_off[n_terms + 1] = a_term_off[min(t, a_terms)] + b_term_off[min(t, b_terms)] and post_doc / post_tf: inside a
+ * term the two segments merged by mapped document, post_doc = the mapped index, post_tf copied.  MSR_ERR_INVALID, before
+ * anything is written: a malformed offset array, a map out of range or not strictly increasing, capacity < the number of
+ * postings, or a document with postings of the same term on both sides (never merged silently).  A posting-level
+ * malformation (document index outside its side, a descent inside a term) is found during the merge: MSR_ERR_INVALID, with
+ * the output written but unspecified.  All arrays are device pointers. */
+int msr_merge_postings(const int64_t* a_term_off, int64_t a_terms, const int32_t* a_doc, const int32_t* a_tf,
+                       const int32_t* a_map, int64_t a_docs, const int64_t* b_term_off, int64_t b_terms, const int32_t* b_doc,
+                       const int32_t* b_tf, const int32_t* b_map, int64_t b_docs, int64_t n_terms, int64_t n_docs,
+                       int64_t* term_off, int32_t* post_doc, int32_t* post_tf, int64_t capacity, void* stream);
 
 /* Timing hooks for bench.py: while enabled, every launch of the dominant kernels is bracketed by a
  * hipEvent pair recorded on the caller's stream (ring of 256 launches per kernel).  msr_kernel_time_ms

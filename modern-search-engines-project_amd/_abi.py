@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 3
+MSR_ABI_VERSION = 4
 MSR_CFG_NO_ROW_COPY = 1
 MSR_DIM = 768
 MSR_MAX_K = 1024
@@ -41,6 +41,7 @@ _SIGNATURES = {
                                     C.c_double, C.c_double, _P]),
     "msr_bind_chunks": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     "msr_bind_doc_meta": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "msr_unbind": (C.c_int, [_P]),
     "msr_scan_arith": (C.c_int, [_P]),
     "msr_scan_width": (C.c_int, [_P]),
     "msr_dense_path": (C.c_int, [_P]),
@@ -84,6 +85,8 @@ _SIGNATURES = {
     "msr_merge_topk_payload": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                          _P, _P]),
     "msr_build_postings": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "msr_merge_postings": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64,
+                                     C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "msr_set_timing": (C.c_int, [_P, C.c_int32]),
     "msr_tune": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "msr_kernel_time_ms": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

@@ -22,9 +22,14 @@ class BM25:
         else:
             source.k1, source.b = k1, b
             self.engine = DeviceEngine(source, device=device, **engine_kw)
-        self.index = self.engine.index
-        self.k1, self.b = self.index.k1, self.index.b
         self._tokenize = tokenizer or simple_tokenize
+        self.attach(self.engine.index)
+
+    def attach(self, index: CorpusIndex):
+        """Point the facade at the index its engine now serves (DeviceEngine.rebind)."""
+        self.index = index
+        self.k1, self.b = index.k1, index.b
+        self._pos = None
 
     # -- engine-level entry points (usable without spaCy: pre-tokenised terms or term ids) ----------
     def search_terms(self, terms: Sequence[Union[str, int]], top_k: int = 1000, min_score: float = 0.0):

@@ -679,6 +679,32 @@ extern "C" int msr_bind_chunks(msr_engine* e, const float* emb, int64_t n_chunks
     return MSR_OK;
 }
 
+extern "C" int msr_unbind(msr_engine* e) {
+    if (!e) return MSR_ERR_INVALID;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    // the engine counts as unbound before anything is freed
+    e->have_postings = e->have_chunks = false;
+    e->split_pending = 0;
+    e->bm25 = Bm25Index{};
+    e->dense = e->dense_bf16 = DenseIndex{};
+    e->url_group = nullptr; e->url_group_n = 0;
+    e->doc_domain = nullptr; e->doc_domain_n = 0;
+    // tables built at bind and scratch sized by the corpus (the per-query scratch of msr_create stays)
+    for (void** p : {(void**)&e->chunk_doc, &e->emb_presplit, &e->row_meta, (void**)&e->inv_norm_own, (void**)&e->span_doc,
+                     (void**)&e->wspan_doc, (void**)&e->wspan12_doc, &e->emb_bf16, &e->score_rows, (void**)&e->bm_heavy_id,
+                     &e->bm_post, (void**)&e->bm_dense_id, (void**)&e->bm_dense, (void**)&e->bm_tile_off,
+                     (void**)&e->bm_cand_doc, (void**)&e->bm_cand_n, (void**)&e->bm_win}) {
+        free_dev(e, *p);
+        *p = nullptr;
+    }
+    e->score_rows_bytes = e->bm_cand_bytes = 0;
+    free_gemm(e);
+    free_gf(e);
+    e->row_copy_state = e->row_image_state = 0;
+    e->last_dense_width = 0;
+    return MSR_OK;
+}
+
 extern "C" int msr_bind_doc_meta(msr_engine* e, const int32_t* url_group, int64_t n_docs, void* stream) {
     (void)stream;
     if (!e) return MSR_ERR_INVALID;
@@ -879,6 +905,7 @@ extern "C" int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_que
 extern "C" int msr_dense_topk_end(msr_engine* e, int32_t n_queries, int32_t k, const float* bound, int32_t* out_doc,
                                   float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
+    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk_end: chunks not bound");
     if (e->split_pending != n_queries || n_queries <= 0)
         return fail(e, MSR_ERR_INVALID, "msr_dense_topk_end: no matching msr_dense_topk_begin (pending %d, got %d)", e->split_pending, n_queries);
     if (!out_doc || !out_score || !out_n || k < 1 || k > e->cfg.max_k) return fail(e, MSR_ERR_INVALID, "msr_dense_topk_end: bad argument");

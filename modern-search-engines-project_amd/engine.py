@@ -76,6 +76,7 @@ class DeviceEngine:
         if rc != 0:
             raise _abi.MsrError(rc, (self.lib.msr_last_error(None) or b"?").decode())
         self._t = {}          # device tensors that the engine borrows: keep them alive
+        self._bf16 = False    # enable_bf16 was called: a rebind rebuilds the image
         self._bind(index)
 
     # ------------------------------------------------------------------ plumbing
@@ -142,6 +143,25 @@ class DeviceEngine:
                 t["url_group"] = self._dev(ix.url_group(), torch.int32)
                 self._check(self.lib.msr_bind_doc_meta(self.handle, _ptr(t["url_group"]), ix.n_docs, self._stream()))
             torch.cuda.synchronize(self.device)
+
+    def rebind(self, ix: CorpusIndex):
+        """Serve another index (e.g. index_build.bm25_add_token_ids(self.index, ...)) with this engine: synchronise, drop the
+        old binding (msr_unbind: tables, copies, a pending dense_begin), bind `ix` -- any number of documents -- and rebuild
+        the bf16 image if it was enabled.  The old index's device copies are released before the new ones are made.  If a
+        bind fails the engine is left unbound (every call raises MSR_ERR_NOT_BOUND) and the error is raised."""
+        torch.cuda.synchronize(self.device)
+        self._check(self.lib.msr_unbind(self.handle))
+        self._t = {}
+        self.index = ix
+        try:
+            self._bind(ix)
+            if self._bf16:
+                self.enable_bf16()
+        except Exception:
+            torch.cuda.synchronize(self.device)
+            self.lib.msr_unbind(self.handle)
+            self._t = {}
+            raise
 
     def scan_arith(self):
         """'f32' (exact f32 MFMA) or 'f16x2' (f32 rows split into two f16 pieces, f32 accumulation)."""
@@ -253,6 +273,7 @@ class DeviceEngine:
         """Build the bf16 copy of the embeddings used by dense_topk_batched (+7.7 GB at 5 M chunks)."""
         self._check(self.lib.msr_enable_bf16(self.handle, self._stream()))
         torch.cuda.synchronize(self.device)
+        self._bf16 = True
 
     def dense_topk_batched(self, qvec, k=100, max_chunks_per_doc=0, want_chunk=True):
         """Throughput variant of dense_topk: bf16 candidate sweep (up to 128 queries per sweep) + exact f32 rescoring.

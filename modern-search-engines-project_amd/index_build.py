@@ -160,3 +160,169 @@ def _bm25_index_from_token_ids_hip(doc_ids, tok_off, tok_ids, n_terms, dev, k1, 
                      idf=torch.as_tensor(idf).to(dev), avgdl=avgdl, total_docs=N, k1=k1, b=b, vocab=vocab)
     ix.n_docs_global = N
     return ix
+
+
+# ---------------------------------------------------------------------------------------------------------------- updates
+def merge_postings(a_term_off, a_doc, a_tf, a_map, b_term_off, b_doc, b_tf, b_map, n_terms, n_docs, device="cpu", a_docs=None):
+    """Two CSR-by-term posting tables -> one (msr_merge_postings on a GPU device; a torch / numpy restatement on the CPU).
+    Side A (a built index) and side B (new documents) each: term_off [terms + 1], doc / tf [postings] with documents strictly
+    ascending inside a term, and a strictly increasing map of its dense document indices into [0, n_docs) (a_map None =
+    identity over a_docs documents, default n_docs).  Returns (term_off int64 [n_terms + 1], post_doc int32, post_tf int32)
+    tensors on `device`: inside a term the two segments merged by mapped document, post_doc = the mapped index.  The same merged document in one term on both sides
+    raises (ValueError on the CPU, MsrError on the GPU): postings are never merged silently."""
+    import torch
+    from .index import _np
+    dev = torch.device(device)
+    if dev.type == "cuda":
+        return _merge_postings_hip(a_term_off, a_doc, a_tf, a_map, b_term_off, b_doc, b_tf, b_map, n_terms, n_docs, dev, a_docs)
+    a_off, b_off = np.asarray(_np(a_term_off), np.int64), np.asarray(_np(b_term_off), np.int64)
+    a_terms, b_terms = len(a_off) - 1, len(b_off) - 1
+    if n_terms < max(a_terms, b_terms):
+        raise ValueError("n_terms is smaller than a side's vocabulary")
+    a_doc, b_doc = np.asarray(_np(a_doc), np.int64)[:a_off[-1]], np.asarray(_np(b_doc), np.int64)[:b_off[-1]]
+    keys = []
+    for m, d in ((a_map, a_doc), (b_map, b_doc)):
+        if m is None:
+            if len(d) and (d.min() < 0 or d.max() >= (n_docs if a_docs is None else a_docs)):
+                raise ValueError("a posting's document index is outside its side's documents")
+            keys.append(d)
+            continue
+        m = np.asarray(_np(m), np.int64)
+        if len(m) and (m.min() < 0 or m.max() >= n_docs or np.any(np.diff(m) <= 0)):
+            raise ValueError("a document map is out of [0, n_docs) or not strictly increasing")
+        keys.append(m[d])
+    a_term = np.repeat(np.arange(a_terms, dtype=np.int64), np.diff(a_off))
+    b_term = np.repeat(np.arange(b_terms, dtype=np.int64), np.diff(b_off))
+    key = np.concatenate([a_term * max(n_docs, 1) + keys[0], b_term * max(n_docs, 1) + keys[1]])
+    order = np.argsort(key, kind="stable")
+    sk = key[order]
+    if np.any(sk[1:] == sk[:-1]):
+        raise ValueError("the same merged document has postings of one term on both sides")
+    t = np.arange(n_terms + 1)
+    term_off = a_off[np.minimum(t, a_terms)] + b_off[np.minimum(t, b_terms)]
+    post_doc = np.concatenate(keys)[order].astype(np.int32)
+    post_tf = np.concatenate([np.asarray(_np(a_tf), np.int32)[:a_off[-1]], np.asarray(_np(b_tf), np.int32)[:b_off[-1]]])[order]
+    return torch.as_tensor(term_off), torch.as_tensor(post_doc), torch.as_tensor(post_tf)
+
+
+def _merge_postings_hip(a_term_off, a_doc, a_tf, a_map, b_term_off, b_doc, b_tf, b_map, n_terms, n_docs, dev, a_docs):
+    """merge_postings through the C ABI (msr_merge_postings); no fallback."""
+    import ctypes as C
+
+    import torch
+
+    from . import _abi
+    lib = _abi.load()
+
+    def on_dev(x, dtype):
+        if x is None:
+            return None
+        t = x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x))
+        return t.to(dev, dtype).contiguous()
+    a_off, b_off = on_dev(a_term_off, torch.int64), on_dev(b_term_off, torch.int64)
+    a_doc, a_tf, b_doc, b_tf = (on_dev(x, torch.int32) for x in (a_doc, a_tf, b_doc, b_tf))
+    a_map, b_map = on_dev(a_map, torch.int32), on_dev(b_map, torch.int32)
+    a_docs = int(a_map.numel()) if a_map is not None else int(n_docs if a_docs is None else a_docs)
+    b_docs = int(b_map.numel()) if b_map is not None else 0
+    P = int(a_off[-1].item()) + int(b_off[-1].item())
+    term_off = torch.empty(int(n_terms) + 1, dtype=torch.int64, device=dev)
+    post_doc = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    post_tf = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check(None, lib.msr_merge_postings(ptr(a_off), int(a_off.numel()) - 1, ptr(a_doc), ptr(a_tf), ptr(a_map), a_docs,
+                                                ptr(b_off), int(b_off.numel()) - 1, ptr(b_doc), ptr(b_tf), ptr(b_map), b_docs,
+                                                int(n_terms), int(n_docs), ptr(term_off), ptr(post_doc), ptr(post_tf), max(P, 1),
+                                                stream))
+    return term_off, post_doc[:P], post_tf[:P]
+
+
+def bm25_add_token_ids(ix, doc_ids, tok_off, tok_ids, n_terms, device="cpu", vocab=None, docs_meta=None):
+    """The incremental BM25.build_index (indexer/bm25_indexer.py:252-344): a NEW CorpusIndex with the documents of this batch
+    that have no bm25_doc_stats row yet added to `ix` (which is left unchanged: an engine bound to it stays valid until it
+    rebinds).  doc_ids / tok_off / tok_ids as bm25_index_from_token_ids; token ids below n_terms, n_terms >= ix.n_terms.
+
+      * processed: a document whose doc_id is not in ix.doc_ids, or whose doc_len is 0 there (a urlsDB-only document of
+        from_duckdb / from_tables: it keeps its dense index).  Documents with a row are skipped (bm25_indexer.py:157-179) and
+        counted in the result's `update_counts`; a document without tokens gets no row.  Duplicate ids raise.
+      * the batch's postings come from the from-scratch builder (msr_build_postings on a GPU device), documents numbered by
+        ascending doc_id, and join the index's through merge_postings (msr_merge_postings) with both sides renumbered;
+        total_docs += added; avg_doc_length and the idf of EVERY term are recomputed as the reference does (:346-369,
+        :130-147), with the builders' float64 -> REAL rounding: the tables equal a from-scratch build of the union bit for bit.
+      * corpus side: doc_off gets zero-chunk entries for the new documents (attach_chunks then appends their chunk rows);
+        emb / chunk_ids are kept; urls / titles / texts are extended from docs_meta {doc_id: (url, title, text)} (None where
+        absent); the URL groups are recomputed over the whole corpus.  vocab, when given, replaces ix.vocab.
+    A shard (doc_base != 0 or n_docs_global != n_docs) is refused: update the whole index, then shard it."""
+    import torch
+    from .index import _np
+    if ix.doc_base != 0 or (ix.n_docs_global and ix.n_docs_global != ix.n_docs):
+        raise ValueError("bm25_add_token_ids: the index is a shard; update the whole index, then shard it (CorpusIndex.shard)")
+    if ix.term_off is None:
+        raise ValueError("bm25_add_token_ids: the index has no postings")
+    if int(n_terms) < ix.n_terms:
+        raise ValueError(f"bm25_add_token_ids: n_terms {n_terms} < the index's {ix.n_terms} (the vocabulary may grow, not shrink)")
+    if docs_meta is not None and ix.urls is None:
+        raise ValueError("bm25_add_token_ids: docs_meta given, but the index has no urlsDB columns")
+    dev = torch.device(device)
+    ids = np.asarray(_np(doc_ids), np.int64)
+    if len(np.unique(ids)) != len(ids):
+        raise ValueError("duplicate doc_id")
+    off = np.asarray(_np(tok_off), np.int64)
+    lens = np.diff(off)
+    tok = tok_ids if torch.is_tensor(tok_ids) else torch.as_tensor(np.asarray(tok_ids, np.int32))
+    if tok.numel() and (int(tok.min()) < 0 or int(tok.max()) >= n_terms):
+        raise ValueError("token id outside [0, n_terms)")
+    old_ids = np.asarray(_np(ix.doc_ids), np.int64)
+    old_len = np.asarray(_np(ix.doc_len), np.int32)
+    pos = np.minimum(np.searchsorted(old_ids, ids), max(len(old_ids) - 1, 0))
+    known = (old_ids[pos] == ids) if len(old_ids) else np.zeros(len(ids), bool)
+    has_row = known & (old_len[pos] > 0 if len(old_ids) else known)
+    sel = np.nonzero(~has_row & (lens > 0))[0]
+    # the batch's own tables (documents 0 .. Nb-1 in ascending doc_id): the from-scratch builder on its tokens
+    s_off = np.zeros(len(sel) + 1, np.int64)
+    s_off[1:] = np.cumsum(lens[sel])
+    src = np.repeat(off[sel] - s_off[:-1], lens[sel]) + np.arange(s_off[-1])
+    nb = bm25_index_from_token_ids(ids[sel], s_off, tok[torch.as_tensor(src, device=tok.device)], int(n_terms), device=dev)
+    b_ids = np.asarray(nb.doc_ids, np.int64)
+    merged = np.union1d(old_ids, b_ids)
+    M = len(merged)
+    a_idx = np.searchsorted(merged, old_ids)
+    identity = np.array_equal(a_idx, np.arange(len(old_ids)))
+    b_map = np.searchsorted(merged, b_ids).astype(np.int32)
+    term_off, post_doc, post_tf = merge_postings(ix.term_off, ix.post_doc, ix.post_tf, None if identity else a_idx.astype(np.int32),
+                                                 nb.term_off, nb.post_doc, nb.post_tf, b_map, int(n_terms), M, device=dev,
+                                                 a_docs=len(old_ids))
+    doc_len = np.zeros(M, np.int32)
+    doc_len[a_idx] = old_len
+    doc_len[b_map] = np.asarray(_np(nb.doc_len), np.int32)
+    added = len(b_ids)
+    total_docs = int(ix.total_docs) + added
+    rows = doc_len[doc_len > 0]
+    avgdl = float(np.float32(rows.astype(np.float64).mean())) if len(rows) else 0.0
+    idf = idf_real(total_docs, np.diff(np.asarray(_np(term_off), np.int64)))
+    out = CorpusIndex(doc_ids=merged, doc_len=torch.as_tensor(doc_len).to(dev), term_off=term_off, post_doc=post_doc,
+                      post_tf=post_tf, idf=torch.as_tensor(idf).to(dev), avgdl=avgdl, total_docs=total_docs, k1=ix.k1, b=ix.b,
+                      vocab=vocab if vocab is not None else ix.vocab, chunk_ids=ix.chunk_ids, emb=ix.emb)
+    out.n_docs_global = M
+    if ix.doc_off is not None:
+        cnt = np.zeros(M, np.int64)
+        cnt[a_idx] = np.diff(np.asarray(_np(ix.doc_off), np.int64))
+        doc_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
+        out.doc_off = torch.as_tensor(doc_off).to(ix.doc_off.device) if torch.is_tensor(ix.doc_off) else doc_off
+    if ix.urls is not None:
+        meta = docs_meta or {}
+        new = ~np.isin(b_ids, old_ids)
+        for j, name in enumerate(("urls", "titles", "texts")):
+            old = getattr(ix, name)
+            if old is None:
+                continue
+            col = [None] * M
+            for i, v in zip(a_idx.tolist(), old):
+                col[i] = v
+            for i, d in zip(b_map[new].tolist(), b_ids[new].tolist()):
+                m = meta.get(d)
+                col[i] = m[j] if m is not None else None
+            setattr(out, name, col)
+    out.update_counts = dict(added=added, already_indexed=int(has_row.sum()), no_tokens=int((~has_row & (lens == 0)).sum()))
+    return out

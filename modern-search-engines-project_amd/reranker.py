@@ -64,10 +64,14 @@ def diversify(results, relevance_threshold=0.8, top_k=100):
 class Reranker:
     def __init__(self, source, config: Optional[dict] = None, encoder=None, device=0, **engine_kw):
         self.engine = source if isinstance(source, DeviceEngine) else DeviceEngine(source, device=device, **engine_kw)
-        self.index: CorpusIndex = self.engine.index
         self.cfg = dict(SIMILARITY_DEFAULTS)
         self.cfg.update(config or {})
         self.encoder = encoder
+        self.attach(self.engine.index)
+
+    def attach(self, index: CorpusIndex):
+        """Point the facade (and its id maps) at the index its engine now serves (DeviceEngine.rebind)."""
+        self.index = index
         ids = self.index.doc_ids
         ids = ids.cpu().numpy() if hasattr(ids, "cpu") else np.asarray(ids)
         self._pos = {int(d): i for i, d in enumerate(ids)}

@@ -45,6 +45,34 @@ class Retriever:
             gc.collect()
             gc.freeze()
 
+    def update_index(self, ix: CorpusIndex):
+        """Serve `ix` from now on (an index grown by index_build.bm25_add_token_ids + chunk_index.attach_chunks): the engine
+        rebinds (DeviceEngine.rebind), and everything copied from the old index is refreshed -- the id map, the domain table,
+        the line formatter, the per-chunk engine of return_unique_docs=False (closed; rebuilt on first use), the BM25 and
+        Reranker facades."""
+        ce = getattr(self, "_chunk_engine", None)
+        if ce is not None:
+            ce.close()
+        self._chunk_engine = None
+        self.engine.rebind(ix)
+        self.index = ix
+        ids = ix.doc_ids
+        self._ids = ids.cpu().numpy() if hasattr(ids, "cpu") else np.asarray(ids)
+        self._domains_bound = False
+        self._formatter = None
+        if ix.term_off is None:
+            self.bm25 = None
+        elif self.bm25 is None:
+            self.bm25 = BM25(self.engine)
+        else:
+            self.bm25.attach(ix)
+        if ix.doc_off is None:
+            self.reranker = None
+        elif self.reranker is None:
+            self.reranker = Reranker(self.engine, encoder=self.embedder)
+        else:
+            self.reranker.attach(ix)
+
     def _embed(self, query, query_embedding=None):
         if query_embedding is not None:
             return np.asarray(query_embedding, np.float32)

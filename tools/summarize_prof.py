@@ -3,6 +3,8 @@
 
     python tools/summarize_prof.py stats  <kernel_stats.csv> <kernel_trace.csv> <out.md>
     python tools/summarize_prof.py pmc    <fetch counter_collection.csv> <write counter_collection.csv> <out.json>
+    python tools/summarize_prof.py rocpd  <results.db> <out.md> [kernel]   (rocprofv3's SQLite output; the durations of every
+                                                                            dispatch of `kernel` in launch order are listed too)
 
 HBM bytes follow /opt/skills/guides/MI355X_MICROARCH.md (HBM section): FETCH_SIZE and WRITE_SIZE are in KiB and
 are collected in separate passes; on gfx950 FETCH_SIZE counts exactly half of a wide (16 B/lane) streaming
@@ -30,7 +32,9 @@ def stats(stats_csv, trace_csv, out):
     ours = [r for r in rows if any(k in r["Name"] for k in ("dense_scan", "dense_ksplit", "build_qimage", "thr_compact", "rescore", "bm25_taat", "sel_", "rerank_", "best_chunk",
                                                              "prep_queries", "merge_kernel", "interleave", "row_inv_norm",
                                                              "fill_chunk_doc", "gemm_", "build_qimg", "qmat_kernel", "batch_margin",
-                                                             "unit_bf16", "pad_inv", "rescore", "f16_", "build_qimg1", "enc_"))]
+                                                             "unit_bf16", "pad_inv", "rescore", "f16_", "build_qimg1", "enc_",
+                                                             "partition_kernel", "term_off_kernel", "shared_kernel", "clash_kernel",
+                                                             "unique_kernel", "scatter_kernel", "hist_kernel"))]
     lines = ["| kernel | calls | avg us | min us | max us | total ms |", "|---|---|---|---|---|---|"]
     for r in sorted(ours, key=lambda r: -float(r["TotalDurationNs"])):
         lines.append(f"| {short(r['Name'])} | {r['Calls']} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['MinNs']) / 1e3:.1f} | "
@@ -57,6 +61,22 @@ def stats(stats_csv, trace_csv, out):
     open(out, "w").write("\n".join(lines + step) + "\n")
 
 
+def rocpd(db, out, kernel=None):
+    import sqlite3
+    con = sqlite3.connect(db)
+    rows = con.execute("SELECT name, duration FROM kernels ORDER BY start").fetchall()
+    agg = collections.OrderedDict()
+    for name, d in rows:
+        agg.setdefault(short(name), []).append(int(d))
+    lines = ["| kernel | calls | avg us | min us | max us | total ms |", "|---|---|---|---|---|---|"]
+    for n, ds in sorted(agg.items(), key=lambda x: -sum(x[1])):
+        lines.append(f"| {n} | {len(ds)} | {sum(ds) / len(ds) / 1e3:.1f} | {min(ds) / 1e3:.1f} | {max(ds) / 1e3:.1f} | {sum(ds) / 1e6:.3f} |")
+    if kernel:
+        lines += ["", f"Every dispatch of {kernel}, in launch order (us): " +
+                  ", ".join(f"{d / 1e3:.1f}" for n, d in rows if short(n) == kernel)]
+    open(out, "w").write("\n".join(lines) + "\n")
+
+
 def pmc(fetch_csv, write_csv, out):
     res = collections.defaultdict(dict)
     for key, f in (("FETCH_SIZE_KiB", fetch_csv), ("WRITE_SIZE_KiB", write_csv)):
@@ -74,4 +94,4 @@ def pmc(fetch_csv, write_csv, out):
 
 
 if __name__ == "__main__":
-    {"stats": stats, "pmc": pmc}[sys.argv[1]](*sys.argv[2:])
+    {"stats": stats, "pmc": pmc, "rocpd": rocpd}[sys.argv[1]](*sys.argv[2:])
