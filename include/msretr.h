@@ -218,7 +218,8 @@ int msr_dense_topk_bf16(msr_engine* e, const float* q, int32_t n_queries, int32_
  * dedup (MIN(id) wins) or without chunks are dropped; the others come back ordered by
  * (new_similarity desc, doc index asc): out_doc, out_score (new_similarity), out_orig (min-max
  * normalised BM25 of the winning row), out_chunk (row index of the winning chunk), out_n, and
- * out_rows[qi] = number of chunk rows that took part (RerankResponse.total_documents, :410). */
+ * out_rows[qi] = number of chunk rows that took part (RerankResponse.total_documents, :410).  A document repeated in
+ * the candidate list counts once, with the BM25 score of its FIRST slot. */
 int msr_rerank(msr_engine* e, const float* q, int32_t n_queries, const int32_t* cand_doc,
                const double* cand_bm25, const int32_t* cand_n, int32_t max_cand,
                const msr_rerank_params* params, int32_t* out_doc, double* out_score, double* out_orig,
@@ -261,7 +262,8 @@ int64_t msr_format_lines(const char* qnum_blob, const int64_t* qnum_off, int32_t
  *     Summing out_cos / out_meta over the shards (one RCCL all-reduce, integer SUM of the raw bits,) yields the arrays of the whole
  *     candidate list, because exactly one shard contributes a non-zero entry.
  *   msr_rerank_fuse: the float64 chain of reranker_api.py:360-372 on those arrays; touches no index, so
- *     every rank computes the same result.  Outputs as msr_rerank (out_doc are global indices). */
+ *     every rank computes the same result.  Outputs as msr_rerank (out_doc are global indices); of repeated slots of one
+ *     document the first counts. */
 int msr_rerank_gather(msr_engine* e, const float* q, int32_t n_queries, const int32_t* cand_doc,
                       const int32_t* cand_n, int32_t max_cand, int32_t doc_base, int32_t row_base,
                       int32_t max_chunks, float* out_cos, int32_t* out_meta, void* stream);

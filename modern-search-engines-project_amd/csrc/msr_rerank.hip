@@ -178,7 +178,8 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_fuse_kernel(
     const double* cb = cand_bm25 + (int64_t)q * max_cand;
     const int32_t* mt = meta + (int64_t)q * max_cand * 3;      // (rows, url group, first row) per candidate
 
-    // 1. sort candidates by (url group, doc) so the first entry of each group is MIN(id)   (:38-47)
+    // 1. sort candidates by (url group, doc, slot) so the first entry of each group is MIN(id)   (:38-47) and, among repeated
+    //    slots of that document, the first slot (msretr.h): the network is not stable, so the slot is part of the key
     for (int i = tid; i < P; i += RR_THREADS) {
         uint64_t key = ~0ull;
         if (i < n) {
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_fuse_kernel(
             const int g = mt[3 * i + 1] - 2;
             if (d >= 0 && g >= 0) key = ((uint64_t)(uint32_t)g << 32) | (uint32_t)d;
         }
-        khi[i] = key; klo[i] = 0; val[i] = (uint32_t)i;
+        khi[i] = key; klo[i] = (uint32_t)i; val[i] = (uint32_t)i;
     }
     if (tid < 2) cnt[tid] = 0;
     __syncthreads();

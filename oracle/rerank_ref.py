@@ -105,19 +105,19 @@ def fetch_candidates(urls, chunk_id, chunk_doc, doc_ids):
     return [d for d in kept if rows[d]], rows
 
 
-def positional_adjust(new, n):
+def positional_adjust(new, n, max_boost=MAX_BOOST, max_decay=MAX_DECAY):
     """Apply reranker_api.py:299-334 to one document's chunk scores `new` (chunk_id order)."""
     if n == 1:
         return new
     best = max(range(n), key=lambda i: (new[i], -i))     # idxmax: first maximum
     ratio = best / max(1, n - 1)
-    adj = MAX_BOOST - (MAX_BOOST + MAX_DECAY) * ratio
+    adj = max_boost - (max_boost + max_decay) * ratio
     new = list(new)
     new[best] = max(0.0, min(1.0, new[best] + adj))
     return new
 
 
-def chain_from_cosines(docs, n_rows, bm25, cos, smoothing=0.15):
+def chain_from_cosines(docs, n_rows, bm25, cos, smoothing=0.15, max_boost=MAX_BOOST, max_decay=MAX_DECAY):
     """reranker_api.py:360-372 on the cosines of the candidates' chunk rows: min-max of the cosines and of the BM25 scores
     (repeated per chunk row) over ALL rows, blend, positional weighting per document, per-document first maximum.
     docs: the kept documents in the order of their rows; n_rows[i] chunk rows of docs[i] (>= 1), bm25[i] its stage-1 score;
@@ -130,13 +130,50 @@ def chain_from_cosines(docs, n_rows, bm25, cos, smoothing=0.15):
     st["blend"] = list(new)
     out, pos, p = [], [], 0
     for d, n in zip(docs, n_rows):
-        adj = positional_adjust(new[p:p + n], n)
+        adj = positional_adjust(new[p:p + n], n, max_boost, max_decay)
         pos += adj
         best = max(range(n), key=lambda i: (adj[i], -i))
         out.append((d, adj[best], old[p + best], best))
         p += n
     st["positional"] = pos
     return out, st
+
+
+def fuse_from_gather(cand_doc, cand_bm25, cand_n, cos, meta, smoothing=0.15, max_boost=MAX_BOOST, max_decay=MAX_DECAY,
+                     return_stages=False):
+    """What the fuse kernel (msr_rerank_fuse) computes for ONE query from the gather's arrays: cand_doc [M] document indices,
+    cand_bm25 [M] float64, cand_n, cos [M, 10] float32 and meta [M, 3] = (rows, url group + 2, first row) per slot.
+      * slots past min(cand_n, M) are not read; a slot with doc < 0 or group < 0 (meta[1] < 2) is dropped;
+      * within a URL group the lowest document wins (reranker_api.py:38-47); among repeated slots of that document the first
+        slot wins, BM25 score included (rerank() keeps the first with setdefault); a winner with 0 rows drops its group;
+      * the kept documents, ascending, with their first meta[0] (<= 10) cosines go through chain_from_cosines: min-max over
+        ALL their rows, blend, positional weighting, first maximum;
+      * final order (new_similarity desc, doc asc).
+    -> (doc int32 [M], score f64 [M], orig f64 [M], chunk row int32 [M], n, rows): entries past n are -1 / -inf / 0.0 / -1;
+    rows = the chunk rows that took part.  return_stages: also (kept documents ascending, their row counts, the stages of
+    chain_from_cosines)."""
+    M = len(cand_doc)
+    n = max(0, min(int(cand_n), M))
+    winner = {}
+    for m in range(n):
+        d, g = int(cand_doc[m]), int(meta[m][1]) - 2
+        if d < 0 or g < 0:
+            continue
+        if g not in winner or d < int(cand_doc[winner[g]]):
+            winner[g] = m
+    kept = sorted((m for m in winner.values() if int(meta[m][0]) > 0), key=lambda m: int(cand_doc[m]))
+    out_doc = np.full(M, -1, np.int32); out_score = np.full(M, -np.inf); out_orig = np.zeros(M); out_chunk = np.full(M, -1, np.int32)
+    if not kept:
+        return (out_doc, out_score, out_orig, out_chunk, 0, 0) + (([], [], {}),) * return_stages
+    n_rows = [int(meta[m][0]) for m in kept]
+    assert max(n_rows) <= MAX_CHUNKS_PER_DOC
+    flat = [float(cos[m][j]) for m, r in zip(kept, n_rows) for j in range(r)]
+    docs = [int(cand_doc[m]) for m in kept]
+    pooled, st = chain_from_cosines(docs, n_rows, [float(cand_bm25[m]) for m in kept], flat, smoothing, max_boost, max_decay)
+    res = sorted(((s_, d, o_, int(meta[m][2]) + b_) for (d, s_, o_, b_), m in zip(pooled, kept)), key=lambda r: (-r[0], r[1]))
+    for r, (s_, d, o_, c_) in enumerate(res):
+        out_doc[r], out_score[r], out_orig[r], out_chunk[r] = d, s_, o_, c_
+    return (out_doc, out_score, out_orig, out_chunk, len(res), sum(n_rows)) + ((docs, n_rows, st),) * return_stages
 
 
 def rerank(urls, chunk_id, chunk_doc, emb, qvec, doc_ids, similarities, smoothing=0.15, top_k=100,

@@ -106,7 +106,7 @@ class OracleEngine:
         cos = np.zeros((Q, M, 10), np.float32); meta = np.zeros((Q, M, 3), np.int32)
         N = len(self.doc_off) - 1
         for i in range(Q):
-            for m in range(cn[i]):
+            for m in range(min(int(cn[i]), M)):
                 d = cand[i, m] - doc_base
                 if d < 0 or d >= N:
                     continue
@@ -185,32 +185,7 @@ class OracleEngine:
     def rerank_fuse(self, cand_doc_global, cand_bm25, cand_n, cos, meta, smoothing=0.15, max_boost=0.1,
                     max_decay=0.05, max_chunks=10):
         cand, bm, cn, cos, meta = map(_np, (cand_doc_global, cand_bm25, cand_n, cos, meta))
-        Q, M = cand.shape
-        out_doc = np.full((Q, M), -1, np.int32); out_score = np.full((Q, M), -np.inf); out_orig = np.zeros((Q, M))
-        out_chunk = np.full((Q, M), -1, np.int32); out_n = np.zeros(Q, np.int32); out_rows = np.zeros(Q, np.int32)
-        for i in range(Q):
-            best_of_group = {}
-            for m in range(cn[i]):
-                g = meta[i, m, 1] - 2
-                if cand[i, m] >= 0 and g >= 0:
-                    if g not in best_of_group or cand[i, m] < cand[i, best_of_group[g]]:
-                        best_of_group[g] = m
-            kept = sorted((m for m in best_of_group.values() if meta[i, m, 0] > 0), key=lambda m: cand[i, m])
-            if not kept:
-                continue
-            flat = [(m, j) for m in kept for j in range(meta[i, m, 0])]
-            new = rerank_ref.normalise([float(cos[i, m, j]) for m, j in flat])
-            old = rerank_ref.normalise([float(bm[i, m]) for m, _ in flat])
-            new = [a * (1 - smoothing) + b * smoothing for a, b in zip(new, old)]
-            res, p = [], 0
-            for m in kept:
-                n = int(meta[i, m, 0])
-                adj = rerank_ref.positional_adjust(new[p:p + n], n)
-                b = max(range(n), key=lambda t: (adj[t], -t))
-                res.append((-adj[b], int(cand[i, m]), adj[b], old[p + b], int(meta[i, m, 2]) + b))
-                p += n
-            res.sort()
-            for r, (_, d, s, o, c) in enumerate(res):
-                out_doc[i, r], out_score[i, r], out_orig[i, r], out_chunk[i, r] = d, s, o, c
-            out_n[i], out_rows[i] = len(res), len(flat)
-        return tuple(torch.as_tensor(x) for x in (out_doc, out_score, out_orig, out_chunk, out_n, out_rows))
+        out = [rerank_ref.fuse_from_gather(cand[i], bm[i], cn[i], cos[i], meta[i], smoothing, max_boost, max_decay)
+               for i in range(cand.shape[0])]
+        return tuple(torch.as_tensor(np.stack([o[k] for o in out]) if k < 4 else np.array([o[k] for o in out], np.int32))
+                     for k in range(6))

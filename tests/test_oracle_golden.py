@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import bm25_ref, build_ref, dense_ref, rerank_ref
+import rerank_cases
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -438,3 +439,33 @@ def test_encoder_restatement_pointwise_forms():
     assert torch.equal(pool[0], torch.zeros(4, dtype=torch.float64))
     assert torch.allclose(pool[1:], torch.nn.functional.normalize(torch.stack([h[:2].mean(0), h[2:].mean(0)]), dim=1))
     assert encoder_ref.positions([0, 3, 3, 5]).tolist() == [0, 1, 2, 0, 1]
+
+
+@pytest.mark.parametrize("f", rerank_cases.fixture_cases(), ids=lambda f: f"case{f['case']}")
+def test_rerank_chain_exact(f):
+    """chain_from_cosines on the reference's own f32 cosines (stage 0) gives every later stage of the fixture bit for bit:
+    the min-max, blend, positional weighting and pooling are the reference's float64 operations in the reference's order.
+    Pooled per document (the groupby stage) exactly; sorted, the scores exactly and each group of equal scores as a set
+    (the reference's quicksort leaves the order of equal scores open)."""
+    pooled, st = rerank_ref.chain_from_cosines(f["docs"], f["n_rows"], f["bm25"], f["cos"])
+    s = f["stages"]
+    assert st["cos_norm"] == s[1]["new_similarity"] and st["bm25_norm"] == s[2]["old_similarity"]
+    assert st["blend"] == s[3]["new_similarity"] and st["positional"] == s[5]["new_similarity"]
+    assert st["bm25_norm"] == s[5]["old_similarity"]
+    off = np.concatenate([[0], np.cumsum(f["n_rows"])])
+    per_doc = s[-2]                                          # idxmax per document, document order
+    assert per_doc["doc_id"] == [p[0] for p in pooled]
+    assert per_doc["new_similarity"] == [p[1] for p in pooled] and per_doc["old_similarity"] == [p[2] for p in pooled]
+    assert per_doc["chunk_id"] == [f["chunk_id"][off[i] + p[3]] for i, p in enumerate(pooled)]
+    ranked = s[-1]
+    mine = sorted(pooled, key=lambda p: (-p[1], p[0]))
+    assert ranked["new_similarity"] == [p[1] for p in mine]
+    key = lambda t: sorted(t)
+    groups = {}
+    for d, sc, o, ch in zip(ranked["doc_id"], ranked["new_similarity"], ranked["old_similarity"], ranked["chunk_id"]):
+        groups.setdefault(sc, []).append((d, o, ch))
+    mine_groups = {}
+    for p in mine:
+        j = f["docs"].index(p[0])
+        mine_groups.setdefault(p[1], []).append((p[0], p[2], f["chunk_id"][off[j] + p[3]]))
+    assert {k: key(v) for k, v in groups.items()} == {k: key(v) for k, v in mine_groups.items()}
