@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 4         /* 4: msr_unbind, msr_merge_postings */
+#define MSR_ABI_VERSION 5         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -368,6 +368,19 @@ int msr_merge_postings(const int64_t* a_term_off, int64_t a_terms, const int32_t
                        const int32_t* a_map, int64_t a_docs, const int64_t* b_term_off, int64_t b_terms, const int32_t* b_doc,
                        const int32_t* b_tf, const int32_t* b_map, int64_t b_docs, int64_t n_terms, int64_t n_docs,
                        int64_t* term_off, int32_t* post_doc, int32_t* post_tf, int64_t capacity, void* stream);
+
+/* Compaction of a CSR-by-term posting table (index update: documents removed from a built index; OFFLINE and handle-less
+ * like msr_build_postings: allocates its workspace and synchronises).  Input: term_off[n_terms + 1] i64, post_doc / post_tf
+ * i32 (documents ascending inside a term) and keep[n_docs] u8, nonzero = the document stays.  The new index of a kept
+ * document is the number of kept documents before it.  Writes out_term_off[n_terms + 1] = the kept postings before each
+ * term_off[t], and out_doc / out_tf: the kept postings in their order, out_doc renumbered, out_tf copied.  *n_postings
+ * [host] always receives the number of kept postings: call once with capacity 0 to size the arrays (that call writes
+ * nothing), then again.  MSR_ERR_INVALID, before anything is written: term_off not monotone from 0, a post_doc value
+ * outside [0, n_docs), or 0 < capacity < the kept count.  No atomics on the data path: the output is the same every run.
+ * All arrays are device pointers. */
+int msr_compact_postings(const int64_t* term_off, int64_t n_terms, const int32_t* post_doc, const int32_t* post_tf,
+                         const uint8_t* keep, int64_t n_docs, int64_t* out_term_off, int32_t* out_doc, int32_t* out_tf,
+                         int64_t capacity, int64_t* n_postings, void* stream);
 
 /* Timing hooks for bench.py: while enabled, every launch of the dominant kernels is bracketed by a
  * hipEvent pair recorded on the caller's stream (ring of 256 launches per kernel).  msr_kernel_time_ms

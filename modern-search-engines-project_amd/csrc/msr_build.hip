@@ -32,7 +32,7 @@ namespace {
 
 constexpr int CH = 4096;                 // tokens per chunk (16 KB of LDS)
 constexpr int RB = 4096;                 // entries per radix block
-constexpr int SB = 4096;                 // elements per scan block
+constexpr int SB = MSR_SCAN_BLOCK;       // elements per scan block
 
 #define BUILD_TRY(call)                                                                                      \
     do {                                                                                                     \
@@ -73,8 +73,10 @@ __global__ __launch_bounds__(1024) void scan_add_kernel(int64_t* __restrict__ ou
     for (int j = 0; j < 4; ++j)
         if (base + j < n) out[base + j] += add;
 }
-// out[0..n) = exclusive scan of in[0..n); tmp: >= 2 * ceil(n / SB) + 2 * ceil(n / SB^2) + 8 words.  *total (device,
-// nullable) <- sum of all elements.  Two levels: n <= SB^3.
+
+}  // namespace
+
+// declared in msr_internal.h (also used by msr_compact.hip)
 hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* tmp, int64_t* total, hipStream_t st) {
     if (n <= 0) {
         if (total) return hipMemsetAsync(total, 0, 8, st);
@@ -98,6 +100,8 @@ hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* t
     if (total) scan_total_kernel<<<1, 1, 0, st>>>(in, out, n, total);
     return hipGetLastError();
 }
+
+namespace {
 
 // ---- 1. per-chunk sort + run lengths -----------------------------------------------------------------------------
 // chunk c: tokens [c_start[c], c_start[c] + c_len[c]) of document c_doc[c].  WRITE = false: cnt[c] <- number of distinct

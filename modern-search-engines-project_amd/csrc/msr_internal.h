@@ -56,6 +56,13 @@ hipError_t msr_merge_lists(int score_bits, const int32_t* in_doc, const void* in
 // error text of handle-less entry points, read back with msr_last_error(NULL) (msr_engine.hip)
 int msr_fail_global(int code, const char* fmt, ...);
 
+// ---- K7: offline index build / update ----------------------------------------------------------------
+// out[0..n) = exclusive scan of in[0..n) (msr_build.hip: three kernels, MSR_SCAN_BLOCK elements per block); tmp: >=
+// 2 * ceil(n / MSR_SCAN_BLOCK) + 2 * ceil(n / MSR_SCAN_BLOCK^2) + 8 words.  *total (device, nullable) <- sum of all
+// elements.  Two levels: n <= MSR_SCAN_BLOCK^3.
+constexpr int MSR_SCAN_BLOCK = 4096;
+hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* tmp, int64_t* total, hipStream_t st);
+
 // ---- K1: BM25 term-at-a-time ----------------------------------------------------------------------
 // One posting as the scoring kernel streams it (engine-owned copy, built at bind): the document and the posting's
 // tf_component = (tf (k1 + 1)) / (tf + k1 (1 - b + b dl / avgdl)) (indexer/bm25_indexer.py:473-475), which depends on

@@ -326,3 +326,121 @@ def bm25_add_token_ids(ix, doc_ids, tok_off, tok_ids, n_terms, device="cpu", voc
             setattr(out, name, col)
     out.update_counts = dict(added=added, already_indexed=int(has_row.sum()), no_tokens=int((~has_row & (lens == 0)).sum()))
     return out
+
+
+def compact_postings(term_off, post_doc, post_tf, keep, device="cpu"):
+    """A CSR-by-term posting table without the postings of some documents (msr_compact_postings on a GPU device; a torch
+    restatement on the CPU, the reference the GPU tests compare against).  term_off int64 [n_terms + 1], post_doc / post_tf
+    int32 (documents ascending inside a term), keep [n_docs] (nonzero / True = the document stays).  A kept document's new
+    index is the number of kept documents before it.  Returns (term_off int64 [n_terms + 1], post_doc int32, post_tf int32)
+    tensors on `device`: the kept postings in their order, renumbered.  A term_off that is not monotone from 0 or a document
+    index outside [0, n_docs) raises (ValueError on the CPU, MsrError on the GPU)."""
+    import torch
+    dev = torch.device(device)
+    if dev.type == "cuda":
+        return _compact_postings_hip(term_off, post_doc, post_tf, keep, dev)
+    as_t = lambda x, dt: (x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x))).to(dev, dt)
+    off = as_t(term_off, torch.int64)
+    kp = as_t(keep, torch.bool)
+    if off.numel() == 0 or int(off[0]) != 0 or bool((off[1:] < off[:-1]).any()):
+        raise ValueError("term_off is not a monotone offset array from 0")
+    P = int(off[-1])
+    doc = as_t(post_doc, torch.int64)[:P]
+    tf = as_t(post_tf, torch.int32)[:P]
+    if doc.numel() and (int(doc.min()) < 0 or int(doc.max()) >= kp.numel()):
+        raise ValueError("a posting's document index is outside [0, n_docs)")
+    new = torch.cumsum(kp, 0) - kp.to(torch.int64)                          # kept documents before each document
+    kept = kp[doc]
+    before = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    before[1:] = torch.cumsum(kept, 0)
+    return before[off], new[doc[kept]].to(torch.int32), tf[kept]
+
+
+def _compact_postings_hip(term_off, post_doc, post_tf, keep, dev):
+    """compact_postings through the C ABI (msr_compact_postings); no fallback."""
+    import ctypes as C
+
+    import torch
+
+    from . import _abi
+    lib = _abi.load()
+    on_dev = lambda x, dt: (x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x))).to(dev, dt).contiguous()
+    off, doc, tf = on_dev(term_off, torch.int64), on_dev(post_doc, torch.int32), on_dev(post_tf, torch.int32)
+    kp = on_dev(keep, torch.bool).to(torch.uint8)
+    n_terms = int(off.numel()) - 1
+    out_off = torch.empty(n_terms + 1, dtype=torch.int64, device=dev)
+    n_post = C.c_int64(0)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+    P = int(off[-1].item()) if n_terms >= 0 else 0
+    if P > min(doc.numel(), tf.numel()):
+        raise ValueError(f"term_off[-1] = {P} postings, but post_doc / post_tf hold {min(doc.numel(), tf.numel())}")
+    # one call, sized by the input (the kept postings are at most P): no sizing call and no second counting pass
+    out_doc = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    out_tf = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _abi.check(None, lib.msr_compact_postings(ptr(off), n_terms, ptr(doc), ptr(tf), ptr(kp), int(kp.numel()), ptr(out_off),
+                                                  ptr(out_doc), ptr(out_tf), max(P, 1), C.byref(n_post), stream))
+    K = int(n_post.value)
+    return out_off, out_doc[:K], out_tf[:K]
+
+
+def remove_documents(ix, doc_ids, device="cpu"):
+    """A NEW CorpusIndex without the documents `doc_ids` (`ix` is left unchanged: an engine bound to it stays valid until it
+    rebinds).  The counterpart of bm25_add_token_ids; a document that changed is replaced by removing it and adding its new
+    version under the same doc_id.
+
+      * every listed document the index has goes, urlsDB-only documents (doc_len 0) included: from doc_ids / doc_len, the
+        postings (compact_postings: msr_compact_postings on a GPU device), the chunk rows (doc_off / chunk_ids / emb, gathered
+        on emb's own device), urls / titles / texts; the kept documents keep their order and are renumbered densely; the
+        URL groups are recomputed.
+      * total_docs -= the removed documents that had a BM25 row; avg_doc_length and the idf of EVERY term are recomputed
+        with the builders' float64 -> REAL rounding (n_terms stays: a term left without postings gets the idf a
+        from-scratch build gives it), so the tables equal a from-scratch build of the remaining documents bit for bit.
+      * ids the index does not have are counted, not raised; a duplicate id raises.  `update_counts` = dict(removed,
+        removed_rows, not_found).
+    A shard (doc_base != 0 or n_docs_global != n_docs) is refused: remove from the whole index, then shard it."""
+    import torch
+    from .index import _np
+    if ix.doc_base != 0 or (ix.n_docs_global and ix.n_docs_global != ix.n_docs):
+        raise ValueError("remove_documents: the index is a shard; remove from the whole index, then shard it (CorpusIndex.shard)")
+    dev = torch.device(device)
+    ids = np.asarray(_np(doc_ids), np.int64).reshape(-1)
+    if len(np.unique(ids)) != len(ids):
+        raise ValueError("duplicate doc_id")
+    old_ids = np.asarray(_np(ix.doc_ids), np.int64)
+    N = len(old_ids)
+    pos = np.minimum(np.searchsorted(old_ids, ids), max(N - 1, 0))
+    found = (old_ids[pos] == ids) if N else np.zeros(len(ids), bool)
+    keep = np.ones(N, bool)
+    keep[pos[found]] = False
+    old_len = None if ix.doc_len is None else np.asarray(_np(ix.doc_len), np.int32)
+    removed_rows = int((old_len[~keep] > 0).sum()) if old_len is not None else 0
+    out = CorpusIndex(doc_ids=old_ids[keep], avgdl=ix.avgdl, total_docs=int(ix.total_docs) - removed_rows, k1=ix.k1, b=ix.b,
+                      vocab=ix.vocab)
+    out.n_docs_global = out.n_docs
+    if old_len is not None:
+        doc_len = old_len[keep]
+        rows = doc_len[doc_len > 0]
+        out.avgdl = float(np.float32(rows.astype(np.float64).mean())) if len(rows) else 0.0
+        out.doc_len = torch.as_tensor(doc_len).to(dev)
+    if ix.term_off is not None:
+        out.term_off, out.post_doc, out.post_tf = compact_postings(ix.term_off, ix.post_doc, ix.post_tf, keep, device=dev)
+        out.idf = torch.as_tensor(idf_real(out.total_docs, np.diff(np.asarray(_np(out.term_off), np.int64)))).to(dev)
+    if ix.doc_off is not None:
+        cnt = np.diff(np.asarray(_np(ix.doc_off), np.int64))
+        doc_off = np.concatenate([[0], np.cumsum(cnt[keep])]).astype(np.int32)
+        out.doc_off = torch.as_tensor(doc_off).to(ix.doc_off.device) if torch.is_tensor(ix.doc_off) else doc_off
+        rows = np.repeat(keep, cnt)
+        if ix.chunk_ids is not None:
+            out.chunk_ids = np.asarray(_np(ix.chunk_ids), np.int64)[rows]
+        if torch.is_tensor(ix.emb):
+            out.emb = ix.emb.index_select(0, torch.as_tensor(np.nonzero(rows)[0], device=ix.emb.device))
+        elif ix.emb is not None:
+            out.emb = np.asarray(ix.emb)[rows]
+    for name in ("urls", "titles", "texts"):
+        col = getattr(ix, name)
+        if col is not None:
+            setattr(out, name, [v for v, k in zip(col, keep.tolist()) if k])
+    out.update_counts = dict(removed=int(found.sum()), removed_rows=removed_rows, not_found=int((~found).sum()))
+    return out

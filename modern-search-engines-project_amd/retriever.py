@@ -46,7 +46,8 @@ class Retriever:
             gc.freeze()
 
     def update_index(self, ix: CorpusIndex):
-        """Serve `ix` from now on (an index grown by index_build.bm25_add_token_ids + chunk_index.attach_chunks): the engine
+        """Serve `ix` from now on (an index grown by index_build.bm25_add_token_ids + chunk_index.attach_chunks, shrunk by
+        index_build.remove_documents, or both -- a replace): the engine
         rebinds (DeviceEngine.rebind), and everything copied from the old index is refreshed -- the id map, the domain table,
         the line formatter, the per-chunk engine of return_unique_docs=False (closed; rebuilt on first use), the BM25 and
         Reranker facades."""

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Time adding documents to a built index (index_build.bm25_add_token_ids, msr_merge_postings, DeviceEngine.rebind).
+"""Time adding documents to and removing them from a built index (index_build.bm25_add_token_ids, msr_merge_postings,
+index_build.remove_documents, msr_compact_postings, DeviceEngine.rebind).
 
-    python tools/index_update_bench.py [--rows build,merge,rebind] [--reps 5]
+    python tools/index_update_bench.py [--rows build,merge,rebind,remove] [--reps 5]
 
-Three rows, one JSON line each:
+Four rows, one JSON line each (remove: one per pattern):
   build   the build_index_bench.py corpus (200 k documents, 200 k terms) plus 2 k / 20 k new documents (ids above the old ones):
           the whole update on the GPU and its parts -- the new documents' tables (msr_build_postings), the merge, the host idf.
   merge   the headline shape: a 1 M-document index of ~2.35e8 postings (synthetic.synthetic_corpus) plus 1 % new documents
@@ -13,6 +14,11 @@ Three rows, one JSON line each:
   rebind  a 200 k-document index with 1 M chunk rows bound to a DeviceEngine(max_queries=256), grown by 2 k documents and
           their chunks: rebind split into postings and chunks (the chunk bind includes the fragment-order copy), and the
           device memory in use before and after (both indices resident).
+  remove  the merge row's index (the same seed: ~2.37e8 postings) with 5 M chunk rows; 1 % of the documents removed, scattered
+          and as one contiguous block: the msr_compact_postings call with the bytes it must move (the counting pass reads
+          doc, the write pass reads doc + tf and writes the kept doc + tf, term_off read and written), the whole
+          remove_documents, its chunk-row gather alone (index_select of the kept rows: read + write), and the rebind of a
+          DeviceEngine(max_queries=256) from the old index to the new one.
 """
 import argparse
 import json
@@ -24,7 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from msretr.index_build import bm25_add_token_ids, bm25_index_from_token_ids, idf_real, merge_postings  # noqa: E402
+from msretr.index_build import (bm25_add_token_ids, bm25_index_from_token_ids, compact_postings, idf_real,  # noqa: E402
+                                merge_postings, remove_documents)
 
 
 def sync_time(fn, reps):
@@ -142,12 +149,55 @@ def row_rebind(reps):
     eng.close()
 
 
+def row_remove(reps):
+    from msretr.engine import DeviceEngine
+    from msretr.index import _np
+    from msretr.synthetic import synthetic_corpus
+    a = synthetic_corpus(1_000_000, n_chunks=5_000_000, device="cuda", seed=5)    # postings: the merge row's A
+    N, V, P = a.n_docs, a.n_terms, int(a.post_doc.numel())
+    ids = np.asarray(_np(a.doc_ids))
+    cnt = np.diff(np.asarray(_np(a.doc_off), np.int64))
+    eng = DeviceEngine(a, max_queries=256)
+    rng = np.random.default_rng(9)
+    for pattern in ("scattered", "block"):
+        gone = np.sort(rng.choice(N, N // 100, replace=False)) if pattern == "scattered" else np.arange(N // 2, N // 2 + N // 100)
+        keep = np.ones(N, bool)
+        keep[gone] = False
+        kt = torch.as_tensor(keep, device="cuda")
+        out, t_call = sync_time(lambda: compact_postings(a.term_off, a.post_doc, a.post_tf, kt, device="cuda"), reps)
+        K = int(out[1].numel())
+        moved = 4 * P + 8 * P + 8 * K + 8 * 2 * (V + 1)
+        del out
+        new, t_all = sync_time(lambda: remove_documents(a, ids[gone], device="cuda"), reps)
+        rows = torch.as_tensor(np.nonzero(np.repeat(keep, cnt))[0], device="cuda")
+        _, t_gather = sync_time(lambda: a.emb.index_select(0, rows), reps)
+        gather_bytes = 2 * int(rows.numel()) * 768 * 4
+        t_rebind = []
+        for _ in range(max(1, min(reps, 3))):
+            eng.rebind(a)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            eng.rebind(new)
+            torch.cuda.synchronize()
+            t_rebind.append(time.perf_counter() - t)
+        eng.rebind(a)
+        print(json.dumps({"row": "remove", "pattern": pattern, "docs": N, "removed_docs": len(gone), "postings": P, "kept_postings": K,
+                          "terms": V, "chunks": a.n_chunks, "kept_chunks": int(rows.numel()), "call_ms": round(t_call, 3),
+                          "bytes_moved": moved, "call_effective_TBps": round(moved / (t_call * 1e-3) / 1e12, 3),
+                          "remove_documents_ms": round(t_all, 2), "chunk_gather_ms": round(t_gather, 2),
+                          "chunk_gather_TBps": round(gather_bytes / (t_gather * 1e-3) / 1e12, 3),
+                          "rest_ms": round(t_all - t_call - t_gather, 2), "rebind_ms": round(float(np.median(t_rebind)) * 1e3, 1),
+                          "row_copy": eng.row_copy_state()}), flush=True)
+        del new
+    eng.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", default="build,merge,rebind")
+    ap.add_argument("--rows", default="build,merge,rebind,remove")
     ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("index_update_bench.py needs a GPU")
     for r in args.rows.split(","):
-        {"build": row_build, "merge": row_merge, "rebind": row_rebind}[r](args.reps)
+        {"build": row_build, "merge": row_merge, "rebind": row_rebind, "remove": row_remove}[r](args.reps)
