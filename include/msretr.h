@@ -6,6 +6,7 @@
  * call site would bind (see INTEGRATION.md for the ctypes stubs):
  *
  *   msr_bm25_topk   <- BM25.search scoring loop + sort + cut      indexer/bm25_indexer.py:434-488
+ *     (+ _within: the same restricted to document sets, e.g. a site: search; no reference counterpart)
  *   msr_dense_topk  <- Retriever.quick_search (dense full scan)   search_api.py:60,87 (retriever.py absent;
  *                      cosine reranker/reranker_api.py:285, per-doc max :370, report p.2)
  *   msr_rerank      <- /rerank endpoint arithmetic                reranker/reranker_api.py:27-63,273-334,357-372
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 5         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings */
+#define MSR_ABI_VERSION 6         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -170,6 +171,23 @@ int msr_bm25_topk(msr_engine* e, const int32_t* q_term_off, const int32_t* q_ter
                   int32_t n_queries, int32_t k, double min_score, int32_t* out_doc, double* out_score,
                   int32_t* out_n, void* stream);
 
+/* Document sets (restriction of a query to part of the corpus).  A set is a bitset of
+ * uint32 words: document d is bit d & 31 of word d >> 5.  set_bits holds n_sets such rows, set_stride words apart
+ * (set_stride >= ceil(n_docs / 32); bits at or above n_docs are ignored).  q_set[n_queries] (int32) picks query q's row;
+ * -1 = unrestricted; any other value outside [0, n_sets) = the empty set (no row outside the n_sets rows is read).
+ * n_sets == 0 is the unrestricted call (set_bits / q_set are not read).  Refused with MSR_ERR_INVALID, outputs untouched:
+ * n_sets < 0; set_bits or q_set NULL while n_sets > 0; set_stride < ceil(n_docs / 32) while n_sets > 0.
+ *
+ * msr_bm25_topk_within: row q holds the first k entries, in msr_bm25_topk's order, of the documents of query q's set that
+ *   msr_bm25_topk's rule accepts (touched by a posting, score >= min_score), with msr_bm25_topk's scores bit for bit: idf and
+ *   avgdl stay those of the whole bound index (a set is not a sub-corpus).  out_n[q] may be below k; the rest of the row is
+ *   -1 / -inf.  The set acts where the candidates are emitted (inside the scoring kernel), so the documents of the set
+ *   ranked behind the whole corpus's top k are found.  Cost: that of msr_bm25_topk (one bit load per candidate). */
+int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
+                         int32_t n_queries, int32_t k, double min_score,
+                         const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
+                         int32_t* out_doc, double* out_score, int32_t* out_n, void* stream);
+
 /* Dense full scan for Q queries: score(d) = max over the document's first `max_chunks_per_doc` chunks
  * (0 = all) of cosine(q, chunk), cosine as sklearn computes it in float32 (reranker_api.py:285), to within the
  * 1e-5 tolerance of the task (see msr_scan_arith for the arithmetic actually used).
@@ -177,6 +195,18 @@ int msr_bm25_topk(msr_engine* e, const int32_t* q_term_off, const int32_t* q_ter
  * with float32 scores and out_chunk = row index of the arg-max chunk (first maximum). */
 int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc,
                    int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream);
+
+/* msr_dense_topk restricted to document sets (encoding and refusals: msr_bm25_topk_within).  Every query of a restricted call
+ * runs on the SWEEPS -- the kernels an unrestricted call of <= 64 queries runs (K-split 64 / narrow 32 queries per pass over
+ * the matrix, msr_scan_arith's arithmetic, msr_dense_path() = 64 or 32) --, whatever n_queries: not the 256-query streaming
+ * pass, so the scores are the sweep's (|error| <= 8e-6 with the f16-split products), not exact-f32 rescored ones.  Row q is the
+ * top k of query q's set by the per-document maximum cosine, same order, ties, chunk rows and max_chunks_per_doc as
+ * msr_dense_topk; documents outside the set never enter the select.  A cosine does not depend on other documents: with the
+ * same sweep kernel the result equals msr_dense_topk over the index without the documents outside the set, bit for bit.
+ * Cost: one sweep per 64 queries (~4.5 x the per-query cost of the 256-query pass at 5 M chunks). */
+int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc,
+                          const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
+                          int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream);
 
 /* msr_dense_topk in two halves, for a doc-sharded index: between them the caller exchanges ONE float per query across the
  * shards (msretr/distributed.py: an all-reduce MIN over RCCL), after which every shard rescores only the documents that can

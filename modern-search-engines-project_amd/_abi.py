@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 5
+MSR_ABI_VERSION = 6
 MSR_CFG_NO_ROW_COPY = 1
 MSR_DIM = 768
 MSR_MAX_K = 1024
@@ -60,6 +60,10 @@ _SIGNATURES = {
     "msr_interleave_rows": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
     "msr_bm25_topk": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P]),
     "msr_dense_topk": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "msr_bm25_topk_within": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_double, _P, C.c_int32, C.c_int64, _P, _P, _P,
+                                       _P, _P]),
+    "msr_dense_topk_within": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P,
+                                        _P]),
     "msr_dense_split_max": (C.c_int, [_P, C.c_int32]),
     "msr_dense_topk_begin": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "msr_dense_topk_end": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),

@@ -32,24 +32,25 @@ class BM25:
         self._pos = None
 
     # -- engine-level entry points (usable without spaCy: pre-tokenised terms or term ids) ----------
-    def search_terms(self, terms: Sequence[Union[str, int]], top_k: int = 1000, min_score: float = 0.0):
-        return self.search_terms_batch([terms], top_k, min_score)[0]
+    def search_terms(self, terms: Sequence[Union[str, int]], top_k: int = 1000, min_score: float = 0.0, within=None):
+        return self.search_terms_batch([terms], top_k, min_score, within=within)[0]
 
-    def search_terms_batch(self, term_lists, top_k: int = 1000, min_score: float = 0.0):
-        """-> per query: list of (doc_id, score) in rank order (before the urlsDB join)."""
+    def search_terms_batch(self, term_lists, top_k: int = 1000, min_score: float = 0.0, within=None):
+        """-> per query: list of (doc_id, score) in rank order (before the urlsDB join).  within: None, a DocSet (every query)
+        or a list of DocSet / None per query -- the top_k of the documents in the set (docset.py)."""
         ids = [self.index.term_ids(t) for t in term_lists]
-        doc, score, n = self.engine.bm25_topk(ids, k=top_k, min_score=min_score)
+        doc, score, n = self.engine.bm25_topk(ids, k=top_k, min_score=min_score, within=within)
         doc, score, n = doc.cpu().numpy(), score.cpu().numpy(), n.cpu().numpy()
         doc_ids = self.index.doc_ids
         doc_ids = doc_ids.cpu().numpy() if hasattr(doc_ids, "cpu") else doc_ids
         return [[(int(doc_ids[d]), float(s)) for d, s in zip(doc[q, :n[q]], score[q, :n[q]])] for q in range(len(ids))]
 
     # -- the reference's method ------------------------------------------------------------------------
-    def search(self, query: str, top_k: int = 1000, min_score: float = 0.0):
+    def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None):
         query_terms = self._tokenize(query)
         if not query_terms:
             return []                                              # bm25_indexer.py:396-397
-        return self._finish(self.search_terms(query_terms, top_k, min_score))
+        return self._finish(self.search_terms(query_terms, top_k, min_score, within=within))
 
     def _finish(self, ranked):
         """urlsDB join after the cut: documents without a row are dropped, snippet = title + 200 chars

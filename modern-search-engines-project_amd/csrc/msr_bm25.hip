@@ -79,6 +79,9 @@ enum : int { K_DEAD = 0, K_LOOKUP = 1, K_HEAVY = 2, K_RANGE = 3 };
 #ifndef BM25_WPE
 #define BM25_WPE 4                                             // waves per SIMD the register budget is cut for
 #endif
+// Set: empty (the unrestricted kernel) or one MsrSetView (msr_bm25_topk_within): a touched document outside the query's set is
+// not emitted.  Only the emission at the end of a tile differs; the scores are the same operations either way.
+template <typename... Set>
 __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM25_WPE, BM25_WPE))) void bm25_taat_kernel(Bm25Index ix,
                                                                   const int32_t* __restrict__ q_term_off,
                                                                   const int32_t* __restrict__ q_terms,
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
                                                                   int q_first, int nq, double min_score, int tpw, int n_spans,
                                                                   double* __restrict__ cand_score,
                                                                   int32_t* __restrict__ cand_doc,
-                                                                  int32_t* __restrict__ seg_n, int dbg_arg) {
+                                                                  int32_t* __restrict__ seg_n, int dbg_arg, Set... set) {
 #ifdef MSR_DIAG
     const int dbg = dbg_arg;   // timing experiments (wrong results): 1 no table lookups, 2 no accumulator update, 4 no streaming
                                // beyond the prefetch, 8 no prefetch, 16 no emission, 64 stream every list (no pruning)
@@ -107,6 +110,15 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
     // with an atomic; the segment's length is written once, at the end.
     int32_t* seg_len = seg_n + (int64_t)q * n_spans + span;
     int seg_cnt = 0;
+    constexpr bool WITHIN = sizeof...(Set) > 0;
+    MsrSetRow srow{nullptr, 0};                                // the query's set (wave-uniform: one query per wave)
+    if constexpr (WITHIN) {
+        srow = msr_set_row(q_first + q, set...);
+        if (srow.mode == 2) {                                  // the empty set: no candidate
+            if (lane == 0) *seg_len = 0;
+            return;
+        }
+    }
     const int tile0 = span * tpw;                              // this wave's tiles: tile0 .. tile0 + n_my - 1
     const int n_my = tile0 + tpw <= ix.n_tiles ? tpw : ix.n_tiles - tile0;
     double* acc = acc_all[wave];
@@ -379,7 +391,10 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
             const bool in = e < list_n;
             const uint32_t d = list[in ? e : 0];
             const double sc = acc[d];
-            const bool keep = in && sc >= min_score && !(dbg & 16);
+            bool keep = in && sc >= min_score && !(dbg & 16);
+            if constexpr (WITHIN) {                          // one 32-bit load per candidate from a row that stays in the L2
+                if (keep) keep = msr_in_set(srow, lo + d);
+            }
             const unsigned long long km = __ballot(keep);
             if (keep) {
                 const int64_t w = seg_base + seg_cnt + lane_rank(km);
@@ -576,7 +591,8 @@ hipError_t msr_bm25_window(const Bm25Index& ix, const int32_t* q_term_off, const
 
 hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms,
                            const int32_t* q_qtf, int q_first, int nq, double min_score, double* cand_score,
-                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream) {
+                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream,
+                           const MsrSetView* set) {
     *n_seg = 0; *seg_stride = 0;
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
     // A wave looks its query's terms up once and then walks `tpw` consecutive tiles with that plan in registers.  More tiles
@@ -589,7 +605,12 @@ hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const
     if (items >= (1ll << 31)) return hipErrorInvalidValue;
     *n_seg = n_spans;
     *seg_stride = (int64_t)tpw * BM25_TILE;
-    bm25_taat_kernel<<<(unsigned)((items + BM25_WAVES - 1) / BM25_WAVES), BM25_THREADS, 0, stream>>>(
-        ix, q_term_off, q_terms, q_qtf, q_first, nq, min_score, tpw, n_spans, cand_score, cand_doc, seg_n, g_bm25_dbg);
+    const unsigned blocks = (unsigned)((items + BM25_WAVES - 1) / BM25_WAVES);
+    if (set)
+        bm25_taat_kernel<<<blocks, BM25_THREADS, 0, stream>>>(ix, q_term_off, q_terms, q_qtf, q_first, nq, min_score, tpw, n_spans,
+                                                              cand_score, cand_doc, seg_n, g_bm25_dbg, *set);
+    else
+        bm25_taat_kernel<<<blocks, BM25_THREADS, 0, stream>>>(ix, q_term_off, q_terms, q_qtf, q_first, nq, min_score, tpw, n_spans,
+                                                              cand_score, cand_doc, seg_n, g_bm25_dbg);
     return hipGetLastError();
 }

@@ -806,14 +806,33 @@ extern "C" int msr_kernel_time_ms(msr_engine* e, int32_t which, float* out_ms, i
     return MSR_OK;
 }
 
-extern "C" int msr_bm25_topk(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
-                             int32_t n_queries, int32_t k, double min_score, int32_t* out_doc, double* out_score,
-                             int32_t* out_n, void* stream) {
+// Document sets of a *_within call: refused as the header says, before anything is launched (outputs untouched).
+static int within_args_ok(msr_engine* e, const char* fn, int64_t n_docs, const uint32_t* set_bits, int32_t n_sets,
+                          int64_t set_stride, const int32_t* q_set) {
+    if (n_sets < 0) return fail(e, MSR_ERR_INVALID, "%s: bad argument (n_sets=%d)", fn, n_sets);
+    if (n_sets == 0) return MSR_OK;
+    if (!set_bits || !q_set) return fail(e, MSR_ERR_INVALID, "%s: bad argument (set_bits or q_set is NULL with n_sets=%d)", fn, n_sets);
+    if (set_stride < (n_docs + 31) / 32)
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (set_stride=%lld < ceil(n_docs / 32) = %lld)", fn, (long long)set_stride,
+                    (long long)((n_docs + 31) / 32));
+    return MSR_OK;
+}
+
+static int bm25_topk_impl(msr_engine* e, const char* fn, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
+                          int32_t n_queries, int32_t k, double min_score, int32_t* out_doc, double* out_score, int32_t* out_n,
+                          void* stream, const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_bm25_topk: postings not bound");
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "%s: postings not bound", fn);
     if (n_queries < 0 || k < 1 || k > e->cfg.max_k || !q_term_off || !out_doc || !out_score || !out_n)
-        return fail(e, MSR_ERR_INVALID, "msr_bm25_topk: bad argument (k=%d, max_k=%d)", k, e->cfg.max_k);
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (k=%d, max_k=%d)", fn, k, e->cfg.max_k);
+    {
+        const int rc = within_args_ok(e, fn, e->bm25.n_docs, set_bits, n_sets, set_stride, q_set);
+        if (rc) return rc;
+    }
     if (n_queries == 0) return MSR_OK;
+    // n_sets > 0: the restricted scoring kernel (q_set indexed by the call's query number); the select is the same
+    const MsrSetView set_view{set_bits, set_stride, q_set, n_sets};
+    const MsrSetView* set = n_sets > 0 ? &set_view : nullptr;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     const int slice = e->cfg.max_queries;
@@ -828,7 +847,7 @@ extern "C" int msr_bm25_topk(msr_engine* e, const int32_t* q_term_off, const int
         int64_t seg_stride = 0;
         if (timed) HIP_TRY(e, hipEventRecord(e->ev_start[1][e->ev_count[1]], st));
         HIP_TRY(e, msr_bm25_scores(e->bm25, q_term_off, q_terms, q_qtf, q0, nq, min_score, (double*)e->score_rows, e->bm_cand_doc,
-                                   e->bm_cand_n, &n_seg, &seg_stride, st));
+                                   e->bm_cand_n, &n_seg, &seg_stride, st, set));
         if (timed) {
             HIP_TRY(e, hipEventRecord(e->ev_stop[1][e->ev_count[1]], st));
             e->ev_count[1]++;
@@ -844,6 +863,21 @@ extern "C" int msr_bm25_topk(msr_engine* e, const int32_t* q_term_off, const int
                                         e->sel, o_doc, o_score, out_n + q0, st, win));
     }
     return MSR_OK;
+}
+
+extern "C" int msr_bm25_topk(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
+                             int32_t n_queries, int32_t k, double min_score, int32_t* out_doc, double* out_score,
+                             int32_t* out_n, void* stream) {
+    return bm25_topk_impl(e, "msr_bm25_topk", q_term_off, q_terms, q_qtf, n_queries, k, min_score, out_doc, out_score, out_n,
+                          stream, nullptr, 0, 0, nullptr);
+}
+
+extern "C" int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
+                                    int32_t n_queries, int32_t k, double min_score, const uint32_t* set_bits, int32_t n_sets,
+                                    int64_t set_stride, const int32_t* q_set, int32_t* out_doc, double* out_score,
+                                    int32_t* out_n, void* stream) {
+    return bm25_topk_impl(e, "msr_bm25_topk_within", q_term_off, q_terms, q_qtf, n_queries, k, min_score, out_doc, out_score,
+                          out_n, stream, set_bits, n_sets, set_stride, q_set);
 }
 
 // A query whose entries overflowed in the streaming pass (huge tie groups, a zero vector) raised the gate word of its 64-query
@@ -864,10 +898,16 @@ static int dense_gated_fallback(msr_engine* e, int nq, int k, int32_t* out_doc, 
     return MSR_OK;
 }
 
+// Which sweep msr_dense_topk's <= 64-query slices run: true = the K-split kernel (64 queries per pass), false = the narrow
+// kernel (32).  msr_dense_topk_within takes the same decision, so a restricted call sweeps with the kernel an unrestricted
+// call of <= 64 queries would run (its bit-for-bit contract).
+static bool dense_sweep_wide(const msr_engine* e, int max_chunks_per_doc) {
+    return (e->dense.variant == 2 || e->dense.variant == 14 || e->dense.variant == 15) && e->dense.layout == 0 &&
+           e->dense.wide_ok && max_chunks_per_doc == 0;
+}
+
 static bool dense_stream_ok(const msr_engine* e, int k) {
-    const bool wide = (e->dense.variant == 2 || e->dense.variant == 14 || e->dense.variant == 15) && e->dense.layout == 0 &&
-                      e->dense.wide_ok;
-    return wide && e->gf_ok && e->dense.variant == 14 && e->gf.n_tiles >= 2 * k;
+    return dense_sweep_wide(e, 0) && e->gf_ok && e->dense.variant == 14 && e->gf.n_tiles >= 2 * k;
 }
 
 extern "C" int msr_dense_split_max(const msr_engine* e, int32_t k) {
@@ -916,6 +956,48 @@ extern "C" int msr_dense_topk_end(msr_engine* e, int32_t n_queries, int32_t k, c
     return dense_gated_fallback(e, n_queries, k, out_doc, out_score, out_chunk, out_n, st);
 }
 
+// The sweeps of msr_dense_topk for queries [q0, q0 + cnt): one pass over the matrix per `wide ? 64 : 32` queries (msr_dense_scan:
+// K-split or narrow kernel), the select of each slice, its best-chunk rows.  `gate` non-null = fallback launches that only do
+// work when *gate != 0.  `set` non-null (msr_dense_topk_within; set->q_set indexed by the call's query number): the restricted
+// select -- the sweep kernels and the best-chunk pass are the same.
+static int dense_sweeps(msr_engine* e, const float* q, int q0, int cnt, int k, int max_chunks_per_doc, bool wide, const int32_t* gate,
+                        int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, hipStream_t st,
+                        const MsrSetView* set) {
+    const int64_t N = e->dense.n_docs;
+    const int slice = wide ? 64 : 32;
+    DenseIndex ix = e->dense;
+    SelScratch sel = e->sel;
+    for (int s0 = q0; s0 < q0 + cnt; s0 += slice) {
+        const int nq = std::min(slice, q0 + cnt - s0);
+        // gated fallback: one gate word per slice of 64 queries (the streaming path raises the gates of the slices that
+        // hold an overflowed query)
+        ix.gate = sel.gate = gate ? gate + (s0 - q0) / 64 : nullptr;
+        // zero rows up to the query-block count of the kernel that runs (1, 2 or 4 blocks of 16)
+        const int nq_pad = nq > 32 ? 64 : (nq > 16 || (wide && e->dense.variant >= 14)) ? 32 : 16;
+        const bool timed = !gate && e->timing && e->ev_count[0] < msr_engine::EV_RING;
+        HIP_TRY(e, msr_prep_queries(q + (int64_t)s0 * MSR_DIM, nq, e->qn, nq_pad, st));
+        if (timed) HIP_TRY(e, hipEventRecord(e->ev_start[0][e->ev_count[0]], st));
+        HIP_TRY(e, msr_dense_scan(ix, e->qn, nq, max_chunks_per_doc, (float*)e->score_rows, st));
+        if (timed) {
+            HIP_TRY(e, hipEventRecord(e->ev_stop[0][e->ev_count[0]], st));
+            e->ev_count[0]++;
+        }
+        if (set) {
+            MsrSetView sv = *set;
+            sv.q_set += s0;                                      // (the select numbers the slice's queries from 0)
+            HIP_TRY(e, msr_select_topk_within((const float*)e->score_rows, N, e->dense.score_stride, nq, k, sel, sv,
+                                              out_doc + (int64_t)s0 * k, out_score + (int64_t)s0 * k, out_n + s0, st));
+        } else {
+            HIP_TRY(e, msr_select_topk(32, e->score_rows, N, e->dense.score_stride, nq, k, sel, out_doc + (int64_t)s0 * k,
+                                       out_score + (int64_t)s0 * k, out_n + s0, st));
+        }
+        if (out_chunk)
+            HIP_TRY(e, msr_best_chunk(ix, e->qn, nq, k, max_chunks_per_doc, out_doc + (int64_t)s0 * k,
+                                      out_n + s0, out_chunk + (int64_t)s0 * k, st));
+    }
+    return MSR_OK;
+}
+
 extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc,
                               int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
@@ -929,39 +1011,9 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     // one sweep of E serves up to 32 queries (wave-streaming kernel) or 64 (K-split kernel); batches of more than 64
     // queries run as a GEMM over the f32 rows, 128 queries per pass (msr_gemm_f32.hip), when the corpus allows it
-    const bool wide = (e->dense.variant == 2 || e->dense.variant == 14 || e->dense.variant == 15) && e->dense.layout == 0 &&
-                      e->dense.wide_ok && max_chunks_per_doc == 0;
+    const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
     const bool gemm = wide && e->gf_ok && e->dense.variant == 14 && e->gf.n_tiles >= 2 * k;
-    const int64_t N = e->dense.n_docs;
     e->last_dense_width = gemm && n_queries > 64 ? 0 : (wide ? 64 : 32);       // (the streaming path reports its own width below)
-    // sweeps for queries [q0, q0 + cnt): `gate` non-null = fallback launches that only do work when *gate != 0
-    auto sweeps = [&](int q0, int cnt, const int32_t* gate) -> int {
-        const int slice = wide ? 64 : 32;
-        DenseIndex ix = e->dense;
-        SelScratch sel = e->sel;
-        for (int s0 = q0; s0 < q0 + cnt; s0 += slice) {
-            const int nq = std::min(slice, q0 + cnt - s0);
-            // gated fallback: one gate word per slice of 64 queries (the streaming path raises the gates of the slices that
-            // hold an overflowed query)
-            ix.gate = sel.gate = gate ? gate + (s0 - q0) / 64 : nullptr;
-            // zero rows up to the query-block count of the kernel that runs (1, 2 or 4 blocks of 16)
-            const int nq_pad = nq > 32 ? 64 : (nq > 16 || (wide && e->dense.variant >= 14)) ? 32 : 16;
-            const bool timed = !gate && e->timing && e->ev_count[0] < msr_engine::EV_RING;
-            HIP_TRY(e, msr_prep_queries(q + (int64_t)s0 * MSR_DIM, nq, e->qn, nq_pad, st));
-            if (timed) HIP_TRY(e, hipEventRecord(e->ev_start[0][e->ev_count[0]], st));
-            HIP_TRY(e, msr_dense_scan(ix, e->qn, nq, max_chunks_per_doc, (float*)e->score_rows, st));
-            if (timed) {
-                HIP_TRY(e, hipEventRecord(e->ev_stop[0][e->ev_count[0]], st));
-                e->ev_count[0]++;
-            }
-            HIP_TRY(e, msr_select_topk(32, e->score_rows, N, e->dense.score_stride, nq, k, sel, out_doc + (int64_t)s0 * k,
-                                       out_score + (int64_t)s0 * k, out_n + s0, st));
-            if (out_chunk)
-                HIP_TRY(e, msr_best_chunk(ix, e->qn, nq, k, max_chunks_per_doc, out_doc + (int64_t)s0 * k,
-                                          out_n + s0, out_chunk + (int64_t)s0 * k, st));
-        }
-        return MSR_OK;
-    };
     int q0 = 0;
     while (q0 < n_queries) {
         const int left = n_queries - q0;
@@ -992,12 +1044,38 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
             q0 += nq;
         } else {
             const int nq = std::min(wide ? 64 : 32, left);
-            int rc = sweeps(q0, nq, nullptr);
+            int rc = dense_sweeps(e, q, q0, nq, k, max_chunks_per_doc, wide, nullptr, out_doc, out_score, out_chunk, out_n, st,
+                                  nullptr);
             if (rc) return rc;
             q0 += nq;
         }
     }
     return MSR_OK;
+}
+
+extern "C" int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc,
+                                     const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
+                                     int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk_within: chunks not bound");
+    if (e->split_pending)
+        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_within: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first");
+    if (n_queries < 0 || k < 1 || k > e->cfg.max_k || max_chunks_per_doc < 0 || !q || !out_doc || !out_score || !out_n)
+        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_within: bad argument (k=%d, max_k=%d)", k, e->cfg.max_k);
+    {
+        const int rc = within_args_ok(e, "msr_dense_topk_within", e->dense.n_docs, set_bits, n_sets, set_stride, q_set);
+        if (rc) return rc;
+    }
+    if (n_sets == 0)                                             // the unrestricted call
+        return msr_dense_topk(e, q, n_queries, k, max_chunks_per_doc, out_doc, out_score, out_chunk, out_n, stream);
+    if (n_queries == 0) return MSR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    // every query on the sweeps (the kernels an unrestricted call of <= 64 queries runs), the restriction in the select
+    const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
+    e->last_dense_width = wide ? 64 : 32;
+    const MsrSetView set{set_bits, set_stride, q_set, n_sets};
+    return dense_sweeps(e, q, 0, n_queries, k, max_chunks_per_doc, wide, nullptr, out_doc, out_score, out_chunk, out_n, st, &set);
 }
 
 static int rerank_args_ok(msr_engine* e, const char* fn, int32_t n_queries, int32_t max_cand, int32_t max_chunks) {

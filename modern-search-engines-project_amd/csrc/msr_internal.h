@@ -29,12 +29,40 @@ struct SelScratch {
                          // 64-query slices of which only some need the fallback)
 };
 
+// ---- document sets (msr_bm25_topk_within / msr_dense_topk_within) ---------------------------------
+// n_sets bitset rows `stride` words apart: document d is bit d & 31 of word d >> 5 of a row.  q_set[q] picks query q's row;
+// -1 = every document, any other value outside [0, n_sets) = no document.  The restricted kernels take ONE MsrSetView as a
+// trailing argument of a parameter pack; the unrestricted instantiations (empty pack) keep their signature and code.
+struct MsrSetView {
+    const uint32_t* bits;
+    int64_t stride;
+    const int32_t* q_set;        // indexed by the query number the kernel is given (see each launcher)
+    int32_t n_sets;
+};
+struct MsrSetRow {
+    const uint32_t* bits;
+    int32_t mode;                // 0 every document, 1 the documents of `bits`, 2 none
+};
+__device__ __forceinline__ MsrSetRow msr_set_row(int q, const MsrSetView& s) {
+    const int32_t v = s.q_set[q];
+    if (v == -1) return MsrSetRow{nullptr, 0};
+    if (v < -1 || v >= s.n_sets) return MsrSetRow{nullptr, 2};
+    return MsrSetRow{s.bits + (int64_t)v * s.stride, 1};
+}
+__device__ __forceinline__ bool msr_in_set(const MsrSetRow& r, int64_t d) {
+    return r.mode == 0 || (r.mode == 1 && ((r.bits[d >> 5] >> (d & 31)) & 1u));
+}
+
 // Select the top-k of scores[q][0..n) (row stride `stride` elements) for q in [0, nq).
 // score_bits 32: float scores / float out_score; 64: double.  Rows of out_* have stride k.
 // Order: score desc, index asc.  Entries past out_n[q] are (-1, -inf).
 hipError_t msr_select_topk(int score_bits, const void* scores, int64_t n, int64_t stride, int nq, int k,
                            const SelScratch& sc, int32_t* out_doc, void* out_score, int32_t* out_n,
                            hipStream_t stream);
+// The same over float rows with query q restricted to the documents of msr_set_row(q, set) (set.q_set indexed by the
+// select's own query number 0 .. nq-1): a document outside the set enters no histogram, no compaction and no count.
+hipError_t msr_select_topk_within(const float* scores, int64_t n, int64_t stride, int nq, int k, const SelScratch& sc,
+                                  const MsrSetView& set, int32_t* out_doc, float* out_score, int32_t* out_n, hipStream_t stream);
 
 // The same over segmented LISTS: row q (stride elements apart) is cut into n_seg segments seg_stride elements apart; segment s
 // holds counts[q * n_seg + s] pairs (scores, idx) in any order, from its first position on.
@@ -117,7 +145,10 @@ hipError_t msr_bm25_window(const Bm25Index& ix, const int32_t* q_term_off, const
                            int q_first, int nq, uint64_t* out /*[nq]: see msr_select_topk_list*/, hipStream_t stream);
 hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms,
                            const int32_t* q_qtf, int q_first, int nq, double min_score, double* cand_score,
-                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream);
+                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream,
+                           const MsrSetView* set = nullptr);
+// set (nullable): the restricted instantiation of the scoring kernel, set->q_set indexed by the CALL's query number
+// (q_first + q): a touched document outside query q's set is not emitted -- the candidate lists only get shorter.
 
 // *flag (device) <- 0x7F7F7F7F if the CSR is well formed, else the lowest violated rule number (msr_bm25.hip).
 hipError_t msr_bm25_validate(const Bm25Index& ix, int32_t* flag, hipStream_t stream);

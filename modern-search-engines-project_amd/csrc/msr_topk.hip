@@ -172,16 +172,28 @@ __device__ __forceinline__ void segment_range(const RowView& v, int q, int64_t n
     }
 }
 
+// The row kernels below take a trailing parameter pack Set: empty (every element of a row takes part), or one MsrSetView
+// (msr_select_topk_within): an element whose index is outside query q's document set takes part in nothing -- no histogram,
+// no compaction, no count -- exactly as if it were not in the row.
+template <typename... Set>
+__device__ __forceinline__ MsrSetRow sel_set_row(int q, const Set&... set) {
+    if constexpr (sizeof...(Set) > 0) return msr_set_row(q, set...);
+    else return MsrSetRow{nullptr, 0};
+}
+
 // Histogram of digit `digit` over the elements that match the resolved prefix.  digit 0 needs no state.
-template <typename T>
+template <typename T, typename... Set>
 __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const T* __restrict__ scores, int64_t n_dense,
                                                                 int64_t stride, RowView view, int digit,
                                                                 const SelState* __restrict__ st,
                                                                 uint32_t* __restrict__ hist, const int32_t* __restrict__ gate,
-                                                                int gate_per64) {
+                                                                int gate_per64, Set... set) {
     constexpr int SB = ScoreTraits<T>::SB;
+    constexpr bool WITHIN = sizeof...(Set) > 0;
     const int q = blockIdx.y;
     if (gate && gate[gate_per64 ? q >> 6 : 0] == 0) return;      // a fallback launch that is not needed (for this query's slice)
+    const MsrSetRow srow = sel_set_row(q, set...);
+    if (WITHIN && srow.mode == 2) return;                        // the empty set: nothing to count
     SelState S;
     S.pref_hi = S.mask_hi = 0; S.pref_lo = S.mask_lo = 0; S.done = 0;
     if (digit > 0) {
@@ -199,7 +211,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const T* __restri
     const T* row = scores + (int64_t)q * stride;
     // (a pass over the score part of the key with no index bits resolved does not look at the index: a list's 4 bytes of
     // index per element are then not loaded -- a third of the pass' bytes)
-    const bool need_index = part != 0 || S.mask_lo != 0;
+    const bool need_index = part != 0 || S.mask_lo != 0 || WITHIN;
     const int32_t* irow = view.idx && need_index ? view.idx + (int64_t)q * stride : nullptr;
     int s_first, s_last;
     part_segments(view, (int)blockIdx.x, (int)gridDim.x, s_first, s_last);
@@ -221,6 +233,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const T* __restri
                 uint64_t khi; uint32_t klo;
                 if (!key_of(v[u], ix[u], khi, klo)) continue;
                 if ((khi & S.mask_hi) != S.pref_hi || (klo & S.mask_lo) != S.pref_lo) continue;
+                if (WITHIN && !msr_in_set(srow, ix[u])) continue;
                 uint32_t dg = part == 0 ? (uint32_t)(khi >> shift) & wmask : (klo >> shift) & wmask;
                 if (window) {
                     const int64_t b = (int64_t)(khi >> WIN_SHIFT) - wbase;
@@ -273,15 +286,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void sel_scan_kernel(SelState* __rest
 // query's candidate list with ONE global atomic per workgroup (same-address atomics from every lane made
 // this the slowest kernel of the select in the first profile).  Queries that two passes could not resolve
 // (superset still > MSR_SEL_CAP: huge tie groups) are left to the final kernel's in-kernel loop.
-template <typename T>
+template <typename T, typename... Set>
 __global__ __launch_bounds__(SEL_THREADS) void sel_compact_kernel(const T* __restrict__ scores, int64_t n_dense,
                                                                    int64_t stride, RowView view,
                                                                    const SelState* __restrict__ st,
                                                                    uint64_t* __restrict__ cand_hi,
                                                                    uint32_t* __restrict__ cand_lo,
                                                                    int32_t* __restrict__ cand_n,
-                                                                   const int32_t* __restrict__ gate, int gate_per64) {
+                                                                   const int32_t* __restrict__ gate, int gate_per64, Set... set) {
+    constexpr bool WITHIN = sizeof...(Set) > 0;
     if (gate && gate[gate_per64 ? (int)blockIdx.y >> 6 : 0] == 0) return;
+    const MsrSetRow srow = sel_set_row((int)blockIdx.y, set...);
+    if (WITHIN && srow.mode == 2) return;
     constexpr int STAGE = 1024;                                  // staged matches per workgroup (12 KB of LDS)
     __shared__ uint64_t s_hi[STAGE];
     __shared__ uint32_t s_lo[STAGE];
@@ -314,6 +330,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_compact_kernel(const T* __res
                 const uint64_t mh = khi & S.mask_hi;
                 const bool ge = mh > S.pref_hi || (mh == S.pref_hi && (klo & S.mask_lo) >= S.pref_lo);
                 if (!ge) continue;
+                if (WITHIN && !msr_in_set(srow, ix[u])) continue;
                 const int pos = atomicAdd(&s_n, 1);              // LDS atomic
                 if (pos < STAGE) {
                     s_hi[pos] = khi; s_lo[pos] = klo;
@@ -353,7 +370,7 @@ using msr_sort::stage_sync;
 // resolve the query (state not done), this workgroup finishes the radix select on its own over the score
 // row -- slow (one CU reads the row once per remaining digit) but exact, and only reached with tie groups
 // larger than MSR_SEL_CAP.
-template <typename T>
+template <typename T, typename... Set>
 __global__ __launch_bounds__(SCAN_THREADS) void sel_final_kernel(const T* __restrict__ scores, int64_t n_dense,
                                                                   int64_t stride, RowView view,
                                                                   SelState* __restrict__ st,
@@ -363,8 +380,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void sel_final_kernel(const T* __rest
                                                                   int32_t* __restrict__ out_doc,
                                                                   T* __restrict__ out_score,
                                                                   int32_t* __restrict__ out_n,
-                                                                  const int32_t* __restrict__ gate, int gate_per64) {
+                                                                  const int32_t* __restrict__ gate, int gate_per64, Set... set) {
     constexpr int SB = ScoreTraits<T>::SB;
+    constexpr bool WITHIN = sizeof...(Set) > 0;
     if (gate && gate[gate_per64 ? (int)blockIdx.x >> 6 : 0] == 0) return;
     __shared__ uint64_t khi[MSR_SEL_CAP];
     __shared__ uint32_t klo[MSR_SEL_CAP];
@@ -374,6 +392,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void sel_final_kernel(const T* __rest
     const int q = blockIdx.x, t = threadIdx.x;
     const T* row = scores + (int64_t)q * stride;
     const int32_t* irow = view.idx ? view.idx + (int64_t)q * stride : nullptr;
+    const MsrSetRow srow = sel_set_row(q, set...);           // (the done path's candidates were filtered by the compaction)
     int n_sg = 1, sg0 = 0;
     part_segments(view, 0, 1, sg0, n_sg);                        // (this workgroup walks every segment of the row)
     DBG_TS(0);
@@ -458,6 +477,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void sel_final_kernel(const T* __rest
                     uint64_t a; uint32_t b;
                     if (!key_of(row[i], row_index(irow, i), a, b)) continue;
                     if ((a & S.mask_hi) != S.pref_hi || (b & S.mask_lo) != S.pref_lo) continue;
+                    if (WITHIN && !msr_in_set(srow, row_index(irow, i))) continue;
                     atomicAdd(&h[part == 0 ? (uint32_t)(a >> shift) & wmask : (b >> shift) & wmask], 1u);
                 }
             }
@@ -474,6 +494,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void sel_final_kernel(const T* __rest
             for (int64_t i = lo + t; i < hi; i += SCAN_THREADS) {
                 uint64_t a; uint32_t b;
                 if (!key_of(row[i], row_index(irow, i), a, b)) continue;
+                if (WITHIN && !msr_in_set(srow, row_index(irow, i))) continue;
                 const uint64_t mh = a & S.mask_hi;
                 if (mh > S.pref_hi || (mh == S.pref_hi && (b & S.mask_lo) >= S.pref_lo)) {
                     const int pos = atomicAdd(&s_cnt, 1);
@@ -509,9 +530,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void sel_final_kernel(const T* __rest
 #endif
 }
 
-template <typename T>
+template <typename T, typename... Set>
 hipError_t select_impl(const T* scores, int64_t n, int64_t stride, RowView view, int nq, int k, const SelScratch& sc,
-                       int32_t* out_doc, T* out_score, int32_t* out_n, hipStream_t stream) {
+                       int32_t* out_doc, T* out_score, int32_t* out_n, hipStream_t stream, Set... set) {
     constexpr int SB = ScoreTraits<T>::SB;
     if (nq <= 0) return hipSuccess;
     int64_t parts = view.counts ? view.n_seg : (n + 8191) / 8192;     // lists: whole segments per workgroup
@@ -523,13 +544,15 @@ hipError_t select_impl(const T* scores, int64_t n, int64_t stride, RowView view,
     // sort: 6 (4) launches
     const bool window = SB == 64 && view.win_base != nullptr;
     for (int d = window ? -1 : 0; d < (window ? 0 : 2); ++d) {
-        sel_hist_kernel<T><<<grid, SEL_THREADS, 0, stream>>>(scores, n, stride, view, d, sc.state, sc.hist, sc.gate, sc.gate_per64);
+        sel_hist_kernel<T, Set...><<<grid, SEL_THREADS, 0, stream>>>(scores, n, stride, view, d, sc.state, sc.hist, sc.gate,
+                                                                     sc.gate_per64, set...);
         sel_scan_kernel<SB><<<nq, SCAN_THREADS, 0, stream>>>(sc.state, sc.hist, d, k, sc.gate, sc.gate_per64, view.win_base);
     }
-    sel_compact_kernel<T><<<grid, SEL_THREADS, 0, stream>>>(scores, n, stride, view, sc.state, sc.cand_hi, sc.cand_lo,
-                                                             sc.cand_n, sc.gate, sc.gate_per64);
-    sel_final_kernel<T><<<nq, SCAN_THREADS, 0, stream>>>(scores, n, stride, view, sc.state, sc.cand_hi, sc.cand_lo,
-                                                          sc.cand_n, k, out_doc, out_score, out_n, sc.gate, sc.gate_per64);
+    sel_compact_kernel<T, Set...><<<grid, SEL_THREADS, 0, stream>>>(scores, n, stride, view, sc.state, sc.cand_hi, sc.cand_lo,
+                                                                     sc.cand_n, sc.gate, sc.gate_per64, set...);
+    sel_final_kernel<T, Set...><<<nq, SCAN_THREADS, 0, stream>>>(scores, n, stride, view, sc.state, sc.cand_hi, sc.cand_lo,
+                                                                  sc.cand_n, k, out_doc, out_score, out_n, sc.gate, sc.gate_per64,
+                                                                  set...);
     return hipGetLastError();
 }
 
@@ -803,6 +826,12 @@ hipError_t msr_select_topk(int score_bits, const void* scores, int64_t n, int64_
     if (score_bits == 32)
         return select_impl<float>((const float*)scores, n, stride, dense, nq, k, sc, out_doc, (float*)out_score, out_n, stream);
     return select_impl<double>((const double*)scores, n, stride, dense, nq, k, sc, out_doc, (double*)out_score, out_n, stream);
+}
+
+hipError_t msr_select_topk_within(const float* scores, int64_t n, int64_t stride, int nq, int k, const SelScratch& sc,
+                                  const MsrSetView& set, int32_t* out_doc, float* out_score, int32_t* out_n, hipStream_t stream) {
+    const RowView dense{nullptr, nullptr, 1, 0, nullptr};
+    return select_impl<float>(scores, n, stride, dense, nq, k, sc, out_doc, out_score, out_n, stream, set);
 }
 
 hipError_t msr_select_topk_list(const double* scores, const int32_t* idx, const int32_t* counts, int n_seg, int64_t seg_stride,

@@ -215,28 +215,64 @@ class DeviceEngine:
         mk = lambda a: torch.tensor(a if a else [0], dtype=torch.int32, device=self.device)
         return mk(off), mk(terms), mk(qtf), len(term_lists)
 
-    def bm25_topk(self, term_lists, k=1000, min_score=0.0, packed=None):
-        """-> (doc index int32 [Q, k], score float64 [Q, k], n int32 [Q]) device tensors."""
+    def pack_within(self, within, n_queries):
+        """within (None | DocSet | list / tuple of DocSet / None per query) -> (set words int32 [n_sets, stride] device, q_set
+        int32 [n_queries] device, n_sets, stride) for msr_*_topk_within; identical sets are stacked once (docset.pack_within).
+        One DocSet for every query: its cached device copy and q_set = 0, nothing packed on the host."""
+        from .docset import DocSet, pack_within
+        if isinstance(within, DocSet):
+            within.check(self.index)
+            stride = max(1, (self.index.n_docs + 31) // 32)
+            bits = within.to(self.device).reshape(1, -1)
+            if bits.shape[1] < stride:                       # (an index without documents: one zero word)
+                bits = torch.nn.functional.pad(bits, (0, stride - bits.shape[1]))
+            return bits, torch.zeros((n_queries,), dtype=torch.int32, device=self.device), 1, stride
+        words, q_set, n_sets, stride = pack_within(within, n_queries, self.index)
+        bits = torch.from_numpy(words.view(np.int32)).to(self.device)
+        return bits, torch.from_numpy(q_set).to(self.device), n_sets, stride
+
+    def bm25_topk(self, term_lists, k=1000, min_score=0.0, packed=None, within=None):
+        """-> (doc index int32 [Q, k], score float64 [Q, k], n int32 [Q]) device tensors.  within: None, a DocSet (every
+        query) or a list of DocSet / None per query -- the top k of each query's set (msr_bm25_topk_within)."""
         q_off, q_terms, q_qtf, Q = packed if packed is not None else self.pack_queries(term_lists)
         out_doc = torch.empty((Q, k), dtype=torch.int32, device=self.device)
         out_score = torch.empty((Q, k), dtype=torch.float64, device=self.device)
         out_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
-        self._check(self.lib.msr_bm25_topk(self.handle, _ptr(q_off), _ptr(q_terms), _ptr(q_qtf), Q, k,
-                                           C.c_double(min_score), _ptr(out_doc), _ptr(out_score), _ptr(out_n),
-                                           self._stream()))
+        n_sets = 0
+        if within is not None:
+            bits, q_set, n_sets, stride = self.pack_within(within, Q)
+        if n_sets == 0:
+            self._check(self.lib.msr_bm25_topk(self.handle, _ptr(q_off), _ptr(q_terms), _ptr(q_qtf), Q, k,
+                                               C.c_double(min_score), _ptr(out_doc), _ptr(out_score), _ptr(out_n),
+                                               self._stream()))
+        else:
+            self._check(self.lib.msr_bm25_topk_within(self.handle, _ptr(q_off), _ptr(q_terms), _ptr(q_qtf), Q, k,
+                                                      C.c_double(min_score), _ptr(bits), n_sets, stride, _ptr(q_set),
+                                                      _ptr(out_doc), _ptr(out_score), _ptr(out_n), self._stream()))
         return out_doc, out_score, out_n
 
+
     # ------------------------------------------------------------------ stage 2 (full scan)
-    def dense_topk(self, qvec, k=100, max_chunks_per_doc=0, want_chunk=True):
-        """qvec float32 [Q, 768] (not normalised) -> (doc [Q,k] i32, score [Q,k] f32, chunk row [Q,k] i32, n [Q])."""
+    def dense_topk(self, qvec, k=100, max_chunks_per_doc=0, want_chunk=True, within=None):
+        """qvec float32 [Q, 768] (not normalised) -> (doc [Q,k] i32, score [Q,k] f32, chunk row [Q,k] i32, n [Q]).
+        within: None, a DocSet or a list of DocSet / None per query (msr_dense_topk_within: every query on the sweeps, whose
+        scores are the sweep's -- not the exact-f32 rescoring of the 256-query pass)."""
         q = self._dev(qvec, torch.float32).reshape(-1, DIM)
         Q = int(q.shape[0])
         out_doc = torch.empty((Q, k), dtype=torch.int32, device=self.device)
         out_score = torch.empty((Q, k), dtype=torch.float32, device=self.device)
         out_chunk = torch.empty((Q, k), dtype=torch.int32, device=self.device) if want_chunk else None
         out_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
-        self._check(self.lib.msr_dense_topk(self.handle, _ptr(q), Q, k, int(max_chunks_per_doc), _ptr(out_doc),
-                                            _ptr(out_score), _ptr(out_chunk), _ptr(out_n), self._stream()))
+        n_sets = 0
+        if within is not None:
+            bits, q_set, n_sets, stride = self.pack_within(within, Q)
+        if n_sets == 0:
+            self._check(self.lib.msr_dense_topk(self.handle, _ptr(q), Q, k, int(max_chunks_per_doc), _ptr(out_doc),
+                                                _ptr(out_score), _ptr(out_chunk), _ptr(out_n), self._stream()))
+        else:
+            self._check(self.lib.msr_dense_topk_within(self.handle, _ptr(q), Q, k, int(max_chunks_per_doc), _ptr(bits), n_sets,
+                                                       stride, _ptr(q_set), _ptr(out_doc), _ptr(out_score), _ptr(out_chunk),
+                                                       _ptr(out_n), self._stream()))
         return out_doc, out_score, out_chunk, out_n
 
     def dense_split_max(self, k=100):

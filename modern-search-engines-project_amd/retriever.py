@@ -7,6 +7,8 @@
         the live two-stage path of search_api.py:69-152 and :204-367: preprocess_query -> BM25 top-1000 ->
         rerank -> top-100, formatted for the UI / as `qnum<TAB>rank<TAB>url<TAB>score` lines.
 """
+import weakref
+
 import numpy as np
 
 from .bm25 import BM25
@@ -84,12 +86,15 @@ class Retriever:
 
     # ------------------------------------------------------------------ dense full scan
     def quick_search_batch(self, queries=None, top_k=10, return_unique_docs=True, query_embeddings=None,
-                           max_chunks_per_doc=0):
+                           max_chunks_per_doc=0, within=None):
+        """within: None, a DocSet of this index (every query) or a list of DocSet / None per query: the dense top_k of the
+        documents in the set (msr_dense_topk_within; docset.py)."""
         if not return_unique_docs:
-            return self._chunk_search_batch(queries, top_k, query_embeddings)
+            return self._chunk_search_batch(queries, top_k, query_embeddings, within)
         qv = np.stack([self._embed(q, None if query_embeddings is None else query_embeddings[i])
                        for i, q in enumerate(queries if queries is not None else [None] * len(query_embeddings))])
-        doc, score, chunk, n = [x.cpu().numpy() for x in self.engine.dense_topk(qv, k=top_k, max_chunks_per_doc=max_chunks_per_doc)]
+        doc, score, chunk, n = [x.cpu().numpy() for x in self.engine.dense_topk(qv, k=top_k, max_chunks_per_doc=max_chunks_per_doc,
+                                                                                within=within)]
         ix = self.index
         cid = ix.chunk_ids.cpu().numpy() if hasattr(ix.chunk_ids, "cpu") else np.asarray(ix.chunk_ids)
         out = []
@@ -104,7 +109,7 @@ class Retriever:
             out.append(rows)
         return out
 
-    def _chunk_search_batch(self, queries, top_k, query_embeddings):
+    def _chunk_search_batch(self, queries, top_k, query_embeddings, within=None):
         """return_unique_docs=False: the top_k CHUNKS by cosine, several per document allowed (the other half of the call
         shape at search_api.py:87; retriever.py itself is absent from the reference, so the row format is ours: the
         unique-document row plus `chunk_id`).  Runs the same scan kernels over a view of the corpus in which every chunk is
@@ -124,7 +129,9 @@ class Retriever:
             self._chunk_doc_off = off.astype(np.int64)
         qv = np.stack([self._embed(q, None if query_embeddings is None else query_embeddings[i])
                        for i, q in enumerate(queries if queries is not None else [None] * len(query_embeddings))])
-        row, score, _, n = self._chunk_engine.dense_topk(qv, k=top_k, want_chunk=False)
+        if within is not None:                               # document sets -> the chunk view's sets: a chunk is in if its document is
+            within = [self._chunk_set(s) for s in within] if isinstance(within, (list, tuple)) else self._chunk_set(within)
+        row, score, _, n = self._chunk_engine.dense_topk(qv, k=top_k, want_chunk=False, within=within)
         row, score, n = row.cpu().numpy(), score.cpu().numpy(), n.cpu().numpy()
         cid = ix.chunk_ids.cpu().numpy() if hasattr(ix.chunk_ids, "cpu") else np.asarray(ix.chunk_ids)
         out = []
@@ -139,9 +146,25 @@ class Retriever:
             out.append(rows)
         return out
 
-    def quick_search(self, query=None, top_k=10, return_unique_docs=True, query_embedding=None, max_chunks_per_doc=0):
+    def _chunk_set(self, ds):
+        """A DocSet of this index -> the DocSet of the per-chunk view (every chunk of a document in the set).  Cached on `ds`
+        itself for the current view, so it lives exactly as long as the caller's set."""
+        from .docset import DocSet
+        if ds is None:
+            return None
+        ds.check(self.index)
+        view = self._chunk_engine.index
+        got = getattr(ds, "_chunk_view", None)
+        if got is None or got[0]() is not view:
+            got = ds._chunk_view = (weakref.ref(view),
+                                    DocSet.from_mask(view, np.repeat(ds.mask, np.diff(self._chunk_doc_off))))
+        return got[1]
+
+    def quick_search(self, query=None, top_k=10, return_unique_docs=True, query_embedding=None, max_chunks_per_doc=0,
+                     within=None):
         return self.quick_search_batch([query], top_k, return_unique_docs,
-                                       None if query_embedding is None else [query_embedding], max_chunks_per_doc)[0]
+                                       None if query_embedding is None else [query_embedding], max_chunks_per_doc,
+                                       within=None if within is None else [within])[0]
 
     # ------------------------------------------------------------------ live two-stage path
     # search_api.py:88-130 (single query) and :243-304 (batch): preprocess_query -> bm_25.search(top 1000) -> POST /rerank ->
@@ -174,11 +197,12 @@ class Retriever:
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
-    def _enqueue_chunk(self, term_ids, qv, top_k, slot):
-        """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues."""
+    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None):
+        """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
+        within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
-        b = eng.bm25_topk(term_ids, k=top_k)
+        b = eng.bm25_topk(term_ids, k=top_k, within=within)
         cos, meta = eng.rerank_gather(qv, b[0], b[2], max_chunks=RERANK_MAX_CHUNKS)
         fused = eng.rerank_fuse(b[0], b[1], b[2], cos, meta, smoothing=cfg["smoothing"], max_chunks=RERANK_MAX_CHUNKS)
         fin = eng.diversify(fused, top_k=int(cfg["top_k"]), diversification=bool(cfg.get("diversification", False)))
@@ -211,12 +235,14 @@ class Retriever:
         return pin[0][:Qc, :S].numpy().copy(), pin[1][:Qc, :S].numpy().copy(), pin[2][:Qc, :S].numpy().copy(), n
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
-                          n_queries=None):
+                          n_queries=None, within=None):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
         prepare(a, b) (optional, with n_queries) -> (term id lists, vectors) of queries a .. b, evaluated just before the chunk
-        is enqueued (text preprocessing inside the pipeline); otherwise term_id_lists / query_vectors hold all queries."""
+        is enqueued (text preprocessing inside the pipeline); otherwise term_id_lists / query_vectors hold all queries.
+        within: None, a DocSet (every query) or a list of DocSet / None per query: BM25 stage restricted to the set, then the
+        unchanged rerank / fuse / diversify on those candidates (the min-max normalisation spans the restricted candidates)."""
         import torch
         eng = self.engine
         if top_k > eng.rerank_max_docs or top_k > eng.max_k:
@@ -224,23 +250,26 @@ class Retriever:
         self._ensure_response_tables()
         Q = len(term_id_lists) if prepare is None else int(n_queries)
         step = int(chunk or max(256, eng.max_queries))
+        if isinstance(within, (list, tuple)) and len(within) != Q:
+            raise ValueError(f"within: {len(within)} entries for {Q} queries")
         pending = None
         for i, a in enumerate(range(0, Q, step)):
             b = min(Q, a + step)
             ids, qv = prepare(a, b) if prepare is not None else (term_id_lists[a:b], query_vectors[a:b])
             qv = eng._dev(np.asarray(qv, np.float32) if not torch.is_tensor(qv) else qv, torch.float32).reshape(-1, 768)
-            job = self._enqueue_chunk(ids, qv, top_k, i & 1)
+            w = list(within[a:b]) if isinstance(within, (list, tuple)) else within
+            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w)
             if pending is not None:
                 yield (pending[0],) + self._collect_chunk(pending[1])
             pending = (a, job)
         if pending is not None:
             yield (pending[0],) + self._collect_chunk(pending[1])
 
-    def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None):
+    def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768]."""
-        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk))
+        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)
@@ -262,10 +291,11 @@ class Retriever:
                            for i in range(len(queries))]) if len(queries) else np.zeros((0, 768), np.float32)
         return ids, qv
 
-    def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None):
-        """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing."""
+    def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None):
+        """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
+        (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks)."""
         ids, qv = self._prepare(queries, query_embeddings, term_lists)
-        doc, score, _, n = self.final_lists(ids, qv, top_k)
+        doc, score, _, n = self.final_lists(ids, qv, top_k, within=within)
         ix = self.index
         out = []
         for q in range(len(queries)):
@@ -283,16 +313,16 @@ class Retriever:
             out.append(rows)
         return out
 
-    def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None):
+    def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None):
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
-                                 None if terms is None else [terms], None if query_id is None else [query_id])[0]
+                                 None if terms is None else [terms], None if query_id is None else [query_id], within=within)[0]
 
-    def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None):
+    def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any."""
         ids, qv = self._prepare([q for _, q in numbered_queries], query_embeddings, term_lists)
-        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL)
+        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within)
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         return BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)

@@ -13,7 +13,9 @@ The reference runs two processes (Flask :5000 + FastAPI :8000) that talk JSON ov
 routes sit on one FastAPI app over one Retriever.  The LLM summariser (search_assistant/, a cloud call) is
 out of scope: `llm` is an optional callable(query, windows) -> str, otherwise llm_response is "".
 Requests may carry `query_embedding` (768 floats) and `terms` (pre-tokenised query) for deployments that
-keep the encoder / spaCy in another process.
+keep the encoder / spaCy in another process.  /api/search also takes `sites` (a list of domains): results only from
+documents whose URL's host is one of them or a subdomain (a `site:` search; docset.DocSet.from_sites, restricted inside
+the BM25 stage; the sets of the last `site_cache_size` distinct site lists are kept).  The response shape does not change.
 """
 import uuid
 from typing import List, Optional
@@ -24,8 +26,12 @@ from .text import preprocess_query, read_queries_file
 LLM_MAX_WINDOWS = 10          # config.py:22
 
 
-def create_app(retriever, llm=None, queries_file="queries.txt", results_file="batch_search_results.txt", ui_dir=None):
+def create_app(retriever, llm=None, queries_file="queries.txt", results_file="batch_search_results.txt", ui_dir=None,
+               site_cache_size=32):
     import os
+    import threading
+    import weakref
+    from collections import OrderedDict
 
     from fastapi import FastAPI
     from fastapi.responses import HTMLResponse, JSONResponse
@@ -43,8 +49,32 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         query_id: Optional[str] = None
         query_embedding: Optional[List[float]] = None
         terms: Optional[List[str]] = None
+        sites: Optional[List[str]] = None
 
     app = FastAPI(title="Document Reranker API", version="1.0.0")
+
+    # DocSet per normalised list of sites, for the index the retriever serves now: at most `site_cache_size` of them, least
+    # recently used first out (an evicted set releases its host mask and its device copy); cleared by an update_index
+    site_sets = {"index": lambda: None, "sets": OrderedDict(), "lock": threading.Lock()}   # (routes run on a thread pool)
+
+    def within_sites(sites):
+        from .docset import DocSet, normalise_sites
+        ix = retriever.index
+        key = normalise_sites(sites)
+        with site_sets["lock"]:
+            if site_sets["index"]() is not ix:   # (an update_index since: the old sets belong to the old index)
+                site_sets["index"], site_sets["sets"] = weakref.ref(ix), OrderedDict()
+            cache = site_sets["sets"]
+            ds = cache.get(key)
+            if ds is None:
+                ds = cache[key] = DocSet.from_sites(ix, key)
+                while len(cache) > max(0, int(site_cache_size)):
+                    cache.popitem(last=False)
+            else:
+                cache.move_to_end(key)
+            return ds
+
+    app.state.site_sets = site_sets
 
     @app.post("/rerank")
     def rerank(req: RerankRequest):
@@ -63,8 +93,12 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             if not query:
                 return JSONResponse(status_code=400, content={"error": "Query is required"})
             qid = req.query_id or uuid.uuid4().hex
-            docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
-                                    terms=req.terms, query_id=qid)
+            if req.sites is None:
+                docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
+                                        terms=req.terms, query_id=qid)
+            else:
+                docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
+                                        terms=req.terms, query_id=qid, within=within_sites(req.sites))
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
