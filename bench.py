@@ -16,10 +16,15 @@ fused lists cross xGMI.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with one extra object:
   roofline      dense-scan kernel: algorithmic bytes per launch / mean launch duration (hipEvents recorded on
                 the launch stream inside the timed region) against the 8 TB/s HBM peak
-  cpu_baseline  the C restatement in oracle/ (kind "port") timed on the host cores on a bounded sample
+A plain run does nothing else: set up, warm up, time the steps, --dump-outputs, print.  With --full the line also carries
+what takes runs of its own: the single-query p50 latency, the variants (bf16 candidates, exact f32 products, from token
+ids through the encoder), the drop-in API (`facade`) and
+  cpu_baseline  the C restatement in oracle/ (kind "port") timed on the host cores on a bounded sample, with the parity of
+                the GPU path against it
+(--no-variants / --no-cpu-baseline leave parts of that out again).
 """
 import argparse
 import json
@@ -513,11 +518,15 @@ def main():
     ap.add_argument("--k2", type=int, default=100, help="final top-k (reranker/config.yaml:30)")
     ap.add_argument("--scan-layout", type=int, default=0)
     ap.add_argument("--scan-variant", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: single-query latency, the variants, the drop-in "
+                         "API, the CPU baseline and the GPU path's parity against it (a plain run only times the steps)")
     ap.add_argument("--cpu-queries", type=int, default=20, help="timed queries per CPU baseline leg (after 3 warm-ups)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="OpenMP threads of the CPU baseline (a 1-GPU box is entitled to 16 host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra timed loop with the bf16 candidate sweep")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-variants", action="store_true",
+                    help="with --full: skip the extra timed loops of the variants and the drop-in API")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="ONE GPU does the per-rank GPU work of an N-GPU step (run with 1/N of --docs/--chunks and N times the "
                          "queries): local stages, the merges of N gathered lists, the rerank gather of the 1/N of the candidates "
@@ -525,10 +534,12 @@ def main():
     ap.add_argument("--pipelined", action="store_true",
                     help="also time the steps with stage 1 of the next batch overlapped with the tail of this one (variant_pipelined)")
     ap.add_argument("--with-encoder", action="store_true",
-                    help="time the variant that starts from token ids (QueryEncoder -> hybrid step) even with --no-variants")
+                    help="time the variant that starts from token ids (QueryEncoder -> hybrid step) even without --full or "
+                         "with --no-variants")
     ap.add_argument("--facade", action="store_true",
-                    help="time the drop-in API (Retriever.batch_search_to_file / Retriever.search) even with --no-variants")
-    ap.add_argument("--latency-queries", type=int, default=20)
+                    help="time the drop-in API (Retriever.batch_search_to_file / Retriever.search) even without --full or "
+                         "with --no-variants")
+    ap.add_argument("--latency-queries", type=int, default=20, help="with --full: queries of the single-query p50")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal: every rank uses cuda:0 (with --backend gloo), to exercise the N>1 path on one GPU")
@@ -704,18 +715,23 @@ def main():
         kept = write_outputs(host_outputs(out), args.dump_outputs)
         log(f"outputs of the last timed step ({kept} queries) written to {args.dump_outputs}")
 
+    # everything below the headline takes runs of its own: --full (or the option that asks for one part by name)
+    variants = args.full and not args.no_variants
+
     # single-query latency (p50), same path with a batch of one
-    lat = []
-    one = [(eng.pack_queries([shard.term_ids(terms[i])]), qvec[i:i + 1].contiguous()) for i in range(args.latency_queries)]
-    for rep in range(2):
-        for packed, qv in one:
-            fence()
-            t1 = time.perf_counter()
-            step(0, one=(packed, qv))
-            torch.cuda.synchronize()
-            if rep:
-                lat.append(time.perf_counter() - t1)
-    p50_ms = 1e3 * float(np.median(lat)) if lat else None
+    p50_ms = None
+    if args.full:
+        lat = []
+        one = [(eng.pack_queries([shard.term_ids(terms[i])]), qvec[i:i + 1].contiguous()) for i in range(args.latency_queries)]
+        for rep in range(2):
+            for packed, qv in one:
+                fence()
+                t1 = time.perf_counter()
+                step(0, one=(packed, qv))
+                torch.cuda.synchronize()
+                if rep:
+                    lat.append(time.perf_counter() - t1)
+        p50_ms = 1e3 * float(np.median(lat)) if lat else None
 
     # The same steps with the stages of CONSECUTIVE batches overlapped (one GPU, `--pipelined` only: measured at +1.8 %, 59.0 ->
     # 60.1 k queries/s on one box -- the latency-bound BM25 stage and the gather both want every wave slot of the chip, side by
@@ -780,7 +796,7 @@ def main():
     # rescoring; final scores and top-100 are those of the default path up to f32 rounding).  Reported NEXT TO the
     # headline, never as `value`.
     variant = None
-    if args.workload == "hybrid" and args.dense_mode == "f32" and not args.no_variants:
+    if args.workload == "hybrid" and args.dense_mode == "f32" and variants:
         try:
             eng.enable_bf16()
             vstep = lambda i: se.search(None, batches[i % len(batches)][1], k1=args.k1, k2=args.k2,
@@ -827,7 +843,7 @@ def main():
     # k-ordered fmaf chain; 64 queries per sweep on the K-split kernel, which is then bound by the f32 matrix rate).
     # Reported NEXT TO the headline as `roofline_exact_f32`, so that the strict-f32 line is a driver-timed number too.
     exact = None
-    if args.workload == "hybrid" and args.dense_mode == "f32" and not args.no_variants and args.scan_variant == 0 \
+    if args.workload == "hybrid" and args.dense_mode == "f32" and variants and args.scan_variant == 0 \
             and eng.scan_arith() == "f16x2" and shard.n_chunks > 0:
         try:
             eng_x = DeviceEngine(shard, device=local_rank, max_queries=max(Q, 1), max_k=max(args.k1, args.k2),
@@ -873,7 +889,7 @@ def main():
     # pooling, reranker_api.py:137-139,355; random weights, 8 tokens per query) -> the hybrid step above with the vectors it
     # produced.  Reported NEXT TO the headline (the headline's queries arrive as vectors, as BASELINE.json's metric has them).
     with_enc = None
-    if args.workload == "hybrid" and args.dense_mode == "f32" and (args.with_encoder or not args.no_variants):
+    if args.workload == "hybrid" and args.dense_mode == "f32" and (args.with_encoder or variants):
         try:
             from msretr.encoder import QueryEncoder, random_weights
             enc = QueryEncoder(random_weights(seed=5), device=local_rank)
@@ -1053,8 +1069,10 @@ def main():
                        "n_docs": args.docs, "n_chunks": args.chunks, "n_terms": args.terms,
                        "queries_per_step": Q, "k_stage1": args.k1, "k_final": args.k2,
                        "scan_layout": args.scan_layout, "scan_variant": args.scan_variant},
-            "p50_latency_ms_single_query": p50_ms, "outputs_sane": ok, "roofline": roof,
+            "outputs_sane": ok, "roofline": roof,
         }
+        if args.full:
+            line["p50_latency_ms_single_query"] = p50_ms
         if args.emulate_ranks > 1:
             line["emulated_ranks"] = args.emulate_ranks
             line["metric"] += f" [per-rank GPU work of a {args.emulate_ranks}-GPU step on ONE GPU: no collectives executed]"
@@ -1068,12 +1086,12 @@ def main():
             line["roofline_exact_f32"] = exact
         if with_enc is not None:
             line["variant_with_encoder"] = with_enc
-        if world == 1 and args.workload == "hybrid" and (args.facade or not args.no_variants):
+        if world == 1 and args.workload == "hybrid" and (args.facade or variants):
             try:
                 line["facade"] = facade_bench(args, shard, eng, terms, qvec, n_queries=min(1024, n_pool))
             except Exception as ex:
                 line["facade"] = {"error": repr(ex)}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "hybrid":
+        if world == 1 and args.full and not args.no_cpu_baseline and args.workload == "hybrid":
             try:
                 cb, cres, cdense, crerank = cpu_baseline(args, shard, terms, qvec, dev)
                 line["cpu_baseline"] = cb

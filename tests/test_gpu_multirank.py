@@ -21,7 +21,7 @@ def test_bench_two_ranks_on_one_gpu(nproc, batch):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--backend", "gloo", "--same-device", "--verify", "--docs", "60000", "--chunks", "250000",
            "--terms", "50000", "--queries-per-step", str(batch), "--steps", "2", "--warmup", "1", "--latency-queries", "2",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     torch.cuda.empty_cache()                                     # hand cached blocks of earlier tests back before the ranks start
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)

@@ -3,7 +3,7 @@
 # (latency from the L1's point of view, read level at the L2 <-> fabric interface, TLB misses; separate passes)
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; shift; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="--steps 3 --warmup 1 --no-cpu-baseline --no-variants"
+B="--steps 3 --warmup 1 --full --no-cpu-baseline --no-variants"
 i=0
 for C in "TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum GRBM_GUI_ACTIVE" \
          "TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum TCC_TAG_STALL_sum" \

@@ -3,7 +3,7 @@
 # (on the GPU box; writes gpurun_out/<tag>_*): kernel table of the step + FETCH_SIZE / WRITE_SIZE in separate --pmc passes.
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; Q=$2; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-A="--queries-per-step $Q --no-cpu-baseline --no-variants"
+A="--queries-per-step $Q --full --no-cpu-baseline --no-variants"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_q$Q -- python3 $R/bench.py --steps 6 --warmup 2 $A > $O/${T}_bench_q${Q}_under_rocprof.json 2> $O/${T}_prof_q$Q.err
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/${T}_pmcq${Q}_$C -- python3 $R/bench.py --steps 3 --warmup 1 $A > /dev/null 2> $O/${T}_pmcq${Q}_$C.err

@@ -4,10 +4,10 @@
 # 3. FETCH_SIZE / WRITE_SIZE in separate --pmc passes (MI355X_MICROARCH.md, HBM section).
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="--no-cpu-baseline --no-variants"
+B="--full --no-cpu-baseline --no-variants"
 D="--workload dense --dense-mode bf16 --queries-per-step 1024"
-python3 $R/bench.py > $O/${T}_bench.json 2> $O/${T}_bench.err
-python3 $R/bench.py $D --no-cpu-baseline > $O/${T}_bench_dense_bf16_q1024.json 2> $O/${T}_bench_bf16.err
+python3 $R/bench.py --full > $O/${T}_bench.json 2> $O/${T}_bench.err
+python3 $R/bench.py $D --full --no-cpu-baseline > $O/${T}_bench_dense_bf16_q1024.json 2> $O/${T}_bench_bf16.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python3 $R/bench.py --steps 6 --warmup 2 $B > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_bf16 -- python3 $R/bench.py --steps 6 --warmup 2 $D $B > $O/${T}_bench_bf16_under_rocprof.json 2> $O/${T}_prof_bf16.err
 for C in FETCH_SIZE WRITE_SIZE; do

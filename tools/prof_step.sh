@@ -3,7 +3,7 @@
 # (per-kernel table + one timed step) and the raw trace of the timed steps (gpurun_out/<tag>_trace.csv) for timeline analysis.
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; shift; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-variants "$@" > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -- python3 $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-variants "$@" > $O/${T}_bench_under_rocprof.json 2> $O/${T}_prof.err
 cd $R
 python3 tools/summarize_prof.py stats $(ls $O/${T}_prof/*/*kernel_stats.csv) $(ls $O/${T}_prof/*/*kernel_trace.csv) $O/${T}_kernel_stats.md
 python3 - "$(ls $O/${T}_prof/*/*kernel_trace.csv)" $O/${T}_trace.csv <<'PY'
