@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 6         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within */
+#define MSR_ABI_VERSION 7         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+                                     7: msr_gather_rows, msr_dense_topk_grouped */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -207,6 +208,38 @@ int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, int32_t k, 
 int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc,
                           const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
                           int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream);
+
+/* Documents similar to documents ("pages like this one", near-duplicate checks).
+ *   msr_gather_rows: out[i][0..768) <- chunk row rows[i] as given to msr_bind_chunks (f32, NOT normalised), bit for bit,
+ *     whatever layout the engine holds (row-major, or the 16-row interleaved image of scan_layout 1).  A row outside
+ *     [0, n_chunks) is refused (MSR_ERR_INVALID, out untouched): checked on the device, so the call synchronises the stream.
+ *   msr_dense_topk_grouped: q [n_rows][768] query rows (typically gathered source rows), cut into n_groups groups by the CSR
+ *     group_off [n_groups + 1] (group g = rows [group_off[g], group_off[g + 1])); excl_off [n_groups + 1] / excl_doc: per group
+ *     the documents never returned (typically the sources themselves).  For group g and a document d not excluded,
+ *       S_g(d) = max over the rows r of g of score_r(d),
+ *     score_r(d) the f32 score msr_dense_topk returns for query row r (max over all chunks of d, max_chunks_per_doc = 0).
+ *     Row g of the output holds the top k of the documents with S_g(d) >= min_score (-INFINITY: no threshold) in the order
+ *     (score desc, doc index asc): out_doc, out_score = S_g(d), out_chunk = the arg-max chunk row of d in the row that gave the
+ *     maximum, out_src_row = that row (an index into q; equal maxima: the lowest row).  out_n[g] <= k entries (all eligible
+ *     documents when there are fewer); the rest of the row is -1 / -inf / -1 / -1.  A group without rows has out_n = 0.
+ *     Where the per-row lists come from: with n_rows <= max_queries from exactly ONE msr_dense_topk(q, n_rows,
+ *     k + max_g |excl_g|, 0) call -- with sets (n_sets > 0; encoding and refusals of msr_bm25_topk_within, g_set [n_groups]
+ *     picks group g's row) the msr_dense_topk_within call in which every row takes its group's set -- so the result equals that
+ *     call followed by a merge on the host, bit for bit.  Larger calls make one such call per max_queries rows (whole rows);
+ *     a group may hold any number of rows.  A row whose dense list is empty (a NaN row) adds nothing; a zero row adds the
+ *     cosines 0 msr_dense_topk gives it.  Exact, ties included: a document of the group's top k reaches its maximum in some row
+ *     r, where at most k - 1 eligible and |excl_g| excluded documents rank above it -- it is in row r's top k + |excl_g|.
+ *     Refused with MSR_ERR_INVALID, outputs untouched: k < 1; k + max |excl_g| > max_k; group_off not monotone from 0 to
+ *     n_rows; excl_off not monotone from 0; an excl_doc outside [0, n_docs) (checked on the device); min_score NaN; q NULL with
+ *     n_rows > 0; group_off / excl_off NULL; an output NULL with n_groups > 0; excl_doc NULL with exclusions; the set rules;
+ *     while an msr_dense_topk_begin is pending.  MSR_ERR_NOT_BOUND without chunks.  The call reads the two offset arrays on
+ *     the host (one synchronisation of the stream); scratch ~44 bytes per row and list entry is kept by the engine. */
+int msr_gather_rows(msr_engine* e, const int32_t* rows, int32_t n, float* out, void* stream);
+int msr_dense_topk_grouped(msr_engine* e, const float* q, int32_t n_rows, const int32_t* group_off, int32_t n_groups,
+                           const int32_t* excl_off, const int32_t* excl_doc, int32_t k, float min_score,
+                           const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* g_set,
+                           int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_src_row, int32_t* out_n,
+                           void* stream);
 
 /* msr_dense_topk in two halves, for a doc-sharded index: between them the caller exchanges ONE float per query across the
  * shards (msretr/distributed.py: an all-reduce MIN over RCCL), after which every shard rescores only the documents that can

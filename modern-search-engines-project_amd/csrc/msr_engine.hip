@@ -89,6 +89,11 @@ struct msr_engine {
                                        // msr_config.flags, 3 allocation failed (the row-major instantiation of the kernel runs)
     int row_image_state = 0;           // f16 image of the rows (launches of several query groups): the same four states
     int last_dense_width = 0;          // queries per pass over the matrix of the most recent msr_dense_topk call (msr_dense_path)
+    // msr_gather_rows / msr_dense_topk_grouped (grown on demand, kept until msr_destroy): a check flag, the per-row lists, the
+    // per-row set indices and the merge's overflow records
+    int32_t* sim_flag = nullptr;
+    void* sim_lists = nullptr; size_t sim_lists_bytes = 0;
+    void* sim_over = nullptr; size_t sim_over_bytes = 0;
     // timing
     bool timing = false;
     static constexpr int EV_RING = 256;
@@ -247,6 +252,7 @@ extern "C" int msr_destroy(msr_engine* e) {
     free_dev(e, e->sel.cand_lo); free_dev(e, e->sel.cand_n); free_dev(e, e->rerank_cos); free_dev(e, e->rerank_meta);
     free_dev(e, e->bt_top_doc); free_dev(e, e->bt_top_score); free_dev(e, e->bt_top_n); free_dev(e, e->bt_cand_doc);
     free_dev(e, e->bt_cand_score); free_dev(e, e->bt_cand_chunk); free_dev(e, e->bt_cand_n);
+    free_dev(e, e->sim_flag); free_dev(e, e->sim_lists); free_dev(e, e->sim_over);
     free_gemm(e);
     free_gf(e);
     for (int w = 0; w < msr_engine::EV_KINDS; ++w)
@@ -1076,6 +1082,125 @@ extern "C" int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_qu
     e->last_dense_width = wide ? 64 : 32;
     const MsrSetView set{set_bits, set_stride, q_set, n_sets};
     return dense_sweeps(e, q, 0, n_queries, k, max_chunks_per_doc, wide, nullptr, out_doc, out_score, out_chunk, out_n, st, &set);
+}
+
+// ---- K9: similar documents (msr_similar.hip) ---------------------------------------------------------------------------------
+// Grow-only scratch of these calls.
+static int sim_grow(msr_engine* e, void** p, size_t* have, size_t need, const char* what) {
+    if (need <= *have && *p) return MSR_OK;
+    free_dev(e, *p);
+    *p = nullptr;
+    *have = 0;
+    hipError_t herr = eng_malloc(e, p, need);
+    if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "%s (%zu bytes): %s", what, need, hipGetErrorString(herr));
+    *have = need;
+    return MSR_OK;
+}
+
+// 1 if some v[0..n) lies outside [0, hi) (device check, one synchronisation of the stream), 0 if none, < 0 on failure
+static int sim_out_of_range(msr_engine* e, const int32_t* v, int64_t n, int64_t hi, hipStream_t st) {
+    if (!e->sim_flag) {
+        hipError_t herr = eng_malloc(e, (void**)&e->sim_flag, 64);
+        if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "check flag: %s", hipGetErrorString(herr));
+    }
+    int32_t flag = 0;
+    HIP_TRY(e, hipMemsetAsync(e->sim_flag, 0, sizeof(int32_t), st));
+    HIP_TRY(e, msr_check_range(v, n, hi, e->sim_flag, st));
+    HIP_TRY(e, hipMemcpyAsync(&flag, e->sim_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    return flag ? 1 : 0;
+}
+
+extern "C" int msr_gather_rows(msr_engine* e, const int32_t* rows, int32_t n, float* out, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_gather_rows: chunks not bound");
+    if (n < 0 || (n > 0 && (!rows || !out))) return fail(e, MSR_ERR_INVALID, "msr_gather_rows: bad argument (n=%d)", n);
+    if (n == 0) return MSR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const int bad = sim_out_of_range(e, rows, n, e->dense.n_chunks, st);
+    if (bad < 0) return bad;
+    if (bad) return fail(e, MSR_ERR_INVALID, "msr_gather_rows: a row lies outside [0, n_chunks = %lld)", (long long)e->dense.n_chunks);
+    HIP_TRY(e, msr_gather_rows_run(e->dense, rows, n, out, st));
+    return MSR_OK;
+}
+
+extern "C" int msr_dense_topk_grouped(msr_engine* e, const float* q, int32_t n_rows, const int32_t* group_off, int32_t n_groups,
+                                      const int32_t* excl_off, const int32_t* excl_doc, int32_t k, float min_score,
+                                      const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* g_set,
+                                      int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_src_row,
+                                      int32_t* out_n, void* stream) {
+    static const char* fn = "msr_dense_topk_grouped";
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "%s: chunks not bound", fn);
+    if (e->split_pending)
+        return fail(e, MSR_ERR_INVALID, "%s: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first", fn);
+    if (n_rows < 0 || n_groups < 0 || k < 1 || k > e->cfg.max_k || min_score != min_score || !group_off || !excl_off ||
+        (n_rows > 0 && !q) || (n_groups > 0 && (!out_doc || !out_score || !out_chunk || !out_src_row || !out_n)))
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (n_rows=%d, n_groups=%d, k=%d, max_k=%d)", fn, n_rows, n_groups, k,
+                    e->cfg.max_k);
+    {
+        const int rc = within_args_ok(e, fn, e->dense.n_docs, set_bits, n_sets, set_stride, g_set);
+        if (rc) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    // the offsets on the host: their checks, and the list depth k + max |excl_g| every row is asked for
+    std::vector<int32_t> h_goff((size_t)n_groups + 1), h_eoff((size_t)n_groups + 1);
+    HIP_TRY(e, hipMemcpyAsync(h_goff.data(), group_off, h_goff.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipMemcpyAsync(h_eoff.data(), excl_off, h_eoff.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (h_goff[0] != 0 || h_goff[n_groups] != n_rows)
+        return fail(e, MSR_ERR_INVALID, "%s: group_off must run from 0 to n_rows = %d (got %d .. %d)", fn, n_rows, h_goff[0],
+                    h_goff[n_groups]);
+    if (h_eoff[0] != 0) return fail(e, MSR_ERR_INVALID, "%s: excl_off[0] = %d, must be 0", fn, h_eoff[0]);
+    int max_excl = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (h_goff[g + 1] < h_goff[g]) return fail(e, MSR_ERR_INVALID, "%s: group_off not monotone at group %d", fn, g);
+        if (h_eoff[g + 1] < h_eoff[g]) return fail(e, MSR_ERR_INVALID, "%s: excl_off not monotone at group %d", fn, g);
+        max_excl = std::max(max_excl, h_eoff[g + 1] - h_eoff[g]);
+    }
+    if ((int64_t)k + max_excl > e->cfg.max_k)
+        return fail(e, MSR_ERR_INVALID, "%s: k + max |excl_g| = %lld exceeds max_k = %d", fn, (long long)k + max_excl, e->cfg.max_k);
+    const int64_t n_excl = h_eoff[n_groups];
+    if (n_excl > 0) {
+        if (!excl_doc) return fail(e, MSR_ERR_INVALID, "%s: excl_doc is NULL with %lld exclusions", fn, (long long)n_excl);
+        const int bad = sim_out_of_range(e, excl_doc, n_excl, e->dense.n_docs, st);
+        if (bad < 0) return bad;
+        if (bad) return fail(e, MSR_ERR_INVALID, "%s: an excluded document lies outside [0, n_docs = %lld)", fn, (long long)e->dense.n_docs);
+    }
+    if (n_groups == 0) return MSR_OK;
+    // scratch: the per-row lists (doc, score, chunk [n_rows][kk], n [n_rows]), the per-row set indices, the overflow records
+    const int kk = k + max_excl;
+    const size_t L = (size_t)n_rows * kk;
+    const size_t lists_bytes = (L * 3 + 2 * (size_t)n_rows + 64) * 4;
+    int rc = sim_grow(e, &e->sim_lists, &e->sim_lists_bytes, lists_bytes, "grouped lists");
+    if (rc) return rc;
+    rc = sim_grow(e, &e->sim_over, &e->sim_over_bytes, 2 * L * 16 + 64, "grouped merge records");
+    if (rc) return rc;
+    int32_t* l_doc = (int32_t*)e->sim_lists;
+    float* l_score = (float*)(l_doc + L);
+    int32_t* l_chunk = (int32_t*)(l_score + L);
+    int32_t* l_n = l_chunk + L;
+    int32_t* row_set = l_n + n_rows;
+    if (n_sets > 0) HIP_TRY(e, msr_group_row_sets(group_off, n_groups, g_set, row_set, st));
+    // the per-row lists: one msr_dense_topk(_within) call per max_queries rows (one call when n_rows <= max_queries)
+    for (int r0 = 0; r0 < n_rows; r0 += e->cfg.max_queries) {
+        const int cnt = std::min(e->cfg.max_queries, n_rows - r0);
+        const int64_t o = (int64_t)r0 * kk;
+        rc = msr_dense_topk_within(e, q + (int64_t)r0 * MSR_DIM, cnt, kk, 0, set_bits, n_sets, set_stride,
+                                   n_sets > 0 ? row_set + r0 : nullptr, l_doc + o, l_score + o, l_chunk + o, l_n + r0, stream);
+        if (rc) return rc;
+    }
+    GroupedMergeArgs a{};
+    a.l_doc = l_doc; a.l_score = l_score; a.l_chunk = l_chunk; a.l_n = l_n; a.kk = kk;
+    a.group_off = group_off; a.excl_off = excl_off; a.excl_doc = excl_doc; a.k = k; a.min_score = min_score;
+    a.out_doc = out_doc; a.out_score = out_score; a.out_chunk = out_chunk; a.out_src = out_src_row; a.out_n = out_n;
+    a.g_hi = (uint64_t*)e->sim_over;
+    a.g_lo = (uint32_t*)(a.g_hi + 2 * L);
+    a.g_val = a.g_lo + 2 * L;
+    HIP_TRY(e, msr_grouped_merge(a, n_groups, st));
+    return MSR_OK;
 }
 
 static int rerank_args_ok(msr_engine* e, const char* fn, int32_t n_queries, int32_t max_cand, int32_t max_chunks) {

@@ -221,6 +221,27 @@ hipError_t msr_interleave(const float* src, int64_t n_rows, float* dst, hipStrea
 hipError_t msr_best_chunk(const DenseIndex& ix, const float* qn, int nq, int k, int max_chunks,
                           const int32_t* out_doc, const int32_t* out_n, int32_t* out_chunk, hipStream_t stream);
 
+// ---- K9: similar documents (msr_similar.hip) ---------------------------------------------------------
+// *flag <- 1 if some v[i] (i < n) lies outside [0, hi); the caller zeroes the flag first
+hipError_t msr_check_range(const int32_t* v, int64_t n, int64_t hi, int32_t* flag, hipStream_t stream);
+// out[i][0..768) <- bound row rows[i] (rows checked by the caller), either layout of ix.emb
+hipError_t msr_gather_rows_run(const DenseIndex& ix, const int32_t* rows, int n, float* out, hipStream_t stream);
+// row_set[r] <- g_set[g] for every row r of group g
+hipError_t msr_group_row_sets(const int32_t* group_off, int n_groups, const int32_t* g_set, int32_t* row_set, hipStream_t stream);
+struct GroupedMergeArgs {
+    const int32_t* l_doc; const float* l_score; const int32_t* l_chunk; const int32_t* l_n;   // per-row lists [n_rows][kk] / [n_rows]
+    int32_t kk;
+    const int32_t* group_off;  // [n_groups + 1] (validated)
+    const int32_t* excl_off;   // [n_groups + 1] (validated)
+    const int32_t* excl_doc;   // documents in [0, n_docs) (validated)
+    int32_t k;
+    float min_score;
+    int32_t* out_doc; float* out_score; int32_t* out_chunk; int32_t* out_src; int32_t* out_n;   // [n_groups][k] / [n_groups]
+    uint64_t* g_hi; uint32_t* g_lo; uint32_t* g_val;   // overflow records: [2 n_rows kk] each (group g: from 2 group_off[g] kk)
+};
+// One workgroup per group: the group's top k of the per-document maximum over its rows' lists (see msr_similar.hip).
+hipError_t msr_grouped_merge(const GroupedMergeArgs& a, int n_groups, hipStream_t stream);
+
 // ---- K6: rerank / fuse ----------------------------------------------------------------------------
 struct RerankParams {
     double smoothing, max_boost, max_decay;

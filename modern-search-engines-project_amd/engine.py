@@ -275,6 +275,48 @@ class DeviceEngine:
                                                        _ptr(out_n), self._stream()))
         return out_doc, out_score, out_chunk, out_n
 
+    def gather_rows(self, rows):
+        """rows int [n] chunk row indices -> float32 [n, 768] device tensor: the bound rows as given to the index (not
+        normalised), bit for bit, whatever scan_layout the engine holds (msr_gather_rows; a row outside [0, n_chunks) raises)."""
+        r = self._dev(np.asarray(rows, np.int64).reshape(-1) if not torch.is_tensor(rows) else rows.reshape(-1), torch.int32)
+        n = int(r.numel())
+        out = torch.empty((n, DIM), dtype=torch.float32, device=self.device)
+        self._check(self.lib.msr_gather_rows(self.handle, _ptr(r), n, _ptr(out), self._stream()))
+        return out
+
+    def dense_topk_grouped(self, qvec, group_off, exclude=None, k=10, min_score=None, within=None):
+        """Per group of query rows the top k documents by the maximum over the group's rows of the dense score
+        (msr_dense_topk_grouped).  qvec float32 [R, 768]; group_off int [G + 1] (group g = rows group_off[g] ..
+        group_off[g + 1]); exclude: None or G iterables of document indices never returned for that group; min_score: None or
+        a float threshold; within: None, a DocSet (every group) or a list of DocSet / None per group.
+        -> (doc [G, k] i32, score [G, k] f32, chunk row [G, k] i32, source row [G, k] i32 (index into qvec), n [G]) device."""
+        q = self._dev(qvec, torch.float32).reshape(-1, DIM)
+        R = int(q.shape[0])
+        goff = np.asarray(group_off, np.int64).reshape(-1)
+        G = int(goff.shape[0]) - 1
+        if G < 0:
+            raise ValueError("group_off needs at least one entry")
+        excl = [[] for _ in range(G)] if exclude is None else [list(x) for x in exclude]
+        if len(excl) != G:
+            raise ValueError(f"exclude: {len(excl)} entries for {G} groups")
+        eoff = np.zeros(G + 1, np.int64)
+        eoff[1:] = np.cumsum([len(x) for x in excl], dtype=np.int64)
+        edoc = np.asarray([int(d) for x in excl for d in x] or [0], np.int64)
+        t_goff, t_eoff, t_edoc = self._dev(goff, torch.int32), self._dev(eoff, torch.int32), self._dev(edoc, torch.int32)
+        out_doc = torch.empty((G, k), dtype=torch.int32, device=self.device)
+        out_score = torch.empty((G, k), dtype=torch.float32, device=self.device)
+        out_chunk = torch.empty((G, k), dtype=torch.int32, device=self.device)
+        out_src = torch.empty((G, k), dtype=torch.int32, device=self.device)
+        out_n = torch.empty((G,), dtype=torch.int32, device=self.device)
+        bits, g_set, n_sets, stride = None, None, 0, 0
+        if within is not None:
+            bits, g_set, n_sets, stride = self.pack_within(within, G)
+        ms = -np.inf if min_score is None else float(min_score)
+        self._check(self.lib.msr_dense_topk_grouped(self.handle, _ptr(q), R, _ptr(t_goff), G, _ptr(t_eoff), _ptr(t_edoc), int(k),
+                                                    C.c_float(ms), _ptr(bits), n_sets, stride, _ptr(g_set), _ptr(out_doc),
+                                                    _ptr(out_score), _ptr(out_chunk), _ptr(out_src), _ptr(out_n), self._stream()))
+        return out_doc, out_score, out_chunk, out_src, out_n
+
     def dense_split_max(self, k=100):
         """Most queries one dense_begin / dense_end pair takes (0: this engine cannot split the dense call)."""
         return int(self.lib.msr_dense_split_max(self.handle, int(k)))

@@ -166,6 +166,58 @@ class Retriever:
                                        None if query_embedding is None else [query_embedding], max_chunks_per_doc,
                                        within=None if within is None else [within])[0]
 
+    # ------------------------------------------------------------------ similar documents (msr_dense_topk_grouped)
+    def similar_batch(self, groups, top_k=10, max_source_chunks=RERANK_MAX_CHUNKS, within=None, min_score=None):
+        """Documents like the given ones, one ranked list per group, in ONE engine call.  groups: per entry one doc_id or a list
+        of doc_ids (the sources).  Each source contributes its first max_source_chunks chunk rows (0 = all; the default 10 is
+        the reference's <= 10 chunks per document, reranker_api.py:35,58); a document's score is its best cosine to any
+        source row.  The sources are never returned.  within: None, a DocSet (every group) or a list of DocSet / None per
+        group; min_score: None or a threshold (e.g. 0.95 for a near-duplicate check).  Rows as quick_search's plus
+        source_doc_id / source_chunk_id (the source row that gave the score).  An unknown doc_id raises LookupError."""
+        ix = self.index
+        ids = self._ids
+        off = ix.doc_off.cpu().numpy() if hasattr(ix.doc_off, "cpu") else np.asarray(ix.doc_off)
+        rows, row_src, group_off, exclude = [], [], [0], []
+        for grp in groups:
+            src = [grp] if np.ndim(grp) == 0 else list(grp)
+            seen = []
+            for d in src:
+                i = int(np.searchsorted(ids, int(d)))
+                if i >= len(ids) or int(ids[i]) != int(d):
+                    raise LookupError(f"doc_id {d} is not in the index")
+                if i not in seen:
+                    seen.append(i)
+            for i in seen:
+                a, b = int(off[i]), int(off[i + 1])
+                if max_source_chunks:
+                    b = min(b, a + int(max_source_chunks))
+                rows.extend(range(a, b))
+                row_src.extend([i] * (b - a))
+            group_off.append(len(rows))
+            exclude.append(seen)
+        eng = self.engine
+        q = eng.gather_rows(np.asarray(rows, np.int64))
+        doc, score, chunk, srow, n = [x.cpu().numpy() for x in eng.dense_topk_grouped(q, group_off, exclude, k=top_k,
+                                                                                        min_score=min_score, within=within)]
+        cid = ix.chunk_ids.cpu().numpy() if hasattr(ix.chunk_ids, "cpu") else np.asarray(ix.chunk_ids)
+        out = []
+        for g in range(len(exclude)):
+            res = []
+            for j in range(int(n[g])):
+                i, r = int(doc[g, j]), int(srow[g, j])
+                res.append({"rank": j + 1, "doc_id": int(ids[i]), "score": float(score[g, j]),
+                            "best_chunk_id": int(cid[int(chunk[g, j])]),
+                            "url": ix.urls[i] if ix.urls is not None else None,
+                            "title": ix.titles[i] if ix.titles is not None else None,
+                            "source_doc_id": int(ids[row_src[r]]), "source_chunk_id": int(cid[rows[r]])})
+            out.append(res)
+        return out
+
+    def similar(self, doc_ids, top_k=10, max_source_chunks=RERANK_MAX_CHUNKS, within=None, min_score=None):
+        """The documents most similar to doc_ids (one id or a list): similar_batch with one group."""
+        return self.similar_batch([doc_ids], top_k, max_source_chunks, within=None if within is None else [within],
+                                  min_score=min_score)[0]
+
     # ------------------------------------------------------------------ live two-stage path
     # search_api.py:88-130 (single query) and :243-304 (batch): preprocess_query -> bm_25.search(top 1000) -> POST /rerank ->
     # formatted rows.  In the reference every arrow is a Python list of dicts (1000 per query, each with a 200-character

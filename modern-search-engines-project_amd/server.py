@@ -4,6 +4,9 @@
     POST /api/search         search_api.py:69-152               ({llm_response, documents:[...]})
     POST /api/batch_search   search_api.py:204-328              (queries.txt -> qnum<TAB>rank<TAB>url<TAB>score lines)
     POST /api/batch_search_file  search_api.py:331-367          (the same, written to batch_search_results.txt)
+    POST /api/similar        (no reference counterpart) {doc_ids | doc_id, top_k, sites?, min_score?} -> {documents:[...]}
+                             in the /api/search document shape: the pages most like the given ones
+                             (Retriever.similar; 400 without ids, 404 for an unknown id)
     GET  /api/health         search_api.py:369-375
     GET  /                   search_api.py:377-380              (the UI page: templates/index.html of the deployment when
                                                                  `ui_dir` is given -- the reference's D3 front end is not
@@ -18,10 +21,12 @@ documents whose URL's host is one of them or a subdomain (a `site:` search; docs
 the BM25 stage; the sets of the last `site_cache_size` distinct site lists are kept).  The response shape does not change.
 """
 import uuid
-from typing import List, Optional
+from typing import List, Optional, Union
+
+import numpy as np
 
 from .reranker import RerankNotFound
-from .text import preprocess_query, read_queries_file
+from .text import extract_domain_topic, preprocess_query, read_queries_file
 
 LLM_MAX_WINDOWS = 10          # config.py:22
 
@@ -50,6 +55,13 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         query_embedding: Optional[List[float]] = None
         terms: Optional[List[str]] = None
         sites: Optional[List[str]] = None
+
+    class SimilarRequest(BaseModel):
+        doc_ids: Optional[List[Union[int, str]]] = None
+        doc_id: Optional[Union[int, str]] = None
+        top_k: int = 10
+        sites: Optional[List[str]] = None
+        min_score: Optional[float] = None
 
     app = FastAPI(title="Document Reranker API", version="1.0.0")
 
@@ -105,6 +117,43 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             return {"llm_response": llm_response, "documents": docs}
         except Exception:
             return JSONResponse(status_code=500, content={"error": "Internal server error"})
+
+    @app.post("/api/similar")
+    def similar(req: SimilarRequest):
+        # pages like the given ones (Retriever.similar): the sources themselves are left out; 400 without ids, 404 for an id the
+        # index does not hold
+        try:
+            ids = list(req.doc_ids or []) + ([] if req.doc_id is None else [req.doc_id])
+            if not ids:
+                return JSONResponse(status_code=400, content={"error": "doc_ids is required"})
+            try:
+                ids = [int(d) for d in ids]
+            except (TypeError, ValueError):
+                return JSONResponse(status_code=400, content={"error": "doc_ids must be integers"})
+            within = None if req.sites is None else within_sites(req.sites)
+            try:
+                rows = retriever.similar(ids, top_k=req.top_k, within=within, min_score=req.min_score)
+            except LookupError as e:
+                return JSONResponse(status_code=404, content={"error": str(e)})
+            ix = retriever.index
+            docs = []
+            for r in rows:
+                url = r["url"] or ""
+                text = _doc_text(ix, r["doc_id"])
+                docs.append({"query_id": None, "rank": r["rank"], "url": url, "score": r["score"],
+                             "title": r["title"] or "No Title",
+                             "snippet": (text[:200] + "..." if len(text) > 200 else text) or "No content available",
+                             "domain": extract_domain_topic(url), "doc_id": str(r["doc_id"]),
+                             "source_doc_id": str(r["source_doc_id"])})
+            return {"documents": docs}
+        except Exception as e:
+            return JSONResponse(status_code=500, content={"error": f"Internal server error: {e}"})
+
+    def _doc_text(ix, doc_id):
+        if ix.texts is None:
+            return ""
+        i = int(np.searchsorted(retriever._ids, doc_id))
+        return ix.texts[i] or ""
 
     def _batch():
         """-> (status, body): the body of /api/batch_search (search_api.py:204-328)."""
