@@ -35,8 +35,8 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 7         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
-                                     7: msr_gather_rows, msr_dense_topk_grouped */
+#define MSR_ABI_VERSION 8         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+                                     7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -188,6 +188,36 @@ int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, const int32_t
                          int32_t n_queries, int32_t k, double min_score,
                          const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
                          int32_t* out_doc, double* out_score, int32_t* out_n, void* stream);
+
+/* Hybrid candidates (dense hits join the BM25 list).
+ *   msr_bm25_score_docs: the BM25 scores of NAMED documents -- a point lookup, no posting list is streamed.  Queries packed as
+ *     for msr_bm25_topk (unique term ids in first-occurrence order, <= 64 per query).  doc is [n_queries][max_docs] document
+ *     indices, doc_n[q] of row q valid (doc_n NULL: all max_docs; a value outside [0, max_docs] is clamped).  For a valid
+ *     slot naming document d: out_score = the float64 sum the reference forms for d (bm25_indexer.py:466-478): the
+ *     contributions (idf * tf_component) * qtf of the query's valid terms that d contains, added in the query's order from
+ *     0.0 -- bit for bit the score msr_bm25_topk returns for (query, d); out_touched = 1 if d contains at least one of them
+ *     (msr_bm25_topk's "touched by a posting"), else 0 with score 0.0.  No min_score: a negative sum is returned as it is.
+ *     A slot past doc_n[q], or holding an index outside [0, n_docs), gets 0.0 / 0 and reads nothing of the index.  A document
+ *     may repeat in a row (equal results).  Reads only what msr_bind_postings built (postings with tf_components, skip table,
+ *     dense tables): no engine scratch, no state, valid after any re-bind.  Cost: per (slot, term) one table load, or a
+ *     binary search of <= 11 dependent loads; ~25 600 slots in a few tens of microseconds.
+ *     Refused with MSR_ERR_INVALID: n_queries < 0, max_docs < 0, a NULL array that would be read or written.
+ *   msr_union_candidates: row q of the output = the lexical list lex_doc / lex_score [n_queries][k_lex] (lex_n[q] entries)
+ *     unchanged and in its order, followed by the documents of dense_doc [n_queries][k_dense] (dense_n[q] entries) that the
+ *     lexical list does not hold, in dense rank order, each with its score dense_bm25[q][j] (from msr_bm25_score_docs).
+ *     Entries of the dense list that are negative, or repeat an earlier entry of it, are skipped.  out_src[q][m]: 1 = the
+ *     lexical list only, 2 = the dense list only, 3 = both.  out_n[q] <= k_lex + k_dense; the rest of a row (max_cand columns)
+ *     is -1 / -inf / 0.  The output is what msr_rerank_gather / msr_rerank_fuse take as cand_doc / cand_bm25 / cand_n.
+ *     Counts outside [0, k] are clamped.  Refused with MSR_ERR_INVALID, outputs untouched: k_lex or k_dense outside
+ *     [0, MSR_MAX_K]; k_lex + k_dense > max_cand; max_cand < 1; a NULL array that would be read or written. */
+int msr_bm25_score_docs(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
+                        int32_t n_queries, const int32_t* doc, const int32_t* doc_n, int32_t max_docs,
+                        double* out_score, int32_t* out_touched, void* stream);
+int msr_union_candidates(msr_engine* e, int32_t n_queries,
+                         const int32_t* lex_doc, const double* lex_score, const int32_t* lex_n, int32_t k_lex,
+                         const int32_t* dense_doc, const double* dense_bm25, const int32_t* dense_n, int32_t k_dense,
+                         int32_t* out_doc, double* out_score, int32_t* out_src, int32_t* out_n, int32_t max_cand,
+                         void* stream);
 
 /* Dense full scan for Q queries: score(d) = max over the document's first `max_chunks_per_doc` chunks
  * (0 = all) of cosine(q, chunk), cosine as sklearn computes it in float32 (reranker_api.py:285), to within the

@@ -45,6 +45,30 @@ class BM25:
         doc_ids = doc_ids.cpu().numpy() if hasattr(doc_ids, "cpu") else doc_ids
         return [[(int(doc_ids[d]), float(s)) for d, s in zip(doc[q, :n[q]], score[q, :n[q]])] for q in range(len(ids))]
 
+    # -- BM25 scores of named documents (msr_bm25_score_docs) -----------------------------------------
+    def score_terms(self, terms: Sequence[Union[str, int]], doc_ids):
+        """-> [(doc_id, score, matched)] in the order of doc_ids: the BM25 score search_terms gives (query, document) -- also
+        for documents outside its top_k or below its min_score -- and whether the document holds any of the terms (False:
+        score 0.0).  What a caller of POST /rerank needs who has doc ids but no similarities.  A doc_id the index does not
+        hold raises KeyError."""
+        import numpy as np
+        ids = np.asarray([int(d) for d in doc_ids], np.int64).reshape(-1)
+        have = self.index.doc_ids
+        have = np.asarray(have.cpu().numpy() if hasattr(have, "cpu") else have, np.int64)
+        if len(ids) == 0:
+            return []
+        pos = np.minimum(np.searchsorted(have, ids), max(len(have) - 1, 0))
+        bad = ids[have[pos] != ids] if len(have) else ids
+        if len(bad):
+            raise KeyError(f"doc_id {int(bad[0])} is not in the index")
+        score, touched = self.engine.bm25_score_docs([self.index.term_ids(terms)], pos.astype(np.int32).reshape(1, -1))
+        score, touched = score.cpu().numpy()[0], touched.cpu().numpy()[0]
+        return [(int(d), float(s), bool(t)) for d, s, t in zip(ids, score, touched)]
+
+    def score_docs(self, query: str, doc_ids):
+        """score_terms for a query string (tokenised like search)."""
+        return self.score_terms(self._tokenize(query), doc_ids)
+
     # -- the reference's method ------------------------------------------------------------------------
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None):
         query_terms = self._tokenize(query)

@@ -20,6 +20,7 @@ UNITS = {
     "msr_engine.hip": [],
     "msr_topk.hip": [],
     "msr_bm25.hip": ["-ffp-contract=off"],
+    "msr_bm25_point.hip": ["-ffp-contract=off"],
     "msr_dense.hip": [],
     "msr_dense_ks.hip": [],
     "msr_rerank.hip": ["-ffp-contract=off"],

@@ -886,6 +886,40 @@ extern "C" int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, co
                           out_n, stream, set_bits, n_sets, set_stride, q_set);
 }
 
+// K10: BM25 scores of named documents (everything read was built by msr_bind_postings; no engine scratch)
+extern "C" int msr_bm25_score_docs(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
+                                   int32_t n_queries, const int32_t* doc, const int32_t* doc_n, int32_t max_docs,
+                                   double* out_score, int32_t* out_touched, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_bm25_score_docs: postings not bound");
+    if (n_queries < 0 || max_docs < 0 || !q_term_off || (n_queries > 0 && max_docs > 0 && (!doc || !out_score || !out_touched)))
+        return fail(e, MSR_ERR_INVALID, "msr_bm25_score_docs: bad argument (n_queries=%d, max_docs=%d)", n_queries, max_docs);
+    if (n_queries == 0 || max_docs == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_bm25_point(e->bm25, q_term_off, q_terms, q_qtf, n_queries, doc, doc_n, max_docs, out_score, out_touched,
+                              (hipStream_t)stream));
+    return MSR_OK;
+}
+
+extern "C" int msr_union_candidates(msr_engine* e, int32_t n_queries, const int32_t* lex_doc, const double* lex_score,
+                                    const int32_t* lex_n, int32_t k_lex, const int32_t* dense_doc, const double* dense_bm25,
+                                    const int32_t* dense_n, int32_t k_dense, int32_t* out_doc, double* out_score, int32_t* out_src,
+                                    int32_t* out_n, int32_t max_cand, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (n_queries < 0 || k_lex < 0 || k_lex > MSR_MAX_K || k_dense < 0 || k_dense > MSR_MAX_K || max_cand < 1 ||
+        (int64_t)k_lex + k_dense > max_cand)
+        return fail(e, MSR_ERR_INVALID, "msr_union_candidates: bad argument (k_lex=%d, k_dense=%d: each in [0, %d], their sum <= "
+                    "max_cand=%d)", k_lex, k_dense, MSR_MAX_K, max_cand);
+    if (!out_doc || !out_score || !out_src || !out_n || (k_lex > 0 && (!lex_doc || !lex_score || !lex_n)) ||
+        (k_dense > 0 && (!dense_doc || !dense_bm25 || !dense_n)))
+        return fail(e, MSR_ERR_INVALID, "msr_union_candidates: bad argument (NULL list)");
+    if (n_queries == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_union_lists(n_queries, lex_doc, lex_score, lex_n, k_lex, dense_doc, dense_bm25, dense_n, k_dense, out_doc,
+                               out_score, out_src, out_n, max_cand, (hipStream_t)stream));
+    return MSR_OK;
+}
+
 // A query whose entries overflowed in the streaming pass (huge tie groups, a zero vector) raised the gate word of its 64-query
 // slice: that slice once more on the sweeps, which handle any input.  One scan per slice, gated on its word, into its own score
 // rows; then ONE select and ONE best-chunk pass over all rows of the call, in which a query takes part only if its slice's word

@@ -150,6 +150,19 @@ hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const
 // set (nullable): the restricted instantiation of the scoring kernel, set->q_set indexed by the CALL's query number
 // (q_first + q): a touched document outside query q's set is not emitted -- the candidate lists only get shorter.
 
+// K10 (msr_bm25_point.hip).  out_score / out_touched [nq][max_docs] <- the BM25 sum / "holds a query term" of document
+// doc[q][m] for query q (queries packed as for msr_bm25_scores, q_first = 0); doc_n (nullable: every slot) valid slots per row;
+// a slot past doc_n[q] or naming no document of the index gets 0.0 / 0.
+hipError_t msr_bm25_point(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf, int nq,
+                          const int32_t* doc, const int32_t* doc_n, int max_docs, double* out_score, int32_t* out_touched,
+                          hipStream_t stream);
+// Row q of out_* [nq][max_cand] <- the lexical list, then the dense list's documents it lacks (see msretr.h
+// msr_union_candidates); hipErrorInvalidValue unless 0 <= k_lex, k_dense <= 1024 and k_lex + k_dense <= max_cand.
+hipError_t msr_union_lists(int nq, const int32_t* lex_doc, const double* lex_score, const int32_t* lex_n, int k_lex,
+                           const int32_t* dense_doc, const double* dense_bm25, const int32_t* dense_n, int k_dense,
+                           int32_t* out_doc, double* out_score, int32_t* out_src, int32_t* out_n, int max_cand,
+                           hipStream_t stream);
+
 // *flag (device) <- 0x7F7F7F7F if the CSR is well formed, else the lowest violated rule number (msr_bm25.hip).
 hipError_t msr_bm25_validate(const Bm25Index& ix, int32_t* flag, hipStream_t stream);
 

@@ -251,6 +251,47 @@ class DeviceEngine:
                                                       _ptr(out_doc), _ptr(out_score), _ptr(out_n), self._stream()))
         return out_doc, out_score, out_n
 
+    # ------------------------------------------------------------------ hybrid candidates (msr_bm25_point.hip)
+    def bm25_score_docs(self, term_lists, doc, doc_n=None, packed=None):
+        """BM25 scores of NAMED documents (msr_bm25_score_docs): doc int32 [Q, M] document indices, doc_n int32 [Q] valid
+        slots per row (None: all M) -> (score float64 [Q, M], touched int32 [Q, M]) device tensors: bm25_topk's score of
+        (query, document) bit for bit, touched = the document holds a query term.  A slot past doc_n or naming no document of
+        the index gets 0.0 / 0.  Only enqueues."""
+        q_off, q_terms, q_qtf, Q = packed if packed is not None else self.pack_queries(term_lists)
+        d = self._dev(doc if torch.is_tensor(doc) else np.asarray(doc, np.int32), torch.int32)
+        if d.dim() != 2 or int(d.shape[0]) != Q:
+            raise ValueError(f"doc: shape {tuple(d.shape)} for {Q} queries (want [Q, M])")
+        M = int(d.shape[1])
+        dn = None if doc_n is None else self._dev(doc_n if torch.is_tensor(doc_n) else np.asarray(doc_n, np.int32), torch.int32)
+        if dn is not None and tuple(dn.shape) != (Q,):
+            raise ValueError(f"doc_n: shape {tuple(dn.shape)} for {Q} queries")
+        out_score = torch.empty((Q, M), dtype=torch.float64, device=self.device)
+        out_touched = torch.empty((Q, M), dtype=torch.int32, device=self.device)
+        self._check(self.lib.msr_bm25_score_docs(self.handle, _ptr(q_off), _ptr(q_terms), _ptr(q_qtf), Q, _ptr(d), _ptr(dn), M,
+                                                 _ptr(out_score), _ptr(out_touched), self._stream()))
+        return out_score, out_touched
+
+    def union_candidates(self, lex, dense_doc, dense_bm25, dense_n, max_cand=None):
+        """lex = (doc int32 [Q, k_lex], score float64 [Q, k_lex], n int32 [Q]) of bm25_topk; dense_doc int32 [Q, k_dense] /
+        dense_n int32 [Q] of dense_topk; dense_bm25 float64 [Q, k_dense] of bm25_score_docs -> (doc int32 [Q, max_cand],
+        score float64, src int32 (1 lexical, 2 dense, 3 both), n int32 [Q]): the lexical list, then the dense list's new
+        documents in dense rank order (msr_union_candidates) -- the cand_doc / cand_bm25 / cand_n of rerank_gather /
+        rerank_fuse.  max_cand: columns of the output (default k_lex + k_dense).  Only enqueues."""
+        ld, ls, ln = (self._dev(x, dt) for x, dt in zip(lex[:3], (torch.int32, torch.float64, torch.int32)))
+        dd, db, dn = self._dev(dense_doc, torch.int32), self._dev(dense_bm25, torch.float64), self._dev(dense_n, torch.int32)
+        Q, k_lex, k_dense = int(ld.shape[0]), int(ld.shape[1]), int(dd.shape[1])
+        if int(dd.shape[0]) != Q or tuple(ls.shape) != (Q, k_lex) or tuple(db.shape) != (Q, k_dense) or \
+                tuple(ln.shape) != (Q,) or tuple(dn.shape) != (Q,):
+            raise ValueError("union_candidates: the lists do not have the shapes [Q, k_lex] / [Q, k_dense] / [Q]")
+        M = k_lex + k_dense if max_cand is None else int(max_cand)
+        out_doc = torch.empty((Q, max(M, 0)), dtype=torch.int32, device=self.device)
+        out_score = torch.empty((Q, max(M, 0)), dtype=torch.float64, device=self.device)
+        out_src = torch.empty((Q, max(M, 0)), dtype=torch.int32, device=self.device)
+        out_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        self._check(self.lib.msr_union_candidates(self.handle, Q, _ptr(ld), _ptr(ls), _ptr(ln), k_lex, _ptr(dd), _ptr(db),
+                                                  _ptr(dn), k_dense, _ptr(out_doc), _ptr(out_score), _ptr(out_src), _ptr(out_n),
+                                                  M, self._stream()))
+        return out_doc, out_score, out_src, out_n
 
     # ------------------------------------------------------------------ stage 2 (full scan)
     def dense_topk(self, qvec, k=100, max_chunks_per_doc=0, want_chunk=True, within=None):

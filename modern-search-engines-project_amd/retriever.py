@@ -21,6 +21,25 @@ from .text import (LineFormatter, extract_domain, extract_domain_topic, format_r
 TOP_K_RETRIEVAL = 1000     # config.py:13
 TOP_K_RERANKING = 100      # config.py:14
 RERANK_MAX_CHUNKS = 10     # reranker_api.py:58
+DENSE_K = 100              # mode="hybrid": dense candidates that join the BM25 list (default)
+MATCHED_BY = {1: "lexical", 2: "dense", 3: "both"}       # msr_union_candidates' out_src
+
+
+def hybrid_k_lex(top_k, rerank_max_docs, dense_k):
+    """Lexical candidates of a hybrid step: the rerank chain holds <= rerank_max_docs candidates per query, dense_k of them are
+    the dense stage's.  ValueError when either list would be empty."""
+    if int(dense_k) < 1:
+        raise ValueError(f"dense_k must be >= 1 (got {dense_k})")
+    k_lex = min(int(top_k), int(rerank_max_docs) - int(dense_k))
+    if k_lex < 1:
+        raise ValueError(f"dense_k {dense_k} leaves no room for lexical candidates (top_k {top_k}, rerank_max_docs "
+                         f"{rerank_max_docs})")
+    return k_lex
+
+
+def _check_mode(mode):
+    if mode not in ("lexical", "hybrid"):
+        raise ValueError(f"mode must be 'lexical' or 'hybrid' (got {mode!r})")
 
 
 class Retriever:
@@ -249,12 +268,25 @@ class Retriever:
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
-    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None):
+    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K):
         """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
-        within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged."""
+        within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
+        mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
+        with its true BM25 score (msr_bm25_score_docs, msr_union_candidates); the candidates and where each came from are
+        copied to pinned buffers beside the final rows (the job's sixth entry)."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
-        b = eng.bm25_topk(term_ids, k=top_k, within=within)
+        union = None
+        if mode == "hybrid":
+            k_lex = hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
+            packed = eng.pack_queries(term_ids)
+            lex = eng.bm25_topk(None, k=k_lex, packed=packed, within=within)
+            dd, _, _, dn = eng.dense_topk(qv, k=int(dense_k), want_chunk=False, within=within)
+            dbm, _ = eng.bm25_score_docs(None, dd, dn, packed=packed)
+            union = eng.union_candidates(lex, dd, dbm, dn)
+            b = (union[0], union[1], union[3])
+        else:
+            b = eng.bm25_topk(term_ids, k=top_k, within=within)
         cos, meta = eng.rerank_gather(qv, b[0], b[2], max_chunks=RERANK_MAX_CHUNKS)
         fused = eng.rerank_fuse(b[0], b[1], b[2], cos, meta, smoothing=cfg["smoothing"], max_chunks=RERANK_MAX_CHUNKS)
         fin = eng.diversify(fused, top_k=int(cfg["top_k"]), diversification=bool(cfg.get("diversification", False)))
@@ -270,15 +302,27 @@ class Retriever:
         pin[1][:Qc].copy_(fin[1][:, :W], non_blocking=True)
         pin[2][:Qc].copy_(fin[3][:, :W], non_blocking=True)
         pin[3][:Qc].copy_(fin[4], non_blocking=True)
+        upin = None
+        if union is not None:
+            M = int(union[0].shape[1])
+            upin = self._pinned.get(("union", slot))
+            if upin is None or upin[0].shape[0] < Qc or upin[0].shape[1] != M:
+                rows = max(Qc, 256)
+                upin = self._pinned[("union", slot)] = (torch.empty((rows, M), dtype=torch.int32, pin_memory=True),
+                                                        torch.empty((rows, M), dtype=torch.int32, pin_memory=True),
+                                                        torch.empty((rows,), dtype=torch.int32, pin_memory=True))
+            upin[0][:Qc].copy_(union[0], non_blocking=True)
+            upin[1][:Qc].copy_(union[2], non_blocking=True)
+            upin[2][:Qc].copy_(union[3], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(eng.device))
-        return fin, pin, ev, Qc, W
+        return (fin, pin, ev, Qc, W) if upin is None else (fin, pin, ev, Qc, W, upin)
 
     @staticmethod
     def _collect_chunk(job):
         """Wait for a chunk's copies -> (doc, score, chunk row, n) numpy arrays of that chunk (copies: the pinned buffers are
         reused two chunks later)."""
-        fin, pin, ev, Qc, W = job
+        fin, pin, ev, Qc, W = job[:5]
         ev.synchronize()
         n = pin[3][:Qc].numpy().copy()
         S = int(n.max()) if Qc else 0
@@ -286,19 +330,50 @@ class Retriever:
             return fin[0][:, :S].cpu().numpy(), fin[1][:, :S].cpu().numpy(), fin[3][:, :S].cpu().numpy(), n
         return pin[0][:Qc, :S].numpy().copy(), pin[1][:Qc, :S].numpy().copy(), pin[2][:Qc, :S].numpy().copy(), n
 
+    @staticmethod
+    def _collect_source(job, doc, n):
+        """Hybrid mode, after _collect_chunk: int32 [Qc, S], where each final row's document came from (msr_union_candidates'
+        out_src: 1 lexical, 2 dense, 3 both; 0 past n) -- looked up by document index in the chunk's candidate lists."""
+        udoc, usrc, un = job[5]
+        Qc = job[3]
+        udoc, usrc, un = udoc[:Qc].numpy(), usrc[:Qc].numpy(), un[:Qc].numpy()
+        S = doc.shape[1]
+        live = np.arange(S)[None, :] < np.asarray(n)[:, None]
+        src = np.where(live, 1, 0).astype(np.int32)              # lexical only, unless the dense list names the document
+        uq, um = np.nonzero((usrc >= 2) & (np.arange(udoc.shape[1])[None, :] < un[:, None]))      # <= dense_k slots per query
+        if len(uq) == 0 or not live.any():
+            return src
+        key = (uq.astype(np.int64) << 32) | udoc[uq, um].astype(np.int64)
+        order = np.argsort(key, kind="stable")
+        key, val = key[order], usrc[uq, um][order]
+        fq, fr = np.nonzero(live)
+        want = (fq.astype(np.int64) << 32) | doc[fq, fr].astype(np.int64)
+        pos = np.minimum(np.searchsorted(key, want), len(key) - 1)
+        hit = key[pos] == want
+        src[fq[hit], fr[hit]] = val[pos[hit]]
+        return src
+
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
-                          n_queries=None, within=None):
+                          n_queries=None, within=None, mode="lexical", dense_k=DENSE_K):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
         prepare(a, b) (optional, with n_queries) -> (term id lists, vectors) of queries a .. b, evaluated just before the chunk
         is enqueued (text preprocessing inside the pipeline); otherwise term_id_lists / query_vectors hold all queries.
         within: None, a DocSet (every query) or a list of DocSet / None per query: BM25 stage restricted to the set, then the
-        unchanged rerank / fuse / diversify on those candidates (the min-max normalisation spans the restricted candidates)."""
+        unchanged rerank / fuse / diversify on those candidates (the min-max normalisation spans the restricted candidates).
+        mode="hybrid": the candidates are the BM25 top min(top_k, rerank_max_docs - dense_k) AND the dense top dense_k (both
+        within the set, if any), see _enqueue_chunk; every chunk then carries a sixth array, int32 [Qc, S]: where each row's
+        document came from (1 lexical, 2 dense, 3 both).  A query without a known term still gets its dense candidates."""
         import torch
         eng = self.engine
+        _check_mode(mode)
         if top_k > eng.rerank_max_docs or top_k > eng.max_k:
             raise ValueError(f"top_k {top_k} exceeds the engine's max_k / rerank_max_docs ({eng.max_k} / {eng.rerank_max_docs})")
+        if mode == "hybrid":
+            hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
+            if int(dense_k) > eng.max_k:
+                raise ValueError(f"dense_k {dense_k} exceeds the engine's max_k ({eng.max_k})")
         self._ensure_response_tables()
         Q = len(term_id_lists) if prepare is None else int(n_queries)
         step = int(chunk or max(256, eng.max_queries))
@@ -310,26 +385,37 @@ class Retriever:
             ids, qv = prepare(a, b) if prepare is not None else (term_id_lists[a:b], query_vectors[a:b])
             qv = eng._dev(np.asarray(qv, np.float32) if not torch.is_tensor(qv) else qv, torch.float32).reshape(-1, 768)
             w = list(within[a:b]) if isinstance(within, (list, tuple)) else within
-            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w)
+            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k)
             if pending is not None:
-                yield (pending[0],) + self._collect_chunk(pending[1])
+                yield (pending[0],) + self._collect(pending[1])
             pending = (a, job)
         if pending is not None:
-            yield (pending[0],) + self._collect_chunk(pending[1])
+            yield (pending[0],) + self._collect(pending[1])
 
-    def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None):
+    @classmethod
+    def _collect(cls, job):
+        out = cls._collect_chunk(job)
+        return out if len(job) == 5 else out + (cls._collect_source(job, out[0], out[3]),)
+
+    def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
+                    dense_k=DENSE_K, with_source=False):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
-        query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768]."""
-        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within))
+        query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
+        with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n)."""
+        _check_mode(mode)
+        if with_source and mode != "hybrid":
+            raise ValueError("with_source needs mode='hybrid'")
+        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k))
         if not parts:
             z = np.zeros((0, 0), np.int32)
-            return z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)
+            return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
         S = max(p[1].shape[1] for p in parts)
         pad = lambda x, fill: x if x.shape[1] == S else np.concatenate(
             [x, np.full((x.shape[0], S - x.shape[1]), fill, x.dtype)], axis=1)
-        return (np.concatenate([pad(p[1], -1) for p in parts]), np.concatenate([pad(p[2], -np.inf) for p in parts]),
-                np.concatenate([pad(p[3], -1) for p in parts]), np.concatenate([p[4] for p in parts]))
+        out = (np.concatenate([pad(p[1], -1) for p in parts]), np.concatenate([pad(p[2], -np.inf) for p in parts]),
+               np.concatenate([pad(p[3], -1) for p in parts]), np.concatenate([p[4] for p in parts]))
+        return out + ((np.concatenate([pad(p[5], 0) for p in parts]),) if with_source else ())
 
     def _prepare(self, queries, query_embeddings, term_lists):
         processed = [preprocess_query(q) for q in queries]
@@ -343,11 +429,20 @@ class Retriever:
                            for i in range(len(queries))]) if len(queries) else np.zeros((0, 768), np.float32)
         return ids, qv
 
-    def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None):
+    def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
+                     mode="lexical", dense_k=DENSE_K):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
-        (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks)."""
+        (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
+        mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
+        be returned; a query of unknown words only still gets results); every row then carries "matched_by": "lexical" |
+        "dense" | "both".  mode="lexical" (default): the reference's path, rows without that key."""
+        _check_mode(mode)
         ids, qv = self._prepare(queries, query_embeddings, term_lists)
-        doc, score, _, n = self.final_lists(ids, qv, top_k, within=within)
+        src = None
+        if mode == "hybrid":
+            doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True)
+        else:
+            doc, score, _, n = self.final_lists(ids, qv, top_k, within=within)
         ix = self.index
         out = []
         for q in range(len(queries)):
@@ -362,19 +457,26 @@ class Retriever:
                              "title": title or "No Title",
                              "snippet": (text[:200] + "..." if len(text) > 200 else text) or "No content available",
                              "domain": extract_domain_topic(url), "doc_id": str(int(self._ids[i]))})
+                if src is not None:
+                    rows[-1]["matched_by"] = MATCHED_BY[int(src[q, r])]
             out.append(rows)
         return out
 
-    def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None):
+    def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
+               mode="lexical", dense_k=DENSE_K):
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
-                                 None if terms is None else [terms], None if query_id is None else [query_id], within=within)[0]
+                                 None if terms is None else [terms], None if query_id is None else [query_id], within=within,
+                                 mode=mode, dense_k=dense_k)[0]
 
-    def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None):
+    def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
+                     dense_k=DENSE_K):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
-        .text() / .write() produce all formatted lines natively (msr_format_lines) without building any."""
+        .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
+        search_batch (the entries keep the reference's keys in either mode)."""
+        _check_mode(mode)
         ids, qv = self._prepare([q for _, q in numbered_queries], query_embeddings, term_lists)
-        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within)
+        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         return BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)

@@ -55,6 +55,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         query_embedding: Optional[List[float]] = None
         terms: Optional[List[str]] = None
         sites: Optional[List[str]] = None
+        mode: str = "lexical"         # "hybrid": the dense top dense_k documents join the BM25 candidates (Retriever.search)
+        dense_k: int = 100
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -104,13 +106,19 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             query = preprocess_query(req.query.strip())
             if not query:
                 return JSONResponse(status_code=400, content={"error": "Query is required"})
+            if req.mode not in ("lexical", "hybrid"):
+                return JSONResponse(status_code=400, content={"error": "mode must be 'lexical' or 'hybrid'"})
             qid = req.query_id or uuid.uuid4().hex
-            if req.sites is None:
+            kw = {} if req.mode == "lexical" else {"mode": req.mode, "dense_k": req.dense_k}
+            if req.sites is not None:
+                kw["within"] = within_sites(req.sites)
+            try:
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
-                                        terms=req.terms, query_id=qid)
-            else:
-                docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
-                                        terms=req.terms, query_id=qid, within=within_sites(req.sites))
+                                        terms=req.terms, query_id=qid, **kw)
+            except ValueError as e:
+                if req.mode == "lexical":
+                    raise
+                return JSONResponse(status_code=400, content={"error": str(e)})      # a dense_k the engine cannot hold
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
