@@ -35,8 +35,9 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 8         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
-                                     7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates */
+#define MSR_ABI_VERSION 9         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+                                     7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
+                                     9: msr_debug_bm25_split */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -188,6 +189,14 @@ int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, const int32_t
                          int32_t n_queries, int32_t k, double min_score,
                          const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
                          int32_t* out_doc, double* out_score, int32_t* out_n, void* stream);
+
+/* Read-only, launches nothing: how msr_bm25_topk(_within) splits the work of ONE internal slice of n_queries queries
+ * (1 <= n_queries <= max_queries; a call of more queries runs slices of max_queries and one of the rest) over the bound
+ * postings.  *tiles_per_item = consecutive 1024-document tiles one wave of the scoring kernel walks (1, 2, 4 or 8);
+ * *n_segments = ceil(tiles / *tiles_per_item) = work items per query = segments of a query's candidate row that the select
+ * walks.  Results never depend on the split; the export exists so that tests can ASSERT which split a call ran instead of
+ * assuming it.  MSR_ERR_NOT_BOUND without postings, MSR_ERR_INVALID for n_queries out of range or a NULL output. */
+int msr_debug_bm25_split(msr_engine* e, int32_t n_queries, int32_t* tiles_per_item, int32_t* n_segments);
 
 /* Hybrid candidates (dense hits join the BM25 list).
  *   msr_bm25_score_docs: the BM25 scores of NAMED documents -- a point lookup, no posting list is streamed.  Queries packed as

@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 8
+MSR_ABI_VERSION = 9
 MSR_CFG_NO_ROW_COPY = 1
 MSR_DIM = 768
 MSR_MAX_K = 1024
@@ -64,6 +64,7 @@ _SIGNATURES = {
                                        _P, _P]),
     "msr_dense_topk_within": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P,
                                         _P]),
+    "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_bm25_score_docs": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "msr_union_candidates": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     "msr_gather_rows": (C.c_int, [_P, _P, C.c_int32, _P, _P]),

@@ -589,18 +589,24 @@ hipError_t msr_bm25_window(const Bm25Index& ix, const int32_t* q_term_off, const
     return hipGetLastError();
 }
 
+// A wave looks its query's terms up once and then walks `tpw` consecutive tiles with that plan in registers.  More tiles
+// per wave amortise the lookups (chains of dependent loads) but leave fewer work items: large batches take 8, a single
+// query one tile per wave (its ~1000 waves are all the parallelism it has).
+void msr_bm25_split(int n_tiles, int nq, int* tpw_out, int* n_spans_out) {
+    int tpw = BM25_TPW;
+    while (tpw > 1 && (int64_t)nq * ((n_tiles + tpw - 1) / tpw) < 8192) tpw >>= 1;
+    *tpw_out = tpw;
+    *n_spans_out = (n_tiles + tpw - 1) / tpw;
+}
+
 hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms,
                            const int32_t* q_qtf, int q_first, int nq, double min_score, double* cand_score,
                            int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream,
                            const MsrSetView* set) {
     *n_seg = 0; *seg_stride = 0;
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    // A wave looks its query's terms up once and then walks `tpw` consecutive tiles with that plan in registers.  More tiles
-    // per wave amortise the lookups (chains of dependent loads) but leave fewer work items: large batches take 8, a single
-    // query one tile per wave (its ~1000 waves are all the parallelism it has).
-    int tpw = BM25_TPW;
-    while (tpw > 1 && (int64_t)nq * ((ix.n_tiles + tpw - 1) / tpw) < 8192) tpw >>= 1;
-    const int n_spans = (ix.n_tiles + tpw - 1) / tpw;
+    int tpw = 1, n_spans = 0;
+    msr_bm25_split(ix.n_tiles, nq, &tpw, &n_spans);
     const int64_t items = (int64_t)nq * n_spans;
     if (items >= (1ll << 31)) return hipErrorInvalidValue;
     *n_seg = n_spans;

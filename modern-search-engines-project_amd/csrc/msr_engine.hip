@@ -886,6 +886,19 @@ extern "C" int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, co
                           out_n, stream, set_bits, n_sets, set_stride, q_set);
 }
 
+extern "C" int msr_debug_bm25_split(msr_engine* e, int32_t n_queries, int32_t* tiles_per_item, int32_t* n_segments) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_debug_bm25_split: postings not bound");
+    if (n_queries < 1 || n_queries > e->cfg.max_queries || !tiles_per_item || !n_segments)
+        return fail(e, MSR_ERR_INVALID, "msr_debug_bm25_split: bad argument (n_queries=%d, max_queries=%d)", n_queries,
+                    e->cfg.max_queries);
+    int tpw = 1, n_spans = 0;
+    msr_bm25_split(e->bm25.n_tiles, n_queries, &tpw, &n_spans);
+    *tiles_per_item = tpw;
+    *n_segments = n_spans;
+    return MSR_OK;
+}
+
 // K10: BM25 scores of named documents (everything read was built by msr_bind_postings; no engine scratch)
 extern "C" int msr_bm25_score_docs(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
                                    int32_t n_queries, const int32_t* doc, const int32_t* doc_n, int32_t max_docs,

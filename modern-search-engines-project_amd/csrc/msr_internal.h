@@ -143,6 +143,9 @@ hipError_t msr_bm25_build_skip(const Bm25Index& ix, const int32_t* heavy_terms, 
 int msr_bm25_max_segments(int64_t n_docs);
 hipError_t msr_bm25_window(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
                            int q_first, int nq, uint64_t* out /*[nq]: see msr_select_topk_list*/, hipStream_t stream);
+// The work split of msr_bm25_scores for one slice of nq queries over n_tiles document tiles: *tpw consecutive tiles per wave
+// (1, 2, 4 or 8) and *n_spans = ceil(n_tiles / *tpw) spans -- the n_seg / seg_stride (= *tpw * MSR_BM25_TILE) of the lists.
+void msr_bm25_split(int n_tiles, int nq, int* tpw, int* n_spans);
 hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms,
                            const int32_t* q_qtf, int q_first, int nq, double min_score, double* cand_score,
                            int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream,

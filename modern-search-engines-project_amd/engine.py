@@ -251,6 +251,14 @@ class DeviceEngine:
                                                       _ptr(out_doc), _ptr(out_score), _ptr(out_n), self._stream()))
         return out_doc, out_score, out_n
 
+    def bm25_split(self, n_queries):
+        """(tiles per work item, segments per query) of the scoring kernel for ONE internal slice of n_queries queries
+        (1 .. max_queries) on the bound postings (msr_debug_bm25_split: launches nothing).  For tests that must know which
+        split a call ran; results never depend on it."""
+        tpw, n_seg = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.msr_debug_bm25_split(self.handle, int(n_queries), C.byref(tpw), C.byref(n_seg)))
+        return int(tpw.value), int(n_seg.value)
+
     # ------------------------------------------------------------------ hybrid candidates (msr_bm25_point.hip)
     def bm25_score_docs(self, term_lists, doc, doc_n=None, packed=None):
         """BM25 scores of NAMED documents (msr_bm25_score_docs): doc int32 [Q, M] document indices, doc_n int32 [Q] valid
