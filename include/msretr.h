@@ -35,13 +35,15 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 9         /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 10        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
-                                     9: msr_debug_bm25_split */
+                                     9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
+                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES) */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
 #define MSR_RERANK_MAX_CHUNKS 10  /* reranker_api.py:58 */
+#define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
     MSR_OK = 0,
@@ -197,6 +199,45 @@ int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, const int32_t
  * walks.  Results never depend on the split; the export exists so that tests can ASSERT which split a call ran instead of
  * assuming it.  MSR_ERR_NOT_BOUND without postings, MSR_ERR_INVALID for n_queries out of range or a NULL output. */
 int msr_debug_bm25_split(msr_engine* e, int32_t n_queries, int32_t* tiles_per_item, int32_t* n_segments);
+
+/* Test-only: the engine's own exact top-k select (its scratch, its kernels: what every *_topk entry point ends in) over RAW
+ * score rows of the caller, so that tests can steer it by the bit patterns of the scores.  Only enqueues; every array is a
+ * device pointer.  mode:
+ *   MSR_SELECT_F32         scores float  [n_queries][stride], row q = elements 0 .. n-1, element i = document i
+ *   MSR_SELECT_F64         the same over double rows
+ *   MSR_SELECT_F32_WITHIN  MSR_SELECT_F32 with query q restricted to set q_set[q] of set_bits [n_sets][set_stride] (bit d & 31
+ *                          of word d >> 5; q_set -1 = every document, any other value outside [0, n_sets) = none)
+ *   MSR_SELECT_F64_LIST    scores double / idx int32 [n_queries][stride]: row q is cut into n_seg segments seg_stride elements
+ *                          apart, segment s holds counts[q * n_seg + s] pairs (score, document idx) in any order from its first
+ *                          position on (n is ignored).  win_base (nullable, [n_queries]): the first pass bins the 20-bit key
+ *                          prefixes win_base[q] .. win_base[q] + 4095, both ends clamped (what msr_bm25_topk does with a bound
+ *                          derived from the query); the result never depends on it.
+ * Arguments a mode does not use are ignored.  gate (nullable): device word(s); where the word is 0 every kernel returns at once
+ * and the outputs (and out_state) of those queries are left as they were: gate_per64 = 0: gate[0] decides for all queries, else
+ * gate[q / 64] for query q.
+ * Result, rows of k: the k best VALID elements in the order (score descending, document ascending), out_n[q] = min(k, valid
+ * elements), (-1, -inf) behind it.  Valid: not NaN and not -inf; +inf is valid.  Scores come back bit for bit, except that
+ * -0.0 and +0.0 are ONE key: both order by document alone among themselves and come back as +0.0.
+ * out_state (nullable, [n_queries]): the select's per-query state after its streaming passes, before the final kernel (which
+ * does not write it back): done = 1: the candidates at or above the resolved prefix were compacted (n_above + the tie bin's
+ * members <= 4096, or fewer valid elements than k -- then n_sel < k is their number); done = 0: more than 4096 elements share
+ * the resolved prefix (or a window pass ended in a clamped bin: mask_hi = 0) and the final kernel resolves the remaining digits
+ * over the row itself.  mask_hi / mask_lo: the key bits resolved (score part / ~document part), pref_*: their values; n_above:
+ * elements strictly above the prefix; k_rem = k - n_above.
+ * Refused with MSR_ERR_INVALID before any launch: mode unknown; n_queries outside [1, max_queries]; k outside [1, max_k];
+ * scores or an output NULL; n < 0, n >= 2^31 or stride < n; list mode: idx or counts NULL, n_seg < 1, seg_stride < 0 or
+ * n_seg * seg_stride > stride; within mode: n_sets < 1, set_bits or q_set NULL, set_stride < ceil(n / 32). */
+enum { MSR_SELECT_F32 = 0, MSR_SELECT_F64 = 1, MSR_SELECT_F32_WITHIN = 2, MSR_SELECT_F64_LIST = 3 };
+typedef struct msr_select_state {
+    uint64_t pref_hi, mask_hi;
+    uint32_t pref_lo, mask_lo;
+    int32_t k_rem, n_above, done, n_sel;
+} msr_select_state;
+int msr_debug_select(msr_engine* e, int32_t mode, const void* scores, int64_t n, int64_t stride, int32_t n_queries, int32_t k,
+                     const int32_t* idx, const int32_t* counts, int32_t n_seg, int64_t seg_stride, const uint64_t* win_base,
+                     const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set, const int32_t* gate,
+                     int32_t gate_per64, int32_t* out_doc, void* out_score, int32_t* out_n, msr_select_state* out_state,
+                     void* stream);
 
 /* Hybrid candidates (dense hits join the BM25 list).
  *   msr_bm25_score_docs: the BM25 scores of NAMED documents -- a point lookup, no posting list is streamed.  Queries packed as
@@ -430,7 +471,16 @@ int msr_rerank_scatter(msr_engine* e, const int32_t* records, int64_t capacity_r
  * in_doc [n_parts][n_queries][k] i32 GLOBAL doc indices, in_score same shape (score_bits = 32: f32,
  * 64: f64), in_n [n_parts][n_queries].  Order: score desc, doc index asc -- identical on every rank.
  * Every part must be in that order already (what msr_bm25_topk / msr_dense_topk return, with doc indices made global by
- * adding the shard's base): the kernel merges sorted lists, it does not sort. */
+ * adding the shard's base): the kernel merges sorted lists, it does not sort.
+ *   - in_n[p][q] outside [0, k] is clamped to it.  An entry inside the counted prefix whose score is NaN or -inf is dropped
+ *     (the rest of its list is merged as if it were not there); out_n[q] = min(k, entries that remain), (-1, -inf) behind it.
+ *     -0.0 and +0.0 are one key and come back as +0.0.
+ *   - The same document in two lists (nothing a sharded run produces: a document has one owner) is NOT de-duplicated: both
+ *     entries are merged like any other; with equal scores they come out next to each other, and which of the two payloads
+ *     stands first is unspecified.
+ *   - Limit: n_parts <= 64, k <= MSR_MAX_K and pow2ceil(n_parts) * max(64, pow2ceil(k)) <= MSR_MERGE_MAX_ENTRIES (the merge
+ *     tree's layout in LDS: 8 x 1000, 16 x 512, 64 x 128 are served; 17 x 480 = 32 x 512 is not, although 17 * 480 <= 8192).
+ *     Anything else is refused with MSR_ERR_INVALID and a message naming the limit, before any launch, outputs untouched. */
 int msr_merge_topk(msr_engine* e, const int32_t* in_doc, const void* in_score, const int32_t* in_n,
                    int32_t n_parts, int32_t n_queries, int32_t k, int32_t score_bits, int32_t* out_doc,
                    void* out_score, int32_t* out_n, void* stream);

@@ -7,11 +7,13 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 9
+MSR_ABI_VERSION = 10
 MSR_CFG_NO_ROW_COPY = 1
 MSR_DIM = 768
 MSR_MAX_K = 1024
 MSR_RERANK_MAX_CHUNKS = 10
+MSR_MERGE_MAX_ENTRIES = 8192
+MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
 
 
 class MsrError(RuntimeError):
@@ -24,6 +26,11 @@ class MsrConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("dim", C.c_int32),
                 ("max_queries", C.c_int32), ("max_k", C.c_int32), ("rerank_max_docs", C.c_int32),
                 ("scan_layout", C.c_int32), ("scan_variant", C.c_int32), ("flags", C.c_int32)]
+
+
+class MsrSelectState(C.Structure):
+    _fields_ = [("pref_hi", C.c_uint64), ("mask_hi", C.c_uint64), ("pref_lo", C.c_uint32), ("mask_lo", C.c_uint32),
+                ("k_rem", C.c_int32), ("n_above", C.c_int32), ("done", C.c_int32), ("n_sel", C.c_int32)]
 
 
 class MsrRerankParams(C.Structure):
@@ -65,6 +72,8 @@ _SIGNATURES = {
     "msr_dense_topk_within": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P,
                                         _P]),
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,
+                                   _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     "msr_bm25_score_docs": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "msr_union_candidates": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     "msr_gather_rows": (C.c_int, [_P, _P, C.c_int32, _P, _P]),

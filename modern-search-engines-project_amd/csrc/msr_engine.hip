@@ -899,6 +899,57 @@ extern "C" int msr_debug_bm25_split(msr_engine* e, int32_t n_queries, int32_t* t
     return MSR_OK;
 }
 
+// Test-only: the engine's own select (e->sel and the internal entry points of msr_topk.hip, nothing else) over a caller's raw
+// score rows, and the SelState of every query as the streaming passes left it (msretr.h).
+extern "C" int msr_debug_select(msr_engine* e, int32_t mode, const void* scores, int64_t n, int64_t stride, int32_t n_queries,
+                                int32_t k, const int32_t* idx, const int32_t* counts, int32_t n_seg, int64_t seg_stride,
+                                const uint64_t* win_base, const uint32_t* set_bits, int32_t n_sets, int64_t set_stride,
+                                const int32_t* q_set, const int32_t* gate, int32_t gate_per64, int32_t* out_doc, void* out_score,
+                                int32_t* out_n, msr_select_state* out_state, void* stream) {
+    static_assert(sizeof(msr_select_state) == sizeof(SelState), "msr_select_state mirrors SelState");
+    if (!e) return MSR_ERR_INVALID;
+    if (mode < MSR_SELECT_F32 || mode > MSR_SELECT_F64_LIST)
+        return fail(e, MSR_ERR_INVALID, "msr_debug_select: bad argument (mode=%d)", mode);
+    if (n_queries < 1 || n_queries > e->cfg.max_queries || k < 1 || k > e->cfg.max_k)
+        return fail(e, MSR_ERR_INVALID, "msr_debug_select: bad argument (n_queries=%d, max_queries=%d, k=%d, max_k=%d)", n_queries,
+                    e->cfg.max_queries, k, e->cfg.max_k);
+    if (!scores || !out_doc || !out_score || !out_n || n < 0 || n >= (1ll << 31) || stride < n)
+        return fail(e, MSR_ERR_INVALID, "msr_debug_select: bad argument (NULL scores or output, or n=%lld, stride=%lld)",
+                    (long long)n, (long long)stride);
+    if (mode == MSR_SELECT_F64_LIST && (!idx || !counts || n_seg < 1 || seg_stride < 0 || (int64_t)n_seg * seg_stride > stride))
+        return fail(e, MSR_ERR_INVALID, "msr_debug_select: bad argument (list: idx or counts NULL, n_seg=%d < 1, or n_seg * "
+                    "seg_stride=%lld > stride=%lld)", n_seg, (long long)seg_stride, (long long)stride);
+    if (mode == MSR_SELECT_F32_WITHIN &&
+        (n_sets < 1 || !set_bits || !q_set || set_stride < (n + 31) / 32))
+        return fail(e, MSR_ERR_INVALID, "msr_debug_select: bad argument (within: n_sets=%d < 1, set_bits or q_set NULL, or "
+                    "set_stride=%lld < ceil(n / 32))", n_sets, (long long)set_stride);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    SelScratch sel = e->sel;
+    sel.gate = gate;
+    sel.gate_per64 = gate && gate_per64 ? 1 : 0;
+    switch (mode) {
+    case MSR_SELECT_F32:
+        HIP_TRY(e, msr_select_topk(32, scores, n, stride, n_queries, k, sel, out_doc, out_score, out_n, st));
+        break;
+    case MSR_SELECT_F64:
+        HIP_TRY(e, msr_select_topk(64, scores, n, stride, n_queries, k, sel, out_doc, out_score, out_n, st));
+        break;
+    case MSR_SELECT_F32_WITHIN: {
+        const MsrSetView set{set_bits, set_stride, q_set, n_sets};
+        HIP_TRY(e, msr_select_topk_within((const float*)scores, n, stride, n_queries, k, sel, set, out_doc, (float*)out_score,
+                                          out_n, st));
+        break;
+    }
+    default:
+        HIP_TRY(e, msr_select_topk_list((const double*)scores, idx, counts, n_seg, seg_stride, stride, n_queries, k, sel, out_doc,
+                                        (double*)out_score, out_n, st, win_base));
+    }
+    if (out_state)
+        HIP_TRY(e, hipMemcpyAsync(out_state, e->sel.state, (size_t)n_queries * sizeof(SelState), hipMemcpyDeviceToDevice, st));
+    return MSR_OK;
+}
+
 // K10: BM25 scores of named documents (everything read was built by msr_bind_postings; no engine scratch)
 extern "C" int msr_bm25_score_docs(msr_engine* e, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
                                    int32_t n_queries, const int32_t* doc, const int32_t* doc_n, int32_t max_docs,
@@ -1578,9 +1629,18 @@ extern "C" int msr_merge_topk_payload(msr_engine* e, const int32_t* in_doc, cons
                                       int32_t* out_n, int32_t* out_payload, void* stream) {
     if (!e) return MSR_ERR_INVALID;
     if (!in_doc || !in_score || !in_n || !out_doc || !out_score || !out_n || n_parts < 1 || n_parts > 64 ||
-        n_queries < 0 || k < 1 || k > MSR_MAX_K || (score_bits != 32 && score_bits != 64) || (int64_t)n_parts * k > 8192 ||
+        n_queries < 0 || k < 1 || k > MSR_MAX_K || (score_bits != 32 && score_bits != 64) ||
         (in_payload != nullptr) != (out_payload != nullptr) || part_stride_bytes < 0 || (part_stride_bytes & 7))
         return fail(e, MSR_ERR_INVALID, "msr_merge_topk: bad argument (n_parts=%d, k=%d)", n_parts, k);
+    {   // the merge tree's LDS layout: n_parts rounded up to a power of two lists of k rounded up to a power of two (>= 64) entries
+        int64_t lists = 1, entries = 64;
+        while (lists < n_parts) lists <<= 1;
+        while (entries < k) entries <<= 1;
+        if (lists * entries > MSR_MERGE_MAX_ENTRIES)
+            return fail(e, MSR_ERR_INVALID, "msr_merge_topk: n_parts=%d x k=%d needs %lld lists x %lld entries (both rounded up to "
+                        "powers of two) = %lld > the limit of %d entries", n_parts, k, (long long)lists, (long long)entries,
+                        (long long)(lists * entries), MSR_MERGE_MAX_ENTRIES);
+    }
     if (n_queries == 0) return MSR_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_merge_lists(score_bits, in_doc, in_score, in_n, in_payload, n_parts, part_stride_bytes, n_queries, k, out_doc,

@@ -584,7 +584,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void merge_kernel(const int32_t* __re
     uint64_t* khi = (uint64_t*)smem;
     uint32_t* klo = (uint32_t*)(smem + (size_t)P * 8);
     int32_t* pay = (int32_t*)(smem + (size_t)P * 12);            // (only touched when in_pay is given)
-    __shared__ int n_valid;
+    __shared__ int n_valid, n_bad;
     // part p of every array starts pstride BYTES after part p - 1 (pstride = 0: the parts are contiguous arrays)
     auto part = [&](const auto* base, int p, int64_t elems) {
         typedef decltype(base) PT;
@@ -597,7 +597,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void merge_kernel(const int32_t* __re
             s += c < 0 ? 0 : (c > k ? k : c);
         }
         n_valid = s;
+        n_bad = 0;
     }
+    __syncthreads();
     for (int i = threadIdx.x; i < P; i += SCAN_THREADS) {
         uint64_t h = 0; uint32_t l = 0; int32_t v = -1;
         const int p = i >> lg, r = i & (Pk - 1);
@@ -610,6 +612,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void merge_kernel(const int32_t* __re
                     h = ScoreTraits<T>::ord(s);
                     l = ~(uint32_t)part(in_doc, p, (int64_t)nq * k)[off];
                     if (in_pay) v = part(in_pay, p, (int64_t)nq * k)[off];
+                } else {
+                    atomicAdd(&n_bad, 1);                         // (LDS; an invalid score inside a counted prefix: rare)
                 }
             }
         }
@@ -617,7 +621,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void merge_kernel(const int32_t* __re
         if (in_pay) pay[i] = v;
     }
     __syncthreads();
-    for (int step = 1; step < NP; step <<= 1) {                   // lists a = 2 m step and b = a + step -> a
+    // An invalid score (NaN, -inf) inside a counted prefix is dropped: it leaves a hole -- the smallest key -- in its list, which
+    // is then no longer sorted, and the merge tree's compare-exchange stages assume sorted lists.  Such a query gets a full sort
+    // of all P entries instead (91 stages for 8192 entries: slow, exact, and nothing a sharded run produces).
+    const bool holes = n_bad > 0;
+    if (holes) {
+        if (in_pay) msr_sort::bitonic_sort<SCAN_THREADS, true>(khi, klo, (uint32_t*)pay, P, false);
+        else msr_sort::bitonic_sort<SCAN_THREADS, false>(khi, klo, nullptr, P, false);
+    }
+    for (int step = 1; step < NP && !holes; step <<= 1) {         // lists a = 2 m step and b = a + step -> a
         const int n_pairs = NP / (2 * step);
         for (int idx = threadIdx.x; idx < (n_pairs << lg); idx += SCAN_THREADS) {
             const int m = idx >> lg, i = idx & (Pk - 1);
@@ -644,7 +656,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void merge_kernel(const int32_t* __re
             stage_sync(j, j > 1 ? j >> 1 : Pk);                   // (after j = 1: the next round's maximum stage, or the output)
         }
     }
-    const int n_sel = n_valid < k ? n_valid : k;
+    const int n_sel = n_valid - n_bad < k ? n_valid - n_bad : k;
     for (int i = threadIdx.x; i < k; i += SCAN_THREADS) {
         const bool ok = i < n_sel && !(khi[i] == 0 && klo[i] == 0);
         out_doc[(int64_t)q * k + i] = ok ? (int32_t)~klo[i] : -1;

@@ -259,6 +259,44 @@ class DeviceEngine:
         self._check(self.lib.msr_debug_bm25_split(self.handle, int(n_queries), C.byref(tpw), C.byref(n_seg)))
         return int(tpw.value), int(n_seg.value)
 
+    SELECT_STATE = np.dtype([("pref_hi", "<u8"), ("mask_hi", "<u8"), ("pref_lo", "<u4"), ("mask_lo", "<u4"), ("k_rem", "<i4"),
+                             ("n_above", "<i4"), ("done", "<i4"), ("n_sel", "<i4")])
+
+    def debug_select(self, scores, k, n=None, idx=None, counts=None, seg_stride=0, win_base=None, set_bits=None, q_set=None,
+                     gate=None, gate_per64=False, out=None):
+        """Test-only (msr_debug_select): the engine's own select over raw score rows.  scores: device tensor [Q, stride],
+        float32 or float64, row q = its first n elements (default: the whole row).  Lists (float64 only): idx int32
+        [Q, stride], counts int32 [Q, n_seg], seg_stride, optional win_base int64 [Q] (the bits of the uint64 anchors).
+        Within (float32 only): set_bits int32 [n_sets, words], q_set int32 [Q].  gate: int32 device word(s).  out: optional
+        (doc, score, n) tensors to write into (a gated-off call leaves them alone).
+        -> (doc int32 [Q, k], score [Q, k], n int32 [Q], state: numpy record array [Q] of SELECT_STATE, as the streaming
+        passes left it).  Synchronises (the state is copied to the host)."""
+        assert scores.is_cuda and scores.dim() == 2 and scores.is_contiguous()
+        Q, stride = int(scores.shape[0]), int(scores.shape[1])
+        f64 = scores.dtype == torch.float64
+        if idx is not None:
+            mode = _abi.MSR_SELECT_F64_LIST
+        elif set_bits is not None:
+            mode = _abi.MSR_SELECT_F32_WITHIN
+        else:
+            mode = _abi.MSR_SELECT_F64 if f64 else _abi.MSR_SELECT_F32
+        assert f64 == (mode in (_abi.MSR_SELECT_F64, _abi.MSR_SELECT_F64_LIST)) and scores.dtype in (torch.float32, torch.float64)
+        n_seg = int(counts.shape[1]) if counts is not None else 0
+        n_sets, set_stride = (int(set_bits.shape[0]), int(set_bits.shape[1])) if set_bits is not None else (0, 0)
+        if out is None:
+            out = (torch.empty((Q, k), dtype=torch.int32, device=self.device),
+                   torch.empty((Q, k), dtype=scores.dtype, device=self.device),
+                   torch.empty((Q,), dtype=torch.int32, device=self.device))
+        out_doc, out_score, out_n = out
+        state = torch.zeros((max(Q, 1) * self.SELECT_STATE.itemsize,), dtype=torch.uint8, device=self.device)
+        keep = [t.contiguous() if t is not None else None for t in (idx, counts, win_base, set_bits, q_set, gate)]
+        self._check(self.lib.msr_debug_select(
+            self.handle, mode, _ptr(scores), stride if n is None else int(n), stride, Q, int(k), _ptr(keep[0]), _ptr(keep[1]),
+            n_seg, int(seg_stride), _ptr(keep[2]), _ptr(keep[3]), n_sets, set_stride, _ptr(keep[4]), _ptr(keep[5]),
+            1 if gate_per64 else 0, _ptr(out_doc), _ptr(out_score), _ptr(out_n), _ptr(state), self._stream()))
+        st = state.cpu().numpy().view(self.SELECT_STATE)[:Q].copy()
+        return out_doc, out_score, out_n, st
+
     # ------------------------------------------------------------------ hybrid candidates (msr_bm25_point.hip)
     def bm25_score_docs(self, term_lists, doc, doc_n=None, packed=None):
         """BM25 scores of NAMED documents (msr_bm25_score_docs): doc int32 [Q, M] document indices, doc_n int32 [Q] valid
