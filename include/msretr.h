@@ -35,10 +35,10 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 10        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 11        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
-                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES) */
+                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -533,6 +533,14 @@ int msr_merge_postings(const int64_t* a_term_off, int64_t a_terms, const int32_t
 int msr_compact_postings(const int64_t* term_off, int64_t n_terms, const int32_t* post_doc, const int32_t* post_tf,
                          const uint8_t* keep, int64_t n_docs, int64_t* out_term_off, int32_t* out_doc, int32_t* out_tf,
                          int64_t capacity, int64_t* n_postings, void* stream);
+
+/* Test-only: the exclusive scan the index build and the compaction share (its kernels, its scratch sized by the one helper
+ * both use), over an int64 array of the caller, so that tests can run it at its level boundaries (4096 elements per block: two
+ * levels above 4096 elements, three above 4096^2) without building an index of that size.  OFFLINE and handle-less like
+ * msr_build_postings: allocates its scratch, synchronises and frees.  out[i] <- in[0] + .. + in[i - 1] for i < n (nothing
+ * behind out[n - 1] is written); *total (device pointer, nullable) <- the sum of all n elements (0 for n = 0).  in / out are
+ * device pointers to n elements and may not overlap.  MSR_ERR_INVALID for n < 0 or, with n > 0, a NULL in or out. */
+int msr_debug_exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, void* stream);
 
 /* Timing hooks for bench.py: while enabled, every launch of the dominant kernels is bracketed by a
  * hipEvent pair recorded on the caller's stream (ring of 256 launches per kernel).  msr_kernel_time_ms

@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 10
+MSR_ABI_VERSION = 11
 MSR_CFG_NO_ROW_COPY = 1
 MSR_DIM = 768
 MSR_MAX_K = 1024
@@ -107,6 +107,7 @@ _SIGNATURES = {
     "msr_merge_postings": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, C.c_int64,
                                      C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "msr_compact_postings": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
+    "msr_debug_exclusive_scan": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "msr_set_timing": (C.c_int, [_P, C.c_int32]),
     "msr_tune": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "msr_kernel_time_ms": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

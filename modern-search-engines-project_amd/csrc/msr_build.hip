@@ -15,8 +15,9 @@
 //   3. combine_kernel     only when a document was longer than one chunk: its chunks' entries of one term are adjacent
 //                         after the sort; add their tf into the first and drop the rest.
 //   4. df / term_off      term boundaries of the sorted entries give doc_freq without atomics; exclusive scan -> offsets.
-// scan: three-kernel exclusive scan (4096 per block, block sums scanned by one block, offsets added), used for the chunk
-// counts, the radix histograms (bin-major [256][blocks]) and doc_freq.
+// scan: three-kernel exclusive scan (4096 per block; the block sums scanned the same way, a third level above 4096^2
+// elements; offsets added), used for the chunk counts, the radix histograms (bin-major [256][blocks]), the keep flags of
+// the chunk merge and doc_freq.  Its scratch is sized by exclusive_scan_tmp_words (msr_internal.h) for the largest of them.
 //
 // This is an offline step: the entry point allocates its workspace, synchronises, and returns the number of postings.
 #include <hip/hip_runtime.h>
@@ -99,6 +100,27 @@ hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* t
     }
     if (total) scan_total_kernel<<<1, 1, 0, st>>>(in, out, n, total);
     return hipGetLastError();
+}
+
+// Test-only (msretr.h): the product exclusive_scan over a caller's array, its scratch sized by exclusive_scan_tmp_words.
+extern "C" int msr_debug_exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, void* stream) {
+    if (n < 0 || (n > 0 && (!in || !out)))
+        return msr_fail_global(MSR_ERR_INVALID, "msr_debug_exclusive_scan: bad argument (n=%lld, or NULL in / out)", (long long)n);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = MSR_OK;
+    if (n > 0) {   // handle-less entry point: run on the device that holds the caller's arrays
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, in) == hipSuccess && attr.type == hipMemoryTypeDevice) (void)hipSetDevice(attr.device);
+        else (void)hipGetLastError();
+    }
+    int64_t* d_tmp = nullptr;
+    BUILD_TRY(hipMalloc((void**)&d_tmp, (size_t)std::max<int64_t>(exclusive_scan_tmp_words(n), 1) * 8));
+    BUILD_TRY(exclusive_scan(in, n, out, d_tmp, total, st));
+    BUILD_TRY(hipStreamSynchronize(st));
+done:
+    (void)hipStreamSynchronize(st);
+    if (d_tmp) (void)hipFree(d_tmp);
+    return rc;
 }
 
 namespace {
@@ -307,7 +329,10 @@ extern "C" int msr_build_postings(const int64_t* tok_off, const int32_t* tok_ids
         *n_postings = 0;
         return MSR_OK;
     }
-    tmp_words = 4 * ((std::max<int64_t>(std::max<int64_t>(n_chunks, n_terms + 1), 256 * ((n_tok + RB - 1) / RB + 1)) + SB - 1) / SB + 4) + 64;
+    // one scratch for every scan below: the chunk counts, the radix histograms (256 per block of <= n_tok entries), the keep
+    // flags of the chunk merge (<= n_tok entries) and doc_freq; + the flag word of the id check
+    tmp_words = exclusive_scan_tmp_words(std::max(std::max<int64_t>(n_chunks, (int64_t)n_terms + 1),
+                                                  std::max<int64_t>(256 * ((n_tok + RB - 1) / RB), n_tok))) + 1;
     BUILD_TRY(hipMalloc((void**)&d_cstart, n_chunks * 8));
     BUILD_TRY(hipMalloc((void**)&d_clen, n_chunks * 4));
     BUILD_TRY(hipMalloc((void**)&d_cdoc, n_chunks * 4));
@@ -320,7 +345,7 @@ extern "C" int msr_build_postings(const int64_t* tok_off, const int32_t* tok_ids
     BUILD_TRY(hipMemcpyAsync(d_cdoc, c_doc.data(), n_chunks * 4, hipMemcpyHostToDevice, st));
     {   // every token id inside [0, n_terms): checked on the device before anything is indexed with one
         int32_t h_bad = 0;
-        int32_t* d_bad = (int32_t*)(d_tmp + tmp_words - 1);      // (the last word of the scan scratch: unused by the scans)
+        int32_t* d_bad = (int32_t*)(d_tmp + tmp_words - 1);      // (the word behind the scan scratch)
         BUILD_TRY(hipMemsetAsync(d_bad, 0, 4, st));
         id_range_kernel<<<1024, 256, 0, st>>>(tok_ids, n_tok, n_terms, d_bad);
         BUILD_TRY(hipGetLastError());

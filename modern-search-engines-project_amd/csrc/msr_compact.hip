@@ -250,10 +250,7 @@ extern "C" int msr_compact_postings(const int64_t* term_off, int64_t n_terms, co
     if (P < 0) { rc = msr_fail_global(MSR_ERR_INVALID, "msr_compact_postings: %s", why[F_OFFSETS]); goto done; }
     if (P > 0 && (!post_doc || !post_tf)) { rc = msr_fail_global(MSR_ERR_INVALID, "msr_compact_postings: null posting array"); goto done; }
     n_tiles = (P + TILE - 1) / TILE;
-    {
-        const int64_t n = std::max<int64_t>(std::max<int64_t>(n_blk, n_tiles), 1);
-        n_tmp = 2 * ((n + MSR_SCAN_BLOCK - 1) / MSR_SCAN_BLOCK) + 2 * ((n + MSR_SCAN_BLOCK - 1) / MSR_SCAN_BLOCK / MSR_SCAN_BLOCK + 1) + 16;
-    }
+    n_tmp = exclusive_scan_tmp_words(std::max(n_blk, n_tiles));          // both scans share the scratch
     COMPACT_TRY(hipMalloc((void**)&d_flag, 4));
     COMPACT_TRY(hipMalloc((void**)&d_tmp, (size_t)(n_tmp + 1) * 8));      // + the total
     COMPACT_TRY(hipMalloc((void**)&d_tcnt, (size_t)std::max<int64_t>(n_tiles, 1) * 8));

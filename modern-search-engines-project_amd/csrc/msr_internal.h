@@ -86,10 +86,18 @@ int msr_fail_global(int code, const char* fmt, ...);
 
 // ---- K7: offline index build / update ----------------------------------------------------------------
 // out[0..n) = exclusive scan of in[0..n) (msr_build.hip: three kernels, MSR_SCAN_BLOCK elements per block); tmp: >=
-// 2 * ceil(n / MSR_SCAN_BLOCK) + 2 * ceil(n / MSR_SCAN_BLOCK^2) + 8 words.  *total (device, nullable) <- sum of all
-// elements.  Two levels: n <= MSR_SCAN_BLOCK^3.
+// exclusive_scan_tmp_words(n) words.  *total (device, nullable) <- sum of all elements.  Up to three levels:
+// n <= MSR_SCAN_BLOCK^3.
 constexpr int MSR_SCAN_BLOCK = 4096;
 hipError_t exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* tmp, int64_t* total, hipStream_t st);
+// Words of scratch exclusive_scan needs for n elements: the block sums and their scan (ceil(n / MSR_SCAN_BLOCK) each), the
+// sums of those and their scan (ceil(n / MSR_SCAN_BLOCK^2) each).  Nondecreasing in n: scratch sized for the largest n of
+// several scans serves them all.  Every caller sizes its scratch with this (and adds its own words behind it).
+inline int64_t exclusive_scan_tmp_words(int64_t n) {
+    if (n <= 0) return 0;
+    const int64_t nb = (n + MSR_SCAN_BLOCK - 1) / MSR_SCAN_BLOCK, nb2 = (nb + MSR_SCAN_BLOCK - 1) / MSR_SCAN_BLOCK;
+    return 2 * nb + 2 * nb2;
+}
 
 // ---- K1: BM25 term-at-a-time ----------------------------------------------------------------------
 // One posting as the scoring kernel streams it (engine-owned copy, built at bind): the document and the posting's

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from index_cases import table
 from msretr import _abi
 from msretr.chunk_index import ChunkTable, attach_chunks
 from msretr.index import DIM, _np
@@ -15,22 +16,6 @@ from msretr.index_build import bm25_add_token_ids, bm25_index_from_token_ids, co
 pytestmark = pytest.mark.gpu
 TILE = 2048                                                  # postings per workgroup of msr_compact.hip
 TABLES = ("doc_ids", "doc_len", "term_off", "post_doc", "post_tf", "idf")
-
-
-def table(rng, n_docs, n_terms, n_post, head=0, empty_tail=0):
-    """CSR of n_post postings over [0, n_docs) x [0, n_terms) (+ a head term 0 holding the first `head` documents, + the
-    last `empty_tail` terms without postings), documents ascending inside a term."""
-    live = n_terms - empty_tail
-    keys = np.unique(rng.integers(0, live * n_docs, int(n_post * 1.3) + 16))
-    keys = np.sort(rng.choice(keys, min(n_post, len(keys)), replace=False))
-    term, doc = keys // n_docs, keys % n_docs
-    if head:
-        keep = term != 0
-        term = np.concatenate([np.zeros(head, np.int64), term[keep]])
-        doc = np.concatenate([np.arange(head), doc[keep]])
-    off = np.zeros(n_terms + 1, np.int64)
-    off[1:] = np.cumsum(np.bincount(term, minlength=n_terms))
-    return off, doc.astype(np.int32), rng.integers(1, 50, len(doc)).astype(np.int32)
 
 
 def check(t, keep):

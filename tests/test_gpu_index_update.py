@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from index_cases import maps, side
 from msretr import _abi
 from msretr.chunk_index import ChunkTable, attach_chunks
 from msretr.engine import DeviceEngine
@@ -16,32 +17,6 @@ from msretr.index_build import bm25_add_token_ids, bm25_index_from_token_ids, me
 pytestmark = pytest.mark.gpu
 TILE = 2048                                                  # outputs per workgroup of msr_merge.hip
 TABLES = ("doc_ids", "doc_len", "term_off", "post_doc", "post_tf", "idf")
-
-
-def side(rng, n_docs, n_terms, n_post, head=0, first_term=0):
-    """CSR of exactly n_post postings over [0, n_docs) x [first_term, n_terms) (+ a head term 0 holding the first `head`
-    documents), documents ascending inside a term."""
-    span = (n_terms - first_term) * n_docs
-    keys = np.unique(rng.integers(0, span, int(n_post * 1.3) + 16))
-    keys = np.sort(rng.choice(keys, min(n_post, len(keys)), replace=False))
-    term = keys // n_docs + first_term
-    doc = keys % n_docs
-    if head:
-        keep = term != 0
-        term = np.concatenate([np.zeros(head, np.int64), term[keep]])
-        doc = np.concatenate([np.arange(head), doc[keep]])
-    off = np.zeros(n_terms + 1, np.int64)
-    off[1:] = np.cumsum(np.bincount(term, minlength=n_terms))
-    tf = rng.integers(1, 50, len(doc))
-    return off, doc.astype(np.int32), tf.astype(np.int32)
-
-
-def maps(rng, na, nb, pattern):
-    if pattern == "appended":
-        return None, np.arange(na, na + nb, dtype=np.int32)
-    b = np.sort(rng.choice(na + nb, nb, replace=False)).astype(np.int32)
-    a = np.setdiff1d(np.arange(na + nb), b).astype(np.int32)
-    return a, b
 
 
 def check_merge(a, a_map, b, b_map, n_terms, n_docs, a_docs):
