@@ -35,14 +35,15 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 11        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 12        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
-                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan */
+                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
 #define MSR_RERANK_MAX_CHUNKS 10  /* reranker_api.py:58 */
+#define MSR_TERMSET_SPAN_DOCS 8192 /* msr_term_sets: consecutive documents one work item of its kernel owns (a multiple of 1024) */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -191,6 +192,32 @@ int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, const int32_t
                          int32_t n_queries, int32_t k, double min_score,
                          const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
                          int32_t* out_doc, double* out_score, int32_t* out_n, void* stream);
+
+/* Document sets built from posting lists: the producer of the rows that the *_within calls and
+ * msr_dense_topk_grouped consume.  Row r of out_bits (rows out_stride words apart, the layout above: document d is bit d & 31
+ * of word d >> 5) becomes
+ *     base(r)  AND  D(t) for every must term t of row r  AND NOT  D(t) for every not term t of row r
+ * with D(t) the documents of term t's bound posting list; row r's must terms are must_terms[must_off[r] .. must_off[r + 1]),
+ * its not terms not_terms[not_off[r] .. not_off[r + 1]) (int32 offsets from 0, n_rows + 1 of each; lists of any length --
+ * this is not msr_bm25_topk's MSR_MAX_QUERY_TERMS plan).  Conventions:
+ *   - a must term outside [0, n_terms), or with an empty list, makes the row empty;
+ *   - a not term outside [0, n_terms), or with an empty list, is ignored;
+ *   - repeated terms are allowed; a term in both lists makes the row empty; an empty must list means "all documents";
+ *   - base(r) follows q_set's rules: row_base[r] == -1, or n_base == 0 (base_bits / row_base are then not read), is every
+ *     document; a value in [0, n_base) picks that row of base_bits (n_base rows base_stride words apart); any other value is
+ *     the empty set, and no row outside the n_base rows is read.
+ * Every word [0, ceil(n_docs / 32)) of every row is written (the buffer need not be zeroed), bits at or above n_docs are 0,
+ * words [ceil(n_docs / 32), out_stride) are not touched.  out_bits must not alias base_bits.  Repeated calls give the same
+ * bytes.  The call only enqueues on `stream` (every array is a device pointer; the offsets are read on the device) and keeps
+ * no scratch in the engine.  Refused with MSR_ERR_INVALID before any launch, outputs untouched: n_rows < 0; with n_rows > 0 a
+ * NULL out_bits, must_off or not_off; out_stride < ceil(n_docs / 32); n_base < 0; with n_base > 0 a NULL base_bits or
+ * row_base, or base_stride < ceil(n_docs / 32).  MSR_ERR_NOT_BOUND without postings.  n_rows == 0 succeeds and launches
+ * nothing.  Cost: 4 bytes read per posting of every listed term (less what an already empty span of MSR_TERMSET_SPAN_DOCS
+ * documents skips) plus the base rows, 4 ceil(n_docs / 32) bytes written per row. */
+int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_off, const int32_t* must_terms,
+                  const int32_t* not_off, const int32_t* not_terms,
+                  const uint32_t* base_bits, int32_t n_base, int64_t base_stride, const int32_t* row_base,
+                  uint32_t* out_bits, int64_t out_stride, void* stream);
 
 /* Read-only, launches nothing: how msr_bm25_topk(_within) splits the work of ONE internal slice of n_queries queries
  * (1 <= n_queries <= max_queries; a call of more queries runs slices of max_queries and one of the rest) over the bound

@@ -11,7 +11,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 from .engine import DeviceEngine
 from .index import CorpusIndex
-from .text import simple_tokenize
+from .text import parse_operators, simple_tokenize
 
 
 class BM25:
@@ -70,10 +70,24 @@ class BM25:
         return self.score_terms(self._tokenize(query), doc_ids)
 
     # -- the reference's method ------------------------------------------------------------------------
-    def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None):
+    def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
+               must=None, must_not=None):
+        """operators=True: `+word` / `-word` tokens of the query are required / excluded words (text.parse_operators; the
+        query is taken as it is -- no city is appended here); must / must_not: further term strings (or ids) every result
+        must / must not contain.  Both restrict the documents on the device (DeviceEngine.term_sets), inside `within`."""
+        if operators:
+            query, m_words, x_words = parse_operators(query)
         query_terms = self._tokenize(query)
         if not query_terms:
             return []                                              # bm25_indexer.py:396-397
+        if operators or must is not None or must_not is not None:
+            m, x = list(must or ()), list(must_not or ())
+            if operators:
+                m += [t for w in m_words for t in self._tokenize(w)]
+                x += [t for w in x_words for t in self._tokenize(w)]
+            if m or x:
+                within = self.engine.term_sets([self.index.term_ids(m)], [self.index.term_ids(x)],
+                                               within=None if within is None else [within])
         return self._finish(self.search_terms(query_terms, top_k, min_score, within=within))
 
     def _finish(self, ranked):

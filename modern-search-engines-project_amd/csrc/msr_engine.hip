@@ -886,6 +886,30 @@ extern "C" int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, co
                           out_n, stream, set_bits, n_sets, set_stride, q_set);
 }
 
+extern "C" int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_off, const int32_t* must_terms,
+                             const int32_t* not_off, const int32_t* not_terms, const uint32_t* base_bits, int32_t n_base,
+                             int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_term_sets: postings not bound");
+    const int64_t W = (e->bm25.n_docs + 31) / 32;
+    if (n_rows < 0 || n_base < 0) return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (n_rows=%d, n_base=%d)", n_rows, n_base);
+    if (n_rows > 0 && (!out_bits || !must_off || !not_off))
+        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (out_bits, must_off or not_off is NULL with n_rows=%d)", n_rows);
+    if (out_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)out_stride, (long long)W);
+    if (n_base > 0 && (!base_bits || !row_base))
+        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (base_bits or row_base is NULL with n_base=%d)", n_base);
+    if (n_base > 0 && base_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (base_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)base_stride, (long long)W);
+    if (n_rows == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_term_sets_run(e->bm25, n_rows, must_off, must_terms, not_off, not_terms, base_bits, n_base, base_stride,
+                                 row_base, out_bits, out_stride, (hipStream_t)stream));
+    return MSR_OK;
+}
+
 extern "C" int msr_debug_bm25_split(msr_engine* e, int32_t n_queries, int32_t* tiles_per_item, int32_t* n_segments) {
     if (!e) return MSR_ERR_INVALID;
     if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_debug_bm25_split: postings not bound");

@@ -174,6 +174,12 @@ hipError_t msr_union_lists(int nq, const int32_t* lex_doc, const double* lex_sco
                            int32_t* out_doc, double* out_score, int32_t* out_src, int32_t* out_n, int max_cand,
                            hipStream_t stream);
 
+// K11 (msr_termset.hip): rows of document sets from posting lists (see msretr.h msr_term_sets; arguments checked by the caller).
+hipError_t msr_term_sets_run(const Bm25Index& ix, int n_rows, const int32_t* must_off, const int32_t* must_terms,
+                             const int32_t* not_off, const int32_t* not_terms, const uint32_t* base_bits, int n_base,
+                             int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride,
+                             hipStream_t stream);
+
 // *flag (device) <- 0x7F7F7F7F if the CSR is well formed, else the lowest violated rule number (msr_bm25.hip).
 hipError_t msr_bm25_validate(const Bm25Index& ix, int32_t* flag, hipStream_t stream);
 

@@ -134,6 +134,20 @@ class DocSet:
         hit = np.array([h in exact or h.endswith(suffixes) for h in hosts] + [False], bool)
         return cls(ix, hit[host_id])                  # (host id -1 picks the trailing False)
 
+    @classmethod
+    def from_words(cls, ix, words):
+        """The inverse of words(): uint32 (or int32) [>= ceil(N / 32)] bitset words -> the set (document d = bit d & 31 of word
+        d >> 5), e.g. a row of a DeviceSets copied back.  Words past ceil(N / 32) are ignored; a bit at or above N inside the
+        last word raises ValueError (no document has that number)."""
+        N, W = int(ix.n_docs), _n_words(ix.n_docs)
+        w = np.ascontiguousarray(np.asarray(words).reshape(-1)).view(np.uint32)
+        if len(w) < W:
+            raise ValueError(f"DocSet.from_words: {len(w)} words for an index of {N} documents ({W} words)")
+        bits = np.unpackbits(w[:W].astype("<u4").view(np.uint8), bitorder="little")
+        if bits[N:].any():
+            raise ValueError(f"DocSet.from_words: a bit at or above n_docs = {N} is set")
+        return cls(ix, bits[:N].astype(bool))
+
     # ------------------------------------------------------------------ binding
     @property
     def index(self):
@@ -238,3 +252,53 @@ def pack_within(within, n_queries, ix):
     for r, w in enumerate(rows):
         words[r, :len(w)] = w
     return words, q_set, len(rows), stride
+
+
+class DeviceSets:
+    """Document sets that live on the device, as DeviceEngine.term_sets builds them from posting lists (msr_term_sets): the four
+    fields DeviceEngine.pack_within returns -- bits int32 [n_sets, stride] (rows in the layout above), q_set int32 [Q] (query
+    q's row; -1 = every document), n_sets, stride -- tied to the index they were built for.  Pass it as `within=` to
+    bm25_topk / dense_topk / dense_topk_grouped / the Retriever's chain; after a rebind or update_index it is refused like a
+    DocSet.  Unpacks as (bits, q_set, n_sets, stride)."""
+
+    def __init__(self, ix, bits, q_set, n_sets, stride):
+        self._ix = weakref.ref(ix)
+        self.n_docs = int(ix.n_docs)
+        self.bits, self.q_set, self.n_sets, self.stride = bits, q_set, int(n_sets), int(stride)
+
+    def __iter__(self):
+        return iter((self.bits, self.q_set, self.n_sets, self.stride))
+
+    def __len__(self):
+        return int(self.q_set.shape[0])
+
+    @property
+    def index(self):
+        return self._ix()
+
+    def check(self, ix):
+        """Raise ValueError unless these sets belong to `ix` (the same object, with the same number of documents)."""
+        if self._ix() is not ix or ix.n_docs != self.n_docs:
+            raise ValueError("DocSet: built for another index (the index was updated or replaced since): rebuild it from the "
+                             "index being searched")
+
+    def queries(self, a, b):
+        """The sets of queries a .. b: the same rows, their part of q_set (nothing is copied) -- for a caller that works through
+        the queries in chunks."""
+        part = DeviceSets.__new__(DeviceSets)
+        part.__dict__.update(self.__dict__)
+        part.q_set = self.q_set[a:b]
+        return part
+
+    def docset(self, q):
+        """Query q's set as a DocSet of the index (one row copied back): for set algebra, counting, a look at the members."""
+        ix = self._ix()
+        if ix is None:
+            raise ValueError("DocSet: built for another index (the index was updated or replaced since): rebuild it from the "
+                             "index being searched")
+        r = int(self.q_set[q])
+        if r == -1:
+            return DocSet(ix, np.ones(self.n_docs, bool))
+        if r < 0 or r >= self.n_sets:
+            return DocSet(ix, np.zeros(self.n_docs, bool))
+        return DocSet.from_words(ix, self.bits[r].cpu().numpy())

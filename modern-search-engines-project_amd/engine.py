@@ -219,7 +219,12 @@ class DeviceEngine:
         """within (None | DocSet | list / tuple of DocSet / None per query) -> (set words int32 [n_sets, stride] device, q_set
         int32 [n_queries] device, n_sets, stride) for msr_*_topk_within; identical sets are stacked once (docset.pack_within).
         One DocSet for every query: its cached device copy and q_set = 0, nothing packed on the host."""
-        from .docset import DocSet, pack_within
+        from .docset import DeviceSets, DocSet, pack_within
+        if isinstance(within, DeviceSets):                   # built on the device (term_sets): its fields as they are
+            within.check(self.index)
+            if len(within) != n_queries:
+                raise ValueError(f"within: {len(within)} entries for {n_queries} queries")
+            return within.bits, within.q_set, within.n_sets, within.stride
         if isinstance(within, DocSet):
             within.check(self.index)
             stride = max(1, (self.index.n_docs + 31) // 32)
@@ -230,6 +235,85 @@ class DeviceEngine:
         words, q_set, n_sets, stride = pack_within(within, n_queries, self.index)
         bits = torch.from_numpy(words.view(np.int32)).to(self.device)
         return bits, torch.from_numpy(q_set).to(self.device), n_sets, stride
+
+    def term_sets(self, must, must_not=None, within=None):
+        """Per-query document sets from posting lists, built on the device (msr_term_sets): query q's set is the documents of
+        within[q] that hold EVERY term of must[q] and NONE of must_not[q].  must / must_not: per query a list of term ids
+        (None: no lists of that kind), unknown ids < 0 as CorpusIndex.term_ids gives them: an unknown must term empties the
+        set, an unknown must_not term is ignored.  within: None, a DocSet (every query) or a list of DocSet / None per query.
+        -> DeviceSets (bits, q_set, n_sets, stride), to be passed as within= to bm25_topk / dense_topk / dense_topk_grouped.
+        Queries with the same (set of must ids, set of must_not ids, base) share one row -- compared as sets of ids on the
+        host (repeats and order do not matter), never on bits; must_not ids the index lacks or whose list is empty are dropped
+        here.  A query without operators gets its base's row, or -1, and costs no kernel row.  Only enqueues -- except the
+        FIRST call after a bind, which reads the document frequencies (term_off, for the order of the must terms) once: a
+        synchronous copy of 8 bytes per term if the index lives on the device; they are kept until the next bind."""
+        from .docset import DeviceSets, DocSet, pack_within
+        from .index import _np
+        ix = self.index
+        if ix.term_off is None or ix.n_terms <= 0:
+            raise _abi.MsrError(-2, "term_sets: the index has no postings")
+        if must is None and must_not is None:
+            raise ValueError("term_sets: must or must_not is needed (a list of term ids per query)")
+        Q = len(must if must is not None else must_not)
+        must = [()] * Q if must is None else list(must)
+        must_not = [()] * Q if must_not is None else list(must_not)
+        if len(must) != Q or len(must_not) != Q:
+            raise ValueError(f"term_sets: {len(must)} must lists and {len(must_not)} must_not lists")
+        stride = max(1, (ix.n_docs + 31) // 32)
+        base_bits, n_base, base_of = None, 0, [-1] * Q
+        if isinstance(within, DocSet):
+            base_bits, _, n_base, _ = self.pack_within(within, Q)
+            base_of = [0] * Q
+        elif within is not None:
+            if isinstance(within, DeviceSets):
+                raise TypeError("term_sets: within takes DocSets (a DeviceSets is a result, not a base)")
+            words, base_q, n_base, _ = pack_within(within, Q, ix)
+            base_of = base_q.tolist()
+            if n_base:
+                base_bits = torch.from_numpy(words.view(np.int32)).to(self.device)
+        df = getattr(self, "_df", None)
+        if df is None or df[0] is not ix:
+            df = self._df = (ix, np.diff(_np(ix.term_off).astype(np.int64)))
+        df, n_terms = df[1], int(ix.n_terms)
+        EMPTY = ((-1,), ())
+        rows, row_of, q_row, keep_base = [], {}, [], False
+        for q in range(Q):
+            m = {int(t) if 0 <= int(t) < n_terms else -1 for t in must[q]}
+            x = {int(t) for t in must_not[q] if 0 <= int(t) < n_terms and df[int(t)] > 0}
+            if not m and not x:
+                q_row.append(None)
+                keep_base = keep_base or base_of[q] >= 0
+                continue
+            if -1 in m or m & x or any(df[t] == 0 for t in m):
+                key = EMPTY + (-1,)
+            else:                                            # the shortest list first: it empties most spans for the others
+                key = (tuple(sorted(m, key=lambda t: (df[t], t))), tuple(sorted(x)), base_of[q])
+            r = row_of.get(key)
+            if r is None:
+                r = row_of[key] = len(rows)
+                rows.append(key)
+            q_row.append(r)
+        first = n_base if keep_base else 0                   # base rows that operator-less queries still name come first
+        q_set = [(base_of[q] if base_of[q] >= 0 and keep_base else -1) if r is None else first + r for q, r in enumerate(q_row)]
+        bits = torch.empty((first + len(rows), stride), dtype=torch.int32, device=self.device)
+        if first:
+            bits[:first] = base_bits
+        if rows:
+            m_off, m_terms, x_off, x_terms = [0], [], [0], []
+            for m, x, _ in rows:
+                m_terms.extend(m); m_off.append(len(m_terms))
+                x_terms.extend(x); x_off.append(len(x_terms))
+            R = len(rows)
+            host = np.asarray(m_off + x_off + [b for _, _, b in rows] + m_terms + x_terms, np.int32)
+            dev = torch.from_numpy(host).to(self.device)
+            p_moff, p_xoff, p_base = dev[:R + 1], dev[R + 1:2 * R + 2], dev[2 * R + 2:3 * R + 2]
+            p_m = dev[3 * R + 2:3 * R + 2 + len(m_terms)]
+            p_x = dev[3 * R + 2 + len(m_terms):]
+            self._check(self.lib.msr_term_sets(self.handle, R, _ptr(p_moff), _ptr(p_m), _ptr(p_xoff), _ptr(p_x),
+                                               _ptr(base_bits) if n_base else C.c_void_p(0), n_base, stride,
+                                               _ptr(p_base) if n_base else C.c_void_p(0), _ptr(bits[first:]), stride,
+                                               self._stream()))
+        return DeviceSets(ix, bits, torch.tensor(q_set, dtype=torch.int32, device=self.device), first + len(rows), stride)
 
     def bm25_topk(self, term_lists, k=1000, min_score=0.0, packed=None, within=None):
         """-> (doc index int32 [Q, k], score float64 [Q, k], n int32 [Q]) device tensors.  within: None, a DocSet (every

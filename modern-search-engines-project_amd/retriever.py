@@ -12,11 +12,12 @@ import weakref
 import numpy as np
 
 from .bm25 import BM25
+from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .reranker import Reranker
-from .text import (LineFormatter, extract_domain, extract_domain_topic, format_result_line, preprocess_query,
-                   read_queries_file)
+from .text import (LineFormatter, extract_domain, extract_domain_topic, format_result_line, parse_operators,
+                   preprocess_query, read_queries_file)
 
 TOP_K_RETRIEVAL = 1000     # config.py:13
 TOP_K_RERANKING = 100      # config.py:14
@@ -268,15 +269,19 @@ class Retriever:
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
-    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K):
+    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, must=None, must_not=None):
         """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
         within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
         mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
         with its true BM25 score (msr_bm25_score_docs, msr_union_candidates); the candidates and where each came from are
-        copied to pinned buffers beside the final rows (the job's sixth entry)."""
+        copied to pinned buffers beside the final rows (the job's sixth entry).
+        must / must_not (None | term-id lists per query of the chunk): ONE term_sets call in front of stage 1 turns them, inside
+        `within`, into device sets that take within's place in both stages; nothing else changes."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
         union = None
+        if must is not None or must_not is not None:
+            within = eng.term_sets(must, must_not, within=within)
         if mode == "hybrid":
             k_lex = hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
             packed = eng.pack_queries(term_ids)
@@ -354,20 +359,29 @@ class Retriever:
         return src
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
-                          n_queries=None, within=None, mode="lexical", dense_k=DENSE_K):
+                          n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
+                          must_not=None):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
         prepare(a, b) (optional, with n_queries) -> (term id lists, vectors) of queries a .. b, evaluated just before the chunk
         is enqueued (text preprocessing inside the pipeline); otherwise term_id_lists / query_vectors hold all queries.
-        within: None, a DocSet (every query) or a list of DocSet / None per query: BM25 stage restricted to the set, then the
+        within: None, a DocSet (every query), a list of DocSet / None per query or a DeviceSets of all Q queries (each chunk
+        takes its queries' part; not together with must / must_not): BM25 stage restricted to the set, then the
         unchanged rerank / fuse / diversify on those candidates (the min-max normalisation spans the restricted candidates).
         mode="hybrid": the candidates are the BM25 top min(top_k, rerank_max_docs - dense_k) AND the dense top dense_k (both
         within the set, if any), see _enqueue_chunk; every chunk then carries a sixth array, int32 [Qc, S]: where each row's
-        document came from (1 lexical, 2 dense, 3 both).  A query without a known term still gets its dense candidates."""
+        document came from (1 lexical, 2 dense, 3 both).  A query without a known term still gets its dense candidates.
+        must / must_not: None or, per query, the terms (strings or ids) every result must / must not contain -- one
+        DeviceEngine.term_sets call per chunk builds the sets on the device, inside `within`; in hybrid mode the dense
+        candidates are restricted too.  operators: here the queries are term ids, there is no text to parse -- True is refused
+        (search / search_batch / batch_search parse; or text.parse_operators and must= / must_not=)."""
         import torch
         eng = self.engine
         _check_mode(mode)
+        if operators:
+            raise ValueError("operators=True needs the query text: use search / search_batch / batch_search, or parse with "
+                             "text.parse_operators and pass must= / must_not=")
         if top_k > eng.rerank_max_docs or top_k > eng.max_k:
             raise ValueError(f"top_k {top_k} exceeds the engine's max_k / rerank_max_docs ({eng.max_k} / {eng.rerank_max_docs})")
         if mode == "hybrid":
@@ -377,15 +391,21 @@ class Retriever:
         self._ensure_response_tables()
         Q = len(term_id_lists) if prepare is None else int(n_queries)
         step = int(chunk or max(256, eng.max_queries))
-        if isinstance(within, (list, tuple)) and len(within) != Q:
+        if isinstance(within, (list, tuple, DeviceSets)) and len(within) != Q:
             raise ValueError(f"within: {len(within)} entries for {Q} queries")
+        for name, lists in (("must", must), ("must_not", must_not)):
+            if lists is not None and len(lists) != Q:
+                raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
+        op_ids = lambda lists, a, b: None if lists is None else [self.index.term_ids(t) for t in lists[a:b]]
         pending = None
         for i, a in enumerate(range(0, Q, step)):
             b = min(Q, a + step)
             ids, qv = prepare(a, b) if prepare is not None else (term_id_lists[a:b], query_vectors[a:b])
             qv = eng._dev(np.asarray(qv, np.float32) if not torch.is_tensor(qv) else qv, torch.float32).reshape(-1, 768)
-            w = list(within[a:b]) if isinstance(within, (list, tuple)) else within
-            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k)
+            w = (list(within[a:b]) if isinstance(within, (list, tuple))
+                 else within.queries(a, b) if isinstance(within, DeviceSets) else within)
+            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=op_ids(must, a, b),
+                                      must_not=op_ids(must_not, a, b))
             if pending is not None:
                 yield (pending[0],) + self._collect(pending[1])
             pending = (a, job)
@@ -398,15 +418,17 @@ class Retriever:
         return out if len(job) == 5 else out + (cls._collect_source(job, out[0], out[3]),)
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
-                    dense_k=DENSE_K, with_source=False):
+                    dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
-        with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n)."""
+        with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
+        operators / must / must_not: final_list_chunks."""
         _check_mode(mode)
         if with_source and mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
-        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k))
+        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
+                                            operators=operators, must=must, must_not=must_not))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -417,8 +439,38 @@ class Retriever:
                np.concatenate([pad(p[3], -1) for p in parts]), np.concatenate([p[4] for p in parts]))
         return out + ((np.concatenate([pad(p[5], 0) for p in parts]),) if with_source else ())
 
-    def _prepare(self, queries, query_embeddings, term_lists):
-        processed = [preprocess_query(q) for q in queries]
+    def _operators(self, processed, operators, must, must_not):
+        """-> (scoring texts, must term lists, must_not term lists) of the preprocessed queries: the parsed operator words
+        (operators=True), tokenised like the query, joined with the caller's explicit lists; (processed, None, None) when
+        there is neither -- the chain then runs exactly as without the feature."""
+        if not operators and must is None and must_not is None:
+            return processed, None, None
+        Q = len(processed)
+        for name, lists in (("must", must), ("must_not", must_not)):
+            if lists is not None and len(lists) != Q:
+                raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
+        m = [list(t) for t in must] if must is not None else [[] for _ in range(Q)]
+        x = [list(t) for t in must_not] if must_not is not None else [[] for _ in range(Q)]
+        if operators:
+            tok = self.bm25._tokenize
+            processed = list(processed)
+            for q in range(Q):
+                processed[q], m_words, x_words = parse_operators(processed[q])
+                m[q] += [t for w in m_words for t in tok(w)]
+                x[q] += [t for w in x_words for t in tok(w)]
+        if not any(m) and not any(x):
+            return processed, None, None
+        return processed, m, x
+
+    def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not):
+        """_prepare with operators: -> (term ids, vectors, must term lists or None, must_not term lists or None).  The scoring
+        text (excluded words removed) is what gets tokenised and embedded."""
+        processed, must, must_not = self._operators([preprocess_query(q) for q in queries], operators, must, must_not)
+        return self._prepare(queries, query_embeddings, term_lists, processed) + (must, must_not)
+
+    def _prepare(self, queries, query_embeddings, term_lists, processed=None):
+        if processed is None:
+            processed = [preprocess_query(q) for q in queries]
         if term_lists is None:
             term_lists = [self.bm25._tokenize(q) for q in processed]
         ids = [self.index.term_ids(t) for t in term_lists]
@@ -430,19 +482,26 @@ class Retriever:
         return ids, qv
 
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
-                     mode="lexical", dense_k=DENSE_K):
+                     mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
         be returned; a query of unknown words only still gets results); every row then carries "matched_by": "lexical" |
-        "dense" | "both".  mode="lexical" (default): the reference's path, rows without that key."""
+        "dense" | "both".  mode="lexical" (default): the reference's path, rows without that key.
+        operators=True: `+word` / `-word` tokens of a query (text.parse_operators, after preprocess_query) name words every
+        result must / must not contain; `+word` still scores, `-word` does not.  must / must_not: per query a list of term
+        strings (for callers with their own tokenizer, like term_lists), joined with the parsed ones.  Both act inside
+        `within`, in both stages of either mode: a page that holds an excluded word is never returned.  Without operators
+        and lists the call is what it was."""
         _check_mode(mode)
-        ids, qv = self._prepare(queries, query_embeddings, term_lists)
+        ids, qv, must, must_not = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not)
+        ops = {} if must is None else {"must": must, "must_not": must_not}
         src = None
         if mode == "hybrid":
-            doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True)
+            doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
+                                                     **ops)
         else:
-            doc, score, _, n = self.final_lists(ids, qv, top_k, within=within)
+            doc, score, _, n = self.final_lists(ids, qv, top_k, within=within, **ops)
         ix = self.index
         out = []
         for q in range(len(queries)):
@@ -463,20 +522,24 @@ class Retriever:
         return out
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
-               mode="lexical", dense_k=DENSE_K):
+               mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None):
+        """search_batch for one query; must / must_not: ONE list of term strings each."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
-                                 mode=mode, dense_k=dense_k)[0]
+                                 mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
+                                 must_not=None if must_not is None else [must_not])[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
-                     dense_k=DENSE_K):
+                     dense_k=DENSE_K, operators=False, must=None, must_not=None):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
-        search_batch (the entries keep the reference's keys in either mode)."""
+        search_batch (the entries keep the reference's keys in either mode); operators / must / must_not: search_batch."""
         _check_mode(mode)
-        ids, qv = self._prepare([q for _, q in numbered_queries], query_embeddings, term_lists)
-        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k)[:4]
+        ids, qv, must, must_not = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators,
+                                                    must, must_not)
+        ops = {} if must is None else {"must": must, "must_not": must_not}
+        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         return BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)

@@ -57,6 +57,9 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         sites: Optional[List[str]] = None
         mode: str = "lexical"         # "hybrid": the dense top dense_k documents join the BM25 candidates (Retriever.search)
         dense_k: int = 100
+        operators: bool = False       # `+word` / `-word` in the query: required / excluded words (text.parse_operators)
+        must: Optional[List[str]] = None       # terms every result must contain ...
+        must_not: Optional[List[str]] = None   # ... and must not contain (Retriever.search)
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -112,6 +115,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             kw = {} if req.mode == "lexical" else {"mode": req.mode, "dense_k": req.dense_k}
             if req.sites is not None:
                 kw["within"] = within_sites(req.sites)
+            if req.operators or req.must is not None or req.must_not is not None:
+                kw.update(operators=req.operators, must=req.must, must_not=req.must_not)
             try:
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)

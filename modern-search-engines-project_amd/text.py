@@ -63,6 +63,28 @@ def simple_tokenize(text: str):
     return [m.group(0).lower() for m in _WORD.finditer(text)]
 
 
+def parse_operators(processed_query: str):
+    """Search-box operators of a query that has been through preprocess_query -> (scoring_text, must_words, not_words).
+    A whitespace-delimited token that starts with `+` or `-` FOLLOWED BY A LETTER is an operator token: `+word` -- the page
+    must contain the word -- keeps the word (without its sign) in the scoring text; `-word` -- the page must not contain
+    it -- is removed from the scoring text.  Anything else is left as it is: a sign inside a token (`uni-tuebingen`,
+    `c++`), a lone `+` or `-`, a doubled sign (`++a`, `--a`, `+-a`), a sign before a digit (`-123`).  The words come back
+    as written (sign stripped); the caller tokenises them like the query -- a word of several tokens requires (or excludes)
+    all of them.  Because this runs after preprocess_query, the appended city is a plain scoring term, and `-tuebingen`
+    excludes the city's pages instead of scoring them."""
+    keep, must, must_not = [], [], []
+    for tok in processed_query.split():
+        if len(tok) >= 2 and tok[0] in "+-" and tok[1].isalpha():
+            if tok[0] == "+":
+                must.append(tok[1:])
+                keep.append(tok[1:])
+            else:
+                must_not.append(tok[1:])
+        else:
+            keep.append(tok)
+    return " ".join(keep), must, must_not
+
+
 def format_result_line(query_num, rank, url, score) -> str:
     """search_api.py:290"""
     return f"{query_num}\t{rank}\t{url}\t{score:.3f}"
