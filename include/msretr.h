@@ -35,15 +35,17 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 12        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 13        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
-                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets */
+                                     tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets;
+                                     13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
 #define MSR_RERANK_MAX_CHUNKS 10  /* reranker_api.py:58 */
 #define MSR_TERMSET_SPAN_DOCS 8192 /* msr_term_sets: consecutive documents one work item of its kernel owns (a multiple of 1024) */
+#define MSR_PHRASE_MAX_TERMS 16    /* msr_phrase_sets: most term ids a phrase may hold */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -218,6 +220,51 @@ int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_off, const 
                   const int32_t* not_off, const int32_t* not_terms,
                   const uint32_t* base_bits, int32_t n_base, int64_t base_stride, const int32_t* row_base,
                   uint32_t* out_bits, int64_t out_stride, void* stream);
+
+/* Phrase search.  The forward index is the token-id stream every document was indexed from:
+ * tok_off int64 [n_docs + 1] and tok_ids int32 [n_tokens], document d's stream at tok_ids[tok_off[d] .. tok_off[d + 1]), in
+ * the dense document order of the bound postings.
+ *
+ * msr_bind_tokens: device pointers, caller-owned; the engine keeps the pointers, as it does for the postings.  Checked once on
+ *   the device (the call synchronises the stream), MSR_ERR_INVALID otherwise: tok_off[0] == 0, non-decreasing,
+ *   tok_off[n_docs] == n_tokens; n_docs equals the bound postings' document count; every id in [0, n_terms) of the bound
+ *   postings.  tok_ids may be NULL when n_tokens == 0.  MSR_ERR_NOT_BOUND without postings.  msr_unbind and
+ *   msr_bind_postings drop the binding. */
+int msr_bind_tokens(msr_engine* e, const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_tokens,
+                    void* stream);
+
+/* msr_phrase_sets: row r of out_bits becomes { d in cand(r) : document d contains phrase r }, the phrase being
+ *   phrase_terms[phrase_off[r] .. phrase_off[r + 1]) (int32 offsets from 0, n_rows + 1 of them).  Document d contains the
+ *   phrase p[0 .. L) iff some i with 0 <= i <= len(d) - L has tok[d][i + j] == p[j] for every j: a match never crosses from
+ *   one document into the next, a phrase longer than the document never matches, L == 1 is term containment.  A row whose
+ *   phrase is empty, longer than MSR_PHRASE_MAX_TERMS, or holds an id outside [0, n_terms) is written EMPTY (by the kernel,
+ *   no host round trip).  cand(r) follows q_set's and row_base's rules: row_cand[r] == -1, or n_cand == 0 (cand_bits /
+ *   row_cand are then not read), is every document; a value in [0, n_cand) picks that row of cand_bits (rows cand_stride
+ *   words apart); any other value is the empty set, and no row outside the n_cand rows is read.  Candidate bits at or above
+ *   n_docs are ignored.  Layout and write contract as msr_term_sets: every word [0, ceil(n_docs / 32)) of every row is
+ *   written, bits at or above n_docs are 0, words [ceil(n_docs / 32), out_stride) are not touched; out_bits must not alias
+ *   cand_bits; repeated calls give the same bytes; the call only enqueues (offsets are read on the device), no engine
+ *   scratch.  Refused before any launch, outputs untouched: MSR_ERR_NOT_BOUND without tokens; MSR_ERR_INVALID for
+ *   n_rows < 0, with n_rows > 0 a NULL out_bits or phrase_off, out_stride < ceil(n_docs / 32), n_cand < 0, with n_cand > 0 a
+ *   NULL cand_bits or row_cand or cand_stride < ceil(n_docs / 32).  n_rows == 0 succeeds and launches nothing.  Cost per
+ *   row: 4 bytes per token of the candidate documents (less what a hit's early exit skips) plus 4 ceil(n_docs / 32) bytes
+ *   read and written. */
+int msr_phrase_sets(msr_engine* e, int32_t n_rows, const int32_t* phrase_off, const int32_t* phrase_terms,
+                    const uint32_t* cand_bits, int32_t n_cand, int64_t cand_stride, const int32_t* row_cand,
+                    uint32_t* out_bits, int64_t out_stride, void* stream);
+
+/* msr_combine_sets: out[r] = AND of in[s] for s in and_rows[and_off[r] .. and_off[r + 1])  AND NOT  OR of in[s] for s in
+ *   not_rows[not_off[r] .. not_off[r + 1]), rows of in_bits (n_in rows in_stride words apart) in the layout above.  An empty
+ *   AND list means every document below n_docs; a row index outside [0, n_in) empties the row in the AND list and is ignored
+ *   in the NOT list (no row outside the n_in rows is read).  Input bits at or above n_docs are ignored.  The write contract
+ *   of msr_term_sets; out_bits must not alias in_bits; one elementwise kernel, only enqueued.  Refused with MSR_ERR_INVALID
+ *   before any launch, outputs untouched: n_rows < 0; with n_rows > 0 a NULL out_bits, and_off or not_off; out_stride <
+ *   ceil(n_docs / 32); n_in < 0; with n_in > 0 a NULL in_bits or in_stride < ceil(n_docs / 32).  MSR_ERR_NOT_BOUND without
+ *   postings (they give n_docs).  n_rows == 0 succeeds and launches nothing. */
+int msr_combine_sets(msr_engine* e, int32_t n_rows, const int32_t* and_off, const int32_t* and_rows,
+                     const int32_t* not_off, const int32_t* not_rows,
+                     const uint32_t* in_bits, int32_t n_in, int64_t in_stride,
+                     uint32_t* out_bits, int64_t out_stride, void* stream);
 
 /* Read-only, launches nothing: how msr_bm25_topk(_within) splits the work of ONE internal slice of n_queries queries
  * (1 <= n_queries <= max_queries; a call of more queries runs slices of max_queries and one of the rest) over the bound

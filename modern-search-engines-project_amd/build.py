@@ -33,6 +33,7 @@ UNITS = {
     "msr_compact.hip": [],
     "msr_similar.hip": [],
     "msr_termset.hip": [],
+    "msr_phrase.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)

@@ -19,6 +19,10 @@ struct msr_engine {
     // bound index parts (borrowed device pointers)
     Bm25Index bm25;
     bool have_postings = false;
+    const int64_t* tok_off = nullptr;      // msr_bind_tokens (borrowed): the forward index of the bound postings' documents
+    const int32_t* tok_ids = nullptr;
+    int64_t n_tokens = 0;
+    bool have_tokens = false;
     DenseIndex dense;
     bool have_chunks = false;
     const int32_t* url_group = nullptr;
@@ -293,6 +297,7 @@ extern "C" int msr_bind_postings(msr_engine* e, const int64_t* term_off, int64_t
     // from here on the previous binding's tables are being replaced: the engine counts as unbound until this call succeeds
     // (a failed re-bind must not leave msr_bm25_topk reading freed tables)
     e->have_postings = false;
+    e->have_tokens = false; e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;   // (they describe the old documents)
     int rc = ensure_score_rows(e, n_docs);
     if (rc) return rc;
     {   // candidate lists of the BM25 stage: worst case every document of every query
@@ -690,6 +695,7 @@ extern "C" int msr_unbind(msr_engine* e) {
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     // the engine counts as unbound before anything is freed
     e->have_postings = e->have_chunks = false;
+    e->have_tokens = false; e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
     e->split_pending = 0;
     e->bm25 = Bm25Index{};
     e->dense = e->dense_bf16 = DenseIndex{};
@@ -907,6 +913,86 @@ extern "C" int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_term_sets_run(e->bm25, n_rows, must_off, must_terms, not_off, not_terms, base_bits, n_base, base_stride,
                                  row_base, out_bits, out_stride, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+// ---- K12: phrase search (msr_phrase.hip) --------------------------------------------------------------------------------------
+extern "C" int msr_bind_tokens(msr_engine* e, const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_tokens,
+                               void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_bind_tokens: postings not bound");
+    e->have_tokens = false; e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
+    if (!tok_off || n_tokens < 0 || (n_tokens > 0 && !tok_ids)) return fail(e, MSR_ERR_INVALID, "msr_bind_tokens: bad argument");
+    if (n_docs != e->bm25.n_docs)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_tokens: n_docs %lld differs from bound postings (%lld)", (long long)n_docs,
+                    (long long)e->bm25.n_docs);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    if (!e->sim_flag) {
+        hipError_t herr = eng_malloc(e, (void**)&e->sim_flag, 64);
+        if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "check flag: %s", hipGetErrorString(herr));
+    }
+    // one kernel checks the offsets and the ids; it reads tok_off[0 .. n_docs] and tok_ids[0 .. n_tokens), which the caller
+    // vouches for, and never follows an offset into tok_ids, so malformed offsets cannot send a read out of bounds
+    int32_t flag = 0;
+    HIP_TRY(e, hipMemsetAsync(e->sim_flag, 0, sizeof(int32_t), st));
+    HIP_TRY(e, msr_tokens_validate(tok_off, tok_ids, n_docs, n_tokens, e->bm25.n_terms, e->sim_flag, st));
+    HIP_TRY(e, hipMemcpyAsync(&flag, e->sim_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (flag) {
+        static const char* why[] = {"", "tok_off does not run from 0 to n_tokens", "tok_off descends",
+                                    "a token id is outside [0, n_terms)"};
+        return fail(e, MSR_ERR_INVALID, "msr_bind_tokens: malformed forward index: %s", why[std::min(std::max(flag, 0), 3)]);
+    }
+    e->tok_off = tok_off; e->tok_ids = tok_ids; e->n_tokens = n_tokens;
+    e->have_tokens = true;
+    return MSR_OK;
+}
+
+extern "C" int msr_phrase_sets(msr_engine* e, int32_t n_rows, const int32_t* phrase_off, const int32_t* phrase_terms,
+                               const uint32_t* cand_bits, int32_t n_cand, int64_t cand_stride, const int32_t* row_cand,
+                               uint32_t* out_bits, int64_t out_stride, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_tokens)
+        return fail(e, MSR_ERR_NOT_BOUND, "msr_phrase_sets: tokens not bound (msr_bind_tokens: the index has no forward index)");
+    const int64_t W = (e->bm25.n_docs + 31) / 32;
+    if (n_rows < 0 || n_cand < 0) return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (n_rows=%d, n_cand=%d)", n_rows, n_cand);
+    if (n_rows > 0 && (!out_bits || !phrase_off))
+        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (out_bits or phrase_off is NULL with n_rows=%d)", n_rows);
+    if (out_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)out_stride, (long long)W);
+    if (n_cand > 0 && (!cand_bits || !row_cand))
+        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (cand_bits or row_cand is NULL with n_cand=%d)", n_cand);
+    if (n_cand > 0 && cand_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (cand_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)cand_stride, (long long)W);
+    if (n_rows == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_phrase_sets_run(e->tok_off, e->tok_ids, e->bm25.n_docs, e->bm25.n_terms, n_rows, phrase_off, phrase_terms,
+                                   cand_bits, n_cand, cand_stride, row_cand, out_bits, out_stride, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+extern "C" int msr_combine_sets(msr_engine* e, int32_t n_rows, const int32_t* and_off, const int32_t* and_rows,
+                                const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int32_t n_in,
+                                int64_t in_stride, uint32_t* out_bits, int64_t out_stride, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_combine_sets: postings not bound");
+    const int64_t W = (e->bm25.n_docs + 31) / 32;
+    if (n_rows < 0 || n_in < 0) return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (n_rows=%d, n_in=%d)", n_rows, n_in);
+    if (n_rows > 0 && (!out_bits || !and_off || !not_off))
+        return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (out_bits, and_off or not_off is NULL with n_rows=%d)", n_rows);
+    if (out_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)out_stride, (long long)W);
+    if (n_in > 0 && (!in_bits || in_stride < W))
+        return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (in_bits is NULL or in_stride=%lld < ceil(n_docs / 32) = %lld "
+                    "with n_in=%d)", (long long)in_stride, (long long)W, n_in);
+    if (n_rows == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_combine_sets_run(e->bm25.n_docs, n_rows, and_off, and_rows, not_off, not_rows, in_bits, n_in, in_stride,
+                                    out_bits, out_stride, (hipStream_t)stream));
     return MSR_OK;
 }
 

@@ -180,6 +180,18 @@ hipError_t msr_term_sets_run(const Bm25Index& ix, int n_rows, const int32_t* mus
                              int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride,
                              hipStream_t stream);
 
+// K12 (msr_phrase.hip): phrase search on the forward index (see msretr.h; arguments checked by the caller).
+// *flag <- max(*flag, code): 1 tok_off does not run from 0 to n_tokens, 2 it descends, 3 an id outside [0, n_terms)
+hipError_t msr_tokens_validate(const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_tokens, int64_t n_terms,
+                               int32_t* flag, hipStream_t stream);
+hipError_t msr_phrase_sets_run(const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_terms, int n_rows,
+                               const int32_t* phrase_off, const int32_t* phrase_terms, const uint32_t* cand_bits, int n_cand,
+                               int64_t cand_stride, const int32_t* row_cand, uint32_t* out_bits, int64_t out_stride,
+                               hipStream_t stream);
+hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
+                                const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
+                                int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);
+
 // *flag (device) <- 0x7F7F7F7F if the CSR is well formed, else the lowest violated rule number (msr_bm25.hip).
 hipError_t msr_bm25_validate(const Bm25Index& ix, int32_t* flag, hipStream_t stream);
 

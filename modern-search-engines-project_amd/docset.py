@@ -259,12 +259,16 @@ class DeviceSets:
     fields DeviceEngine.pack_within returns -- bits int32 [n_sets, stride] (rows in the layout above), q_set int32 [Q] (query
     q's row; -1 = every document), n_sets, stride -- tied to the index they were built for.  Pass it as `within=` to
     bm25_topk / dense_topk / dense_topk_grouped / the Retriever's chain; after a rebind or update_index it is refused like a
-    DocSet.  Unpacks as (bits, q_set, n_sets, stride)."""
+    DocSet.  Unpacks as (bits, q_set, n_sets, stride).  `layout` says what the rows are when the producer has more than one
+    kind: None (term_sets: base rows, then one row per distinct operator list), or DeviceEngine.phrase_sets' (T, P, C) -- T rows
+    as term_sets makes them, then P verified (phrase, candidate row) pairs, then C rows, one per query with phrases; n_sets =
+    T + P + C.  A part taken with queries() names the same rows and keeps the layout."""
 
     def __init__(self, ix, bits, q_set, n_sets, stride):
         self._ix = weakref.ref(ix)
         self.n_docs = int(ix.n_docs)
         self.bits, self.q_set, self.n_sets, self.stride = bits, q_set, int(n_sets), int(stride)
+        self.layout = None
 
     def __iter__(self):
         return iter((self.bits, self.q_set, self.n_sets, self.stride))

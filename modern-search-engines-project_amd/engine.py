@@ -123,6 +123,11 @@ class DeviceEngine:
                     self.handle, _ptr(t["term_off"]), ix.n_terms, _ptr(t["post_doc"]), _ptr(t["post_tf"]),
                     int(t["post_doc"].numel()), _ptr(t["doc_len"]), ix.n_docs, _ptr(t["idf"]),
                     C.c_float(ix.avgdl), C.c_double(ix.k1), C.c_double(ix.b), self._stream()))
+                if ix.tok_off is not None:                   # the forward index (phrase search, msr_bind_tokens)
+                    tok_off, tok_ids = self._dev(ix.tok_off, torch.int64), self._dev(ix.tok_ids, torch.int32)
+                    self._check(self.lib.msr_bind_tokens(self.handle, _ptr(tok_off), _ptr(tok_ids) if tok_ids.numel() else
+                                                         C.c_void_p(0), ix.n_docs, int(tok_ids.numel()), self._stream()))
+                    t["tok_off"], t["tok_ids"] = tok_off, tok_ids
             if ix.doc_off is not None and ix.emb is not None:
                 t["doc_off"] = self._dev(ix.doc_off, torch.int32)
                 emb = self._dev(ix.emb, torch.float32)
@@ -162,6 +167,11 @@ class DeviceEngine:
             self.lib.msr_unbind(self.handle)
             self._t = {}
             raise
+
+    @property
+    def has_tokens(self):
+        """True if the bound index came with a forward index (CorpusIndex.tok_off / tok_ids): phrase_sets works."""
+        return "tok_off" in self._t
 
     def scan_arith(self):
         """'f32' (exact f32 MFMA) or 'f16x2' (f32 rows split into two f16 pieces, f32 accumulation)."""
@@ -247,6 +257,15 @@ class DeviceEngine:
         here.  A query without operators gets its base's row, or -1, and costs no kernel row.  Only enqueues -- except the
         FIRST call after a bind, which reads the document frequencies (term_off, for the order of the must terms) once: a
         synchronous copy of 8 bytes per term if the index lives on the device; they are kept until the next bind."""
+        from .docset import DeviceSets
+        bits, q_set, n_sets, stride, _ = self._term_rows(must, must_not, within)
+        return DeviceSets(self.index, bits, torch.tensor(q_set, dtype=torch.int32, device=self.device), n_sets, stride)
+
+    def _term_rows(self, must, must_not, within, extra_rows=0, tail=None):
+        """The work of term_sets -> (bits int32 [n_sets + extra_rows, stride] device, q_set as a HOST list, n_sets, stride,
+        tail on the device or None); the extra rows (behind the n_sets rows, not written here) are for a caller that derives
+        further rows (phrase_sets).  tail(q_set, n_sets) -> a list of int32 values that travel in the SAME upload as the term
+        lists (the caller's own lists, built from the row numbers): the call then costs one upload, not two."""
         from .docset import DeviceSets, DocSet, pack_within
         from .index import _np
         ix = self.index
@@ -295,25 +314,140 @@ class DeviceEngine:
             q_row.append(r)
         first = n_base if keep_base else 0                   # base rows that operator-less queries still name come first
         q_set = [(base_of[q] if base_of[q] >= 0 and keep_base else -1) if r is None else first + r for q, r in enumerate(q_row)]
-        bits = torch.empty((first + len(rows), stride), dtype=torch.int32, device=self.device)
+        bits = torch.empty((first + len(rows) + int(extra_rows), stride), dtype=torch.int32, device=self.device)
         if first:
             bits[:first] = base_bits
+        n_sets = first + len(rows)
+        tail_host = [int(v) for v in tail(q_set, n_sets)] if tail is not None else []
+        d_tail = None
+        if not rows and tail_host:
+            d_tail = torch.from_numpy(np.asarray(tail_host, np.int32)).to(self.device)
         if rows:
             m_off, m_terms, x_off, x_terms = [0], [], [0], []
             for m, x, _ in rows:
                 m_terms.extend(m); m_off.append(len(m_terms))
                 x_terms.extend(x); x_off.append(len(x_terms))
             R = len(rows)
-            host = np.asarray(m_off + x_off + [b for _, _, b in rows] + m_terms + x_terms, np.int32)
+            host = np.asarray(m_off + x_off + [b for _, _, b in rows] + m_terms + x_terms + tail_host, np.int32)
             dev = torch.from_numpy(host).to(self.device)
             p_moff, p_xoff, p_base = dev[:R + 1], dev[R + 1:2 * R + 2], dev[2 * R + 2:3 * R + 2]
             p_m = dev[3 * R + 2:3 * R + 2 + len(m_terms)]
-            p_x = dev[3 * R + 2 + len(m_terms):]
+            end = 3 * R + 2 + len(m_terms) + len(x_terms)
+            p_x = dev[3 * R + 2 + len(m_terms):end]
+            if tail_host:
+                d_tail = dev[end:]
             self._check(self.lib.msr_term_sets(self.handle, R, _ptr(p_moff), _ptr(p_m), _ptr(p_xoff), _ptr(p_x),
                                                _ptr(base_bits) if n_base else C.c_void_p(0), n_base, stride,
                                                _ptr(p_base) if n_base else C.c_void_p(0), _ptr(bits[first:]), stride,
                                                self._stream()))
-        return DeviceSets(ix, bits, torch.tensor(q_set, dtype=torch.int32, device=self.device), first + len(rows), stride)
+        return bits, q_set, n_sets, stride, d_tail
+
+    def phrase_sets(self, must_phrases, must_not_phrases=None, must=None, must_not=None, within=None):
+        """Per-query document sets of phrase search, built on the device: query q's set is the documents of within[q] that hold
+        every term of must[q], none of must_not[q] (term_sets' rules), EVERY phrase of must_phrases[q] and NO phrase of
+        must_not_phrases[q].  A phrase is a list of 1 .. MSR_PHRASE_MAX_TERMS term ids (unknown ids < 0 as CorpusIndex.term_ids
+        gives them); a document holds it when the ids stand next to each other, in this order, in its indexed token stream
+        (msretr.h msr_phrase_sets).  A must phrase with an unknown id, or an empty one, empties the set; such a not phrase is
+        ignored; a longer phrase raises ValueError.  -> DeviceSets, for every consumer of term_sets' result.
+
+        Three launches, nothing synchronises: ONE term_sets call builds every phrase's candidate row (a must phrase: its
+        terms AND the query's base and must / must_not terms; a not phrase: its terms AND the base), ONE msr_phrase_sets call
+        verifies the distinct (phrase, candidate row) pairs -- compared as tuples on the host, identical pairs share a row --
+        and ONE msr_combine_sets call gives each query the AND of its must rows without its not rows (a query with only not
+        phrases: its term / base row without them); every list of the three calls and q_set travel in ONE upload.  The
+        result's `layout` is (term rows, phrase rows, per-query rows).  A query without phrases keeps its term_sets row, or -1, and costs no
+        phrase row.  Raises MsrError when the index has no forward index (index_build.attach_tokens, or a build with
+        keep_tokens=True, gives it one)."""
+        from .docset import DeviceSets, DocSet
+        ix = self.index
+        if not self.has_tokens:
+            raise _abi.MsrError(-2, "phrase_sets: the index has no forward index (tok_off / tok_ids): build it with "
+                                    "keep_tokens=True or attach the token streams with index_build.attach_tokens, then rebind")
+        if must_phrases is None and must_not_phrases is None:
+            raise ValueError("phrase_sets: must_phrases or must_not_phrases is needed (a list of phrases per query)")
+        Q = len(must_phrases if must_phrases is not None else must_not_phrases)
+        lists = [[()] * Q if x is None else list(x) for x in (must_phrases, must_not_phrases, must, must_not)]
+        if any(len(x) != Q for x in lists):
+            raise ValueError(f"phrase_sets: {[len(x) for x in lists]} must_phrases / must_not_phrases / must / must_not lists")
+        mp, xp, m, x = lists
+        if isinstance(within, DocSet) or within is None:
+            base = [within] * Q
+        else:
+            if isinstance(within, DeviceSets):
+                raise TypeError("phrase_sets: within takes DocSets (a DeviceSets is a result, not a base)")
+            base = list(within)
+            if len(base) != Q:
+                raise ValueError(f"within: {len(base)} entries for {Q} queries")
+        n_terms = int(ix.n_terms)
+        norm = lambda p: tuple(int(t) if 0 <= int(t) < n_terms else -1 for t in p)
+        # virtual queries of the one term_sets call: per query its own (terms, base) row, then one per phrase
+        v_must, v_not, v_base, plan = [], [], [], []
+        for q in range(Q):
+            ph_m, ph_x = [norm(p) for p in mp[q]], [norm(p) for p in xp[q]]
+            for p in ph_m + ph_x:
+                if len(p) > _abi.MSR_PHRASE_MAX_TERMS:
+                    raise ValueError(f"a phrase may hold at most {_abi.MSR_PHRASE_MAX_TERMS} terms (MSR_PHRASE_MAX_TERMS), got {len(p)}")
+            own = len(v_must)
+            v_must.append(list(m[q])); v_not.append(list(x[q])); v_base.append(base[q])
+            plan.append((own, ph_m, len(v_must), ph_x, len(v_must) + len(ph_m)))
+            for p in ph_m:
+                v_must.append(list(p) + list(m[q])); v_not.append(list(x[q])); v_base.append(base[q])
+            for p in ph_x:
+                v_must.append(list(p)); v_not.append([]); v_base.append(base[q])
+        n_phrase_q = sum(1 for pl in plan if pl[1] or pl[3])
+        if not any(b is not None for b in v_base):
+            v_base = None
+        # the buffer holds the term rows, then the distinct (phrase, candidate row) pairs' rows (at most one per phrase), then
+        # one row per query with phrases.  The phrase and combine lists need the term rows' numbers, which _term_rows knows
+        # before it uploads: it calls lists_of() and sends the result along with its own lists (one upload for the whole call)
+        V = len(v_must)
+        rows, cut = [], []
+
+        def lists_of(v_row, T):
+            row_of = {}
+            and_off, and_rows, not_off, not_rows, q_set = [0], [], [0], [], []
+            for q, (own, ph_m, i_m, ph_x, i_x) in enumerate(plan):
+                if not ph_m and not ph_x:
+                    q_set.append(v_row[own])
+                    continue
+                rm = []
+                for key in [(p, v_row[i_m + j]) for j, p in enumerate(ph_m)] + [(p, v_row[i_x + j]) for j, p in enumerate(ph_x)]:
+                    r = row_of.get(key)
+                    if r is None:
+                        r = row_of[key] = len(rows)
+                        rows.append(key)
+                    rm.append(r)
+                a = [T + r for r in rm[:len(ph_m)]]
+                if not ph_m and v_row[own] != -1:            # only not phrases: the query's own term / base row
+                    a = [v_row[own]]
+                and_rows += a; and_off.append(len(and_rows))
+                not_rows += [T + r for r in rm[len(ph_m):]]; not_off.append(len(not_rows))
+                q_set.append(None)
+            k = 0
+            for q in range(Q):
+                if q_set[q] is None:
+                    q_set[q] = T + len(rows) + k
+                    k += 1
+            p_off, p_terms = [0], []
+            for p, _ in rows:
+                p_terms += list(p); p_off.append(len(p_terms))
+            parts = [p_off, [c for _, c in rows], and_off, not_off, p_terms, and_rows, not_rows, q_set]
+            cut.extend(np.cumsum([0] + [len(part) for part in parts]).tolist())
+            return [v for part in parts for v in part]
+
+        bits, _, T, stride, dev = self._term_rows(v_must, v_not, v_base, extra_rows=(V - Q) + n_phrase_q, tail=lists_of)
+        d_poff, d_cand, d_aoff, d_xoff, d_pt, d_a, d_x, d_q = [dev[cut[i]:cut[i + 1]] for i in range(8)]
+        P, C_ = len(rows), int(d_aoff.numel()) - 1
+        if C_:
+            ptr = lambda t: _ptr(t) if t.numel() else C.c_void_p(0)
+            self._check(self.lib.msr_phrase_sets(self.handle, P, _ptr(d_poff), ptr(d_pt), ptr(bits[:T]) if T else C.c_void_p(0), T,
+                                                 stride, _ptr(d_cand) if T else C.c_void_p(0), _ptr(bits[T:]), stride,
+                                                 self._stream()))
+            self._check(self.lib.msr_combine_sets(self.handle, C_, _ptr(d_aoff), ptr(d_a), _ptr(d_xoff), ptr(d_x), _ptr(bits),
+                                                  T + P, stride, _ptr(bits[T + P:]), stride, self._stream()))
+        out = DeviceSets(ix, bits[:T + P + C_], d_q, T + P + C_, stride)
+        out.layout = (T, P, C_)
+        return out
 
     def bm25_topk(self, term_lists, k=1000, min_score=0.0, packed=None, within=None):
         """-> (doc index int32 [Q, k], score float64 [Q, k], n int32 [Q]) device tensors.  within: None, a DocSet (every

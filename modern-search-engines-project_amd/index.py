@@ -47,6 +47,11 @@ class CorpusIndex:
     doc_base: int = 0                   # first global dense index of this shard
     row_base: int = 0                   # first global chunk row of this shard
     n_docs_global: int = 0
+    # forward index (phrase search, DESIGN K12): document i's indexed token stream is tok_ids[tok_off[i]:tok_off[i+1]], in the
+    # dense document order; None = no forward index (every constructor but the keep_tokens=True builders and
+    # index_build.attach_tokens).  save_dir / load_dir and shard drop it.
+    tok_off: object = None              # int64 [N+1]
+    tok_ids: object = None              # int32 [T]
     _url_group: object = field(default=None, repr=False)
 
     # ------------------------------------------------------------------ basic properties
@@ -144,6 +149,8 @@ class CorpusIndex:
                     url_group=np.asarray(self.url_group(), np.int32))
         if self.doc_off is not None:
             arrs.update(doc_off=_np(self.doc_off), chunk_ids=_np(self.chunk_ids), emb=_np(self.emb))
+        if self.tok_off is not None:
+            arrs.update(tok_off=_np(self.tok_off), tok_ids=_np(self.tok_ids))
         if self.vocab is not None:
             arrs["vocab_terms"] = np.array(list(self.vocab.keys()), dtype=np.str_)
         np.savez(path, **{k: v for k, v in arrs.items() if v is not None})
@@ -162,6 +169,8 @@ class CorpusIndex:
             ix.doc_off, ix.chunk_ids, ix.emb = z["doc_off"], z["chunk_ids"], z["emb"]
         if "vocab_terms" in z:
             ix.vocab = {str(t): i for i, t in enumerate(z["vocab_terms"])}
+        if "tok_off" in z:
+            ix.tok_off, ix.tok_ids = z["tok_off"], z["tok_ids"]
         return ix
 
     # ------------------------------------------------------------------ snapshot directory (memory-mappable)
@@ -172,7 +181,8 @@ class CorpusIndex:
         (+ `docs.jsonl` with url / title / text per document when present).  Every array is written through a
         memory map in blocks, so a 15 GB embedding matrix that lives on the GPU is never held twice on the host.
         `load_dir(..., mmap=True)` maps the files back without reading them; DeviceEngine then streams them to HBM
-        through pinned staging buffers (engine.stream_to_device)."""
+        through pinned staging buffers (engine.stream_to_device).  The forward index (tok_off / tok_ids) is not part of this
+        format: an index loaded from it has none (index_build.attach_tokens puts it back)."""
         import json
         import os
         os.makedirs(path, exist_ok=True)
@@ -342,7 +352,8 @@ class CorpusIndex:
     def shard(self, rank, world):
         """Shard `rank` of `world`: its documents, its slice of every posting list, its chunk rows.
         idf / avgdl / total_docs stay GLOBAL so scores are bit-identical to the unsharded index.
-        Works on numpy arrays and on torch tensors (the 1 M-document corpus is sharded on the GPU)."""
+        Works on numpy arrays and on torch tensors (the 1 M-document corpus is sharded on the GPU).  A shard has no forward
+        index (phrase search runs on the whole index only)."""
         b = self.shard_bounds(world)
         d0, d1 = int(b[rank]), int(b[rank + 1])
         sub = CorpusIndex(doc_ids=self.doc_ids[d0:d1], avgdl=self.avgdl, total_docs=self.total_docs,

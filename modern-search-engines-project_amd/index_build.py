@@ -39,8 +39,9 @@ def idf_real(total_docs, doc_freq):
     return logs[inv].reshape(ratio.shape).astype(np.float32)
 
 
-def bm25_index_from_tokens(doc_ids, token_lists, k1=1.2, b=0.75):
-    """doc_ids: iterable of int; token_lists: one list of term strings per document."""
+def bm25_index_from_tokens(doc_ids, token_lists, k1=1.2, b=0.75, keep_tokens=False):
+    """doc_ids: iterable of int; token_lists: one list of term strings per document.  keep_tokens=True: the kept documents'
+    streams stay on the index as its forward index (tok_off / tok_ids, phrase search)."""
     rows = sorted(((int(d), toks) for d, toks in zip(doc_ids, token_lists) if toks), key=lambda r: r[0])
     ids = np.array([d for d, _ in rows], np.int64)
     if len(set(ids.tolist())) != len(ids):
@@ -64,10 +65,29 @@ def bm25_index_from_tokens(doc_ids, token_lists, k1=1.2, b=0.75):
     ix = CorpusIndex(doc_ids=ids, doc_len=doc_len, term_off=term_off, post_doc=post_doc, post_tf=post_tf, idf=idf,
                      avgdl=avgdl, total_docs=N, k1=k1, b=b, vocab=vocab)
     ix.n_docs_global = N
+    if keep_tokens:
+        ix.tok_off = np.zeros(N + 1, np.int64)
+        ix.tok_off[1:] = np.cumsum(doc_len)
+        ix.tok_ids = np.fromiter((vocab[t] for _, toks in rows for t in toks), np.int32, count=int(ix.tok_off[-1]))
     return ix
 
 
-def bm25_index_from_token_ids(doc_ids, tok_off, tok_ids, n_terms, device="cpu", k1=1.2, b=0.75, vocab=None):
+def _gather_streams(tok_off, tok_ids, docs):
+    """The streams of documents `docs` (indices into tok_off, any order) back to back -> (offsets int64 [len(docs) + 1] on the
+    host, ids: one gather of tok_ids, which may be a torch tensor on any device or a numpy array)."""
+    import torch
+    off = np.asarray(tok_off.cpu() if torch.is_tensor(tok_off) else tok_off, np.int64)
+    docs = np.asarray(docs, np.int64)
+    lens = off[docs + 1] - off[docs]
+    k_off = np.zeros(len(docs) + 1, np.int64)
+    k_off[1:] = np.cumsum(lens)
+    src = np.repeat(off[docs] - k_off[:-1], lens) + np.arange(k_off[-1])
+    if torch.is_tensor(tok_ids):
+        return k_off, tok_ids[torch.as_tensor(src, device=tok_ids.device)].contiguous()
+    return k_off, np.asarray(tok_ids)[src]
+
+
+def bm25_index_from_token_ids(doc_ids, tok_off, tok_ids, n_terms, device="cpu", k1=1.2, b=0.75, vocab=None, keep_tokens=False):
     """The same tables from token-id streams, built on `device` (the build given pre-tokenised
     documents, at corpus scale: one radix sort of (term, document) keys + run lengths instead of Python dicts).
 
@@ -77,11 +97,16 @@ def bm25_index_from_token_ids(doc_ids, tok_off, tok_ids, n_terms, device="cpu", 
     kernels of csrc/msr_build.hip (per-document sort + run lengths, stable radix sort by term, boundary-based doc_freq,
     three-kernel scans; msr_build_postings); on the CPU device torch's sort / unique_consecutive / bincount restate the same
     build (host-side reference for the tests).  idf is evaluated on the host with the same float64 log10 -> float32
-    rounding as bm25_index_from_tokens so that all builders agree bit for bit."""
+    rounding as bm25_index_from_tokens so that all builders agree bit for bit.
+
+    keep_tokens=True: the streams of the kept documents (those with tokens, ascending doc_id) stay on the index as its forward
+    index -- tok_off int64 [N+1], tok_ids int32 [T] on `device`, never the caller's own tensor -- lengths and their cumulative
+    sum on the host (numpy, N values), the ids in one torch gather on `device`.
+    What phrase search reads (DeviceEngine.phrase_sets); off by default."""
     import torch
     dev = torch.device(device)
     if dev.type == "cuda":
-        return _bm25_index_from_token_ids_hip(doc_ids, tok_off, tok_ids, n_terms, dev, k1, b, vocab)
+        return _bm25_index_from_token_ids_hip(doc_ids, tok_off, tok_ids, n_terms, dev, k1, b, vocab, keep_tokens)
     ids = torch.as_tensor(np.asarray(doc_ids, np.int64))
     off = torch.as_tensor(np.asarray(tok_off, np.int64)).to(dev)
     tok = (tok_ids if torch.is_tensor(tok_ids) else torch.as_tensor(np.asarray(tok_ids, np.int32))).to(dev)
@@ -110,10 +135,13 @@ def bm25_index_from_token_ids(doc_ids, tok_off, tok_ids, n_terms, device="cpu", 
                      post_tf=tf.to(torch.int32), idf=torch.as_tensor(idf).to(dev), avgdl=avgdl, total_docs=N, k1=k1, b=b,
                      vocab=vocab)
     ix.n_docs_global = N
+    if keep_tokens:
+        k_off, k_tok = _gather_streams(off, tok, keep.cpu().numpy())
+        ix.tok_off, ix.tok_ids = torch.as_tensor(k_off).to(dev), k_tok.to(torch.int32)
     return ix
 
 
-def _bm25_index_from_token_ids_hip(doc_ids, tok_off, tok_ids, n_terms, dev, k1, b, vocab):
+def _bm25_index_from_token_ids_hip(doc_ids, tok_off, tok_ids, n_terms, dev, k1, b, vocab, keep_tokens=False):
     """bm25_index_from_token_ids on the GPU through the C ABI (msr_build_postings); no fallback."""
     import ctypes as C
 
@@ -159,6 +187,8 @@ def _bm25_index_from_token_ids_hip(doc_ids, tok_off, tok_ids, n_terms, dev, k1, 
     ix = CorpusIndex(doc_ids=ids[keep], doc_len=doc_len, term_off=term_off, post_doc=post_doc[:P], post_tf=post_tf[:P],
                      idf=torch.as_tensor(idf).to(dev), avgdl=avgdl, total_docs=N, k1=k1, b=b, vocab=vocab)
     ix.n_docs_global = N
+    if keep_tokens:                                          # the builder's own input; a copy where that still is the caller's tensor
+        ix.tok_off, ix.tok_ids = d_off, (k_tok.clone() if k_tok is tok_ids else k_tok)
     return ix
 
 
@@ -253,6 +283,9 @@ def bm25_add_token_ids(ix, doc_ids, tok_off, tok_ids, n_terms, device="cpu", voc
       * corpus side: doc_off gets zero-chunk entries for the new documents (attach_chunks then appends their chunk rows);
         emb / chunk_ids are kept; urls / titles / texts are extended from docs_meta {doc_id: (url, title, text)} (None where
         absent); the URL groups are recomputed over the whole corpus.  vocab, when given, replaces ix.vocab.
+      * forward index: if `ix` has one (tok_off / tok_ids) the result has one in merged document order -- an added document
+        gets its stream, a urlsDB-only document that now gets a row keeps its dense index and gets its new stream, every other
+        document keeps its own; if `ix` has none the result has none.
     A shard (doc_base != 0 or n_docs_global != n_docs) is refused: update the whole index, then shard it."""
     import torch
     from .index import _np
@@ -283,7 +316,8 @@ def bm25_add_token_ids(ix, doc_ids, tok_off, tok_ids, n_terms, device="cpu", voc
     s_off = np.zeros(len(sel) + 1, np.int64)
     s_off[1:] = np.cumsum(lens[sel])
     src = np.repeat(off[sel] - s_off[:-1], lens[sel]) + np.arange(s_off[-1])
-    nb = bm25_index_from_token_ids(ids[sel], s_off, tok[torch.as_tensor(src, device=tok.device)], int(n_terms), device=dev)
+    nb = bm25_index_from_token_ids(ids[sel], s_off, tok[torch.as_tensor(src, device=tok.device)], int(n_terms), device=dev,
+                                   keep_tokens=ix.tok_off is not None)
     b_ids = np.asarray(nb.doc_ids, np.int64)
     merged = np.union1d(old_ids, b_ids)
     M = len(merged)
@@ -305,6 +339,21 @@ def bm25_add_token_ids(ix, doc_ids, tok_off, tok_ids, n_terms, device="cpu", voc
                       post_tf=post_tf, idf=torch.as_tensor(idf).to(dev), avgdl=avgdl, total_docs=total_docs, k1=ix.k1, b=ix.b,
                       vocab=vocab if vocab is not None else ix.vocab, chunk_ids=ix.chunk_ids, emb=ix.emb)
     out.n_docs_global = M
+    if ix.tok_off is not None:                               # both sides' streams side by side, gathered into merged order
+        a_off, b_off = np.asarray(_np(ix.tok_off), np.int64), np.asarray(_np(nb.tok_off), np.int64)
+        a_tok = (ix.tok_ids if torch.is_tensor(ix.tok_ids) else torch.as_tensor(np.asarray(ix.tok_ids, np.int32))).to(dev, torch.int32)
+        src_doc = np.full(M, -1, np.int64)                   # index into the concatenated offsets [a's documents, b's documents]
+        src_doc[a_idx] = np.arange(len(old_ids))
+        src_doc[b_map] = len(old_ids) + np.arange(len(b_ids))               # (a document on both sides: its new stream)
+        starts = np.concatenate([a_off[:-1], a_off[-1] + b_off[:-1]])
+        ends = np.concatenate([a_off[1:], a_off[-1] + b_off[1:]])
+        lens_m = (ends - starts)[src_doc]
+        m_off = np.zeros(M + 1, np.int64)
+        m_off[1:] = np.cumsum(lens_m)
+        src = np.repeat(starts[src_doc] - m_off[:-1], lens_m) + np.arange(m_off[-1])
+        both_tok = torch.cat([a_tok, nb.tok_ids.to(dev, torch.int32)])
+        out.tok_off = torch.as_tensor(m_off).to(dev)
+        out.tok_ids = both_tok[torch.as_tensor(src, device=both_tok.device)].contiguous()
     if ix.doc_off is not None:
         cnt = np.zeros(M, np.int64)
         cnt[a_idx] = np.diff(np.asarray(_np(ix.doc_off), np.int64))
@@ -393,7 +442,7 @@ def remove_documents(ix, doc_ids, device="cpu"):
       * every listed document the index has goes, urlsDB-only documents (doc_len 0) included: from doc_ids / doc_len, the
         postings (compact_postings: msr_compact_postings on a GPU device), the chunk rows (doc_off / chunk_ids / emb, gathered
         on emb's own device), urls / titles / texts; the kept documents keep their order and are renumbered densely; the
-        URL groups are recomputed.
+        URL groups are recomputed; a forward index (tok_off / tok_ids) is gathered to the kept documents' streams.
       * total_docs -= the removed documents that had a BM25 row; avg_doc_length and the idf of EVERY term are recomputed
         with the builders' float64 -> REAL rounding (n_terms stays: a term left without postings gets the idf a
         from-scratch build gives it), so the tables equal a from-scratch build of the remaining documents bit for bit.
@@ -438,9 +487,79 @@ def remove_documents(ix, doc_ids, device="cpu"):
             out.emb = ix.emb.index_select(0, torch.as_tensor(np.nonzero(rows)[0], device=ix.emb.device))
         elif ix.emb is not None:
             out.emb = np.asarray(ix.emb)[rows]
+    if ix.tok_off is not None:
+        tok = ix.tok_ids if torch.is_tensor(ix.tok_ids) else torch.as_tensor(np.asarray(ix.tok_ids, np.int32))
+        k_off, k_tok = _gather_streams(ix.tok_off, tok.to(dev, torch.int32), np.nonzero(keep)[0])
+        out.tok_off, out.tok_ids = torch.as_tensor(k_off).to(dev), k_tok
     for name in ("urls", "titles", "texts"):
         col = getattr(ix, name)
         if col is not None:
             setattr(out, name, [v for v, k in zip(col, keep.tolist()) if k])
     out.update_counts = dict(removed=int(found.sum()), removed_rows=removed_rows, not_found=int((~found).sum()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- forward index
+def attach_tokens(ix, tok_off, tok_ids):
+    """Give an index that came without a forward index (CorpusIndex.from_tables / from_duckdb, a loaded snapshot, a build
+    without keep_tokens) the token streams phrase search reads: tok_off int64 [N+1], tok_ids int32 [T], document i's stream
+    (the ids it was indexed from, in the index's dense document order) at tok_ids[tok_off[i]:tok_off[i+1]].  Validated here,
+    ValueError otherwise: N + 1 offsets that start at 0, ascend and end at len(tok_ids); ids in [0, n_terms); every document's
+    length equals its doc_len (a document without a BM25 row has length 0).  Sets ix.tok_off / ix.tok_ids and returns ix; an
+    engine already bound to ix sees them after DeviceEngine.rebind / Retriever.update_index.  CorpusIndex.save / load keep
+    them; save_dir / load_dir and shard drop them."""
+    import torch
+    from .index import _np
+    off = np.asarray(_np(tok_off)).reshape(-1)
+    ids = np.asarray(_np(tok_ids)).reshape(-1)
+    N = ix.n_docs
+    if len(off) != N + 1:
+        raise ValueError(f"attach_tokens: {len(off)} offsets for an index of {N} documents (N + 1 = {N + 1} are needed)")
+    if not np.issubdtype(off.dtype, np.integer) or (len(ids) and not np.issubdtype(ids.dtype, np.integer)):
+        raise ValueError("attach_tokens: offsets and ids are integers")
+    off = off.astype(np.int64)
+    if off[0] != 0:
+        raise ValueError("attach_tokens: tok_off[0] must be 0")
+    if (np.diff(off) < 0).any():
+        raise ValueError("attach_tokens: tok_off descends")
+    if off[-1] != len(ids):
+        raise ValueError(f"attach_tokens: tok_off ends at {int(off[-1])}, tok_ids holds {len(ids)} ids")
+    if len(ids) and (int(ids.min()) < 0 or int(ids.max()) >= ix.n_terms):
+        raise ValueError(f"attach_tokens: a token id is outside [0, n_terms = {ix.n_terms})")
+    want = np.zeros(N, np.int64) if ix.doc_len is None else np.asarray(_np(ix.doc_len), np.int64)
+    bad = np.nonzero(np.diff(off) != want)[0]
+    if len(bad):
+        d = int(bad[0])
+        raise ValueError(f"attach_tokens: document {d} has {int(off[d + 1] - off[d])} tokens, its doc_len is {int(want[d])}")
+    if torch.is_tensor(tok_ids):
+        ix.tok_off, ix.tok_ids = torch.as_tensor(off).to(tok_ids.device), tok_ids.to(torch.int32).reshape(-1).contiguous()
+    else:
+        ix.tok_off, ix.tok_ids = off, ids.astype(np.int32)
+    return ix
+
+
+def tokens_from_texts(ix, tokenizer=None):
+    """(tok_off int64 [N+1], tok_ids int32 [T]) for attach_tokens, from the index's own titles / texts: every document's
+    normalise_document_text(title, text) through `tokenizer` (default text.simple_tokenize; it must be the tokenizer the index
+    was built with) and ix.vocab.  ValueError if the index has no texts or vocabulary, a token is not in the vocabulary, or a
+    document's token count differs from its doc_len (a document without a BM25 row must tokenise to nothing)."""
+    from .index import _np
+    from .text import simple_tokenize
+    tok = tokenizer or simple_tokenize
+    if ix.texts is None or ix.vocab is None:
+        raise ValueError("tokens_from_texts: the index needs texts and a vocabulary")
+    N = ix.n_docs
+    want = np.zeros(N, np.int64) if ix.doc_len is None else np.asarray(_np(ix.doc_len), np.int64)
+    titles = ix.titles if ix.titles is not None else [None] * N
+    off, ids, vocab = np.zeros(N + 1, np.int64), [], ix.vocab
+    for d in range(N):
+        words = tok(normalise_document_text(titles[d], ix.texts[d]))
+        if len(words) != want[d]:
+            raise ValueError(f"tokens_from_texts: document {d} tokenises to {len(words)} tokens, its doc_len is {int(want[d])}")
+        for w in words:
+            t = vocab.get(w)
+            if t is None:
+                raise ValueError(f"tokens_from_texts: token {w!r} of document {d} is not in the vocabulary")
+            ids.append(t)
+        off[d + 1] = len(ids)
+    return off, np.asarray(ids, np.int32)

@@ -16,7 +16,7 @@ from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .reranker import Reranker
-from .text import (LineFormatter, extract_domain, extract_domain_topic, format_result_line, parse_operators,
+from .text import (LineFormatter, extract_domain, extract_domain_topic, format_result_line, parse_operators, parse_phrases,
                    preprocess_query, read_queries_file)
 
 TOP_K_RETRIEVAL = 1000     # config.py:13
@@ -269,18 +269,23 @@ class Retriever:
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
-    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, must=None, must_not=None):
+    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, must=None, must_not=None,
+                       must_phrases=None, must_not_phrases=None):
         """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
         within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
         mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
         with its true BM25 score (msr_bm25_score_docs, msr_union_candidates); the candidates and where each came from are
         copied to pinned buffers beside the final rows (the job's sixth entry).
         must / must_not (None | term-id lists per query of the chunk): ONE term_sets call in front of stage 1 turns them, inside
-        `within`, into device sets that take within's place in both stages; nothing else changes."""
+        `within`, into device sets that take within's place in both stages; nothing else changes.
+        must_phrases / must_not_phrases (None | per query of the chunk a list of phrases, each a list of term ids): ONE
+        phrase_sets call takes the term_sets call's place (it makes that call itself, with the phrases' candidate rows)."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
         union = None
-        if must is not None or must_not is not None:
+        if must_phrases is not None or must_not_phrases is not None:
+            within = eng.phrase_sets(must_phrases, must_not_phrases, must, must_not, within=within)
+        elif must is not None or must_not is not None:
             within = eng.term_sets(must, must_not, within=within)
         if mode == "hybrid":
             k_lex = hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
@@ -360,7 +365,7 @@ class Retriever:
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
-                          must_not=None):
+                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
@@ -375,13 +380,22 @@ class Retriever:
         must / must_not: None or, per query, the terms (strings or ids) every result must / must not contain -- one
         DeviceEngine.term_sets call per chunk builds the sets on the device, inside `within`; in hybrid mode the dense
         candidates are restricted too.  operators: here the queries are term ids, there is no text to parse -- True is refused
-        (search / search_batch / batch_search parse; or text.parse_operators and must= / must_not=)."""
+        (search / search_batch / batch_search parse; or text.parse_operators and must= / must_not=).
+        must_phrases / must_not_phrases: None or, per query, a list of phrases -- each a list of terms (strings or ids) that
+        must stand next to each other, in this order, in a result's indexed token stream / in none of them: one
+        DeviceEngine.phrase_sets call per chunk (in the term_sets call's place), both stages restricted in hybrid mode.  A
+        phrase filters; the BM25 scores stay what they are.  The index needs a forward index (index_build.attach_tokens),
+        MsrError otherwise; a phrase of more than MSR_PHRASE_MAX_TERMS terms raises ValueError.  phrases=True is refused like
+        operators=True (text.parse_phrases needs the text)."""
         import torch
         eng = self.engine
         _check_mode(mode)
         if operators:
             raise ValueError("operators=True needs the query text: use search / search_batch / batch_search, or parse with "
                              "text.parse_operators and pass must= / must_not=")
+        if phrases:
+            raise ValueError("phrases=True needs the query text: use search / search_batch / batch_search, or parse with "
+                             "text.parse_phrases and pass must_phrases= / must_not_phrases=")
         if top_k > eng.rerank_max_docs or top_k > eng.max_k:
             raise ValueError(f"top_k {top_k} exceeds the engine's max_k / rerank_max_docs ({eng.max_k} / {eng.rerank_max_docs})")
         if mode == "hybrid":
@@ -393,10 +407,12 @@ class Retriever:
         step = int(chunk or max(256, eng.max_queries))
         if isinstance(within, (list, tuple, DeviceSets)) and len(within) != Q:
             raise ValueError(f"within: {len(within)} entries for {Q} queries")
-        for name, lists in (("must", must), ("must_not", must_not)):
+        for name, lists in (("must", must), ("must_not", must_not), ("must_phrases", must_phrases),
+                            ("must_not_phrases", must_not_phrases)):
             if lists is not None and len(lists) != Q:
                 raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
         op_ids = lambda lists, a, b: None if lists is None else [self.index.term_ids(t) for t in lists[a:b]]
+        ph_ids = lambda lists, a, b: None if lists is None else [[self.index.term_ids(p) for p in ps] for ps in lists[a:b]]
         pending = None
         for i, a in enumerate(range(0, Q, step)):
             b = min(Q, a + step)
@@ -405,7 +421,8 @@ class Retriever:
             w = (list(within[a:b]) if isinstance(within, (list, tuple))
                  else within.queries(a, b) if isinstance(within, DeviceSets) else within)
             job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=op_ids(must, a, b),
-                                      must_not=op_ids(must_not, a, b))
+                                      must_not=op_ids(must_not, a, b), must_phrases=ph_ids(must_phrases, a, b),
+                                      must_not_phrases=ph_ids(must_not_phrases, a, b))
             if pending is not None:
                 yield (pending[0],) + self._collect(pending[1])
             pending = (a, job)
@@ -418,17 +435,19 @@ class Retriever:
         return out if len(job) == 5 else out + (cls._collect_source(job, out[0], out[3]),)
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
-                    dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None):
+                    dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
+                    must_phrases=None, must_not_phrases=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
         with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
-        operators / must / must_not: final_list_chunks."""
+        operators / must / must_not / phrases / must_phrases / must_not_phrases: final_list_chunks."""
         _check_mode(mode)
         if with_source and mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
         parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
-                                            operators=operators, must=must, must_not=must_not))
+                                            operators=operators, must=must, must_not=must_not, phrases=phrases,
+                                            must_phrases=must_phrases, must_not_phrases=must_not_phrases))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -439,34 +458,53 @@ class Retriever:
                np.concatenate([pad(p[3], -1) for p in parts]), np.concatenate([p[4] for p in parts]))
         return out + ((np.concatenate([pad(p[5], 0) for p in parts]),) if with_source else ())
 
-    def _operators(self, processed, operators, must, must_not):
-        """-> (scoring texts, must term lists, must_not term lists) of the preprocessed queries: the parsed operator words
-        (operators=True), tokenised like the query, joined with the caller's explicit lists; (processed, None, None) when
-        there is neither -- the chain then runs exactly as without the feature."""
-        if not operators and must is None and must_not is None:
-            return processed, None, None
+    def _operators(self, processed, operators, must, must_not, phrases=False, must_phrases=None, must_not_phrases=None):
+        """-> (scoring texts, must term lists, must_not term lists, must phrases, not phrases) of the preprocessed queries: the
+        parsed operator words (operators=True) and quoted phrases (phrases=True, text.parse_phrases, BEFORE the operators),
+        tokenised like the query, joined with the caller's explicit lists; a pair is (None, None) when there is nothing of
+        its kind -- the chain then runs exactly as without the feature.  An explicit phrase is a string (tokenised here) or a
+        list of term strings; a phrase that tokenises to nothing is dropped."""
+        if not operators and must is None and must_not is None and not phrases and must_phrases is None and must_not_phrases is None:
+            return processed, None, None, None, None
         Q = len(processed)
-        for name, lists in (("must", must), ("must_not", must_not)):
+        for name, lists in (("must", must), ("must_not", must_not), ("must_phrases", must_phrases),
+                            ("must_not_phrases", must_not_phrases)):
             if lists is not None and len(lists) != Q:
                 raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
+        tok = self.bm25._tokenize
         m = [list(t) for t in must] if must is not None else [[] for _ in range(Q)]
         x = [list(t) for t in must_not] if must_not is not None else [[] for _ in range(Q)]
-        if operators:
-            tok = self.bm25._tokenize
-            processed = list(processed)
-            for q in range(Q):
+        as_terms = lambda p: tok(p) if isinstance(p, str) else list(p)
+        mp = [[as_terms(p) for p in ps] for ps in must_phrases] if must_phrases is not None else [[] for _ in range(Q)]
+        xp = [[as_terms(p) for p in ps] for ps in must_not_phrases] if must_not_phrases is not None else [[] for _ in range(Q)]
+        processed = list(processed)
+        for q in range(Q):
+            if phrases:
+                processed[q], m_ph, x_ph = parse_phrases(processed[q])
+                mp[q] += [tok(p) for p in m_ph]
+                xp[q] += [tok(p) for p in x_ph]
+            if operators:
                 processed[q], m_words, x_words = parse_operators(processed[q])
                 m[q] += [t for w in m_words for t in tok(w)]
                 x[q] += [t for w in x_words for t in tok(w)]
+            mp[q], xp[q] = [p for p in mp[q] if p], [p for p in xp[q] if p]
         if not any(m) and not any(x):
-            return processed, None, None
-        return processed, m, x
+            m = x = None
+        if not any(mp) and not any(xp):
+            mp = xp = None
+        return processed, m, x, mp, xp
 
-    def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not):
-        """_prepare with operators: -> (term ids, vectors, must term lists or None, must_not term lists or None).  The scoring
-        text (excluded words removed) is what gets tokenised and embedded."""
-        processed, must, must_not = self._operators([preprocess_query(q) for q in queries], operators, must, must_not)
-        return self._prepare(queries, query_embeddings, term_lists, processed) + (must, must_not)
+    def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not, phrases=False, must_phrases=None,
+                     must_not_phrases=None):
+        """_prepare with operators and phrases: -> (term ids, vectors, keyword arguments of final_lists: must / must_not /
+        must_phrases / must_not_phrases where there are any).  The scoring text (excluded words and phrases removed, quotes
+        gone) is what gets tokenised and embedded."""
+        processed, m, x, mp, xp = self._operators([preprocess_query(q) for q in queries], operators, must, must_not, phrases,
+                                                  must_phrases, must_not_phrases)
+        ops = {} if m is None else {"must": m, "must_not": x}
+        if mp is not None:
+            ops.update(must_phrases=mp, must_not_phrases=xp)
+        return self._prepare(queries, query_embeddings, term_lists, processed) + (ops,)
 
     def _prepare(self, queries, query_embeddings, term_lists, processed=None):
         if processed is None:
@@ -482,7 +520,8 @@ class Retriever:
         return ids, qv
 
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
-                     mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None):
+                     mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
+                     must_phrases=None, must_not_phrases=None):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
@@ -492,10 +531,16 @@ class Retriever:
         result must / must not contain; `+word` still scores, `-word` does not.  must / must_not: per query a list of term
         strings (for callers with their own tokenizer, like term_lists), joined with the parsed ones.  Both act inside
         `within`, in both stages of either mode: a page that holds an excluded word is never returned.  Without operators
-        and lists the call is what it was."""
+        and lists the call is what it was.
+        phrases=True: `"a b c"` in a query is a required phrase (its words still score), `-"a b"` an excluded one (removed from
+        the scoring text) -- text.parse_phrases, after preprocess_query and before the operators; must_phrases /
+        must_not_phrases: per query a list of phrases, each a string (tokenised like the query) or a list of term strings.  A
+        result holds every required phrase and no excluded one IN ITS INDEXED TOKEN STREAM (words next to each other, in
+        order, after the tokenizer); the scores are unchanged.  Needs an index with a forward index (index_build.attach_tokens;
+        MsrError otherwise); a phrase of more than 16 terms raises ValueError.  Off by default."""
         _check_mode(mode)
-        ids, qv, must, must_not = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not)
-        ops = {} if must is None else {"must": must, "must_not": must_not}
+        ids, qv, ops = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not, phrases, must_phrases,
+                                         must_not_phrases)
         src = None
         if mode == "hybrid":
             doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
@@ -522,30 +567,36 @@ class Retriever:
         return out
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
-               mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None):
-        """search_batch for one query; must / must_not: ONE list of term strings each."""
+               mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
+               must_not_phrases=None):
+        """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
+        list of phrases each."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
                                  mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
-                                 must_not=None if must_not is None else [must_not])[0]
+                                 must_not=None if must_not is None else [must_not], phrases=phrases,
+                                 must_phrases=None if must_phrases is None else [must_phrases],
+                                 must_not_phrases=None if must_not_phrases is None else [must_not_phrases])[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
-                     dense_k=DENSE_K, operators=False, must=None, must_not=None):
+                     dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
+                     must_not_phrases=None):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
-        search_batch (the entries keep the reference's keys in either mode); operators / must / must_not: search_batch."""
+        search_batch (the entries keep the reference's keys in either mode); operators / must / must_not / phrases /
+        must_phrases / must_not_phrases: search_batch."""
         _check_mode(mode)
-        ids, qv, must, must_not = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators,
-                                                    must, must_not)
-        ops = {} if must is None else {"must": must, "must_not": must_not}
+        ids, qv, ops = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators, must, must_not,
+                                         phrases, must_phrases, must_not_phrases)
         doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         return BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
 
     def batch_search_to_file(self, queries_path, out_path, query_embeddings=None, term_lists=None, chunk=None):
-        """search_api.py:331-367: queries.txt -> one formatted line per result in out_path; -> number of lines.  Three things
+        """search_api.py:331-367: queries.txt -> one formatted line per result in out_path; -> number of lines.  (Quotes and
+        signs in the file's queries are punctuation here: no operators, no phrases.)  Three things
         run side by side, chunk by chunk: this thread preprocesses / tokenises chunk i + 1 and enqueues it, the GPU ranks
         chunk i, a second host thread waits for chunk i - 1's final rows, formats them (native code, outside the interpreter
         lock) and writes them."""

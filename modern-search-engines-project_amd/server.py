@@ -60,6 +60,9 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         operators: bool = False       # `+word` / `-word` in the query: required / excluded words (text.parse_operators)
         must: Optional[List[str]] = None       # terms every result must contain ...
         must_not: Optional[List[str]] = None   # ... and must not contain (Retriever.search)
+        phrases: bool = False         # `"a b"` / `-"a b"` in the query: required / excluded phrases (text.parse_phrases)
+        must_phrases: Optional[List[str]] = None       # phrases every result must hold, words next to each other ...
+        must_not_phrases: Optional[List[str]] = None   # ... and must not hold (Retriever.search; needs a forward index)
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -117,6 +120,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                 kw["within"] = within_sites(req.sites)
             if req.operators or req.must is not None or req.must_not is not None:
                 kw.update(operators=req.operators, must=req.must, must_not=req.must_not)
+            if req.phrases or req.must_phrases is not None or req.must_not_phrases is not None:
+                kw.update(phrases=req.phrases, must_phrases=req.must_phrases, must_not_phrases=req.must_not_phrases)
             try:
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)

@@ -85,6 +85,35 @@ def parse_operators(processed_query: str):
     return " ".join(keep), must, must_not
 
 
+def parse_phrases(processed_query: str):
+    """Quoted phrases of a query that has been through preprocess_query -> (text_without_quotes, must_phrases, not_phrases),
+    the phrases as the text between their quotes.  `"a b c"` -- the page must hold the words next to each other, in this
+    order, in its indexed token stream -- keeps its words in the scoring text (a `+` in front of the opening quote means the
+    same and is dropped); `-"a b"` -- the page must not hold the phrase -- is removed from the scoring text.  The sign counts
+    only at the start of a whitespace-delimited token.  Quotes pair up from the left; an unbalanced last quote is left as it
+    is; empty quotes are dropped.  Runs before parse_operators (which sees the text without quotes); the caller tokenises each
+    phrase like the query, and a phrase that tokenises to nothing is dropped there.  Without a pair of quotes the text comes
+    back unchanged."""
+    at = [i for i, ch in enumerate(processed_query) if ch == '"']
+    if len(at) < 2:
+        return processed_query, [], []
+    out, must, must_not, pos = [], [], [], 0
+    for a, b in zip(at[0::2], at[1::2]):
+        inner = processed_query[a + 1:b].strip()
+        sign = processed_query[a - 1] if a >= 1 and processed_query[a - 1] in "+-" and (a == 1 or processed_query[a - 2].isspace()) else ""
+        out.append(processed_query[pos:a - len(sign)])
+        if sign == "-":
+            if inner:
+                must_not.append(inner)
+        else:
+            if inner:
+                must.append(inner)
+            out.append(" " + inner + " ")
+        pos = b + 1
+    out.append(processed_query[pos:])
+    return " ".join("".join(out).split()), must, must_not
+
+
 def format_result_line(query_num, rank, url, score) -> str:
     """search_api.py:290"""
     return f"{query_num}\t{rank}\t{url}\t{score:.3f}"
