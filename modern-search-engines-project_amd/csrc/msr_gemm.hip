@@ -98,25 +98,66 @@ __global__ __launch_bounds__(256) void batch_margin_kernel(const float* __restri
     }
 }
 
-// out[q][j] = max_p in[j][p][q]: the tile maxima as one row per query for the top-k select (32 x 32 LDS transpose)
+// out[q][j] = max_p in[j][p][q]: the tile maxima as one row per query for the top-k select.  One workgroup joins and
+// transposes 32 tiles x 128 queries: a half wave reads the 128 queries of one (tile, part) row with one 16-byte load per
+// lane, and a thread's 4 x PARTS loads (4 tiles) are independent -- PARTS is a template parameter, so they are all in flight
+// before the first maximum is taken (with a runtime trip count the loop waited for one 128-byte read per thread at a time
+// and the join of the one-group f32 pass' 160 MB ran at 2.8 TB/s).  The maximum is the same in any order.  The 32 x 128
+// block goes through LDS (16-byte stores; rows of 132 words keep them aligned) and leaves as 128-byte pieces of the
+// queries' rows.  PARTS = 0: any number of parts (no caller has one).  nq_pad: a multiple of 128.
+template <int PARTS>
 __global__ __launch_bounds__(256) void gemm_tmax_kernel(const float* __restrict__ in, int n_j, int parts, int nq_pad,
                                                          float* __restrict__ out, int out_stride) {
-    __shared__ float t[32][33];
-    const int j0 = blockIdx.x * 32, q0 = blockIdx.y * 32;
+    __shared__ __attribute__((aligned(16))) float t[32][132];
+    const int j0 = blockIdx.x * 32, q0 = blockIdx.y * 128;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;                 // 32 x 8
+    const float ninf = -__builtin_inff();
+    const size_t step = (size_t)nq_pad / 4;                                 // f32x4 between the parts of a tile
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int j = j0 + ty + 8 * r;
-        float v = -__builtin_inff();
-        if (j < n_j)
-            for (int p = 0; p < parts; ++p) v = fmaxf(v, in[((size_t)j * parts + p) * nq_pad + q0 + tx]);
-        t[ty + 8 * r][tx] = v;
+    for (int h = 0; h < 2; ++h) {                                           // 2 tiles at a time: 2 x PARTS loads in flight
+        const f32x4* src[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int j = j0 + ty + 8 * (2 * h + r);
+            const int jc = j < n_j ? j : n_j - 1;                            // (past the end: a row that exists; never written out)
+            src[r] = (const f32x4*)(in + (size_t)jc * parts * nq_pad + q0) + tx;
+        }
+        f32x4 v[2] = {{ninf, ninf, ninf, ninf}, {ninf, ninf, ninf, ninf}};
+        if constexpr (PARTS > 0) {
+            f32x4 x[2][PARTS];
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int p = 0; p < PARTS; ++p) x[r][p] = src[r][p * step];
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int p = 0; p < PARTS; ++p) {
+                    v[r].x = fmaxf(v[r].x, x[r][p].x); v[r].y = fmaxf(v[r].y, x[r][p].y);
+                    v[r].z = fmaxf(v[r].z, x[r][p].z); v[r].w = fmaxf(v[r].w, x[r][p].w);
+                }
+        } else {
+            for (int p = 0; p < parts; ++p) {
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const f32x4 x = src[r][p * step];
+                    v[r].x = fmaxf(v[r].x, x.x); v[r].y = fmaxf(v[r].y, x.y); v[r].z = fmaxf(v[r].z, x.z); v[r].w = fmaxf(v[r].w, x.w);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) *(f32x4*)&t[ty + 8 * (2 * h + r)][4 * tx] = v[r];
     }
     __syncthreads();
+    const int j = j0 + tx;                                                  // lane = tile: 128-byte pieces of 4 queries' rows
+    if (j < n_j) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int q = q0 + ty + 8 * r, j = j0 + tx;
-        if (j < n_j) out[(size_t)q * out_stride + j] = t[tx][ty + 8 * r];
+        for (int r = 0; r < 4; ++r) {
+            const int ql = 4 * (ty + 8 * r);
+            const f32x4 v = *(const f32x4*)&t[tx][ql];
+            float* o = out + (size_t)(q0 + ql) * out_stride + j;
+            o[0] = v.x; o[(size_t)out_stride] = v.y; o[2 * (size_t)out_stride] = v.z; o[3 * (size_t)out_stride] = v.w;
+        }
     }
 }
 
@@ -344,7 +385,11 @@ int msr_gemm_pair_cap() { return GM_PAIR_CAP; }
 
 hipError_t msr_gemm_tmax(const float* tmax_t, int n_j, int parts, int nq_pad, float* out, int out_stride, hipStream_t stream) {
     if (n_j <= 0 || nq_pad <= 0) return hipSuccess;
-    gemm_tmax_kernel<<<dim3((n_j + 31) / 32, nq_pad / 32), 256, 0, stream>>>(tmax_t, n_j, parts, nq_pad, out, out_stride);
+    if (parts <= 0 || nq_pad % 128 != 0) return hipErrorInvalidValue;
+    const dim3 grid((n_j + 31) / 32, nq_pad / 128);
+    if (parts == 8) gemm_tmax_kernel<8><<<grid, 256, 0, stream>>>(tmax_t, n_j, parts, nq_pad, out, out_stride);
+    else if (parts == 1) gemm_tmax_kernel<1><<<grid, 256, 0, stream>>>(tmax_t, n_j, parts, nq_pad, out, out_stride);
+    else gemm_tmax_kernel<0><<<grid, 256, 0, stream>>>(tmax_t, n_j, parts, nq_pad, out, out_stride);
     return hipGetLastError();
 }
 hipError_t msr_gemm_kth(const float* tmax, int n, int stride, int nq, int nq_pad, int k, const float* margin, float* thr,
@@ -390,14 +435,14 @@ hipError_t msr_gemm_candidates(const GemmIndex& g, const DenseIndex& ix, const f
         if (ev && (err = hipEventRecord(ev[0], stream)) != hipSuccess) return err;
         if ((err = msr_stream256_bf16_launch(false, a, grid, stream)) != hipSuccess) return err;
         if (ev && (err = hipEventRecord(ev[1], stream)) != hipSuccess) return err;
-        gemm_tmax_kernel<<<dim3((n_s + 31) / 32, nq_pad / 32), 256, 0, stream>>>(g.tmax_t, n_s, 1, nq_pad, (float*)g.tmax, g.tmax_stride);
+        if ((err = msr_gemm_tmax(g.tmax_t, n_s, 1, nq_pad, (float*)g.tmax, g.tmax_stride, stream)) != hipSuccess) return err;
         gemm_kth_kernel<<<nq_pad, 1024, 0, stream>>>((const float*)g.tmax, n_s, g.tmax_stride, nq, k, margin, g.thr, g.flag, __builtin_inff(), 1.0f);
         a.t_first = 0; a.t_stride = 1; a.t_count = g.n_tiles;
         a.thr = g.thr; a.wvbuf = g.wgbuf; a.wv_cap = g.wv_cap; a.wv_count = g.wv_count;
         if (ev && (err = hipEventRecord(ev[2], stream)) != hipSuccess) return err;
         if ((err = msr_stream256_bf16_launch(true, a, grid, stream)) != hipSuccess) return err;
         if (ev && (err = hipEventRecord(ev[3], stream)) != hipSuccess) return err;
-        gemm_tmax_kernel<<<dim3((g.n_tiles + 31) / 32, nq_pad / 32), 256, 0, stream>>>(g.tmax_t, g.n_tiles, 1, nq_pad, (float*)g.tmax, g.tmax_stride);
+        if ((err = msr_gemm_tmax(g.tmax_t, g.n_tiles, 1, nq_pad, (float*)g.tmax, g.tmax_stride, stream)) != hipSuccess) return err;
         gemm_kth_kernel<<<nq_pad, 1024, 0, stream>>>((const float*)g.tmax, g.n_tiles, g.tmax_stride, nq, k, margin, g.thr2, nullptr, __builtin_inff(), 1.0f);
     }
     // ---- finish: bucket, per-document maxima, candidates ----

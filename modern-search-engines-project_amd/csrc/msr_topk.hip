@@ -31,6 +31,13 @@ namespace {
 
 constexpr int SEL_THREADS = 256;
 constexpr int SCAN_THREADS = 1024;
+// Workgroups of a streaming pass over all queries, at most.  Dense rows: 2048.  Lists: 4096 -- a workgroup's time is the
+// chain of its strips and BM25 segments are unevenly filled, so a finer split evens the workgroups out.  Measured on 256
+// queries x 123 segments (profiles/select_flat_walk_tile_join.md): 1024 is twice as slow as 2048, 4096 takes 0.8 of 2048,
+// at 6144 the histogram pass' flush (one global atomic per non-empty bin and workgroup) costs more than the walk gains.
+// Results do not depend on either.
+constexpr int SEL_GRID = 2048;
+constexpr int SEL_LIST_GRID = 4096;
 constexpr int WIN_SHIFT = 44;                      // the window pass bins 20-bit prefixes of a 64-bit key (msr_internal.h)
 
 template <int SB> struct KeyCfg {
@@ -172,6 +179,100 @@ __device__ __forceinline__ void segment_range(const RowView& v, int q, int64_t n
     }
 }
 
+// The streaming walk of sel_hist_kernel / sel_compact_kernel: f(score, index) for every element of this workgroup's share of
+// row q, invalid scores (-inf) for the slots past the end of the last strip.  SEL_THREADS threads, all of them must call it.
+//
+// Dense rows: a contiguous range, four independent loads in flight per thread (one per iteration left the pass
+// latency-bound).
+//
+// Lists: the workgroup owns whole segments [s_first, s_last) and walks them FLAT.  The segments' counts are loaded
+// together (one memory round trip for all of them, FLAT_SEGS segments at a time), their exclusive prefix sum goes to the
+// LDS table `pre`, and the threads stride over the element numbers 0 .. total - 1 of the chunk: element e sits in the
+// segment sg with pre[sg] <= e < pre[sg + 1] (binary search in LDS, resumed where the thread's previous element was
+// found: e only grows), at position e - pre[sg] of it.  Walked segment by segment a BM25 list (segments of 8192 slots
+// that hold a few hundred elements) costs two dependent round trips per segment: the count, then a strip of score loads
+// that fills under a third of the lanes.  Flat, every lane has four loads in flight until the workgroup's last strip and
+// only the first strip waits for a count (measured: 6 us off the 52 us compaction of 256 BM25 rows, nothing off the
+// histogram pass; both respond to the work split, see SEL_LIST_GRID).
+constexpr int FLAT_PER = 4;                         // segments per thread and prefix table
+constexpr int FLAT_LOADS = 4;                       // independent loads in flight per thread
+constexpr int FLAT_SEGS = FLAT_PER * SEL_THREADS;
+
+template <typename T, typename F>
+__device__ __forceinline__ void sel_walk(const T* __restrict__ row, const int32_t* __restrict__ irow, const RowView& view, int q,
+                                         int64_t n_dense, uint32_t* pre /* LDS: FLAT_SEGS + 1 */, uint32_t* wave_sum /* LDS: 4 */,
+                                         F&& f) {
+    const int t = threadIdx.x;
+    if (!view.counts) {
+        int64_t lo, hi;
+        segment_range(view, q, n_dense, 0, (int)blockIdx.x, (int)gridDim.x, lo, hi);
+        for (int64_t i0 = lo + t; i0 < hi; i0 += 4 * SEL_THREADS) {
+            T v[4];
+            int64_t ix[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t i = i0 + (int64_t)u * SEL_THREADS;
+                v[u] = i < hi ? row[i] : ScoreTraits<T>::neg_inf();
+                ix[u] = i < hi ? row_index(irow, i) : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) f(v[u], ix[u]);
+        }
+        return;
+    }
+    int s_first, s_last;
+    part_segments(view, (int)blockIdx.x, (int)gridDim.x, s_first, s_last);
+    const int32_t* cnt = view.counts + (int64_t)q * view.n_seg;
+    for (int c0 = s_first; c0 < s_last; c0 += FLAT_SEGS) {       // (a workgroup that owns no segment: no iteration)
+        const int nc = s_last - c0 < FLAT_SEGS ? s_last - c0 : FLAT_SEGS;
+        uint32_t c[FLAT_PER], mine = 0;
+#pragma unroll
+        for (int j = 0; j < FLAT_PER; ++j) {
+            c[j] = FLAT_PER * t + j < nc ? (uint32_t)cnt[c0 + FLAT_PER * t + j] : 0u;
+            mine += c[j];
+        }
+        uint32_t incl = mine;                                    // inclusive scan over the wave, then over the four waves
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if ((t & 63) >= off) incl += up;
+        }
+        if ((t & 63) == 63) wave_sum[t >> 6] = incl;
+        __syncthreads();
+        uint32_t run = incl - mine;
+        for (int w = 0; w < (t >> 6); ++w) run += wave_sum[w];
+#pragma unroll
+        for (int j = 0; j < FLAT_PER; ++j) {
+            pre[FLAT_PER * t + j] = run;
+            run += c[j];
+        }
+        if (t == SEL_THREADS - 1) pre[FLAT_SEGS] = run;
+        __syncthreads();
+        const uint32_t total = pre[FLAT_SEGS];                   // (the segments past nc count 0: pre[nc] = total as well)
+        int sg = 0;
+        for (uint32_t e0 = t; e0 < total; e0 += FLAT_LOADS * SEL_THREADS) {
+            T v[FLAT_LOADS];
+            int64_t ix[FLAT_LOADS];
+#pragma unroll
+            for (int u = 0; u < FLAT_LOADS; ++u) {
+                const uint32_t e = e0 + (uint32_t)u * SEL_THREADS;
+                const uint32_t ec = e < total ? e : total - 1;   // past the end: an element that exists, dropped below
+                int hi = nc;                                     // the largest sg with pre[sg] <= ec (empty segments before it
+                while (hi - sg > 1) {                            // share its prefix and are stepped over)
+                    const int mid = (sg + hi) >> 1;
+                    if (pre[mid] <= ec) sg = mid; else hi = mid;
+                }
+                const int64_t i = (int64_t)(c0 + sg) * view.seg_stride + (ec - pre[sg]);
+                const T s = row[i];
+                v[u] = e < total ? s : ScoreTraits<T>::neg_inf();
+                ix[u] = row_index(irow, i);
+            }
+#pragma unroll
+            for (int u = 0; u < FLAT_LOADS; ++u) f(v[u], ix[u]);
+        }
+        __syncthreads();                                         // (the next chunk overwrites the table)
+    }
+}
+
 // The row kernels below take a trailing parameter pack Set: empty (every element of a row takes part), or one MsrSetView
 // (msr_select_topk_within): an element whose index is outside query q's document set takes part in nothing -- no histogram,
 // no compaction, no count -- exactly as if it were not in the row.
@@ -201,6 +302,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const T* __restri
         if (S.done) return;
     }
     __shared__ uint32_t h[MSR_SEL_BINS];
+    __shared__ uint32_t s_pre[FLAT_SEGS + 1], s_wave[4];          // sel_walk's prefix table (lists)
     for (int b = threadIdx.x; b < MSR_SEL_BINS; b += SEL_THREADS) h[b] = 0;
     __syncthreads();
     const bool window = digit < 0;
@@ -213,36 +315,18 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_hist_kernel(const T* __restri
     // index per element are then not loaded -- a third of the pass' bytes)
     const bool need_index = part != 0 || S.mask_lo != 0 || WITHIN;
     const int32_t* irow = view.idx && need_index ? view.idx + (int64_t)q * stride : nullptr;
-    int s_first, s_last;
-    part_segments(view, (int)blockIdx.x, (int)gridDim.x, s_first, s_last);
-    for (int sg = s_first; sg < s_last; ++sg) {
-        int64_t lo, hi;
-        segment_range(view, q, n_dense, sg, (int)blockIdx.x, (int)gridDim.x, lo, hi);
-        // four independent loads in flight per thread (one per iteration left the pass latency-bound)
-        for (int64_t i0 = lo + threadIdx.x; i0 < hi; i0 += 4 * SEL_THREADS) {
-            T v[4];
-            int64_t ix[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t i = i0 + (int64_t)u * SEL_THREADS;
-                v[u] = i < hi ? row[i] : ScoreTraits<T>::neg_inf();
-                ix[u] = i < hi ? row_index(irow, i) : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                uint64_t khi; uint32_t klo;
-                if (!key_of(v[u], ix[u], khi, klo)) continue;
-                if ((khi & S.mask_hi) != S.pref_hi || (klo & S.mask_lo) != S.pref_lo) continue;
-                if (WITHIN && !msr_in_set(srow, ix[u])) continue;
-                uint32_t dg = part == 0 ? (uint32_t)(khi >> shift) & wmask : (klo >> shift) & wmask;
-                if (window) {
-                    const int64_t b = (int64_t)(khi >> WIN_SHIFT) - wbase;
-                    dg = b < 0 ? 0u : (b > MSR_SEL_BINS - 1 ? (uint32_t)(MSR_SEL_BINS - 1) : (uint32_t)b);
-                }
-                atomicAdd(&h[dg], 1u);
-            }
+    sel_walk(row, irow, view, q, n_dense, s_pre, s_wave, [&](const T v, const int64_t ix) {
+        uint64_t khi; uint32_t klo;
+        if (!key_of(v, ix, khi, klo)) return;
+        if ((khi & S.mask_hi) != S.pref_hi || (klo & S.mask_lo) != S.pref_lo) return;
+        if (WITHIN && !msr_in_set(srow, ix)) return;
+        uint32_t dg = part == 0 ? (uint32_t)(khi >> shift) & wmask : (klo >> shift) & wmask;
+        if (window) {
+            const int64_t b = (int64_t)(khi >> WIN_SHIFT) - wbase;
+            dg = b < 0 ? 0u : (b > MSR_SEL_BINS - 1 ? (uint32_t)(MSR_SEL_BINS - 1) : (uint32_t)b);
         }
-    }
+        atomicAdd(&h[dg], 1u);
+    });
     __syncthreads();
     uint32_t* gh = hist + (int64_t)q * MSR_SEL_BINS;
     for (int b = threadIdx.x; b < MSR_SEL_BINS; b += SEL_THREADS)
@@ -302,6 +386,7 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_compact_kernel(const T* __res
     __shared__ uint64_t s_hi[STAGE];
     __shared__ uint32_t s_lo[STAGE];
     __shared__ int s_n, s_base;
+    __shared__ uint32_t s_pre[FLAT_SEGS + 1], s_wave[4];          // sel_walk's prefix table (lists)
     const int q = blockIdx.y;
     const SelState S = st[q];
     if (!S.done) return;
@@ -309,41 +394,24 @@ __global__ __launch_bounds__(SEL_THREADS) void sel_compact_kernel(const T* __res
     __syncthreads();
     const T* row = scores + (int64_t)q * stride;
     const int32_t* irow = view.idx ? view.idx + (int64_t)q * stride : nullptr;
-    int s_first, s_last;
-    part_segments(view, (int)blockIdx.x, (int)gridDim.x, s_first, s_last);
-    for (int sg = s_first; sg < s_last; ++sg) {
-        int64_t lo, hi;
-        segment_range(view, q, n_dense, sg, (int)blockIdx.x, (int)gridDim.x, lo, hi);
-        for (int64_t i0 = lo + threadIdx.x; i0 < hi; i0 += 4 * SEL_THREADS) {
-            T v[4];
-            int64_t ix[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t i = i0 + (int64_t)u * SEL_THREADS;
-                v[u] = i < hi ? row[i] : ScoreTraits<T>::neg_inf();
-                ix[u] = i < hi ? row_index(irow, i) : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                uint64_t khi; uint32_t klo;
-                if (!key_of(v[u], ix[u], khi, klo)) continue;
-                const uint64_t mh = khi & S.mask_hi;
-                const bool ge = mh > S.pref_hi || (mh == S.pref_hi && (klo & S.mask_lo) >= S.pref_lo);
-                if (!ge) continue;
-                if (WITHIN && !msr_in_set(srow, ix[u])) continue;
-                const int pos = atomicAdd(&s_n, 1);              // LDS atomic
-                if (pos < STAGE) {
-                    s_hi[pos] = khi; s_lo[pos] = klo;
-                } else {                                         // more matches than the stage holds: append directly
-                    const int g = atomicAdd(&cand_n[q], 1);
-                    if (g < MSR_SEL_CAP) {
-                        cand_hi[(int64_t)q * MSR_SEL_CAP + g] = khi;
-                        cand_lo[(int64_t)q * MSR_SEL_CAP + g] = klo;
-                    }
-                }
+    sel_walk(row, irow, view, q, n_dense, s_pre, s_wave, [&](const T v, const int64_t ix) {
+        uint64_t khi; uint32_t klo;
+        if (!key_of(v, ix, khi, klo)) return;
+        const uint64_t mh = khi & S.mask_hi;
+        const bool ge = mh > S.pref_hi || (mh == S.pref_hi && (klo & S.mask_lo) >= S.pref_lo);
+        if (!ge) return;
+        if (WITHIN && !msr_in_set(srow, ix)) return;
+        const int pos = atomicAdd(&s_n, 1);                      // LDS atomic
+        if (pos < STAGE) {
+            s_hi[pos] = khi; s_lo[pos] = klo;
+        } else {                                                 // more matches than the stage holds: append directly
+            const int g = atomicAdd(&cand_n[q], 1);
+            if (g < MSR_SEL_CAP) {
+                cand_hi[(int64_t)q * MSR_SEL_CAP + g] = khi;
+                cand_lo[(int64_t)q * MSR_SEL_CAP + g] = klo;
             }
         }
-    }
+    });
     __syncthreads();
     int cnt = s_n;
     if (cnt > STAGE) cnt = STAGE;
@@ -536,7 +604,8 @@ hipError_t select_impl(const T* scores, int64_t n, int64_t stride, RowView view,
     constexpr int SB = ScoreTraits<T>::SB;
     if (nq <= 0) return hipSuccess;
     int64_t parts = view.counts ? view.n_seg : (n + 8191) / 8192;     // lists: whole segments per workgroup
-    const int64_t max_parts = 2048 / nq > 0 ? 2048 / nq : 1;
+    const int grid_cap = view.counts ? SEL_LIST_GRID : SEL_GRID;
+    const int64_t max_parts = grid_cap / nq > 0 ? grid_cap / nq : 1;
     if (parts > max_parts) parts = max_parts;
     if (parts < 1) parts = 1;
     dim3 grid((unsigned)parts, (unsigned)nq);
