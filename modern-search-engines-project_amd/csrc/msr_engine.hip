@@ -7,29 +7,42 @@
 
 #include <algorithm>
 #include <new>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/msretr.h"
+#include "msr_devmem.h"
 #include "msr_internal.h"
+
+struct HipMem {
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void* p) { (void)hipFree(p); }
+};
+using Group = DevGroup<HipMem>;
 
 struct msr_engine {
     msr_config cfg;
     char err[512];
+    // Engine-owned device memory, one group per lifetime; every allocation is in exactly one, msr_owned_bytes() is their sum.
+    // The groups remember the addresses of the pointer members below: an engine lives on the heap and never moves.
+    Group mem_engine;                  // until msr_destroy: per-query scratch, the grow-only scratch of the similar-documents calls
+    Group mem_corpus;                  // until msr_unbind: grow-only scratch sized by the corpus (score_rows, bm_cand_doc)
+    Group mem_postings;                // until drop_postings: the next msr_bind_postings, msr_unbind
+    Group mem_chunks;                  // until drop_chunks: the next msr_bind_chunks, msr_unbind
+    Group mem_bf16;                    // what msr_enable_bf16 builds; goes with the chunks
     // bound index parts (borrowed device pointers)
-    Bm25Index bm25;
+    Bm25Index bm25{};
     bool have_postings = false;
     const int64_t* tok_off = nullptr;      // msr_bind_tokens (borrowed): the forward index of the bound postings' documents
     const int32_t* tok_ids = nullptr;
     int64_t n_tokens = 0;
     bool have_tokens = false;
-    DenseIndex dense;
+    DenseIndex dense{};
     bool have_chunks = false;
     const int32_t* url_group = nullptr;
     int64_t url_group_n = 0;
     const int32_t* doc_domain = nullptr;   // msr_bind_doc_domains (borrowed): domain id per document, -1 = rejected from responses
     int64_t doc_domain_n = 0;
-    // engine-owned device memory
+    // engine-owned device memory.  mem_chunks:
     int32_t* chunk_doc = nullptr;
     void* emb_presplit = nullptr;     // scan_variant 15: f16 hi/lo image of the rows
     void* row_meta = nullptr;         // packed {document, inverse norm} per row for the K-split kernels
@@ -37,64 +50,62 @@ struct msr_engine {
     int32_t* span_doc = nullptr;
     int32_t* wspan_doc = nullptr;
     int32_t* wspan12_doc = nullptr;
+    // mem_engine:
     float* qn = nullptr;              // [128][768] normalised queries of the current slice
     float* rr_qn = nullptr;           // [max(max_queries, 128)][768] normalised queries of a rerank gather (one launch per call)
     void* qimg = nullptr;             // query image in fragment order (<= 256 KB)
-    void* emb_bf16 = nullptr;         // bf16 copy of the embeddings (msr_enable_bf16)
+    SelScratch sel{};
+    float* rerank_cos = nullptr;
+    int32_t* rerank_meta = nullptr;
+    // mem_corpus:
     void* score_rows = nullptr;       // max_queries rows of n_docs float64 (reused as float32 rows)
     size_t score_rows_bytes = 0;
+    int32_t* bm_cand_doc = nullptr;    // max_queries rows of n_docs i32: document of each BM25 candidate
+    size_t bm_cand_bytes = 0;
+    // mem_postings:
     int32_t* bm_heavy_id = nullptr;    // skip table of the BM25 stage (see Bm25Index)
     void* bm_post = nullptr;           // {doc, tf, tf_component} copy of the postings (see Bm25Index)
     int32_t* bm_dense_id = nullptr;    // dense tf_component tables of the long negative-idf lists (see Bm25Index)
     double* bm_dense = nullptr;
     uint32_t* bm_tile_off = nullptr;
-    int32_t* bm_cand_doc = nullptr;    // max_queries rows of n_docs i32: document of each BM25 candidate
     int32_t* bm_cand_n = nullptr;      // [max_queries][tiles] candidates per (query, segment) of the candidate rows
     uint64_t* bm_win = nullptr;        // [max_queries] anchor of the select's window pass (msr_bm25_window)
-    size_t bm_cand_bytes = 0;
-    SelScratch sel{};
-    float* rerank_cos = nullptr;
-    int32_t* rerank_meta = nullptr;
-    // batched bf16 path scratch (allocated by msr_enable_bf16)
+    // mem_engine: candidate scratch of the batched bf16 path (allocated by the first msr_enable_bf16, kept across re-binds)
     int32_t* bt_top_doc = nullptr; float* bt_top_score = nullptr; int32_t* bt_top_n = nullptr;
     int32_t* bt_cand_doc = nullptr; float* bt_cand_score = nullptr; int32_t* bt_cand_chunk = nullptr;
     int32_t* bt_cand_n = nullptr;
-    // row tiles of <= 256 rows cut at document boundaries (both GEMM paths); built when the chunks are bound
+    // mem_chunks: row tiles of <= 256 rows cut at document boundaries (both GEMM paths); built when the chunks are bound
     int32_t* tile_row = nullptr;
     int n_tiles = 0;
     bool tiles_ok = false;             // every document fits one tile
-    // default scan for 65..128 queries as a tiled GEMM over the f32 rows (msr_gemm_f32.hip)
+    // default scan for 65..128 queries as a tiled GEMM over the f32 rows (msr_gemm_f32.hip).  mem_chunks; its scratch is
+    // allocated straight into `gf`: here is only what `gf` holds as const and what the engine itself uses
     GemmF32Index gf{};
     bool gf_ok = false;
-    float* gf_inv_pad = nullptr; void* gf_qimg = nullptr; float* gf_tmax_t = nullptr; float* gf_tmax = nullptr;
-    float* gf_thr = nullptr; float* gf_thr2 = nullptr; int32_t* gf_flag = nullptr; void* gf_wvbuf = nullptr;
-    int32_t* gf_wv_count = nullptr; void* gf_pairs = nullptr; int32_t* gf_pair_n = nullptr; int32_t* gf_gate = nullptr;
-    uint32_t* gf_err = nullptr; float* gf_margin = nullptr; int32_t* gf_cand_doc = nullptr; float* gf_cand_score = nullptr;
-    int32_t* gf_cand_chunk = nullptr; int32_t* gf_cand_n = nullptr; float* gf_qn = nullptr; void* gf_fb_qimg = nullptr;
+    float* gf_inv_pad = nullptr; float* gf_qn = nullptr; void* gf_fb_qimg = nullptr;
+    int32_t* gf_gate = nullptr;       // GF_GATE_BYTES
     void* gf_emb_tiled = nullptr;     // fragment-order copy of the f32 rows (256-query streaming pass)
     void* gf_emb_f16 = nullptr;       // row-major f16 image of the rows (launches of several 256-query groups)
     int32_t* tile_trow = nullptr;     // [n_tiles] first row of each tile in those copies
-    int64_t n_trows = 0;
-    // batched path as a tiled GEMM (msr_gemm.hip): unit-row bf16 image + tile table + scratch for GM_SLICE queries per pass
+    // batched path as a tiled GEMM (msr_gemm.hip): unit-row bf16 image + tile table + scratch for GM_SLICE queries per pass.
+    // mem_bf16; the GEMM's scratch is allocated straight into `gemm`
+    void* emb_bf16 = nullptr;          // bf16 copy of the embeddings; non-null = msr_enable_bf16 has built the whole path
     GemmIndex gemm{};
     bool gemm_ok = false;
-    void* gm_emb_n = nullptr; void* gm_qmat = nullptr; float* gm_tmax = nullptr; float* gm_tmax_t = nullptr;
-    float* gm_thr = nullptr; float* gm_thr2 = nullptr; int32_t* gm_flag = nullptr; void* gm_wgbuf = nullptr;
-    int32_t* gm_wv_count = nullptr; void* gm_pairs = nullptr; int32_t* gm_pair_n = nullptr; float* gm_qn = nullptr;
+    float* gm_qn = nullptr;
     uint32_t* bf_err = nullptr;        // bits of the largest rounding-error norm of an image row (see msr_batch_margin)
     float* bf_margin = nullptr;        // [GM_SLICE] candidate margin of each query of the current slice
     float* bf_ones = nullptr;          // inverse norms of the unit-row image (all 1) for the <= 128-query bf16 sweeps
     void* bf_row_meta = nullptr;       // {document, 1.0f} per row for the K-split bf16 sweeps
     DenseIndex dense_bf16{};           // `dense` with the unit-row image, its inverse norms and row meta
     int n_cus = 256;
-    std::unordered_map<void*, size_t> owned;   // engine-owned device allocations (msr_owned_bytes)
     int split_pending = 0;             // queries of an msr_dense_topk_begin whose msr_dense_topk_end has not come yet
     int row_copy_state = 0;            // fragment-order copy of the rows: 0 not wanted / not applicable, 1 built, 2 declined by
                                        // msr_config.flags, 3 allocation failed (the row-major instantiation of the kernel runs)
     int row_image_state = 0;           // f16 image of the rows (launches of several query groups): the same four states
     int last_dense_width = 0;          // queries per pass over the matrix of the most recent msr_dense_topk call (msr_dense_path)
-    // msr_gather_rows / msr_dense_topk_grouped (grown on demand, kept until msr_destroy): a check flag, the per-row lists, the
-    // per-row set indices and the merge's overflow records
+    // mem_engine: msr_gather_rows / msr_dense_topk_grouped (grown on demand, kept until msr_destroy): a check flag, the per-row
+    // lists, the per-row set indices and the merge's overflow records
     int32_t* sim_flag = nullptr;
     void* sim_lists = nullptr; size_t sim_lists_bytes = 0;
     void* sim_over = nullptr; size_t sim_over_bytes = 0;
@@ -106,6 +117,9 @@ struct msr_engine {
     hipEvent_t ev_stop[EV_KINDS][EV_RING] = {};
     int ev_count[EV_KINDS] = {0, 0, 0, 0};   // launches recorded since msr_set_timing(1)
 };
+
+// gf_gate: the gate words of the streaming pass, one per slice of 64 queries of a call (at most 8 groups of 128 queries)
+static constexpr size_t GF_GATE_BYTES = 16 * sizeof(int32_t);
 
 static thread_local char g_create_err[512] = "";
 
@@ -124,47 +138,51 @@ static int fail(msr_engine* e, int code, const char* fmt, ...) {
         if (_err != hipSuccess) return fail(e, MSR_ERR_HIP, "%s: %s", #call, hipGetErrorString(_err)); \
     } while (0)
 
-// Every device allocation of an engine goes through these two: msr_owned_bytes() reports what the handle holds.
-static hipError_t eng_malloc(msr_engine* e, void** p, size_t bytes) {
-    hipError_t err = hipMalloc(p, bytes);
-    if (err == hipSuccess && *p) e->owned[*p] = bytes;
-    return err;
-}
-static void free_dev(msr_engine* e, void* p) {
-    if (!p) return;
-    e->owned.erase(p);
-    (void)hipFree(p);
-}
+// slot <- `bytes` of device memory owned by `group`; a failure returns MSR_ERR_NOMEM with the slot's name in the error text
+#define ALLOC(e, group, slot, bytes)                                                              \
+    do {                                                                                          \
+        const size_t _n = (bytes);                                                                \
+        hipError_t _err = (group).alloc(&(slot), _n);                                             \
+        if (_err != hipSuccess) return fail(e, MSR_ERR_NOMEM, "%s (%zu bytes): %s", #slot, _n, hipGetErrorString(_err)); \
+    } while (0)
 
-static void free_gemm(msr_engine* e) {
-    free_dev(e, e->gm_emb_n); free_dev(e, e->gm_qmat); free_dev(e, e->gm_tmax); free_dev(e, e->gm_tmax_t);
-    free_dev(e, e->gm_thr); free_dev(e, e->gm_thr2); free_dev(e, e->gm_flag);
-    free_dev(e, e->gm_wgbuf); free_dev(e, e->gm_wv_count); free_dev(e, e->gm_pairs); free_dev(e, e->gm_pair_n); free_dev(e, e->gm_qn);
-    free_dev(e, e->bf_ones); free_dev(e, e->bf_row_meta); free_dev(e, e->bf_err); free_dev(e, e->bf_margin);
-    e->bf_err = nullptr; e->bf_margin = nullptr;
-    e->gm_emb_n = nullptr; e->gm_qmat = nullptr; e->gm_tmax = nullptr; e->gm_tmax_t = nullptr;
-    e->gm_thr = e->gm_thr2 = nullptr; e->gm_flag = nullptr;
-    e->gm_wgbuf = nullptr; e->gm_wv_count = nullptr; e->gm_pairs = nullptr; e->gm_pair_n = nullptr; e->gm_qn = nullptr;
-    e->bf_ones = nullptr; e->bf_row_meta = nullptr;
+// How a binding goes away, in msr_unbind, in msr_destroy and in each bind where it starts to replace state: the flags and the
+// index structs first, then the memory, so that nothing is left pointing at what is freed.
+static void drop_postings(msr_engine* e) {
+    e->have_postings = e->have_tokens = false;
+    e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
+    e->bm25 = Bm25Index{};
+    e->mem_postings.release();
+}
+static void drop_bf16(msr_engine* e) {
+    e->dense.emb_bf16 = nullptr;
+    e->dense_bf16 = DenseIndex{};
+    e->gemm = GemmIndex{};
     e->gemm_ok = false;
+    e->mem_bf16.release();
+}
+static void drop_chunks(msr_engine* e) {
+    e->have_chunks = false;
+    e->split_pending = 0;                                    // (a pending begin's scratch goes too)
+    e->dense = DenseIndex{};
+    e->gf = GemmF32Index{};
+    e->gf_ok = e->tiles_ok = false;
+    e->n_tiles = 0;
+    e->row_copy_state = e->row_image_state = 0;
+    drop_bf16(e);
+    e->mem_chunks.release();
 }
 
-static void free_gf(msr_engine* e) {
-    free_dev(e, e->tile_row); free_dev(e, e->tile_trow); e->tile_trow = nullptr; e->n_trows = 0; free_dev(e, e->gf_inv_pad); free_dev(e, e->gf_qimg); free_dev(e, e->gf_tmax_t); free_dev(e, e->gf_tmax);
-    free_dev(e, e->gf_thr); free_dev(e, e->gf_thr2);
-    free_dev(e, e->gf_flag); free_dev(e, e->gf_wvbuf); free_dev(e, e->gf_wv_count); free_dev(e, e->gf_pairs); free_dev(e, e->gf_pair_n);
-    free_dev(e, e->gf_gate); free_dev(e, e->gf_err); free_dev(e, e->gf_margin); free_dev(e, e->gf_cand_doc); free_dev(e, e->gf_cand_score);
-    free_dev(e, e->gf_cand_chunk); free_dev(e, e->gf_cand_n); free_dev(e, e->gf_qn); e->gf_qn = nullptr;
-    free_dev(e, e->gf_fb_qimg); e->gf_fb_qimg = nullptr;
-    free_dev(e, e->gf_emb_tiled); e->gf_emb_tiled = nullptr;
-    free_dev(e, e->gf_emb_f16); e->gf_emb_f16 = nullptr;
-    e->gf_err = nullptr; e->gf_margin = nullptr; e->gf_cand_doc = nullptr; e->gf_cand_score = nullptr; e->gf_cand_chunk = nullptr;
-    e->gf_cand_n = nullptr;
-    e->tile_row = nullptr; e->gf_inv_pad = nullptr; e->gf_qimg = nullptr; e->gf_tmax_t = nullptr; e->gf_tmax = nullptr;
-    e->gf_thr = e->gf_thr2 = nullptr;
-    e->gf_flag = nullptr; e->gf_wvbuf = nullptr; e->gf_wv_count = nullptr; e->gf_pairs = nullptr; e->gf_pair_n = nullptr;
-    e->gf_gate = nullptr;
-    e->n_tiles = 0; e->tiles_ok = false; e->gf_ok = false;
+// Grow-only scratch: afterwards *slot holds at least `need` bytes (*have: how many it holds).
+template <class T>
+static int grow(msr_engine* e, Group& group, T** slot, size_t* have, size_t need, const char* what) {
+    if (need <= *have && *slot) return MSR_OK;
+    group.free_one(slot);
+    *have = 0;
+    hipError_t herr = group.alloc(slot, need);
+    if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "%s (%zu bytes): %s", what, need, hipGetErrorString(herr));
+    *have = need;
+    return MSR_OK;
 }
 
 extern "C" int msr_abi_version(void) { return MSR_ABI_VERSION; }
@@ -178,6 +196,37 @@ int msr_fail_global(int code, const char* fmt, ...) {
     vsnprintf(g_create_err, sizeof(g_create_err), fmt, ap);
     va_end(ap);
     return code;
+}
+
+// Device state of a new engine: the per-query scratch (mem_engine) and the timing events.
+static int create_scratch(msr_engine* e) {
+    const msr_config& cfg = e->cfg;
+    HIP_TRY(e, hipSetDevice(cfg.device));
+    hipDeviceProp_t prop;
+    HIP_TRY(e, hipGetDeviceProperties(&prop, cfg.device));
+    e->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // select scratch and query buffers cover the widest sweep (128 queries) whatever max_queries says
+    const size_t nq = (size_t)std::max(cfg.max_queries, 128);
+    ALLOC(e, e->mem_engine, e->qn, 128 * MSR_DIM * sizeof(float));
+    ALLOC(e, e->mem_engine, e->qimg, 256 * 1024);
+    if (cfg.rerank_max_docs > 0) ALLOC(e, e->mem_engine, e->rr_qn, nq * MSR_DIM * sizeof(float));
+    ALLOC(e, e->mem_engine, e->sel.hist, nq * MSR_SEL_BINS * sizeof(uint32_t));
+    ALLOC(e, e->mem_engine, e->sel.state, nq * sizeof(SelState));
+    ALLOC(e, e->mem_engine, e->sel.cand_hi, nq * MSR_SEL_CAP * sizeof(uint64_t));
+    ALLOC(e, e->mem_engine, e->sel.cand_lo, nq * MSR_SEL_CAP * sizeof(uint32_t));
+    ALLOC(e, e->mem_engine, e->sel.cand_n, nq * sizeof(int32_t));
+    HIP_TRY(e, hipMemset(e->sel.hist, 0, nq * MSR_SEL_BINS * sizeof(uint32_t)));
+    HIP_TRY(e, hipMemset(e->sel.cand_n, 0, nq * sizeof(int32_t)));
+    if (cfg.rerank_max_docs > 0) {
+        ALLOC(e, e->mem_engine, e->rerank_cos, nq * (size_t)cfg.rerank_max_docs * MSR_RERANK_MAX_CHUNKS * sizeof(float));
+        ALLOC(e, e->mem_engine, e->rerank_meta, nq * (size_t)cfg.rerank_max_docs * 3 * sizeof(int32_t));
+    }
+    for (int w = 0; w < msr_engine::EV_KINDS; ++w)
+        for (int j = 0; j < msr_engine::EV_RING; ++j) {
+            HIP_TRY(e, hipEventCreate(&e->ev_start[w][j]));
+            HIP_TRY(e, hipEventCreate(&e->ev_stop[w][j]));
+        }
+    return MSR_OK;
 }
 
 extern "C" int msr_create(const msr_config* cfg, msr_engine** out) {
@@ -210,61 +259,26 @@ extern "C" int msr_create(const msr_config* cfg, msr_engine** out) {
     if (!e) return fail(nullptr, MSR_ERR_NOMEM, "msr_create: out of host memory");
     e->cfg = *cfg;
     e->err[0] = 0;
-    memset(&e->bm25, 0, sizeof(e->bm25));
-    memset(&e->dense, 0, sizeof(e->dense));
-    auto bail = [&](int code, const char* what, hipError_t he) {
-        fail(nullptr, code, "msr_create: %s: %s", what, hipGetErrorString(he));
+    const int rc = create_scratch(e);
+    if (rc) {
+        fail(nullptr, rc, "msr_create: %s", e->err);
         msr_destroy(e);
-        return code;
-    };
-    if ((herr = hipSetDevice(cfg->device)) != hipSuccess) return bail(MSR_ERR_HIP, "hipSetDevice", herr);
-    hipDeviceProp_t prop;
-    if ((herr = hipGetDeviceProperties(&prop, cfg->device)) != hipSuccess) return bail(MSR_ERR_HIP, "hipGetDeviceProperties", herr);
-    e->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    // select scratch and query buffers cover the widest sweep (128 queries) whatever max_queries says
-    const size_t nq = (size_t)std::max(cfg->max_queries, 128);
-    if ((herr = eng_malloc(e, (void**)&e->qn, 128 * MSR_DIM * sizeof(float))) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc qn", herr);
-    if ((herr = eng_malloc(e, &e->qimg, 256 * 1024)) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc qimg", herr);
-    if (cfg->rerank_max_docs > 0 && (herr = eng_malloc(e, (void**)&e->rr_qn, nq * MSR_DIM * sizeof(float))) != hipSuccess)
-        return bail(MSR_ERR_NOMEM, "hipMalloc rr_qn", herr);
-    if ((herr = eng_malloc(e, (void**)&e->sel.hist, nq * MSR_SEL_BINS * sizeof(uint32_t))) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc hist", herr);
-    if ((herr = eng_malloc(e, (void**)&e->sel.state, nq * sizeof(SelState))) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc state", herr);
-    if ((herr = eng_malloc(e, (void**)&e->sel.cand_hi, nq * MSR_SEL_CAP * sizeof(uint64_t))) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc cand_hi", herr);
-    if ((herr = eng_malloc(e, (void**)&e->sel.cand_lo, nq * MSR_SEL_CAP * sizeof(uint32_t))) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc cand_lo", herr);
-    if ((herr = eng_malloc(e, (void**)&e->sel.cand_n, nq * sizeof(int32_t))) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc cand_n", herr);
-    if ((herr = hipMemset(e->sel.hist, 0, nq * MSR_SEL_BINS * sizeof(uint32_t))) != hipSuccess) return bail(MSR_ERR_HIP, "hipMemset hist", herr);
-    if ((herr = hipMemset(e->sel.cand_n, 0, nq * sizeof(int32_t))) != hipSuccess) return bail(MSR_ERR_HIP, "hipMemset cand_n", herr);
-    if (cfg->rerank_max_docs > 0) {
-        const size_t bytes = nq * (size_t)cfg->rerank_max_docs * MSR_RERANK_MAX_CHUNKS * sizeof(float);
-        if ((herr = eng_malloc(e, (void**)&e->rerank_cos, bytes)) != hipSuccess) return bail(MSR_ERR_NOMEM, "hipMalloc rerank_cos", herr);
-        if ((herr = eng_malloc(e, (void**)&e->rerank_meta, nq * (size_t)cfg->rerank_max_docs * 3 * sizeof(int32_t))) != hipSuccess)
-            return bail(MSR_ERR_NOMEM, "hipMalloc rerank_meta", herr);
+        return rc;
     }
-    for (int w = 0; w < msr_engine::EV_KINDS; ++w)
-        for (int j = 0; j < msr_engine::EV_RING; ++j) {
-            if ((herr = hipEventCreate(&e->ev_start[w][j])) != hipSuccess) return bail(MSR_ERR_HIP, "hipEventCreate", herr);
-            if ((herr = hipEventCreate(&e->ev_stop[w][j])) != hipSuccess) return bail(MSR_ERR_HIP, "hipEventCreate", herr);
-        }
     *out = e;
     return MSR_OK;
 }
 
 extern "C" int msr_destroy(msr_engine* e) {
     if (!e) return MSR_OK;
-    free_dev(e, e->chunk_doc); free_dev(e, e->emb_presplit); free_dev(e, e->row_meta); free_dev(e, e->inv_norm_own); free_dev(e, e->span_doc); free_dev(e, e->wspan_doc); free_dev(e, e->wspan12_doc); free_dev(e, e->qn); free_dev(e, e->rr_qn); free_dev(e, e->qimg); free_dev(e, e->emb_bf16);
-    free_dev(e, e->score_rows); free_dev(e, e->bm_heavy_id); free_dev(e, e->bm_post); free_dev(e, e->bm_dense_id); free_dev(e, e->bm_dense); free_dev(e, e->bm_tile_off); free_dev(e, e->bm_cand_doc); free_dev(e, e->bm_cand_n); free_dev(e, e->bm_win); free_dev(e, e->sel.hist); free_dev(e, e->sel.state); free_dev(e, e->sel.cand_hi);
-    free_dev(e, e->sel.cand_lo); free_dev(e, e->sel.cand_n); free_dev(e, e->rerank_cos); free_dev(e, e->rerank_meta);
-    free_dev(e, e->bt_top_doc); free_dev(e, e->bt_top_score); free_dev(e, e->bt_top_n); free_dev(e, e->bt_cand_doc);
-    free_dev(e, e->bt_cand_score); free_dev(e, e->bt_cand_chunk); free_dev(e, e->bt_cand_n);
-    free_dev(e, e->sim_flag); free_dev(e, e->sim_lists); free_dev(e, e->sim_over);
-    free_gemm(e);
-    free_gf(e);
+    drop_postings(e);
+    drop_chunks(e);
     for (int w = 0; w < msr_engine::EV_KINDS; ++w)
         for (int j = 0; j < msr_engine::EV_RING; ++j) {
             if (e->ev_start[w][j]) (void)hipEventDestroy(e->ev_start[w][j]);
             if (e->ev_stop[w][j]) (void)hipEventDestroy(e->ev_stop[w][j]);
         }
-    delete e;
+    delete e;                                                // (the groups release what is left: mem_engine, mem_corpus)
     return MSR_OK;
 }
 
@@ -273,13 +287,101 @@ static int ensure_score_rows(msr_engine* e, int64_t n_docs) {
     // f64 candidate scores of max_queries queries, or f32 score rows (padded to 32 documents) of up to 128 queries
     const size_t pad = (size_t)(n_docs + 31) / 32 * 32;
     const size_t need = std::max((size_t)e->cfg.max_queries * pad * sizeof(double), (size_t)128 * pad * sizeof(float));
-    if (need <= e->score_rows_bytes) return MSR_OK;
-    free_dev(e, e->score_rows);
-    e->score_rows = nullptr;
-    e->score_rows_bytes = 0;
-    hipError_t herr = eng_malloc(e, &e->score_rows, need);
-    if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "score rows (%zu bytes): %s", need, hipGetErrorString(herr));
-    e->score_rows_bytes = need;
+    return grow(e, e->mem_corpus, &e->score_rows, &e->score_rows_bytes, need, "score rows");
+}
+
+// The engine's tables and scratch for the posting index `cand`, which is checked on the way.  The engine is unbound meanwhile.
+static int build_postings(msr_engine* e, Bm25Index cand, hipStream_t st) {
+    const int64_t n_terms = cand.n_terms, n_postings = cand.n_postings, n_docs = cand.n_docs;
+    int rc = ensure_score_rows(e, n_docs);
+    if (rc) return rc;
+    // candidate lists of the BM25 stage: worst case every document of every query
+    rc = grow(e, e->mem_corpus, &e->bm_cand_doc, &e->bm_cand_bytes, (size_t)e->cfg.max_queries * (size_t)n_docs * sizeof(int32_t),
+              "BM25 candidate lists");
+    if (rc) return rc;
+    ALLOC(e, e->mem_postings, e->bm_win, (size_t)e->cfg.max_queries * sizeof(uint64_t));
+    ALLOC(e, e->mem_postings, e->bm_cand_n, (size_t)e->cfg.max_queries * msr_bm25_max_segments(n_docs) * sizeof(int32_t));
+    // the scoring kernel indexes LDS with (post_doc - tile start): validate the CSR once, on the device
+    int32_t h_flag = 0;
+    HIP_TRY(e, msr_bm25_validate(cand, e->sel.cand_n, st));           // cand_n[0] as a scratch word (zero between calls)
+    HIP_TRY(e, hipMemcpyAsync(&h_flag, e->sel.cand_n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipMemsetAsync(e->sel.cand_n, 0, sizeof(int32_t), st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (h_flag >= 1 && h_flag <= 5) {
+        static const char* why[] = {"", "term_off is not a monotone offset array ending at n_postings",
+                                    "a posting's document index is outside [0, n_docs)",
+                                    "documents are not strictly ascending inside a posting list",
+                                    "negative doc_len", "non-positive term frequency"};
+        return fail(e, MSR_ERR_INVALID, "msr_bind_postings: malformed index: %s", why[h_flag]);
+    }
+    if (!(cand.avgdl > 0.0) || !(cand.k1 >= 0.0) || !(cand.b >= 0.0 && cand.b <= 1.0))
+        return fail(e, MSR_ERR_INVALID, "msr_bind_postings: avgdl must be > 0, k1 >= 0, 0 <= b <= 1");
+    // skip table for the long posting lists (one-time; the offsets come to the host once for this)
+    std::vector<int32_t> dense_terms;                         // long lists with negative idf, longest first (tables below)
+    if (n_terms > 0) {
+        std::vector<int64_t> h_toff((size_t)n_terms + 1);
+        std::vector<float> h_idf((size_t)n_terms);
+        HIP_TRY(e, hipMemcpyAsync(h_toff.data(), cand.term_off, h_toff.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipMemcpyAsync(h_idf.data(), cand.idf, h_idf.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+        std::vector<int32_t> heavy_id((size_t)n_terms, -1), heavy_terms;
+        for (int64_t t = 0; t < n_terms; ++t)
+            if (h_toff[t + 1] - h_toff[t] >= MSR_BM25_HEAVY_DF && h_toff[t + 1] - h_toff[t] < (1ll << 32)) {
+                heavy_id[t] = (int32_t)heavy_terms.size();
+                heavy_terms.push_back((int32_t)t);
+                if (h_idf[t] < 0.0f) dense_terms.push_back((int32_t)t);
+            }
+        if (!heavy_terms.empty()) {
+            DevTemp<HipMem, int32_t> d_terms;                // (freed at the end of this block on every path; hipFree waits for the device)
+            const size_t rows = heavy_terms.size() * (size_t)(cand.n_tiles + 1);
+            ALLOC(e, e->mem_postings, e->bm_heavy_id, heavy_id.size() * sizeof(int32_t));
+            ALLOC(e, e->mem_postings, e->bm_tile_off, rows * sizeof(uint32_t));
+            ALLOC(e, d_terms.group, d_terms.p, heavy_terms.size() * sizeof(int32_t));
+            HIP_TRY(e, hipMemcpyAsync(e->bm_heavy_id, heavy_id.data(), heavy_id.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(e, hipMemcpyAsync(d_terms.p, heavy_terms.data(), heavy_terms.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            HIP_TRY(e, msr_bm25_build_skip(cand, d_terms.p, (int)heavy_terms.size(), e->bm_tile_off, st));
+            HIP_TRY(e, hipStreamSynchronize(st));
+            cand.heavy_id = e->bm_heavy_id;
+            cand.tile_off = e->bm_tile_off;
+        }
+        // the longest negative-idf lists get a dense table: at most MSR_BM25_MAX_DENSE of them and 4 GiB in all
+        std::stable_sort(dense_terms.begin(), dense_terms.end(), [&](int32_t a, int32_t b2) {
+            return h_toff[a + 1] - h_toff[a] > h_toff[b2 + 1] - h_toff[b2];
+        });
+        const size_t row_bytes = ((size_t)cand.n_tiles * MSR_BM25_TILE + 8) * sizeof(double);
+        const size_t cap = std::min<size_t>(MSR_BM25_MAX_DENSE, (size_t)(4ull << 30) / row_bytes);
+        if (dense_terms.size() > cap) dense_terms.resize(cap);
+    }
+    // the copy the scoring kernel streams (after the validation above: the copy is of a well-formed index): every posting with
+    // its tf_component, from the per-document length norms k1 (1 - b + b dl / avgdl)
+    {
+        const int64_t n_pad = (int64_t)cand.n_tiles * MSR_BM25_TILE;
+        DevTemp<HipMem, double> dnorm;
+        ALLOC(e, e->mem_postings, e->bm_post, (size_t)(n_postings + 1) * sizeof(Bm25Post));      // + the sentinel posting
+        ALLOC(e, dnorm.group, dnorm.p, (size_t)n_pad * sizeof(double));
+        HIP_TRY(e, msr_bm25_dnorm(cand.doc_len, n_docs, n_pad, cand.k1, cand.b, cand.avgdl, dnorm.p, st));
+        HIP_TRY(e, msr_bm25_post_comp(cand.post_doc, cand.post_tf, dnorm.p, cand.k1, n_postings, (Bm25Post*)e->bm_post, st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+    }
+    cand.post = (const Bm25Post*)e->bm_post;
+    if (!dense_terms.empty()) {
+        const int64_t stride = (int64_t)cand.n_tiles * MSR_BM25_TILE + 8;      // the tail of a row stays 0.0 (the kernel's "no value")
+        std::vector<int32_t> dense_id((size_t)n_terms, -1);
+        for (size_t h = 0; h < dense_terms.size(); ++h) dense_id[dense_terms[h]] = (int32_t)h;
+        DevTemp<HipMem, int32_t> d_terms;
+        ALLOC(e, e->mem_postings, e->bm_dense_id, dense_id.size() * sizeof(int32_t));
+        ALLOC(e, e->mem_postings, e->bm_dense, dense_terms.size() * (size_t)stride * sizeof(double));
+        ALLOC(e, d_terms.group, d_terms.p, dense_terms.size() * sizeof(int32_t));
+        HIP_TRY(e, hipMemcpyAsync(e->bm_dense_id, dense_id.data(), dense_id.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(e, hipMemcpyAsync(d_terms.p, dense_terms.data(), dense_terms.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_TRY(e, hipMemsetAsync(e->bm_dense, 0, dense_terms.size() * (size_t)stride * sizeof(double), st));
+        HIP_TRY(e, msr_bm25_build_dense(cand, d_terms.p, (int)dense_terms.size(), e->bm_dense, stride, st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+        cand.dense_id = e->bm_dense_id;
+        cand.dense_comp = e->bm_dense;
+        cand.dense_stride = stride;
+    }
+    e->bm25 = cand;
     return MSR_OK;
 }
 
@@ -296,140 +398,237 @@ extern "C" int msr_bind_postings(msr_engine* e, const int64_t* term_off, int64_t
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     // from here on the previous binding's tables are being replaced: the engine counts as unbound until this call succeeds
     // (a failed re-bind must not leave msr_bm25_topk reading freed tables)
-    e->have_postings = false;
-    e->have_tokens = false; e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;   // (they describe the old documents)
-    int rc = ensure_score_rows(e, n_docs);
-    if (rc) return rc;
-    {   // candidate lists of the BM25 stage: worst case every document of every query
-        const size_t need = (size_t)e->cfg.max_queries * (size_t)n_docs * sizeof(int32_t);
-        hipError_t herr;
-        if (need > e->bm_cand_bytes) {
-            free_dev(e, e->bm_cand_doc); e->bm_cand_doc = nullptr; e->bm_cand_bytes = 0;
-            if ((herr = eng_malloc(e, (void**)&e->bm_cand_doc, need)) != hipSuccess)
-                return fail(e, MSR_ERR_NOMEM, "BM25 candidate lists (%zu bytes): %s", need, hipGetErrorString(herr));
-            e->bm_cand_bytes = need;
-        }
-        free_dev(e, e->bm_cand_n); e->bm_cand_n = nullptr;
-        free_dev(e, e->bm_win); e->bm_win = nullptr;
-        if ((herr = eng_malloc(e, (void**)&e->bm_win, (size_t)e->cfg.max_queries * sizeof(uint64_t))) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "msr_bind_postings: %s", hipGetErrorString(herr));
-        if ((herr = eng_malloc(e, (void**)&e->bm_cand_n, (size_t)e->cfg.max_queries * msr_bm25_max_segments(n_docs) * sizeof(int32_t))) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "BM25 candidate counts: %s", hipGetErrorString(herr));
+    drop_postings(e);
+    const Bm25Index cand{term_off, post_doc, post_tf, doc_len, idf, n_terms, n_postings, n_docs, (double)avgdl, k1, b,
+                         nullptr, nullptr, (int32_t)((n_docs + MSR_BM25_TILE - 1) / MSR_BM25_TILE), nullptr, nullptr, nullptr, 0};
+    const int rc = build_postings(e, cand, (hipStream_t)stream);
+    if (rc) drop_postings(e);                                // (nothing half-built stays behind)
+    e->have_postings = rc == MSR_OK;
+    return rc;
+}
 
-    }
-    Bm25Index cand{term_off, post_doc, post_tf, doc_len, idf, n_terms, n_postings, n_docs, (double)avgdl, k1, b,
-                   nullptr, nullptr, (int32_t)((n_docs + MSR_BM25_TILE - 1) / MSR_BM25_TILE), nullptr, nullptr, nullptr, 0};
-    // the scoring kernel indexes LDS with (post_doc - tile start): validate the CSR once, on the device
-    hipStream_t st = (hipStream_t)stream;
-    int32_t h_flag = 0;
-    HIP_TRY(e, msr_bm25_validate(cand, e->sel.cand_n, st));           // cand_n[0] as a scratch word (zero between calls)
-    HIP_TRY(e, hipMemcpyAsync(&h_flag, e->sel.cand_n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(e, hipMemsetAsync(e->sel.cand_n, 0, sizeof(int32_t), st));
-    HIP_TRY(e, hipStreamSynchronize(st));
-    if (h_flag >= 1 && h_flag <= 5) {
-        static const char* why[] = {"", "term_off is not a monotone offset array ending at n_postings",
-                                    "a posting's document index is outside [0, n_docs)",
-                                    "documents are not strictly ascending inside a posting list",
-                                    "negative doc_len", "non-positive term frequency"};
-        return fail(e, MSR_ERR_INVALID, "msr_bind_postings: malformed index: %s", why[h_flag]);
-    }
-    if (!(avgdl > 0.0f) || !(k1 >= 0.0) || !(b >= 0.0 && b <= 1.0))
-        return fail(e, MSR_ERR_INVALID, "msr_bind_postings: avgdl must be > 0, k1 >= 0, 0 <= b <= 1");
-    // skip table for the long posting lists (one-time; the offsets come to the host once for this)
-    free_dev(e, e->bm_heavy_id); e->bm_heavy_id = nullptr;
-    free_dev(e, e->bm_tile_off); e->bm_tile_off = nullptr;
-    free_dev(e, e->bm_dense_id); e->bm_dense_id = nullptr;
-    free_dev(e, e->bm_dense); e->bm_dense = nullptr;
-    std::vector<int32_t> dense_terms;                         // long lists with negative idf, longest first (tables below)
-    if (n_terms > 0) {
-        std::vector<int64_t> h_toff((size_t)n_terms + 1);
-        std::vector<float> h_idf((size_t)n_terms);
-        HIP_TRY(e, hipMemcpyAsync(h_toff.data(), term_off, h_toff.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(e, hipMemcpyAsync(h_idf.data(), idf, h_idf.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(e, hipStreamSynchronize(st));
-        std::vector<int32_t> heavy_id((size_t)n_terms, -1), heavy_terms;
-        for (int64_t t = 0; t < n_terms; ++t)
-            if (h_toff[t + 1] - h_toff[t] >= MSR_BM25_HEAVY_DF && h_toff[t + 1] - h_toff[t] < (1ll << 32)) {
-                heavy_id[t] = (int32_t)heavy_terms.size();
-                heavy_terms.push_back((int32_t)t);
-                if (h_idf[t] < 0.0f) dense_terms.push_back((int32_t)t);
-            }
-        if (!heavy_terms.empty()) {
-            hipError_t herr;
-            int32_t* d_terms = nullptr;
-            const size_t rows = heavy_terms.size() * (size_t)(cand.n_tiles + 1);
-            if ((herr = eng_malloc(e, (void**)&e->bm_heavy_id, heavy_id.size() * sizeof(int32_t))) != hipSuccess ||
-                (herr = eng_malloc(e, (void**)&e->bm_tile_off, rows * sizeof(uint32_t))) != hipSuccess ||
-                (herr = eng_malloc(e, (void**)&d_terms, heavy_terms.size() * sizeof(int32_t))) != hipSuccess) {
-                free_dev(e, d_terms);
-                return fail(e, MSR_ERR_NOMEM, "BM25 skip table: %s", hipGetErrorString(herr));
-            }
-            hipError_t h1 = hipMemcpyAsync(e->bm_heavy_id, heavy_id.data(), heavy_id.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-            if (h1 == hipSuccess) h1 = hipMemcpyAsync(d_terms, heavy_terms.data(), heavy_terms.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-            if (h1 == hipSuccess) h1 = msr_bm25_build_skip(cand, d_terms, (int)heavy_terms.size(), e->bm_tile_off, st);
-            const hipError_t h2 = hipStreamSynchronize(st);
-            free_dev(e, d_terms);                             // (on every path)
-            if (h1 != hipSuccess || h2 != hipSuccess)
-                return fail(e, MSR_ERR_HIP, "BM25 skip table: %s", hipGetErrorString(h1 != hipSuccess ? h1 : h2));
-            cand.heavy_id = e->bm_heavy_id;
-            cand.tile_off = e->bm_tile_off;
+// ---- msr_bind_chunks in three steps: what doc_off says (host only), the device tables, the streaming pass ------------------
+struct ChunkLayout {
+    std::vector<int32_t> spans, wspans, wspans12;   // equal-chunk-count spans cut at document boundaries
+    int wide_ok = 1, wide_ok64 = 1;                 // see DenseIndex
+    bool tiles_ok = true;                           // every document fits a row tile of <= 256 rows (else: no GEMM paths)
+    std::vector<int32_t> tiles;                     // [n_tiles + 1] first row of each tile
+    std::vector<int32_t> trow;                      // [n_tiles] first row of each tile in the fragment-order copy of the rows, which
+    int64_t n_trows = 0;                            // has n_trows rows (empty, 0: the copy would have 2^31 rows or more)
+};
+
+// Checks the document offsets (host copy) and works out everything the bind derives from them.  No device calls.
+static int chunk_layout(msr_engine* e, const std::vector<int32_t>& h_off, int64_t n_chunks, int64_t n_docs, ChunkLayout& L) {
+    if (h_off[0] != 0 || (int64_t)h_off[n_docs] != n_chunks)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: doc_off[0]=%d, doc_off[n_docs]=%d, n_chunks=%lld",
+                    h_off[0], h_off[n_docs], (long long)n_chunks);
+    for (int64_t d = 0; d < n_docs; ++d)
+        if (h_off[d + 1] < h_off[d]) return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: doc_off not monotone at %lld", (long long)d);
+    // one span per workgroup (variant 1) / per wave (variant 2)
+    auto make_spans = [&](int target, int64_t min_rows) {
+        if ((int64_t)target * min_rows > n_chunks) target = (int)std::max<int64_t>(1, n_chunks / min_rows);
+        std::vector<int32_t> sp;
+        sp.push_back(0);
+        for (int s = 1; s < target; ++s) {
+            const int64_t want = n_chunks * s / target;
+            int64_t d = std::lower_bound(h_off.begin(), h_off.end(), (int32_t)want) - h_off.begin();   // first doc starting at >= want
+            if (d > n_docs) d = n_docs;
+            if (d > sp.back()) sp.push_back((int32_t)d);
         }
-        // the longest negative-idf lists get a dense table: at most MSR_BM25_MAX_DENSE of them and 4 GiB in all
-        std::stable_sort(dense_terms.begin(), dense_terms.end(), [&](int32_t a, int32_t b2) {
-            return h_toff[a + 1] - h_toff[a] > h_toff[b2 + 1] - h_toff[b2];
-        });
-        const size_t row_bytes = ((size_t)cand.n_tiles * MSR_BM25_TILE + 8) * sizeof(double);
-        const size_t cap = std::min<size_t>(MSR_BM25_MAX_DENSE, (size_t)(4ull << 30) / row_bytes);
-        if (dense_terms.size() > cap) dense_terms.resize(cap);
-    }
-    // the copy the scoring kernel streams (after the validation above: the copy is of a well-formed index): every posting with
-    // its tf_component, from the per-document length norms k1 (1 - b + b dl / avgdl)
-    free_dev(e, e->bm_post); e->bm_post = nullptr;
+        if (sp.back() != (int32_t)n_docs) sp.push_back((int32_t)n_docs);
+        return sp;
+    };
+    L.spans = make_spans(e->n_cus, 256);
+    L.wspans = make_spans(e->n_cus * 8, 64);
+    L.wspans12 = make_spans(e->n_cus * 12, 64);
+    // K-split kernels: documents spanned by any two consecutive 16-row groups must fit the LDS ring with a block to spare
     {
-        const int64_t n_pad = (int64_t)cand.n_tiles * MSR_BM25_TILE;
-        double* dnorm = nullptr;
-        const size_t bytes = (size_t)(n_postings + 1) * sizeof(Bm25Post);      // + the sentinel posting
-        hipError_t herr = eng_malloc(e, &e->bm_post, bytes);
-        if (herr != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "postings with tf components (%zu bytes): %s", bytes, hipGetErrorString(herr));
-        if ((herr = eng_malloc(e, (void**)&dnorm, (size_t)n_pad * sizeof(double))) != hipSuccess) {
-            free_dev(e, e->bm_post); e->bm_post = nullptr;
-            return fail(e, MSR_ERR_NOMEM, "length norms: %s", hipGetErrorString(herr));
+        const int64_t n_groups = (n_chunks + 15) / 16;
+        int64_t dl = 0, dr = 0;                              // document of the window's first / last row
+        for (int64_t u = 0; u < n_groups && (L.wide_ok || L.wide_ok64); ++u) {
+            const int64_t first = 16 * u, last = std::min<int64_t>(16 * (u + 2), n_chunks) - 1;
+            while (h_off[dl + 1] <= first) ++dl;
+            if (dr < dl) dr = dl;
+            while (h_off[dr + 1] <= last) ++dr;
+            if (dr - dl + 32 > MSR_WIDE_RING) L.wide_ok = 0;
+            if (dr - dl + 32 > 64) L.wide_ok64 = 0;
+            // ... and one group at most 32 documents: the kernel writes at most two finished blocks per unit
+            int64_t dm = dl;
+            const int64_t glast = std::min<int64_t>(16 * (u + 1), n_chunks) - 1;
+            while (h_off[dm + 1] <= glast) ++dm;
+            if (dm - dl > 32) L.wide_ok = L.wide_ok64 = 0;
         }
-        hipError_t h1 = msr_bm25_dnorm(doc_len, n_docs, n_pad, k1, b, (double)avgdl, dnorm, st);
-        hipError_t h2 = h1 == hipSuccess ? msr_bm25_post_comp(post_doc, post_tf, dnorm, k1, n_postings, (Bm25Post*)e->bm_post, st) : h1;
-        hipError_t h3 = hipStreamSynchronize(st);
-        free_dev(e, dnorm);
-        if (h2 != hipSuccess || h3 != hipSuccess)
-            return fail(e, MSR_ERR_HIP, "tf components: %s", hipGetErrorString(h2 != hipSuccess ? h2 : h3));
     }
-    cand.post = (const Bm25Post*)e->bm_post;
-    if (!dense_terms.empty()) {
-        const int64_t stride = (int64_t)cand.n_tiles * MSR_BM25_TILE + 8;      // the tail of a row stays 0.0 (the kernel's "no value")
-        std::vector<int32_t> dense_id((size_t)n_terms, -1);
-        for (size_t h = 0; h < dense_terms.size(); ++h) dense_id[dense_terms[h]] = (int32_t)h;
-        hipError_t herr;
-        int32_t* d_terms = nullptr;
-        if ((herr = eng_malloc(e, (void**)&e->bm_dense_id, dense_id.size() * sizeof(int32_t))) != hipSuccess ||
-            (herr = eng_malloc(e, (void**)&e->bm_dense, dense_terms.size() * (size_t)stride * sizeof(double))) != hipSuccess ||
-            (herr = eng_malloc(e, (void**)&d_terms, dense_terms.size() * sizeof(int32_t))) != hipSuccess) {
-            free_dev(e, d_terms);
-            return fail(e, MSR_ERR_NOMEM, "BM25 dense tables: %s", hipGetErrorString(herr));
+    // row tiles for the GEMM paths: <= 256 rows, cut at document boundaries
+    int32_t start = 0;
+    L.tiles.push_back(0);
+    for (int64_t d = 0; d < n_docs && L.tiles_ok; ++d) {
+        const int32_t end = h_off[d + 1];
+        if (end - h_off[d] > 256) L.tiles_ok = false;
+        if (end - start > 256) { L.tiles.push_back(h_off[d]); start = h_off[d]; }
+    }
+    if (!L.tiles_ok) return MSR_OK;
+    if (L.tiles.back() != (int32_t)n_chunks) L.tiles.push_back((int32_t)n_chunks);
+    const size_t n_tiles = L.tiles.size() - 1;
+    L.trow.resize(n_tiles);
+    for (size_t t = 0; t < n_tiles; ++t) {                   // every tile starts at a multiple of 16 rows
+        L.trow[t] = (int32_t)L.n_trows;
+        L.n_trows += (L.tiles[t + 1] - L.tiles[t] + 15) / 16 * 16;
+    }
+    if (L.n_trows + MSR_STREAM256_TILE_ROWS >= ((int64_t)1 << 31)) { L.trow.clear(); L.n_trows = 0; }
+    return MSR_OK;
+}
+
+// The device tables of the binding: e->dense, and the tile tables of the GEMM paths.
+static int bind_chunk_tables(msr_engine* e, const float* emb, int64_t n_chunks, const int32_t* doc_off, int64_t n_docs,
+                             const float* inv_norm, const ChunkLayout& L, hipStream_t st) {
+    ALLOC(e, e->mem_chunks, e->chunk_doc, (size_t)n_chunks * sizeof(int32_t));
+    ALLOC(e, e->mem_chunks, e->span_doc, L.spans.size() * sizeof(int32_t));
+    ALLOC(e, e->mem_chunks, e->wspan_doc, L.wspans.size() * sizeof(int32_t));
+    HIP_TRY(e, hipMemcpyAsync(e->span_doc, L.spans.data(), L.spans.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(e, hipMemcpyAsync(e->wspan_doc, L.wspans.data(), L.wspans.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    ALLOC(e, e->mem_chunks, e->wspan12_doc, L.wspans12.size() * sizeof(int32_t));
+    HIP_TRY(e, hipMemcpyAsync(e->wspan12_doc, L.wspans12.data(), L.wspans12.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(e, msr_fill_chunk_doc(doc_off, n_docs, e->chunk_doc, st));
+    if (!inv_norm) {
+        ALLOC(e, e->mem_chunks, e->inv_norm_own, (size_t)n_chunks * sizeof(float));
+        HIP_TRY(e, msr_row_inv_norm(emb, n_chunks, e->inv_norm_own, st));
+        inv_norm = e->inv_norm_own;
+    }
+    if (L.wide_ok) {
+        ALLOC(e, e->mem_chunks, e->row_meta, (size_t)(n_chunks + 16) * 8);
+        HIP_TRY(e, msr_pack_row_meta(e->chunk_doc, inv_norm, n_chunks, e->row_meta, st));
+    }
+    // The default scan multiplies f16-split pieces (error bound in msr_dense.hip); the bound needs row norms near 1
+    // (the reference stores unit-norm rows, indexer/indexer.py:165).  Otherwise fall back to the exact f32 MFMA kernel.
+    int variant = e->cfg.scan_variant;
+    if (variant == 0) {
+        uint32_t h_rng[2] = {0, 0};
+        HIP_TRY(e, msr_inv_norm_range(inv_norm, n_chunks, (uint32_t*)e->sel.cand_n, st));   // 2 scratch words
+        HIP_TRY(e, hipMemcpyAsync(h_rng, e->sel.cand_n, sizeof(h_rng), hipMemcpyDeviceToHost, st));
+        HIP_TRY(e, hipMemsetAsync(e->sel.cand_n, 0, 2 * sizeof(int32_t), st));
+        HIP_TRY(e, hipStreamSynchronize(st));
+        float lo, hi;
+        memcpy(&lo, &h_rng[0], 4); memcpy(&hi, &h_rng[1], 4);
+        variant = (lo >= 0.5f && hi <= 2.0f) ? 7 : 2;
+        if (variant == 7 && e->cfg.scan_layout == 0 && L.wide_ok) variant = 14;   // K-split kernel: up to 64 queries per sweep
+    }
+    if (variant == 15) {                                  // A/B variant: K-split scan over a pre-split copy of the rows
+        if (e->cfg.scan_layout != 0 || !L.wide_ok) {
+            variant = 7;                                  // preconditions of the K-split kernel not met
+        } else {
+            ALLOC(e, e->mem_chunks, e->emb_presplit, (size_t)n_chunks * MSR_DIM * sizeof(float));
+            HIP_TRY(e, msr_presplit_rows(emb, n_chunks, e->emb_presplit, st));
         }
-        hipError_t h1 = hipMemcpyAsync(e->bm_dense_id, dense_id.data(), dense_id.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-        if (h1 == hipSuccess) h1 = hipMemcpyAsync(d_terms, dense_terms.data(), dense_terms.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-        if (h1 == hipSuccess) h1 = hipMemsetAsync(e->bm_dense, 0, dense_terms.size() * (size_t)stride * sizeof(double), st);
-        if (h1 == hipSuccess) h1 = msr_bm25_build_dense(cand, d_terms, (int)dense_terms.size(), e->bm_dense, stride, st);
-        const hipError_t h2 = hipStreamSynchronize(st);
-        free_dev(e, d_terms);                                 // (on every path)
-        if (h1 != hipSuccess || h2 != hipSuccess)
-            return fail(e, MSR_ERR_HIP, "BM25 dense tables: %s", hipGetErrorString(h1 != hipSuccess ? h1 : h2));
-        cand.dense_id = e->bm_dense_id;
-        cand.dense_comp = e->bm_dense;
-        cand.dense_stride = stride;
     }
-    e->bm25 = cand;
-    e->have_postings = true;
+    e->dense = DenseIndex{emb, doc_off, e->chunk_doc, inv_norm, e->span_doc, n_chunks, n_docs, (n_docs + 31) / 32 * 32,
+                          (int)L.spans.size() - 1, e->cfg.scan_layout, e->wspan_doc, (int)L.wspans.size() - 1, e->wspan12_doc,
+                          (int)L.wspans12.size() - 1, e->qimg, nullptr, e->emb_presplit, e->row_meta, L.wide_ok,
+                          L.wide_ok && L.wide_ok64, nullptr, variant};
+    if (L.tiles_ok) {
+        ALLOC(e, e->mem_chunks, e->tile_row, L.tiles.size() * 4);
+        HIP_TRY(e, hipMemcpyAsync(e->tile_row, L.tiles.data(), L.tiles.size() * 4, hipMemcpyHostToDevice, st));
+        e->n_tiles = (int)L.tiles.size() - 1;
+        e->tiles_ok = true;
+    }
+    if (!L.trow.empty()) {
+        ALLOC(e, e->mem_chunks, e->tile_trow, L.trow.size() * 4);
+        HIP_TRY(e, hipMemcpyAsync(e->tile_trow, L.trow.data(), L.trow.size() * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(e, hipStreamSynchronize(st));                 // (the copies out of L's vectors have been made)
+    return MSR_OK;
+}
+
+// Batches of 65..128 queries take ONE streaming pass over the f32 rows (f16 filter + exact f32 finish, msr_gemm_f32.hip) when the
+// corpus allows it: the pass' scratch, the two optional copies of the rows, e->gf.
+static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st) {
+    if (!(e->tiles_ok && e->dense.variant == 14 && e->n_tiles >= 64)) return MSR_OK;
+    const float* emb = e->dense.emb;
+    const float* inv_norm = e->dense.inv_norm;
+    const int64_t n_chunks = e->dense.n_chunks;
+    const int n_tiles = e->n_tiles, nw = e->n_cus * 8, stride = (n_tiles + 31) / 32 * 32;
+    // one call holds up to 8 groups of 128 queries (bounded by the select scratch, which covers max(max_queries, 128) rows)
+    const int groups = std::min(8, std::max(e->cfg.max_queries, 128) / 128);
+    // emitted entries per wave and call: ~600 per 128 queries at 5 M rows (150 x sample stride per query over 2048 waves)
+    const int GF_WV_CAP = 4096 * std::max(1, groups / 2);
+    const size_t QM = (size_t)groups * 128;
+    const int max_nt = std::max(1, std::min(4, groups / 2));      // 256-query groups that share the rows of one launch
+    GemmF32Index& g = e->gf;
+    g.n_tiles = n_tiles; g.n_cus = e->n_cus; g.max_groups = groups; g.tmax_stride = stride; g.wv_cap = GF_WV_CAP; g.max_nt = max_nt;
+    ALLOC(e, e->mem_chunks, e->gf_inv_pad, (size_t)(n_chunks + 512) * 4);
+    ALLOC(e, e->mem_chunks, g.qimg, (size_t)groups * 24 * 8192);
+    ALLOC(e, e->mem_chunks, e->gf_qn, (QM + 64) * MSR_DIM * 4);
+    ALLOC(e, e->mem_chunks, e->gf_fb_qimg, (QM + 63) / 64 * msr_ksplit_slice_image_bytes());
+    ALLOC(e, e->mem_chunks, g.tmax_t, (size_t)n_tiles * 8 * (groups >= 2 ? 256 * max_nt : 128) * 4);   // [tile][wave][queries of a launch]
+    ALLOC(e, e->mem_chunks, g.tmax, QM * stride * 4);
+    ALLOC(e, e->mem_chunks, g.thr, QM * 4);
+    ALLOC(e, e->mem_chunks, g.thr2, QM * 4);
+    ALLOC(e, e->mem_chunks, g.flag, QM * 4);
+    ALLOC(e, e->mem_chunks, g.wvbuf, (size_t)nw * GF_WV_CAP * 16);
+    ALLOC(e, e->mem_chunks, g.wv_count, (size_t)nw * 4);
+    ALLOC(e, e->mem_chunks, g.pairs, QM * 4096 * 8);
+    ALLOC(e, e->mem_chunks, g.pair_n, QM * 4);
+    ALLOC(e, e->mem_chunks, e->gf_gate, GF_GATE_BYTES);
+    ALLOC(e, e->mem_chunks, g.err_max, 4);
+    ALLOC(e, e->mem_chunks, g.margin, QM * 4);
+    ALLOC(e, e->mem_chunks, g.cand_doc, QM * MSR_SEL_CAP * 4);
+    ALLOC(e, e->mem_chunks, g.cand_score, QM * MSR_SEL_CAP * 4);
+    ALLOC(e, e->mem_chunks, g.cand_chunk, QM * MSR_SEL_CAP * 4);
+    ALLOC(e, e->mem_chunks, g.cand_n, QM * 4);
+    g.tile_row = e->tile_row;
+    g.inv_pad = e->gf_inv_pad;
+    HIP_TRY(e, msr_pad_inv_norm(inv_norm, n_chunks, n_chunks + 512, e->gf_inv_pad, st));
+    HIP_TRY(e, hipMemsetAsync(g.pair_n, 0, QM * 4, st));
+    HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
+    HIP_TRY(e, hipMemsetAsync(g.cand_n, 0, QM * 4, st));
+    HIP_TRY(e, msr_f16_row_error(emb, inv_norm, n_chunks, g.err_max, st));   // measured once: the margin of the f16 filter
+    // The 256-query kernel streams a copy of the rows in fragment order (whole cache lines per load instruction; +3 % rows
+    // of padding: every tile starts at a multiple of 16 rows).  Size of the copy: a workgroup's tile visit ALWAYS loads
+    // MSR_STREAM256_TILE_ROWS = 8 waves x 32 rows from the tile's first row on, whatever the tile's own length (rows behind
+    // the tile are masked in the epilogue); all K blocks of a visit, and the prefetch of the next visit's first block,
+    // address rows of [first row of a tile, first row + MSR_STREAM256_TILE_ROWS) -- the "next" tile of a workgroup's last
+    // visit is that same tile again (jn == jt).  So the highest row the kernel touches is max_t tile_trow[t] +
+    // MSR_STREAM256_TILE_ROWS - 1 < n_trows + MSR_STREAM256_TILE_ROWS: that many rows of zero padding behind the last
+    // tile are exactly enough, for every prefetch depth (checked against the tile table here, not assumed).
+    // The row-major matrix stays what every other kernel reads.  Declined by MSR_CFG_NO_ROW_COPY, or when the allocation
+    // fails (the copy doubles the matrix): the TILED = false instantiation of the same kernel reads the caller's matrix.
+    if (groups >= 2 && e->tile_trow) {
+        const size_t copy_rows = (size_t)L.n_trows + MSR_STREAM256_TILE_ROWS;
+        if ((int64_t)L.trow.back() + MSR_STREAM256_TILE_ROWS > (int64_t)copy_rows)
+            return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: internal: tile table exceeds the fragment-order copy");
+        if (e->cfg.flags & MSR_CFG_NO_ROW_COPY) {
+            e->row_copy_state = 2;
+        } else if (e->mem_chunks.alloc(&e->gf_emb_tiled, copy_rows * MSR_DIM * 4) != hipSuccess) {
+            (void)hipGetLastError();                      // clear the sticky error: the engine works without the copy
+            e->row_copy_state = 3;
+        } else {
+            HIP_TRY(e, hipMemsetAsync((char*)e->gf_emb_tiled + (size_t)L.n_trows * MSR_DIM * 4, 0,
+                                      (size_t)MSR_STREAM256_TILE_ROWS * MSR_DIM * 4, st));
+            HIP_TRY(e, msr_tile_rows(emb, e->tile_row, e->tile_trow, n_tiles, e->gf_emb_tiled, st));
+            e->row_copy_state = 1;
+        }
+    }
+    // Launches of SEVERAL 256-query groups (engines for >= 512 queries per call: the batched steps, a rank of a sharded
+    // run) are bound by the matrix pipes and the vector issue beside them; every group converts the same f32 rows to f16
+    // again.  They read an f16 image of the rows instead -- the very values the pass converts in registers (round to
+    // nearest, not normalised): same products, same candidates, same results; 1536 B per row.  Declined with the other
+    // copy (MSR_CFG_NO_ROW_COPY) or when the allocation fails: those launches then convert as before.
+    if (max_nt >= 2 && (e->cfg.flags & MSR_CFG_NO_ROW_COPY)) {
+        e->row_image_state = 2;
+    } else if (max_nt >= 2) {
+        const size_t img_rows = (size_t)n_chunks + 512;
+        if (e->mem_chunks.alloc(&e->gf_emb_f16, img_rows * MSR_DIM * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            e->row_image_state = 3;
+        } else {
+            HIP_TRY(e, msr_f16_rows(emb, n_chunks, (int64_t)img_rows, e->gf_emb_f16, st));
+            e->row_image_state = 1;
+        }
+    }
+    g.emb_tiled = e->gf_emb_tiled;
+    g.tile_trow = e->gf_emb_tiled ? e->tile_trow : nullptr;
+    g.emb_f16 = e->gf_emb_f16;
+    e->gf_ok = true;
     return MSR_OK;
 }
 
@@ -445,275 +644,35 @@ extern "C" int msr_bind_chunks(msr_engine* e, const float* emb, int64_t n_chunks
         return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: inv_norm is required with the interleaved layout");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    int rc = ensure_score_rows(e, n_docs);
-    if (rc) return rc;
     // spans need the document offsets on the host (one-time, at bind)
     std::vector<int32_t> h_off((size_t)n_docs + 1);
     HIP_TRY(e, hipMemcpyAsync(h_off.data(), doc_off, (size_t)(n_docs + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));
-    if (h_off[0] != 0 || (int64_t)h_off[n_docs] != n_chunks)
-        return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: doc_off[0]=%d, doc_off[n_docs]=%d, n_chunks=%lld",
-                    h_off[0], h_off[n_docs], (long long)n_chunks);
-    for (int64_t d = 0; d < n_docs; ++d)
-        if (h_off[d + 1] < h_off[d]) return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: doc_off not monotone at %lld", (long long)d);
-    // equal-chunk-count spans cut at document boundaries: one per workgroup (variant 1) / per wave (variant 2)
-    auto make_spans = [&](int target, int64_t min_rows) {
-        if ((int64_t)target * min_rows > n_chunks) target = (int)std::max<int64_t>(1, n_chunks / min_rows);
-        std::vector<int32_t> sp;
-        sp.push_back(0);
-        for (int s = 1; s < target; ++s) {
-            const int64_t want = n_chunks * s / target;
-            int64_t d = std::lower_bound(h_off.begin(), h_off.end(), (int32_t)want) - h_off.begin();   // first doc starting at >= want
-            if (d > n_docs) d = n_docs;
-            if (d > sp.back()) sp.push_back((int32_t)d);
-        }
-        if (sp.back() != (int32_t)n_docs) sp.push_back((int32_t)n_docs);
-        return sp;
-    };
-    std::vector<int32_t> spans = make_spans(e->n_cus, 256);
-    std::vector<int32_t> wspans = make_spans(e->n_cus * 8, 64);
-    std::vector<int32_t> wspans12 = make_spans(e->n_cus * 12, 64);
-    // K-split kernels: documents spanned by any two consecutive 16-row groups must fit the LDS ring with a block to spare
-    int wide_ok = 1, wide_ok64 = 1;
-    {
-        const int64_t n_groups = (n_chunks + 15) / 16;
-        int64_t dl = 0, dr = 0;                              // document of the window's first / last row
-        for (int64_t u = 0; u < n_groups && (wide_ok || wide_ok64); ++u) {
-            const int64_t first = 16 * u, last = std::min<int64_t>(16 * (u + 2), n_chunks) - 1;
-            while (h_off[dl + 1] <= first) ++dl;
-            if (dr < dl) dr = dl;
-            while (h_off[dr + 1] <= last) ++dr;
-            if (dr - dl + 32 > MSR_WIDE_RING) wide_ok = 0;
-            if (dr - dl + 32 > 64) wide_ok64 = 0;
-            // ... and one group at most 32 documents: the kernel writes at most two finished blocks per unit
-            int64_t dm = dl;
-            const int64_t glast = std::min<int64_t>(16 * (u + 1), n_chunks) - 1;
-            while (h_off[dm + 1] <= glast) ++dm;
-            if (dm - dl > 32) wide_ok = wide_ok64 = 0;
-        }
-    }
-    const int n_spans = (int)spans.size() - 1;
-    const int n_wspans = (int)wspans.size() - 1;
-    const int n_wspans12 = (int)wspans12.size() - 1;
-
-    free_dev(e, e->chunk_doc); e->chunk_doc = nullptr;
-    free_dev(e, e->row_meta); e->row_meta = nullptr;
-    free_dev(e, e->emb_presplit); e->emb_presplit = nullptr;
-    free_dev(e, e->inv_norm_own); e->inv_norm_own = nullptr;
-    free_dev(e, e->span_doc); e->span_doc = nullptr;
-    free_dev(e, e->wspan_doc); e->wspan_doc = nullptr;
-    free_dev(e, e->wspan12_doc); e->wspan12_doc = nullptr;
-    hipError_t herr;
-    if ((herr = eng_malloc(e, (void**)&e->chunk_doc, (size_t)n_chunks * sizeof(int32_t))) != hipSuccess)
-        return fail(e, MSR_ERR_NOMEM, "chunk_doc: %s", hipGetErrorString(herr));
-    if ((herr = eng_malloc(e, (void**)&e->span_doc, spans.size() * sizeof(int32_t))) != hipSuccess)
-        return fail(e, MSR_ERR_NOMEM, "span_doc: %s", hipGetErrorString(herr));
-    if ((herr = eng_malloc(e, (void**)&e->wspan_doc, wspans.size() * sizeof(int32_t))) != hipSuccess)
-        return fail(e, MSR_ERR_NOMEM, "wspan_doc: %s", hipGetErrorString(herr));
-    HIP_TRY(e, hipMemcpyAsync(e->span_doc, spans.data(), spans.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(e, hipMemcpyAsync(e->wspan_doc, wspans.data(), wspans.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if ((herr = eng_malloc(e, (void**)&e->wspan12_doc, wspans12.size() * sizeof(int32_t))) != hipSuccess)
-        return fail(e, MSR_ERR_NOMEM, "wspan12_doc: %s", hipGetErrorString(herr));
-    HIP_TRY(e, hipMemcpyAsync(e->wspan12_doc, wspans12.data(), wspans12.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(e, msr_fill_chunk_doc(doc_off, n_docs, e->chunk_doc, st));
-    if (!inv_norm) {
-        if ((herr = eng_malloc(e, (void**)&e->inv_norm_own, (size_t)n_chunks * sizeof(float))) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "inv_norm: %s", hipGetErrorString(herr));
-        HIP_TRY(e, msr_row_inv_norm(emb, n_chunks, e->inv_norm_own, st));
-        inv_norm = e->inv_norm_own;
-    }
-    if (wide_ok) {
-        if ((herr = eng_malloc(e, &e->row_meta, (size_t)(n_chunks + 16) * 8)) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "row_meta: %s", hipGetErrorString(herr));
-        HIP_TRY(e, msr_pack_row_meta(e->chunk_doc, inv_norm, n_chunks, e->row_meta, st));
-    }
-    // The default scan multiplies f16-split pieces (error bound in msr_dense.hip); the bound needs row norms near 1
-    // (the reference stores unit-norm rows, indexer/indexer.py:165).  Otherwise fall back to the exact f32 MFMA kernel.
-    int variant = e->cfg.scan_variant;
-    if (variant == 0) {
-        uint32_t h_rng[2] = {0, 0};
-        HIP_TRY(e, msr_inv_norm_range(inv_norm, n_chunks, (uint32_t*)e->sel.cand_n, st));   // 2 scratch words
-        HIP_TRY(e, hipMemcpyAsync(h_rng, e->sel.cand_n, sizeof(h_rng), hipMemcpyDeviceToHost, st));
-        HIP_TRY(e, hipMemsetAsync(e->sel.cand_n, 0, 2 * sizeof(int32_t), st));
-        HIP_TRY(e, hipStreamSynchronize(st));
-        float lo, hi;
-        memcpy(&lo, &h_rng[0], 4); memcpy(&hi, &h_rng[1], 4);
-        variant = (lo >= 0.5f && hi <= 2.0f) ? 7 : 2;
-        if (variant == 7 && e->cfg.scan_layout == 0 && wide_ok) variant = 14;   // K-split kernel: up to 64 queries per sweep
-    }
-    if (variant == 15) {                                  // A/B variant: K-split scan over a pre-split copy of the rows
-        if (e->cfg.scan_layout != 0 || !wide_ok) {
-            variant = 7;                                  // preconditions of the K-split kernel not met
-        } else {
-            if ((herr = eng_malloc(e, &e->emb_presplit, (size_t)n_chunks * MSR_DIM * sizeof(float))) != hipSuccess)
-                return fail(e, MSR_ERR_NOMEM, "pre-split rows (%zu bytes): %s", (size_t)n_chunks * MSR_DIM * sizeof(float),
-                            hipGetErrorString(herr));
-            HIP_TRY(e, msr_presplit_rows(emb, n_chunks, e->emb_presplit, st));
-        }
-    }
-    HIP_TRY(e, hipStreamSynchronize(st));                 // spans vector goes out of scope
-    e->dense = DenseIndex{emb, doc_off, e->chunk_doc, inv_norm, e->span_doc, n_chunks, n_docs, (n_docs + 31) / 32 * 32, n_spans,
-                          e->cfg.scan_layout, e->wspan_doc, n_wspans, e->wspan12_doc, n_wspans12, e->qimg, nullptr,
-                          e->emb_presplit, e->row_meta, wide_ok, wide_ok && wide_ok64, nullptr, variant};
-    free_dev(e, e->emb_bf16);                                // a new binding invalidates the bf16 copy
-    e->emb_bf16 = nullptr;
-    free_gemm(e);
-    free_gf(e);
-    e->row_copy_state = e->row_image_state = 0;              // (a re-bind that does not qualify reports "not applicable")
-    // ---- row tiles for the GEMM paths: <= 256 rows, cut at document boundaries (a longer document: no GEMM paths) ----
-    std::vector<int32_t> h_trow;                          // first row of each tile in the fragment-order copy (below): every
-    int64_t n_trows = 0;                                  // tile starts at a multiple of 16 rows
-    {
-        std::vector<int32_t> tiles;
-        bool ok = true;
-        int32_t start = 0;
-        tiles.push_back(0);
-        for (int64_t d = 0; d < n_docs && ok; ++d) {
-            const int32_t end = h_off[d + 1];
-            if (end - h_off[d] > 256) ok = false;
-            if (end - start > 256) { tiles.push_back(h_off[d]); start = h_off[d]; }
-        }
-        if (tiles.back() != (int32_t)n_chunks) tiles.push_back((int32_t)n_chunks);
-        if (ok) {
-            if ((herr = eng_malloc(e, (void**)&e->tile_row, tiles.size() * 4)) != hipSuccess)
-                return fail(e, MSR_ERR_NOMEM, "tile table: %s", hipGetErrorString(herr));
-            HIP_TRY(e, hipMemcpyAsync(e->tile_row, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(e, hipStreamSynchronize(st));
-            e->n_tiles = (int)tiles.size() - 1;
-            e->tiles_ok = true;
-            h_trow.resize(e->n_tiles);
-            for (int t = 0; t < e->n_tiles; ++t) {
-                h_trow[t] = (int32_t)n_trows;
-                n_trows += (tiles[t + 1] - tiles[t] + 15) / 16 * 16;
-            }
-            if (n_trows + MSR_STREAM256_TILE_ROWS < ((int64_t)1 << 31)) {
-                if ((herr = eng_malloc(e, (void**)&e->tile_trow, (size_t)e->n_tiles * 4)) != hipSuccess)
-                    return fail(e, MSR_ERR_NOMEM, "tile table: %s", hipGetErrorString(herr));
-                HIP_TRY(e, hipMemcpyAsync(e->tile_trow, h_trow.data(), (size_t)e->n_tiles * 4, hipMemcpyHostToDevice, st));
-                HIP_TRY(e, hipStreamSynchronize(st));
-                e->n_trows = n_trows;
-            }
-        }
-    }
-    // batches of 65..128 queries take ONE streaming pass over the f32 rows (f16 filter + exact f32 finish, msr_gemm_f32.hip)
-    // when the corpus allows it
-    if (e->tiles_ok && variant == 14 && e->n_tiles >= 64) {
-        const int n_tiles = e->n_tiles, nw = e->n_cus * 8, stride = (n_tiles + 31) / 32 * 32;
-        // one call holds up to 8 groups of 128 queries (bounded by the select scratch, which covers max(max_queries, 128) rows)
-        const int groups = std::min(8, std::max(e->cfg.max_queries, 128) / 128);
-        // emitted entries per wave and call: ~600 per 128 queries at 5 M rows (150 x sample stride per query over 2048 waves)
-        const int GF_WV_CAP = 4096 * std::max(1, groups / 2);
-        const size_t QM = (size_t)groups * 128;
-        const int max_nt = std::max(1, std::min(4, groups / 2));      // 256-query groups that share the rows of one launch
-        auto alloc = [&](void** p, size_t bytes) { return eng_malloc(e, p, bytes); };
-        if ((herr = alloc((void**)&e->gf_inv_pad, (size_t)(n_chunks + 512) * 4)) != hipSuccess ||
-            (herr = alloc(&e->gf_qimg, (size_t)groups * 24 * 8192)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_qn, (QM + 64) * MSR_DIM * 4)) != hipSuccess ||
-            (herr = alloc(&e->gf_fb_qimg, (QM + 63) / 64 * msr_ksplit_slice_image_bytes())) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_tmax_t, (size_t)n_tiles * 8 * (groups >= 2 ? 256 * max_nt : 128) * 4)) != hipSuccess ||   // [tile][wave][queries of a launch]
-            (herr = alloc((void**)&e->gf_tmax, QM * stride * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_thr, QM * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_thr2, QM * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_flag, QM * 4)) != hipSuccess ||
-            (herr = alloc(&e->gf_wvbuf, (size_t)nw * GF_WV_CAP * 16)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_wv_count, (size_t)nw * 4)) != hipSuccess ||
-            (herr = alloc(&e->gf_pairs, QM * 4096 * 8)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_pair_n, QM * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_gate, 16 * 4)) != hipSuccess ||       // one gate word per slice of 64 queries
-            (herr = alloc((void**)&e->gf_err, 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_margin, QM * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_cand_doc, QM * MSR_SEL_CAP * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_cand_score, QM * MSR_SEL_CAP * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_cand_chunk, QM * MSR_SEL_CAP * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gf_cand_n, QM * 4)) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "GEMM scan scratch: %s", hipGetErrorString(herr));
-        HIP_TRY(e, msr_pad_inv_norm(inv_norm, n_chunks, n_chunks + 512, e->gf_inv_pad, st));
-        HIP_TRY(e, hipMemsetAsync(e->gf_pair_n, 0, QM * 4, st));
-        HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, 16 * 4, st));
-        HIP_TRY(e, hipMemsetAsync(e->gf_cand_n, 0, QM * 4, st));
-        HIP_TRY(e, msr_f16_row_error(emb, inv_norm, n_chunks, e->gf_err, st));   // measured once: the margin of the f16 filter
-        // The 256-query kernel streams a copy of the rows in fragment order (whole cache lines per load instruction; +3 % rows
-        // of padding: every tile starts at a multiple of 16 rows).  Size of the copy: a workgroup's tile visit ALWAYS loads
-        // MSR_STREAM256_TILE_ROWS = 8 waves x 32 rows from the tile's first row on, whatever the tile's own length (rows behind
-        // the tile are masked in the epilogue); all K blocks of a visit, and the prefetch of the next visit's first block,
-        // address rows of [first row of a tile, first row + MSR_STREAM256_TILE_ROWS) -- the "next" tile of a workgroup's last
-        // visit is that same tile again (jn == jt).  So the highest row the kernel touches is max_t tile_trow[t] +
-        // MSR_STREAM256_TILE_ROWS - 1 < n_trows + MSR_STREAM256_TILE_ROWS: that many rows of zero padding behind the last
-        // tile are exactly enough, for every prefetch depth (checked against the tile table here, not assumed).
-        // The row-major matrix stays what every other kernel reads.  Declined by MSR_CFG_NO_ROW_COPY, or when the allocation
-        // fails (the copy doubles the matrix): the TILED = false instantiation of the same kernel reads the caller's matrix.
-        e->row_copy_state = 0;
-        if (groups >= 2 && e->tile_trow) {
-            const size_t copy_rows = (size_t)n_trows + MSR_STREAM256_TILE_ROWS;
-            if ((int64_t)h_trow.back() + MSR_STREAM256_TILE_ROWS > (int64_t)copy_rows)
-                return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: internal: tile table exceeds the fragment-order copy");
-            if (e->cfg.flags & MSR_CFG_NO_ROW_COPY) {
-                e->row_copy_state = 2;
-            } else if ((herr = alloc(&e->gf_emb_tiled, copy_rows * MSR_DIM * 4)) != hipSuccess) {
-                (void)hipGetLastError();                      // clear the sticky error: the engine works without the copy
-                e->gf_emb_tiled = nullptr;
-                e->row_copy_state = 3;
-            } else {
-                HIP_TRY(e, hipMemsetAsync((char*)e->gf_emb_tiled + (size_t)n_trows * MSR_DIM * 4, 0,
-                                          (size_t)MSR_STREAM256_TILE_ROWS * MSR_DIM * 4, st));
-                HIP_TRY(e, msr_tile_rows(emb, e->tile_row, e->tile_trow, n_tiles, e->gf_emb_tiled, st));
-                e->row_copy_state = 1;
-            }
-        }
-        // Launches of SEVERAL 256-query groups (engines for >= 512 queries per call: the batched steps, a rank of a sharded
-        // run) are bound by the matrix pipes and the vector issue beside them; every group converts the same f32 rows to f16
-        // again.  They read an f16 image of the rows instead -- the very values the pass converts in registers (round to
-        // nearest, not normalised): same products, same candidates, same results; 1536 B per row.  Declined with the other
-        // copy (MSR_CFG_NO_ROW_COPY) or when the allocation fails: those launches then convert as before.
-        e->row_image_state = 0;
-        if (max_nt >= 2 && (e->cfg.flags & MSR_CFG_NO_ROW_COPY)) {
-            e->row_image_state = 2;
-        } else if (max_nt >= 2) {
-            const size_t img_rows = (size_t)n_chunks + 512;
-            if ((herr = alloc(&e->gf_emb_f16, img_rows * MSR_DIM * 2)) != hipSuccess) {
-                (void)hipGetLastError();
-                e->gf_emb_f16 = nullptr;
-                e->row_image_state = 3;
-            } else {
-                HIP_TRY(e, msr_f16_rows(emb, n_chunks, (int64_t)img_rows, e->gf_emb_f16, st));
-                e->row_image_state = 1;
-            }
-        }
-        e->gf = GemmF32Index{e->tile_row, n_tiles, e->n_cus, groups, e->gf_inv_pad, e->gf_qimg, e->gf_tmax_t, e->gf_tmax, stride,
-                             e->gf_thr, e->gf_thr2, e->gf_flag, e->gf_wvbuf,
-                             GF_WV_CAP, e->gf_wv_count, e->gf_pairs, e->gf_pair_n, e->gf_err, e->gf_margin, e->gf_cand_doc,
-                             e->gf_cand_score, e->gf_cand_chunk, e->gf_cand_n, max_nt, e->gf_emb_tiled,
-                             e->gf_emb_tiled ? e->tile_trow : nullptr, e->gf_emb_f16};
-        e->gf_ok = true;
-    }
-    e->have_chunks = true;
-    return MSR_OK;
+    ChunkLayout L;
+    int rc = chunk_layout(e, h_off, n_chunks, n_docs, L);
+    if (rc) return rc;                                       // (a malformed doc_off: the previous binding keeps serving)
+    // from here on the previous binding is being replaced -- its tables, the bf16 image, a pending msr_dense_topk_begin: the
+    // engine counts as unbound until this call succeeds
+    drop_chunks(e);
+    rc = ensure_score_rows(e, n_docs);
+    if (!rc) rc = bind_chunk_tables(e, emb, n_chunks, doc_off, n_docs, inv_norm, L, st);
+    if (!rc) rc = bind_stream_pass(e, L, st);
+    if (rc) drop_chunks(e);                                  // (nothing half-built stays behind)
+    e->have_chunks = rc == MSR_OK;
+    return rc;
 }
 
 extern "C" int msr_unbind(msr_engine* e) {
     if (!e) return MSR_ERR_INVALID;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    // the engine counts as unbound before anything is freed
-    e->have_postings = e->have_chunks = false;
-    e->have_tokens = false; e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
-    e->split_pending = 0;
-    e->bm25 = Bm25Index{};
-    e->dense = e->dense_bf16 = DenseIndex{};
+    drop_postings(e);
+    drop_chunks(e);
     e->url_group = nullptr; e->url_group_n = 0;
     e->doc_domain = nullptr; e->doc_domain_n = 0;
-    // tables built at bind and scratch sized by the corpus (the per-query scratch of msr_create stays)
-    for (void** p : {(void**)&e->chunk_doc, &e->emb_presplit, &e->row_meta, (void**)&e->inv_norm_own, (void**)&e->span_doc,
-                     (void**)&e->wspan_doc, (void**)&e->wspan12_doc, &e->emb_bf16, &e->score_rows, (void**)&e->bm_heavy_id,
-                     &e->bm_post, (void**)&e->bm_dense_id, (void**)&e->bm_dense, (void**)&e->bm_tile_off,
-                     (void**)&e->bm_cand_doc, (void**)&e->bm_cand_n, (void**)&e->bm_win}) {
-        free_dev(e, *p);
-        *p = nullptr;
-    }
-    e->score_rows_bytes = e->bm_cand_bytes = 0;
-    free_gemm(e);
-    free_gf(e);
-    e->row_copy_state = e->row_image_state = 0;
     e->last_dense_width = 0;
+    // scratch sized by the corpus (the per-query scratch of msr_create stays)
+    e->mem_corpus.release();
+    e->score_rows_bytes = e->bm_cand_bytes = 0;
     return MSR_OK;
 }
 
@@ -782,9 +741,8 @@ extern "C" int msr_dense_path(const msr_engine* e) { return e ? e->last_dense_wi
 
 extern "C" int64_t msr_owned_bytes(const msr_engine* e) {
     if (!e) return -1;
-    int64_t total = 0;
-    for (const auto& kv : e->owned) total += (int64_t)kv.second;
-    return total;
+    return (int64_t)(e->mem_engine.bytes() + e->mem_corpus.bytes() + e->mem_postings.bytes() + e->mem_chunks.bytes() +
+                     e->mem_bf16.bytes());
 }
 
 extern "C" int msr_row_copy_state(const msr_engine* e) { return e ? e->row_copy_state : -1; }
@@ -928,10 +886,7 @@ extern "C" int msr_bind_tokens(msr_engine* e, const int64_t* tok_off, const int3
                     (long long)e->bm25.n_docs);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    if (!e->sim_flag) {
-        hipError_t herr = eng_malloc(e, (void**)&e->sim_flag, 64);
-        if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "check flag: %s", hipGetErrorString(herr));
-    }
+    if (!e->sim_flag) ALLOC(e, e->mem_engine, e->sim_flag, 64);
     // one kernel checks the offsets and the ids; it reads tok_off[0 .. n_docs] and tok_ids[0 .. n_tokens), which the caller
     // vouches for, and never follows an offset into tok_ids, so malformed offsets cannot send a read out of bounds
     int32_t flag = 0;
@@ -1120,13 +1075,31 @@ static bool dense_sweep_wide(const msr_engine* e, int max_chunks_per_doc) {
            e->dense.wide_ok && max_chunks_per_doc == 0;
 }
 
+// The streaming pass (msr_gemm_f32.hip) serves calls of more than 64 queries asking for k documents
 static bool dense_stream_ok(const msr_engine* e, int k) {
     return dense_sweep_wide(e, 0) && e->gf_ok && e->dense.variant == 14 && e->gf.n_tiles >= 2 * k;
 }
 
+// ... this many queries per call: more than 128 queries run in groups of 256, so with an odd number of 128-query groups only
+// the even part is usable
+static int dense_stream_cap(const msr_engine* e) { return e->gf.max_groups >= 2 ? (e->gf.max_groups & ~1) * 128 : 128; }
+
+// Event pairs of a timed two-pass launch: {start, stop} of the sample pass (kind 3), then of the pass of `kind`.  nullptr: not
+// timed (every launch gets its own pair out of a ring of EV_RING; later launches are not recorded).  pass_events_used() after
+// the launch.
+static hipEvent_t* pass_events(msr_engine* e, int kind, hipEvent_t ev[4]) {
+    if (!e->timing || e->ev_count[kind] >= msr_engine::EV_RING || e->ev_count[3] >= msr_engine::EV_RING) return nullptr;
+    ev[0] = e->ev_start[3][e->ev_count[3]]; ev[1] = e->ev_stop[3][e->ev_count[3]];
+    ev[2] = e->ev_start[kind][e->ev_count[kind]]; ev[3] = e->ev_stop[kind][e->ev_count[kind]];
+    return ev;
+}
+static void pass_events_used(msr_engine* e, int kind, const hipEvent_t* ev) {
+    if (ev) { e->ev_count[kind]++; e->ev_count[3]++; }
+}
+
 extern "C" int msr_dense_split_max(const msr_engine* e, int32_t k) {
     if (!e || !e->have_chunks || k < 1 || k > e->cfg.max_k || !dense_stream_ok(e, k)) return 0;
-    return e->gf.max_groups >= 2 ? (e->gf.max_groups & ~1) * 128 : 128;
+    return dense_stream_cap(e);
 }
 
 extern "C" int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t k_part, float* out_part,
@@ -1141,17 +1114,13 @@ extern "C" int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_que
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_prep_queries(q, n_queries, e->gf_qn, (n_queries + 63) / 64 * 64, st));
-    HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, 16 * 4, st));
-    hipEvent_t ev[4];
-    const bool timed = e->timing && e->ev_count[0] < msr_engine::EV_RING && e->ev_count[3] < msr_engine::EV_RING;
-    if (timed) {
-        ev[0] = e->ev_start[3][e->ev_count[3]]; ev[1] = e->ev_stop[3][e->ev_count[3]];
-        ev[2] = e->ev_start[0][e->ev_count[0]]; ev[3] = e->ev_stop[0][e->ev_count[0]];
-    }
+    HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
+    hipEvent_t ev_buf[4];
+    hipEvent_t* ev = pass_events(e, 0, ev_buf);
     int width = 0;
-    HIP_TRY(e, msr_gemm_f32_pass(e->gf, e->dense, e->gf_qn, n_queries, k, k_part, out_part, timed ? ev : nullptr, &width, st));
+    HIP_TRY(e, msr_gemm_f32_pass(e->gf, e->dense, e->gf_qn, n_queries, k, k_part, out_part, ev, &width, st));
     e->last_dense_width = width;
-    if (timed) { e->ev_count[0]++; e->ev_count[3]++; }
+    pass_events_used(e, 0, ev);
     e->split_pending = n_queries;
     return MSR_OK;
 }
@@ -1160,7 +1129,7 @@ extern "C" int msr_dense_topk_end(msr_engine* e, int32_t n_queries, int32_t k, c
                                   float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
     if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk_end: chunks not bound");
-    if (e->split_pending != n_queries || n_queries <= 0)
+    if (!e->gf_ok || e->split_pending != n_queries || n_queries <= 0)
         return fail(e, MSR_ERR_INVALID, "msr_dense_topk_end: no matching msr_dense_topk_begin (pending %d, got %d)", e->split_pending, n_queries);
     if (!out_doc || !out_score || !out_n || k < 1 || k > e->cfg.max_k) return fail(e, MSR_ERR_INVALID, "msr_dense_topk_end: bad argument");
     e->split_pending = 0;
@@ -1226,30 +1195,24 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
     // one sweep of E serves up to 32 queries (wave-streaming kernel) or 64 (K-split kernel); batches of more than 64
     // queries run as a GEMM over the f32 rows, 128 queries per pass (msr_gemm_f32.hip), when the corpus allows it
     const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
-    const bool gemm = wide && e->gf_ok && e->dense.variant == 14 && e->gf.n_tiles >= 2 * k;
+    const bool gemm = wide && dense_stream_ok(e, k);
     e->last_dense_width = gemm && n_queries > 64 ? 0 : (wide ? 64 : 32);       // (the streaming path reports its own width below)
     int q0 = 0;
     while (q0 < n_queries) {
         const int left = n_queries - q0;
         if (gemm && left > 64) {
-            // more than 128 queries run in groups of 256: with an odd number of 128-query groups only the even part is usable
-            const int cap = e->gf.max_groups >= 2 ? (e->gf.max_groups & ~1) * 128 : 128;
-            const int nq = std::min(cap, left);
+            const int nq = std::min(dense_stream_cap(e), left);
             // (normalised once for the pass AND for the gated sweeps behind it: zero rows up to the last slice's 64)
             HIP_TRY(e, msr_prep_queries(q + (int64_t)q0 * MSR_DIM, nq, e->gf_qn, (nq + 63) / 64 * 64, st));
-            HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, 16 * 4, st));
-            hipEvent_t ev[4];
-            const bool timed = e->timing && e->ev_count[0] < msr_engine::EV_RING && e->ev_count[3] < msr_engine::EV_RING;
-            if (timed) {
-                ev[0] = e->ev_start[3][e->ev_count[3]]; ev[1] = e->ev_stop[3][e->ev_count[3]];
-                ev[2] = e->ev_start[0][e->ev_count[0]]; ev[3] = e->ev_stop[0][e->ev_count[0]];
-            }
+            HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
+            hipEvent_t ev_buf[4];
+            hipEvent_t* ev = pass_events(e, 0, ev_buf);
             int width = 0;
             HIP_TRY(e, msr_gemm_f32_topk(e->gf, e->dense, e->gf_qn, nq, k, out_doc + (int64_t)q0 * k,
                                          out_score + (int64_t)q0 * k, out_chunk ? out_chunk + (int64_t)q0 * k : nullptr,
-                                         out_n + q0, e->gf_gate, timed ? ev : nullptr, &width, st));
+                                         out_n + q0, e->gf_gate, ev, &width, st));
             e->last_dense_width = std::max(e->last_dense_width, width);
-            if (timed) { e->ev_count[0]++; e->ev_count[3]++; }
+            pass_events_used(e, 0, ev);
             {
                 int rcf = dense_gated_fallback(e, nq, k, out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k,
                                                out_chunk ? out_chunk + (int64_t)q0 * k : nullptr, out_n + q0, st);
@@ -1293,24 +1256,9 @@ extern "C" int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_qu
 }
 
 // ---- K9: similar documents (msr_similar.hip) ---------------------------------------------------------------------------------
-// Grow-only scratch of these calls.
-static int sim_grow(msr_engine* e, void** p, size_t* have, size_t need, const char* what) {
-    if (need <= *have && *p) return MSR_OK;
-    free_dev(e, *p);
-    *p = nullptr;
-    *have = 0;
-    hipError_t herr = eng_malloc(e, p, need);
-    if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "%s (%zu bytes): %s", what, need, hipGetErrorString(herr));
-    *have = need;
-    return MSR_OK;
-}
-
 // 1 if some v[0..n) lies outside [0, hi) (device check, one synchronisation of the stream), 0 if none, < 0 on failure
 static int sim_out_of_range(msr_engine* e, const int32_t* v, int64_t n, int64_t hi, hipStream_t st) {
-    if (!e->sim_flag) {
-        hipError_t herr = eng_malloc(e, (void**)&e->sim_flag, 64);
-        if (herr != hipSuccess) return fail(e, MSR_ERR_NOMEM, "check flag: %s", hipGetErrorString(herr));
-    }
+    if (!e->sim_flag) ALLOC(e, e->mem_engine, e->sim_flag, 64);
     int32_t flag = 0;
     HIP_TRY(e, hipMemsetAsync(e->sim_flag, 0, sizeof(int32_t), st));
     HIP_TRY(e, msr_check_range(v, n, hi, e->sim_flag, st));
@@ -1382,9 +1330,9 @@ extern "C" int msr_dense_topk_grouped(msr_engine* e, const float* q, int32_t n_r
     const int kk = k + max_excl;
     const size_t L = (size_t)n_rows * kk;
     const size_t lists_bytes = (L * 3 + 2 * (size_t)n_rows + 64) * 4;
-    int rc = sim_grow(e, &e->sim_lists, &e->sim_lists_bytes, lists_bytes, "grouped lists");
+    int rc = grow(e, e->mem_engine, &e->sim_lists, &e->sim_lists_bytes, lists_bytes, "grouped lists");
     if (rc) return rc;
-    rc = sim_grow(e, &e->sim_over, &e->sim_over_bytes, 2 * L * 16 + 64, "grouped merge records");
+    rc = grow(e, e->mem_engine, &e->sim_over, &e->sim_over_bytes, 2 * L * 16 + 64, "grouped merge records");
     if (rc) return rc;
     int32_t* l_doc = (int32_t*)e->sim_lists;
     float* l_score = (float*)(l_doc + L);
@@ -1424,33 +1372,25 @@ static constexpr int BT_SLICE = 128;                        // most queries per 
 static constexpr int GM_SLICE = 1024;                       // queries per pass of the GEMM path (4 query tiles of 256)
 static constexpr int GM_WV_CAP = 16384;                     // emitted entries per wave (x 8 waves x #CU x 16 B = 512 MB at 256 CUs)
 
-extern "C" int msr_enable_bf16(msr_engine* e, void* stream) {
-    if (!e) return MSR_ERR_INVALID;
-    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_enable_bf16: chunks not bound");
-    if (e->cfg.scan_layout != 0) return fail(e, MSR_ERR_INVALID, "msr_enable_bf16: needs the row-major layout");
-    if (e->emb_bf16) return MSR_OK;
-    hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(e, hipSetDevice(e->cfg.device));
-    hipError_t herr;
+// The bf16 image of the bound rows, the sweeps' tables and, when the corpus has the row tiles for it, the GEMM path.
+static int build_bf16(msr_engine* e, hipStream_t st) {
     const int64_t C = e->dense.n_chunks;
     // The image holds the rows NORMALISED and then rounded to bf16 (so a score needs no per-row scale and the error bound
     // of msr_batch.hip is about unit vectors), padded with 512 zero rows: the GEMM reads 256 rows from any tile start.
     const int64_t n_pad = C + 512;
-    if ((herr = eng_malloc(e, &e->emb_bf16, (size_t)n_pad * MSR_DIM * 2)) != hipSuccess)
-        return fail(e, MSR_ERR_NOMEM, "bf16 embeddings (%zu bytes): %s", (size_t)n_pad * MSR_DIM * 2, hipGetErrorString(herr));
-    auto alloc = [&](void** p, size_t bytes) { return *p ? hipSuccess : eng_malloc(e, p, bytes); };
+    ALLOC(e, e->mem_bf16, e->emb_bf16, (size_t)n_pad * MSR_DIM * 2);
     const size_t QS = GM_SLICE;                             // the candidate scratch serves both the sweeps and the GEMM path
-    if ((herr = alloc((void**)&e->bt_top_doc, (size_t)BT_SLICE * MSR_MAX_K * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bt_top_score, (size_t)BT_SLICE * MSR_MAX_K * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bt_top_n, (size_t)BT_SLICE * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bt_cand_doc, QS * MSR_SEL_CAP * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bt_cand_score, QS * MSR_SEL_CAP * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bt_cand_chunk, QS * MSR_SEL_CAP * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bt_cand_n, QS * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bf_ones, (size_t)C * 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bf_err, 4)) != hipSuccess ||
-        (herr = alloc((void**)&e->bf_margin, QS * 4)) != hipSuccess)
-        return fail(e, MSR_ERR_NOMEM, "bf16 path scratch: %s", hipGetErrorString(herr));
+    // (the candidate scratch is the engine's, not the binding's: the first call allocates it, re-binds keep it)
+    if (!e->bt_top_doc) ALLOC(e, e->mem_engine, e->bt_top_doc, (size_t)BT_SLICE * MSR_MAX_K * 4);
+    if (!e->bt_top_score) ALLOC(e, e->mem_engine, e->bt_top_score, (size_t)BT_SLICE * MSR_MAX_K * 4);
+    if (!e->bt_top_n) ALLOC(e, e->mem_engine, e->bt_top_n, (size_t)BT_SLICE * 4);
+    if (!e->bt_cand_doc) ALLOC(e, e->mem_engine, e->bt_cand_doc, QS * MSR_SEL_CAP * 4);
+    if (!e->bt_cand_score) ALLOC(e, e->mem_engine, e->bt_cand_score, QS * MSR_SEL_CAP * 4);
+    if (!e->bt_cand_chunk) ALLOC(e, e->mem_engine, e->bt_cand_chunk, QS * MSR_SEL_CAP * 4);
+    if (!e->bt_cand_n) ALLOC(e, e->mem_engine, e->bt_cand_n, QS * 4);
+    ALLOC(e, e->mem_bf16, e->bf_ones, (size_t)C * 4);
+    ALLOC(e, e->mem_bf16, e->bf_err, 4);
+    ALLOC(e, e->mem_bf16, e->bf_margin, QS * 4);
     HIP_TRY(e, hipMemsetAsync(e->bt_cand_n, 0, QS * 4, st));
     HIP_TRY(e, msr_unit_bf16_rows(e->dense.emb, e->dense.inv_norm, C, n_pad, e->emb_bf16, e->bf_err, st));
     HIP_TRY(e, msr_fill_f32(e->bf_ones, C, 1.0f, st));
@@ -1458,36 +1398,44 @@ extern "C" int msr_enable_bf16(msr_engine* e, void* stream) {
     e->dense_bf16 = e->dense;
     e->dense_bf16.inv_norm = e->bf_ones;
     if (e->dense.wide_ok) {
-        if ((herr = alloc(&e->bf_row_meta, (size_t)(C + 16) * 8)) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "bf16 row meta: %s", hipGetErrorString(herr));
+        ALLOC(e, e->mem_bf16, e->bf_row_meta, (size_t)(C + 16) * 8);
         HIP_TRY(e, msr_pack_row_meta(e->chunk_doc, e->bf_ones, C, e->bf_row_meta, st));
         e->dense_bf16.row_meta = e->bf_row_meta;
     }
     // ---- GEMM path: needs the row tiles built at bind time (every document inside one 256-row tile) ----
-    const bool ok = e->tiles_ok;
     const int n_tiles = e->n_tiles;
     const int grid = e->n_cus / 8 * 8;
-    if (ok && n_tiles >= 64 && grid >= 32) {
+    if (e->tiles_ok && n_tiles >= 64 && grid >= 32) {
         const int stride = (n_tiles + 31) / 32 * 32;
-        if ((herr = alloc(&e->gm_qmat, (size_t)GM_SLICE * MSR_DIM * 2)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_qn, (size_t)GM_SLICE * MSR_DIM * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_tmax, (size_t)GM_SLICE * stride * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_tmax_t, (size_t)n_tiles * 2 * GM_SLICE * 4)) != hipSuccess ||     // [tile][query] (x 2: the diagnostic build's round-2 kernel stores two rows per tile)
-            (herr = alloc((void**)&e->gm_thr, (size_t)GM_SLICE * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_thr2, (size_t)GM_SLICE * 4)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_flag, (size_t)GM_SLICE * 4)) != hipSuccess ||
-            (herr = alloc(&e->gm_wgbuf, (size_t)grid * 8 * GM_WV_CAP * 16)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_wv_count, (size_t)grid * 8 * 4)) != hipSuccess ||
-            (herr = alloc(&e->gm_pairs, (size_t)GM_SLICE * msr_gemm_pair_cap() * 8)) != hipSuccess ||
-            (herr = alloc((void**)&e->gm_pair_n, (size_t)GM_SLICE * 4)) != hipSuccess)
-            return fail(e, MSR_ERR_NOMEM, "GEMM path scratch: %s", hipGetErrorString(herr));
-        HIP_TRY(e, hipMemsetAsync(e->gm_pair_n, 0, (size_t)GM_SLICE * 4, st));
-        e->gemm = GemmIndex{e->emb_bf16, e->tile_row, n_tiles, e->n_cus, GM_SLICE, e->gm_qmat, e->gm_tmax, stride,
-                            e->gm_tmax_t, e->gm_thr, e->gm_thr2, e->gm_flag, e->gm_wgbuf,
-                            GM_WV_CAP, e->gm_wv_count, e->gm_pairs, e->gm_pair_n};
+        GemmIndex& g = e->gemm;
+        g.emb_n = e->emb_bf16; g.tile_row = e->tile_row; g.n_tiles = n_tiles; g.n_cus = e->n_cus; g.max_queries = GM_SLICE;
+        g.tmax_stride = stride; g.wv_cap = GM_WV_CAP;
+        ALLOC(e, e->mem_bf16, g.qmat, (size_t)GM_SLICE * MSR_DIM * 2);
+        ALLOC(e, e->mem_bf16, e->gm_qn, (size_t)GM_SLICE * MSR_DIM * 4);
+        ALLOC(e, e->mem_bf16, g.tmax, (size_t)GM_SLICE * stride * 4);
+        ALLOC(e, e->mem_bf16, g.tmax_t, (size_t)n_tiles * 2 * GM_SLICE * 4);     // [tile][query] (x 2: the diagnostic build's round-2 kernel stores two rows per tile)
+        ALLOC(e, e->mem_bf16, g.thr, (size_t)GM_SLICE * 4);
+        ALLOC(e, e->mem_bf16, g.thr2, (size_t)GM_SLICE * 4);
+        ALLOC(e, e->mem_bf16, g.flag, (size_t)GM_SLICE * 4);
+        ALLOC(e, e->mem_bf16, g.wgbuf, (size_t)grid * 8 * GM_WV_CAP * 16);
+        ALLOC(e, e->mem_bf16, g.wv_count, (size_t)grid * 8 * 4);
+        ALLOC(e, e->mem_bf16, g.pairs, (size_t)GM_SLICE * msr_gemm_pair_cap() * 8);
+        ALLOC(e, e->mem_bf16, g.pair_n, (size_t)GM_SLICE * 4);
+        HIP_TRY(e, hipMemsetAsync(g.pair_n, 0, (size_t)GM_SLICE * 4, st));
         e->gemm_ok = true;
     }
     return MSR_OK;
+}
+
+extern "C" int msr_enable_bf16(msr_engine* e, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_enable_bf16: chunks not bound");
+    if (e->cfg.scan_layout != 0) return fail(e, MSR_ERR_INVALID, "msr_enable_bf16: needs the row-major layout");
+    if (e->emb_bf16) return MSR_OK;                          // (built whole: a failed build leaves nothing behind)
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    const int rc = build_bf16(e, (hipStream_t)stream);
+    if (rc) drop_bf16(e);                                    // a retry starts clean
+    return rc;
 }
 
 extern "C" int msr_tune(msr_engine* e, int32_t key, int32_t value) {
@@ -1507,6 +1455,8 @@ extern "C" int msr_dense_topk_bf16(msr_engine* e, const float* q, int32_t n_quer
                                    int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
     if (!e->have_chunks || !e->emb_bf16) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk_bf16: call msr_enable_bf16 first");
+    if (e->split_pending)                                    // (the two share the score rows and the select scratch)
+        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_bf16: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first");
     if (n_queries < 0 || k < 1 || k > e->cfg.max_k || max_chunks_per_doc < 0 || !q || !out_doc || !out_score || !out_n)
         return fail(e, MSR_ERR_INVALID, "msr_dense_topk_bf16: bad argument (k=%d, max_k=%d)", k, e->cfg.max_k);
     if (n_queries == 0) return MSR_OK;
@@ -1521,16 +1471,12 @@ extern "C" int msr_dense_topk_bf16(msr_engine* e, const float* q, int32_t n_quer
             const int nq = std::min(GM_SLICE, n_queries - q0);
             HIP_TRY(e, msr_prep_queries(q + (int64_t)q0 * MSR_DIM, nq, e->gm_qn, nq, st));
             HIP_TRY(e, msr_batch_margin(e->gm_qn, nq, e->bf_err, e->bf_margin, st));
-            hipEvent_t ev[4];
-            const bool timed = e->timing && e->ev_count[2] < msr_engine::EV_RING && e->ev_count[3] < msr_engine::EV_RING;
-            if (timed) {
-                ev[0] = e->ev_start[3][e->ev_count[3]]; ev[1] = e->ev_stop[3][e->ev_count[3]];
-                ev[2] = e->ev_start[2][e->ev_count[2]]; ev[3] = e->ev_stop[2][e->ev_count[2]];
-            }
+            hipEvent_t ev_buf[4];
+            hipEvent_t* ev = pass_events(e, 2, ev_buf);
             // (candidates with the runs of their emitted rows: bt_cand_chunk carries first | len << 13 in, the arg-max row out)
             HIP_TRY(e, msr_gemm_candidates(e->gemm, e->dense, e->gm_qn, nq, k, e->bf_margin, e->bt_cand_doc, e->bt_cand_chunk,
-                                           e->bt_cand_n, timed ? ev : nullptr, st));
-            if (timed) { e->ev_count[2]++; e->ev_count[3]++; }
+                                           e->bt_cand_n, ev, st));
+            pass_events_used(e, 2, ev);
             HIP_TRY(e, msr_batch_rescore_rows(e->dense, e->gm_qn, nq, k, (const int32_t*)e->gemm.pairs, 2, msr_gemm_pair_cap(),
                                               e->bt_cand_doc, e->bt_cand_score, e->bt_cand_chunk, e->bt_cand_n,
                                               out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k,

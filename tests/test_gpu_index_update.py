@@ -2,6 +2,7 @@
 bm25_add_token_ids on cuda, and a live engine / Retriever rebound to the grown index (DeviceEngine.rebind,
 Retriever.update_index) against fresh ones built on the from-scratch union."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -10,7 +11,7 @@ import torch
 from index_cases import maps, side
 from msretr import _abi
 from msretr.chunk_index import ChunkTable, attach_chunks
-from msretr.engine import DeviceEngine
+from msretr.engine import DeviceEngine, _ptr
 from msretr.index import DIM, _np
 from msretr.index_build import bm25_add_token_ids, bm25_index_from_token_ids, merge_postings
 
@@ -261,4 +262,75 @@ def test_rebind_between_split_halves_and_failed_rebind():
         assert ei.value.code == -2                            # MSR_ERR_NOT_BOUND
     eng.rebind(union)
     assert eng.dense_topk(qv[:2], k=10)[3].cpu().tolist() == [10, 10]
+    eng.close()
+
+
+# ------------------------------------------------------------------------------- what the engine owns, and what is bound
+@functools.lru_cache(maxsize=None)
+def appended():
+    """corpus("appended") built once for the tests below, and 100 query vectors near chunks of its new documents."""
+    base, grown, union, t1, rng = corpus("appended")
+    return base, grown, queries(rng, union, t1, 100)[1]
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_owned_bytes_after_unbind_and_rebind(bf16):
+    """msr_owned_bytes as the ledger of the engine's lifetime groups: a second msr_unbind frees nothing more, and an engine
+    re-bound to an index owns exactly what a fresh engine on that index owns."""
+    base, grown, qv = appended()
+    eng = DeviceEngine(base, max_queries=256)
+    if bf16:
+        eng.enable_bf16()
+    built = eng.owned_bytes()
+    eng.dense_topk(qv, k=10)
+    eng.rebind(grown)
+    fresh = DeviceEngine(grown, max_queries=256)
+    if bf16:
+        fresh.enable_bf16()
+    assert eng.owned_bytes() == fresh.owned_bytes()
+    assert same(eng.dense_topk(qv, k=10), fresh.dense_topk(qv, k=10))
+    fresh.close()
+    torch.cuda.synchronize()
+    eng._check(eng.lib.msr_unbind(eng.handle))
+    unbound = eng.owned_bytes()
+    assert 0 < unbound < built
+    eng._check(eng.lib.msr_unbind(eng.handle))
+    assert eng.owned_bytes() == unbound
+    eng.rebind(base)
+    assert eng.owned_bytes() == built
+    eng.close()
+
+
+def test_raw_rebind_cancels_a_pending_begin():
+    """msr_bind_chunks through the C ABI between the two halves of a split dense call, without an msr_unbind: the bind drops the
+    old binding with its pending begin, so the end is refused (it would read the freed scratch of the pass) and the engine
+    serves the new binding like a fresh one."""
+    base, _, qv = appended()
+    eng = DeviceEngine(base, max_queries=256)
+    assert eng.dense_split_max(10) >= 100
+    eng.dense_begin(qv, k=10)
+    torch.cuda.synchronize()
+    t = eng._t
+    eng._check(eng.lib.msr_bind_chunks(eng.handle, _ptr(t["emb"]), int(t["emb"].shape[0]), _ptr(t["doc_off"]), base.n_docs,
+                                       _ptr(t["inv_norm"]), eng._stream()))
+    with pytest.raises(_abi.MsrError) as ei:
+        eng.dense_end(100, k=10)
+    assert ei.value.code == -1                                # MSR_ERR_INVALID: no matching begin
+    fresh = DeviceEngine(base, max_queries=256)
+    assert eng.owned_bytes() == fresh.owned_bytes()
+    assert same(eng.dense_topk(qv, k=10), fresh.dense_topk(qv, k=10))
+    fresh.close()
+    eng.close()
+
+
+def test_batched_call_is_refused_while_a_begin_is_pending():
+    base, _, qv = appended()
+    eng = DeviceEngine(base, max_queries=256)
+    eng.enable_bf16()
+    want = eng.dense_topk(qv, k=10)
+    eng.dense_begin(qv, k=10)
+    with pytest.raises(_abi.MsrError) as ei:
+        eng.dense_topk_batched(qv, k=10)
+    assert ei.value.code == -1                                # MSR_ERR_INVALID: the two share scratch
+    assert same(eng.dense_end(100, k=10), want)                # the pending call is intact
     eng.close()
