@@ -1546,8 +1546,8 @@ static int rerank_gather_impl(msr_engine* e, const char* fn, const float* q, int
         const bool blocked = q_per_block < n_queries;
         float* co = blocked ? out_cos + (int64_t)(q0 / q_per_block) * block_stride : out_cos + o * MSR_RERANK_MAX_CHUNKS;
         int32_t* mo = blocked ? out_meta + (int64_t)(q0 / q_per_block) * block_stride : out_meta + o * 3;
-        RerankRecords rr{nullptr, nullptr, nullptr, 0};
-        if (rec) rr = RerankRecords{rec->out, rec->q_base + q0, rec->blk_off + (int64_t)q0 * ((max_cand + 7) / 8), rec->capacity};
+        RerankRecords rr{nullptr, nullptr, nullptr, 0, 0};
+        if (rec) rr = RerankRecords{rec->out, rec->q_base + q0, rec->blk_off + (int64_t)q0 * ((max_cand + 7) / 8), rec->capacity, q0};
         HIP_TRY(e, msr_rerank_gather(e->dense, e->url_group, e->rr_qn, nq, cand_doc + o, cand_n + q0, max_cand, doc_base,
                                      row_base, max_chunks, co, mo, blocked ? q_per_block : nq, blocked ? block_stride : 0, rr, st));
     }
@@ -1599,7 +1599,7 @@ extern "C" int msr_rerank_gather_records(msr_engine* e, const float* q, int32_t 
     if (!e) return MSR_ERR_INVALID;
     if (!send_base || !send_blk || !out_records || capacity_records < 0)
         return fail(e, MSR_ERR_INVALID, "msr_rerank_gather_records: bad argument");
-    const RerankRecords rec{out_records, send_base, send_blk, capacity_records};
+    const RerankRecords rec{out_records, send_base, send_blk, capacity_records, 0};
     return rerank_gather_impl(e, "msr_rerank_gather_records", q, n_queries, cand_doc, cand_n, max_cand, doc_base, row_base,
                               max_chunks, nullptr, nullptr, n_queries > 0 ? n_queries : 1, 0, stream, &rec);
 }

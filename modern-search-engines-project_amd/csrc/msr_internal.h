@@ -297,6 +297,7 @@ struct RerankRecords {
     const int32_t* q_base;
     const int32_t* blk_off;
     int64_t capacity;            // records `out` holds: a record at or past it is dropped (a caller's sizing error must not write outside)
+    int q_first;                 // number of the launch's first query within the call (word 14 of a record is the call's query)
 };
 // (A) cosines + (rows, url group, first row) of the candidates this shard owns; zeros for the others.
 hipError_t msr_rerank_gather(const DenseIndex& ix, const int32_t* url_group, const float* qn, int nq,

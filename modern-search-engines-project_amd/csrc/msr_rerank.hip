@@ -84,7 +84,7 @@ __global__ __launch_bounds__(64) void rerank_cos_kernel(DenseIndex ix, const int
             int32_t* r = rec.out + at * MSR_RERANK_RECORD_WORDS;
             out = (float*)(r + 4);
             mt = r + 1;
-            if (lane == 0) { r[0] = m; r[14] = q; r[15] = 0; }
+            if (lane == 0) { r[0] = m; r[14] = rec.q_first + q; r[15] = 0; }
         }
         const int64_t ds = ix.doc_off[d];
         int64_t de = ix.doc_off[d + 1];

@@ -179,6 +179,7 @@ class ShardedEngine:
         assert a2a in ("records", "blocks")
         self.a2a = a2a
         self._bounds = None
+        self._split = {}                                  # k -> the dense split size the ranks agreed on (_agreed_split)
 
     # ------------------------------------------------------------------ exchange helpers
     def _exchange(self, Q, k1, k2, device):
@@ -202,6 +203,27 @@ class ShardedEngine:
             b = torch.cat([every[:, 0], every[-1:, 1]]).to(torch.int32).to(device) if ok and int(every[-1, 1]) < 2 ** 31 else None
             self._bounds = (b,)
         return self._bounds[0]
+
+    def _agreed_split(self, k, device):
+        """The largest number of queries EVERY rank's engine takes in one dense_begin for this k: ONE all-reduce MIN of
+        dense_split_max(k), once per (k, binding), on the device the other collectives use.  dense_split_max follows the
+        shard's own data and the engine's max_queries; a rank deciding by its own value would issue other collectives than
+        its peers (none where it is 0, more where it is smaller) and the run would hang.  0: no rank splits.  A collective:
+        every rank gets here at the same point of search(), whatever its own value."""
+        if k not in self._split:
+            e = self.engine
+            mine = int(e.dense_split_max(k)) if hasattr(e, "dense_split_max") else 0
+            t = torch.tensor([max(0, min(mine, 2 ** 31 - 1))], dtype=torch.int64, device=device)
+            dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
+            self._split[k] = int(t.item())
+        return self._split[k]
+
+    def invalidate(self):
+        """Forget what the ranks agreed on for the bound shards (the shard bounds of the rerank exchange, the dense split
+        size).  ALL ranks call this after ANY rank's engine was rebound (DeviceEngine.rebind) and before the next search: the
+        values are agreed again there by collectives, which every rank has to take part in."""
+        self._bounds = None
+        self._split = {}
 
     def _allgather_bytes(self, parts):
         """parts: list of tensors -> list (per rank) of lists of tensors with the same shapes/dtypes.  One collective:
@@ -239,8 +261,10 @@ class ShardedEngine:
         beside = beside or (lambda: None)
         Q = int(qvec.shape[0]) if hasattr(qvec, "shape") else len(qvec)
         split = 0
-        if self.world > 1 and not dense_batched and max_chunks_per_doc == 0 and hasattr(e, "dense_split_max"):
-            split = e.dense_split_max(k)
+        if self.world > 1 and not dense_batched and max_chunks_per_doc == 0:
+            # (agreed by all ranks, and <= this engine's own limit: the same collectives on every rank, pieces dense_begin takes)
+            dev = getattr(e, "device", None) or (qvec.device if torch.is_tensor(qvec) else "cpu")
+            split = self._agreed_split(k, dev)
         min_q = getattr(e, "dense_split_min", 65)             # (the device engine splits calls of more than 64 queries)
         if split <= 0 or Q < min_q:
             dense = e.dense_topk_batched if dense_batched else e.dense_topk

@@ -4,6 +4,7 @@ its dense form).  The compute is the oracle (tests/oracle_engine.py); what is un
 CorpusIndex.shard."""
 import os
 import sys
+from datetime import timedelta
 
 import numpy as np
 import pytest
@@ -131,6 +132,101 @@ def test_three_ranks_with_fewer_queries_than_ranks_and_a_ragged_block():
                         assert a.shape == b.shape and np.allclose(a, b, rtol=0, atol=2e-6), (r, nq, key)
                     else:
                         assert a.shape == b.shape and np.array_equal(a, b), (r, nq, key, j)
+
+
+# ---- ranks whose engines do not agree on how to split the dense call ---------------------------------------------------------
+# DeviceEngine.dense_split_max follows the shard's data (tiles, document lengths, row norms) and the engine's max_queries; the
+# ranks have to agree on ONE value before any of them decides whether, and in which pieces, to take the dense stage through
+# dense_begin / all-reduce MIN / dense_end.  Every rank's stand-in gets its own dense_split_max here.  A disagreement shows as
+# a gloo time-out (15 s: the process group's limit in these tests), not as a wrong list.
+_BIG = 1 << 20
+#            name              dense_split_max per rank  (then, after invalidate)  min_q  begin_calls  plain dense_topk calls
+_SPLIT_CASES = [
+    ("one_rank_cannot",       ((_BIG, 0, _BIG),),                                  1,     (0,),        (1,)),
+    ("agreed_2_pieces_2_2_1", ((_BIG, 3, 2),),                                     1,     (3,),        (0,)),
+    ("agreed_2_short_last",   ((_BIG, 3, 2),),                                     2,     (2,),        (1,)),
+    ("uniform_4_short_last",  ((4, 4, 4),),                                        2,     (1,),        (1,)),
+    ("rebound_0_then_8",      ((0, 0, 0), (8, 8, 8)),                              1,     (0, 1),      (1, 0)),
+]
+
+
+def _run_split(rank, world, port, ret, phases, min_q):
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=15))
+    try:
+        from msretr.distributed import ShardedEngine
+        from oracle_engine import OracleEngine
+
+        class Engine(OracleEngine):                         # this rank's own answer; counts the calls of either kind
+            dense_split_min = min_q
+            split_max = phases[0][rank]
+            begin_calls = plain_calls = 0
+            in_begin = False
+
+            def dense_split_max(self, k=100):
+                return self.split_max
+
+            def dense_topk(self, qvec, k=100, max_chunks_per_doc=0, want_chunk=True):
+                self.plain_calls += 0 if self.in_begin else 1
+                return super().dense_topk(qvec, k=k, max_chunks_per_doc=max_chunks_per_doc, want_chunk=want_chunk)
+
+            def dense_begin(self, qvec, k=100, k_part=None):
+                assert len(qvec) <= self.split_max, "a piece larger than this engine takes"
+                self.in_begin = True
+                try:
+                    return super().dense_begin(qvec, k=k, k_part=k_part)
+                finally:
+                    self.in_begin = False
+
+        ix, terms, qvec = _corpus()
+        sh = ix.shard(rank, world)
+        se = ShardedEngine(Engine(sh), sh.doc_base, sh.row_base)
+        res = []
+        for i, phase in enumerate(phases):
+            if i:                                           # "any rank's rebind": every rank drops what was agreed
+                se.engine.split_max = phase[rank]
+                se.invalidate()
+            b0, p0 = se.engine.begin_calls, se.engine.plain_calls
+            out = se.search([sh.term_ids(t) for t in terms], qvec, k1=120, k2=30)
+            r = {k: [x.numpy() for x in v] for k, v in out.items()}
+            r["begin_calls"], r["plain_calls"] = se.engine.begin_calls - b0, se.engine.plain_calls - p0
+            res.append(r)
+        assert se._bounds[0] is not None
+        ret[rank] = res
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("case", _SPLIT_CASES, ids=[c[0] for c in _SPLIT_CASES])
+def test_three_ranks_agree_on_the_dense_split(case):
+    """Five queries on three ranks whose engines answer dense_split_max differently: the lists of every rank are the unsharded
+    ones, and every rank took the dense stage through the SAME calls (the pieces follow the smallest answer; nobody splits
+    when one rank cannot).  Without the agreement the ranks issue different collectives and every rank ends in gloo's
+    `Timed out waiting 15000ms for recv/send operation`."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from msretr.distributed import ShardedEngine
+    from oracle_engine import OracleEngine
+    name, phases, min_q, begins, plains = case
+    world = 3
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    port = 33000 + os.getpid() % 2000 + 3 * [c[0] for c in _SPLIT_CASES].index(name)
+    mp.spawn(_run_split, args=(world, port, ret, phases, min_q), nprocs=world, join=True)
+    ix, terms, qvec = _corpus()
+    ref = ShardedEngine(OracleEngine(ix), 0, 0).search([ix.term_ids(t) for t in terms], qvec, k1=120, k2=30)
+    ref = {k: [x.numpy() for x in v] for k, v in ref.items()}
+    for r in range(world):
+        assert len(ret[r]) == len(phases)
+        for i, got in enumerate(ret[r]):
+            assert (got["begin_calls"], got["plain_calls"]) == (begins[i], plains[i]), (r, i)
+            for key in ("bm25", "dense", "rerank"):
+                for j, (a, b) in enumerate(zip(got[key], ref[key])):
+                    if key == "dense" and j == 1:            # (the stand-in's BLAS product: see the test above)
+                        assert a.shape == b.shape and np.allclose(a, b, rtol=0, atol=2e-6), (r, i, key)
+                    else:
+                        assert a.shape == b.shape and np.array_equal(a, b), (r, i, key, j)
 
 
 def test_shard_partition_is_exact():
