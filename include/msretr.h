@@ -35,17 +35,18 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 13        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 14        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
                                      tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets;
-                                     13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets */
+                                     13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
 #define MSR_RERANK_MAX_CHUNKS 10  /* reranker_api.py:58 */
 #define MSR_TERMSET_SPAN_DOCS 8192 /* msr_term_sets: consecutive documents one work item of its kernel owns (a multiple of 1024) */
-#define MSR_PHRASE_MAX_TERMS 16    /* msr_phrase_sets: most term ids a phrase may hold */
+#define MSR_PHRASE_MAX_TERMS 16    /* msr_phrase_sets / msr_proximity_sets: most term ids a row may hold */
+#define MSR_PROX_MAX_SPAN 64       /* msr_proximity_sets: the widest window, in tokens */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -252,6 +253,31 @@ int msr_bind_tokens(msr_engine* e, const int64_t* tok_off, const int32_t* tok_id
 int msr_phrase_sets(msr_engine* e, int32_t n_rows, const int32_t* phrase_off, const int32_t* phrase_terms,
                     const uint32_t* cand_bits, int32_t n_cand, int64_t cand_stride, const int32_t* row_cand,
                     uint32_t* out_bits, int64_t out_stride, void* stream);
+
+/* Proximity search: words within a window of the forward index.  Row r is
+ *   (p[0 .. L), span, ordered): p = phrase_terms[phrase_off[r] .. phrase_off[r + 1]) as in msr_phrase_sets, span = row_span[r],
+ *   ordered = row_ordered[r] != 0 (int32 [n_rows] each), with 1 <= L <= MSR_PHRASE_MAX_TERMS and 1 <= span <=
+ *   MSR_PROX_MAX_SPAN.  Row r of out_bits becomes { d in cand(r) : document d matches row r }, document d being the sequence
+ *   tok[d][0 .. len).
+ *   ORDERED: d matches iff there are positions i_0 < i_1 < ... < i_{L-1} inside d with tok[d][i_j] == p[j] for every j and
+ *   i_{L-1} - i_0 + 1 <= span.  A repeated id needs as many different positions; span == L is exactly msr_phrase_sets'
+ *   phrase; span < L matches nothing.
+ *   ANY ORDER: let T be the set of distinct ids of p; d matches iff there is one position per id of T, all inside d, with
+ *   max - min + 1 <= span.  A repeated id counts once; |T| == 1 is term containment; span < |T| matches nothing.
+ *   BOTH: positions never leave the document (a match never uses tokens of two documents); an empty document matches
+ *   nothing.  A row with L < 1, L > MSR_PHRASE_MAX_TERMS, an id outside [0, n_terms), span < 1 or span > MSR_PROX_MAX_SPAN is
+ *   written EMPTY (by the kernel, no host round trip).  cand(r) follows the row_cand / n_cand rules of msr_phrase_sets.
+ *   Layout and write contract as msr_term_sets / msr_phrase_sets: every word [0, ceil(n_docs / 32)) of every row is written,
+ *   bits at or above n_docs are 0, words [ceil(n_docs / 32), out_stride) are not touched; repeated calls give the same bytes;
+ *   the call only enqueues (offsets, spans and modes are read on the device), no engine scratch; out_bits must not alias
+ *   cand_bits.  Refused before any launch, outputs untouched: MSR_ERR_NOT_BOUND without tokens; MSR_ERR_INVALID for what
+ *   msr_phrase_sets refuses, and for a NULL row_span or row_ordered with n_rows > 0.  n_rows == 0 succeeds and launches
+ *   nothing.  Cost per row: as msr_phrase_sets (every token of a candidate document is read once, 4 bytes, until the first
+ *   match). */
+int msr_proximity_sets(msr_engine* e, int32_t n_rows, const int32_t* phrase_off, const int32_t* phrase_terms,
+                       const int32_t* row_span, const int32_t* row_ordered,
+                       const uint32_t* cand_bits, int32_t n_cand, int64_t cand_stride, const int32_t* row_cand,
+                       uint32_t* out_bits, int64_t out_stride, void* stream);
 
 /* msr_combine_sets: out[r] = AND of in[s] for s in and_rows[and_off[r] .. and_off[r + 1])  AND NOT  OR of in[s] for s in
  *   not_rows[not_off[r] .. not_off[r + 1]), rows of in_bits (n_in rows in_stride words apart) in the layout above.  An empty

@@ -11,7 +11,7 @@ from typing import Callable, List, Optional, Sequence, Union
 
 from .engine import DeviceEngine
 from .index import CorpusIndex
-from .text import parse_operators, parse_phrases, simple_tokenize
+from .text import Near, parse_operators, parse_phrases, parse_proximity, simple_tokenize
 
 
 class BM25:
@@ -71,16 +71,21 @@ class BM25:
 
     # -- the reference's method ------------------------------------------------------------------------
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
-               must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None):
+               must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None,
+               proximity: bool = False):
         """operators=True: `+word` / `-word` tokens of the query are required / excluded words (text.parse_operators; the
         query is taken as it is -- no city is appended here); must / must_not: further term strings (or ids) every result
         must / must not contain.  Both restrict the documents on the device (DeviceEngine.term_sets), inside `within`.
         phrases=True: `"a b"` / `-"a b"` in the query are required / excluded phrases (text.parse_phrases, before the
         operators); must_phrases / must_not_phrases: further phrases, each a string (tokenised like the query) or a list of
         term strings (or ids).  A result holds the phrase's terms next to each other, in order, in its indexed token stream
-        (DeviceEngine.phrase_sets; needs a forward index, index_build.attach_tokens); scores are unchanged."""
+        (DeviceEngine.phrase_sets; needs a forward index, index_build.attach_tokens); scores are unchanged.
+        proximity=True: phrases=True, and `"a b"~N` / `"a b"~>N` are proximity conditions (text.parse_proximity); a text.Near
+        in must_phrases / must_not_phrases is one without the text syntax: the terms within a window, in any order or in
+        order, instead of next to each other (DESIGN K13)."""
+        phrases = phrases or proximity
         if phrases:
-            query, m_ph, x_ph = parse_phrases(query)
+            query, m_ph, x_ph = (parse_proximity if proximity else parse_phrases)(query)
         if operators:
             query, m_words, x_words = parse_operators(query)
         query_terms = self._tokenize(query)
@@ -90,15 +95,17 @@ class BM25:
         if operators:
             m += [t for w in m_words for t in self._tokenize(w)]
             x += [t for w in x_words for t in self._tokenize(w)]
-        as_terms = lambda p: self._tokenize(p) if isinstance(p, str) else list(p)
+        as_terms = lambda p: (p.with_terms(as_terms(p.terms)) if isinstance(p, Near) else self._tokenize(p) if isinstance(p, str)
+                              else list(p))
         mp, xp = [as_terms(p) for p in must_phrases or ()], [as_terms(p) for p in must_not_phrases or ()]
         if phrases:
-            mp += [self._tokenize(p) for p in m_ph]
-            xp += [self._tokenize(p) for p in x_ph]
+            mp += [as_terms(p) for p in m_ph]
+            xp += [as_terms(p) for p in x_ph]
         mp, xp = [p for p in mp if p], [p for p in xp if p]
         ids = self.index.term_ids
+        ph_ids = lambda p: p.with_terms(ids(list(p.terms))) if isinstance(p, Near) else ids(p)
         if mp or xp:
-            within = self.engine.phrase_sets([[ids(p) for p in mp]], [[ids(p) for p in xp]], [ids(m)], [ids(x)],
+            within = self.engine.phrase_sets([[ph_ids(p) for p in mp]], [[ph_ids(p) for p in xp]], [ids(m)], [ids(x)],
                                              within=None if within is None else [within])
         elif m or x:
             within = self.engine.term_sets([ids(m)], [ids(x)], within=None if within is None else [within])

@@ -34,6 +34,7 @@ UNITS = {
     "msr_similar.hip": [],
     "msr_termset.hip": [],
     "msr_phrase.hip": [],
+    "msr_proximity.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)

@@ -929,6 +929,36 @@ extern "C" int msr_phrase_sets(msr_engine* e, int32_t n_rows, const int32_t* phr
     return MSR_OK;
 }
 
+// ---- K13: proximity search (msr_proximity.hip) ----------------------------------------------------------------------------------
+extern "C" int msr_proximity_sets(msr_engine* e, int32_t n_rows, const int32_t* phrase_off, const int32_t* phrase_terms,
+                                  const int32_t* row_span, const int32_t* row_ordered, const uint32_t* cand_bits, int32_t n_cand,
+                                  int64_t cand_stride, const int32_t* row_cand, uint32_t* out_bits, int64_t out_stride,
+                                  void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_tokens)
+        return fail(e, MSR_ERR_NOT_BOUND, "msr_proximity_sets: tokens not bound (msr_bind_tokens: the index has no forward index)");
+    const int64_t W = (e->bm25.n_docs + 31) / 32;
+    if (n_rows < 0 || n_cand < 0)
+        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (n_rows=%d, n_cand=%d)", n_rows, n_cand);
+    if (n_rows > 0 && (!out_bits || !phrase_off || !row_span || !row_ordered))
+        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (out_bits, phrase_off, row_span or row_ordered is NULL "
+                    "with n_rows=%d)", n_rows);
+    if (out_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)out_stride, (long long)W);
+    if (n_cand > 0 && (!cand_bits || !row_cand))
+        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (cand_bits or row_cand is NULL with n_cand=%d)", n_cand);
+    if (n_cand > 0 && cand_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (cand_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)cand_stride, (long long)W);
+    if (n_rows == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_proximity_sets_run(e->tok_off, e->tok_ids, e->bm25.n_docs, e->bm25.n_terms, n_rows, phrase_off, phrase_terms,
+                                      row_span, row_ordered, cand_bits, n_cand, cand_stride, row_cand, out_bits, out_stride,
+                                      (hipStream_t)stream));
+    return MSR_OK;
+}
+
 extern "C" int msr_combine_sets(msr_engine* e, int32_t n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int32_t n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, void* stream) {

@@ -262,13 +262,15 @@ class DeviceSets:
     DocSet.  Unpacks as (bits, q_set, n_sets, stride).  `layout` says what the rows are when the producer has more than one
     kind: None (term_sets: base rows, then one row per distinct operator list), or DeviceEngine.phrase_sets' (T, P, C) -- T rows
     as term_sets makes them, then P verified (phrase, candidate row) pairs, then C rows, one per query with phrases; n_sets =
-    T + P + C.  A part taken with queries() names the same rows and keeps the layout."""
+    T + P + C; `n_near` = how many of the P rows are proximity rows (text.Near; they stand behind the exact phrases' rows).  A
+    part taken with queries() names the same rows and keeps the layout."""
 
     def __init__(self, ix, bits, q_set, n_sets, stride):
         self._ix = weakref.ref(ix)
         self.n_docs = int(ix.n_docs)
         self.bits, self.q_set, self.n_sets, self.stride = bits, q_set, int(n_sets), int(stride)
         self.layout = None
+        self.n_near = 0
 
     def __iter__(self):
         return iter((self.bits, self.q_set, self.n_sets, self.stride))

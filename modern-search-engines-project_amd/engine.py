@@ -357,8 +357,16 @@ class DeviceEngine:
         phrases: its term / base row without them); every list of the three calls and q_set travel in ONE upload.  The
         result's `layout` is (term rows, phrase rows, per-query rows).  A query without phrases keeps its term_sets row, or -1, and costs no
         phrase row.  Raises MsrError when the index has no forward index (index_build.attach_tokens, or a build with
-        keep_tokens=True, gives it one)."""
+        keep_tokens=True, gives it one).
+
+        Proximity (DESIGN K13): wherever a phrase may stand, a text.Near of ids may -- the terms within a window, in order or
+        in any order (msretr.h msr_proximity_sets).  Its candidate row comes from the same term_sets call, built from its
+        ids exactly as a phrase's; the distinct (ids, span, ordered, candidate row) tuples get rows BEHIND the exact phrases'
+        rows, ONE msr_proximity_sets call verifies them, the one msr_combine_sets call reads both kinds, and their lists
+        travel in the same upload.  `layout` stays (T, P, C) with P = exact + proximity rows; `n_near` says how many of the P
+        are proximity rows.  An unknown id follows the phrases' rule.  A call without a Near launches and uploads what it did."""
         from .docset import DeviceSets, DocSet
+        from .text import Near
         ix = self.index
         if not self.has_tokens:
             raise _abi.MsrError(-2, "phrase_sets: the index has no forward index (tok_off / tok_ids): build it with "
@@ -379,7 +387,9 @@ class DeviceEngine:
             if len(base) != Q:
                 raise ValueError(f"within: {len(base)} entries for {Q} queries")
         n_terms = int(ix.n_terms)
-        norm = lambda p: tuple(int(t) if 0 <= int(t) < n_terms else -1 for t in p)
+        ids_of = lambda p: tuple(int(t) if 0 <= int(t) < n_terms else -1 for t in p)
+        norm = lambda p: p.with_terms(ids_of(p.terms)) if isinstance(p, Near) else ids_of(p)
+        terms_of = lambda p: list(p.terms) if isinstance(p, Near) else list(p)
         # virtual queries of the one term_sets call: per query its own (terms, base) row, then one per phrase
         v_must, v_not, v_base, plan = [], [], [], []
         for q in range(Q):
@@ -391,9 +401,9 @@ class DeviceEngine:
             v_must.append(list(m[q])); v_not.append(list(x[q])); v_base.append(base[q])
             plan.append((own, ph_m, len(v_must), ph_x, len(v_must) + len(ph_m)))
             for p in ph_m:
-                v_must.append(list(p) + list(m[q])); v_not.append(list(x[q])); v_base.append(base[q])
+                v_must.append(terms_of(p) + list(m[q])); v_not.append(list(x[q])); v_base.append(base[q])
             for p in ph_x:
-                v_must.append(list(p)); v_not.append([]); v_base.append(base[q])
+                v_must.append(terms_of(p)); v_not.append([]); v_base.append(base[q])
         n_phrase_q = sum(1 for pl in plan if pl[1] or pl[3])
         if not any(b is not None for b in v_base):
             v_base = None
@@ -401,11 +411,11 @@ class DeviceEngine:
         # one row per query with phrases.  The phrase and combine lists need the term rows' numbers, which _term_rows knows
         # before it uploads: it calls lists_of() and sends the result along with its own lists (one upload for the whole call)
         V = len(v_must)
-        rows, cut = [], []
+        rows, near, cut = [], [], []                         # exact rows, proximity rows (behind them): (phrase, candidate row)
 
         def lists_of(v_row, T):
             row_of = {}
-            and_off, and_rows, not_off, not_rows, q_set = [0], [], [0], [], []
+            and_off, and_ref, not_off, not_ref, q_set = [0], [], [0], [], []
             for q, (own, ph_m, i_m, ph_x, i_x) in enumerate(plan):
                 if not ph_m and not ph_x:
                     q_set.append(v_row[own])
@@ -414,39 +424,55 @@ class DeviceEngine:
                 for key in [(p, v_row[i_m + j]) for j, p in enumerate(ph_m)] + [(p, v_row[i_x + j]) for j, p in enumerate(ph_x)]:
                     r = row_of.get(key)
                     if r is None:
-                        r = row_of[key] = len(rows)
-                        rows.append(key)
+                        kind = near if isinstance(key[0], Near) else rows
+                        r = row_of[key] = (kind, len(kind))
+                        kind.append(key)
                     rm.append(r)
-                a = [T + r for r in rm[:len(ph_m)]]
+                a = rm[:len(ph_m)]
                 if not ph_m and v_row[own] != -1:            # only not phrases: the query's own term / base row
                     a = [v_row[own]]
-                and_rows += a; and_off.append(len(and_rows))
-                not_rows += [T + r for r in rm[len(ph_m):]]; not_off.append(len(not_rows))
+                and_ref += a; and_off.append(len(and_ref))
+                not_ref += rm[len(ph_m):]; not_off.append(len(not_ref))
                 q_set.append(None)
+            # a row's number: the exact rows stand at T, the proximity rows behind them
+            at = lambda ref: ref if not isinstance(ref, tuple) else T + ref[1] + (len(rows) if ref[0] is near else 0)
+            and_rows, not_rows = [at(ref) for ref in and_ref], [at(ref) for ref in not_ref]
             k = 0
             for q in range(Q):
                 if q_set[q] is None:
-                    q_set[q] = T + len(rows) + k
+                    q_set[q] = T + len(rows) + len(near) + k
                     k += 1
             p_off, p_terms = [0], []
             for p, _ in rows:
                 p_terms += list(p); p_off.append(len(p_terms))
             parts = [p_off, [c for _, c in rows], and_off, not_off, p_terms, and_rows, not_rows, q_set]
+            if near:
+                n_off, n_terms_ = [0], []
+                for p, _ in near:
+                    n_terms_ += list(p.terms); n_off.append(len(n_terms_))
+                parts += [n_off, [c for _, c in near], [p.span for p, _ in near], [int(p.ordered) for p, _ in near], n_terms_]
             cut.extend(np.cumsum([0] + [len(part) for part in parts]).tolist())
             return [v for part in parts for v in part]
 
         bits, _, T, stride, dev = self._term_rows(v_must, v_not, v_base, extra_rows=(V - Q) + n_phrase_q, tail=lists_of)
         d_poff, d_cand, d_aoff, d_xoff, d_pt, d_a, d_x, d_q = [dev[cut[i]:cut[i + 1]] for i in range(8)]
-        P, C_ = len(rows), int(d_aoff.numel()) - 1
+        P, Pn, C_ = len(rows), len(near), int(d_aoff.numel()) - 1
         if C_:
             ptr = lambda t: _ptr(t) if t.numel() else C.c_void_p(0)
-            self._check(self.lib.msr_phrase_sets(self.handle, P, _ptr(d_poff), ptr(d_pt), ptr(bits[:T]) if T else C.c_void_p(0), T,
-                                                 stride, _ptr(d_cand) if T else C.c_void_p(0), _ptr(bits[T:]), stride,
-                                                 self._stream()))
+            cand = (ptr(bits[:T]) if T else C.c_void_p(0), T, stride)
+            if P:
+                self._check(self.lib.msr_phrase_sets(self.handle, P, _ptr(d_poff), ptr(d_pt), *cand,
+                                                     _ptr(d_cand) if T else C.c_void_p(0), _ptr(bits[T:]), stride, self._stream()))
+            if Pn:
+                d_noff, d_ncand, d_nspan, d_nord, d_nt = [dev[cut[i]:cut[i + 1]] for i in range(8, 13)]
+                self._check(self.lib.msr_proximity_sets(self.handle, Pn, _ptr(d_noff), ptr(d_nt), _ptr(d_nspan), _ptr(d_nord), *cand,
+                                                        _ptr(d_ncand) if T else C.c_void_p(0), _ptr(bits[T + P:]), stride,
+                                                        self._stream()))
             self._check(self.lib.msr_combine_sets(self.handle, C_, _ptr(d_aoff), ptr(d_a), _ptr(d_xoff), ptr(d_x), _ptr(bits),
-                                                  T + P, stride, _ptr(bits[T + P:]), stride, self._stream()))
-        out = DeviceSets(ix, bits[:T + P + C_], d_q, T + P + C_, stride)
-        out.layout = (T, P, C_)
+                                                  T + P + Pn, stride, _ptr(bits[T + P + Pn:]), stride, self._stream()))
+        out = DeviceSets(ix, bits[:T + P + Pn + C_], d_q, T + P + Pn + C_, stride)
+        out.layout = (T, P + Pn, C_)
+        out.n_near = Pn
         return out
 
     def bm25_topk(self, term_lists, k=1000, min_score=0.0, packed=None, within=None):

@@ -16,7 +16,8 @@ from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .reranker import Reranker
-from .text import (LineFormatter, extract_domain, extract_domain_topic, format_result_line, parse_operators, parse_phrases,
+from .text import (LineFormatter, Near, extract_domain, extract_domain_topic, format_result_line, parse_operators, parse_phrases,
+                   parse_proximity,
                    preprocess_query, read_queries_file)
 
 TOP_K_RETRIEVAL = 1000     # config.py:13
@@ -365,7 +366,7 @@ class Retriever:
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
-                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None):
+                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
@@ -386,7 +387,9 @@ class Retriever:
         DeviceEngine.phrase_sets call per chunk (in the term_sets call's place), both stages restricted in hybrid mode.  A
         phrase filters; the BM25 scores stay what they are.  The index needs a forward index (index_build.attach_tokens),
         MsrError otherwise; a phrase of more than MSR_PHRASE_MAX_TERMS terms raises ValueError.  phrases=True is refused like
-        operators=True (text.parse_phrases needs the text)."""
+        operators=True (text.parse_phrases needs the text).
+        A text.Near in must_phrases / must_not_phrases is a proximity condition (DESIGN K13): its terms within a window, in
+        order or in any order; proximity=True is refused like phrases=True (text.parse_proximity needs the text)."""
         import torch
         eng = self.engine
         _check_mode(mode)
@@ -396,6 +399,9 @@ class Retriever:
         if phrases:
             raise ValueError("phrases=True needs the query text: use search / search_batch / batch_search, or parse with "
                              "text.parse_phrases and pass must_phrases= / must_not_phrases=")
+        if proximity:
+            raise ValueError("proximity=True needs the query text: use search / search_batch / batch_search, or parse with "
+                             "text.parse_proximity and pass must_phrases= / must_not_phrases=")
         if top_k > eng.rerank_max_docs or top_k > eng.max_k:
             raise ValueError(f"top_k {top_k} exceeds the engine's max_k / rerank_max_docs ({eng.max_k} / {eng.rerank_max_docs})")
         if mode == "hybrid":
@@ -412,7 +418,7 @@ class Retriever:
             if lists is not None and len(lists) != Q:
                 raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
         op_ids = lambda lists, a, b: None if lists is None else [self.index.term_ids(t) for t in lists[a:b]]
-        ph_ids = lambda lists, a, b: None if lists is None else [[self.index.term_ids(p) for p in ps] for ps in lists[a:b]]
+        ph_ids = lambda lists, a, b: None if lists is None else [[self._phrase_ids(p) for p in ps] for ps in lists[a:b]]
         pending = None
         for i, a in enumerate(range(0, Q, step)):
             b = min(Q, a + step)
@@ -429,6 +435,12 @@ class Retriever:
         if pending is not None:
             yield (pending[0],) + self._collect(pending[1])
 
+    def _phrase_ids(self, p):
+        """A phrase's term ids; a text.Near keeps its slop and mode (a Near of a string is tokenised like the query)."""
+        if isinstance(p, Near):
+            return p.with_terms(self.index.term_ids(self.bm25._tokenize(p.terms) if isinstance(p.terms, str) else list(p.terms)))
+        return self.index.term_ids(p)
+
     @classmethod
     def _collect(cls, job):
         out = cls._collect_chunk(job)
@@ -436,18 +448,18 @@ class Retriever:
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
-                    must_phrases=None, must_not_phrases=None):
+                    must_phrases=None, must_not_phrases=None, proximity=False):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
         with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
-        operators / must / must_not / phrases / must_phrases / must_not_phrases: final_list_chunks."""
+        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity: final_list_chunks."""
         _check_mode(mode)
         if with_source and mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
         parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
                                             operators=operators, must=must, must_not=must_not, phrases=phrases,
-                                            must_phrases=must_phrases, must_not_phrases=must_not_phrases))
+                                            must_phrases=must_phrases, must_not_phrases=must_not_phrases, proximity=proximity))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -458,12 +470,15 @@ class Retriever:
                np.concatenate([pad(p[3], -1) for p in parts]), np.concatenate([p[4] for p in parts]))
         return out + ((np.concatenate([pad(p[5], 0) for p in parts]),) if with_source else ())
 
-    def _operators(self, processed, operators, must, must_not, phrases=False, must_phrases=None, must_not_phrases=None):
+    def _operators(self, processed, operators, must, must_not, phrases=False, must_phrases=None, must_not_phrases=None,
+                   proximity=False):
         """-> (scoring texts, must term lists, must_not term lists, must phrases, not phrases) of the preprocessed queries: the
         parsed operator words (operators=True) and quoted phrases (phrases=True, text.parse_phrases, BEFORE the operators),
         tokenised like the query, joined with the caller's explicit lists; a pair is (None, None) when there is nothing of
         its kind -- the chain then runs exactly as without the feature.  An explicit phrase is a string (tokenised here) or a
-        list of term strings; a phrase that tokenises to nothing is dropped."""
+        list of term strings; a phrase that tokenises to nothing is dropped.  proximity=True: phrases=True with
+        text.parse_proximity in parse_phrases' place; a text.Near, parsed or explicit, keeps its slop and mode."""
+        phrases = phrases or proximity
         if not operators and must is None and must_not is None and not phrases and must_phrases is None and must_not_phrases is None:
             return processed, None, None, None, None
         Q = len(processed)
@@ -474,15 +489,15 @@ class Retriever:
         tok = self.bm25._tokenize
         m = [list(t) for t in must] if must is not None else [[] for _ in range(Q)]
         x = [list(t) for t in must_not] if must_not is not None else [[] for _ in range(Q)]
-        as_terms = lambda p: tok(p) if isinstance(p, str) else list(p)
+        as_terms = lambda p: (p.with_terms(as_terms(p.terms)) if isinstance(p, Near) else tok(p) if isinstance(p, str) else list(p))
         mp = [[as_terms(p) for p in ps] for ps in must_phrases] if must_phrases is not None else [[] for _ in range(Q)]
         xp = [[as_terms(p) for p in ps] for ps in must_not_phrases] if must_not_phrases is not None else [[] for _ in range(Q)]
         processed = list(processed)
         for q in range(Q):
             if phrases:
-                processed[q], m_ph, x_ph = parse_phrases(processed[q])
-                mp[q] += [tok(p) for p in m_ph]
-                xp[q] += [tok(p) for p in x_ph]
+                processed[q], m_ph, x_ph = (parse_proximity if proximity else parse_phrases)(processed[q])
+                mp[q] += [as_terms(p) for p in m_ph]
+                xp[q] += [as_terms(p) for p in x_ph]
             if operators:
                 processed[q], m_words, x_words = parse_operators(processed[q])
                 m[q] += [t for w in m_words for t in tok(w)]
@@ -495,12 +510,12 @@ class Retriever:
         return processed, m, x, mp, xp
 
     def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not, phrases=False, must_phrases=None,
-                     must_not_phrases=None):
+                     must_not_phrases=None, proximity=False):
         """_prepare with operators and phrases: -> (term ids, vectors, keyword arguments of final_lists: must / must_not /
         must_phrases / must_not_phrases where there are any).  The scoring text (excluded words and phrases removed, quotes
         gone) is what gets tokenised and embedded."""
         processed, m, x, mp, xp = self._operators([preprocess_query(q) for q in queries], operators, must, must_not, phrases,
-                                                  must_phrases, must_not_phrases)
+                                                  must_phrases, must_not_phrases, proximity)
         ops = {} if m is None else {"must": m, "must_not": x}
         if mp is not None:
             ops.update(must_phrases=mp, must_not_phrases=xp)
@@ -521,7 +536,7 @@ class Retriever:
 
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
-                     must_phrases=None, must_not_phrases=None):
+                     must_phrases=None, must_not_phrases=None, proximity=False):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
@@ -537,10 +552,14 @@ class Retriever:
         must_not_phrases: per query a list of phrases, each a string (tokenised like the query) or a list of term strings.  A
         result holds every required phrase and no excluded one IN ITS INDEXED TOKEN STREAM (words next to each other, in
         order, after the tokenizer); the scores are unchanged.  Needs an index with a forward index (index_build.attach_tokens;
-        MsrError otherwise); a phrase of more than 16 terms raises ValueError.  Off by default."""
+        MsrError otherwise); a phrase of more than 16 terms raises ValueError.  Off by default.
+        proximity=True: phrases=True, and `"a b"~N` / `"a b"~>N` are proximity conditions (text.parse_proximity): the words
+        within a window with up to N other tokens among them, in any order / in this order.  A text.Near in must_phrases /
+        must_not_phrases (terms: a string or a list of term strings) is such a condition without the text syntax.  A slop
+        below 0, more than 16 terms or a window of more than 64 tokens raises ValueError.  Off by default."""
         _check_mode(mode)
         ids, qv, ops = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not, phrases, must_phrases,
-                                         must_not_phrases)
+                                         must_not_phrases, proximity)
         src = None
         if mode == "hybrid":
             doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
@@ -568,27 +587,28 @@ class Retriever:
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-               must_not_phrases=None):
+               must_not_phrases=None, proximity=False):
         """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
-        list of phrases each."""
+        list of phrases (or text.Near conditions) each."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
                                  mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
                                  must_not=None if must_not is None else [must_not], phrases=phrases,
                                  must_phrases=None if must_phrases is None else [must_phrases],
-                                 must_not_phrases=None if must_not_phrases is None else [must_not_phrases])[0]
+                                 must_not_phrases=None if must_not_phrases is None else [must_not_phrases],
+                                 proximity=proximity)[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-                     must_not_phrases=None):
+                     must_not_phrases=None, proximity=False):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
         search_batch (the entries keep the reference's keys in either mode); operators / must / must_not / phrases /
-        must_phrases / must_not_phrases: search_batch."""
+        must_phrases / must_not_phrases / proximity: search_batch."""
         _check_mode(mode)
         ids, qv, ops = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators, must, must_not,
-                                         phrases, must_phrases, must_not_phrases)
+                                         phrases, must_phrases, must_not_phrases, proximity)
         doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)

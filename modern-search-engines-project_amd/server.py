@@ -48,6 +48,11 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         query: str
         query_embedding: Optional[List[float]] = None
 
+    class NearSpec(BaseModel):        # a proximity condition in a phrase list (text.Near): the words within a window
+        phrase: str
+        slop: int = 0                 # other tokens allowed among the words (between the first and the last when ordered)
+        ordered: bool = False
+
     class SearchRequest(BaseModel):
         query: str = ""
         top_k: int = 1000
@@ -61,8 +66,11 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         must: Optional[List[str]] = None       # terms every result must contain ...
         must_not: Optional[List[str]] = None   # ... and must not contain (Retriever.search)
         phrases: bool = False         # `"a b"` / `-"a b"` in the query: required / excluded phrases (text.parse_phrases)
-        must_phrases: Optional[List[str]] = None       # phrases every result must hold, words next to each other ...
-        must_not_phrases: Optional[List[str]] = None   # ... and must not hold (Retriever.search; needs a forward index)
+        # phrases every result must hold, words next to each other (a NearSpec: within a window), and must not hold
+        # (Retriever.search; needs a forward index)
+        must_phrases: Optional[List[Union[str, NearSpec]]] = None
+        must_not_phrases: Optional[List[Union[str, NearSpec]]] = None
+        proximity: bool = False       # phrases, and `"a b"~N` / `"a b"~>N`: the words within a window (text.parse_proximity)
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -122,11 +130,19 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                 kw.update(operators=req.operators, must=req.must, must_not=req.must_not)
             if req.phrases or req.must_phrases is not None or req.must_not_phrases is not None:
                 kw.update(phrases=req.phrases, must_phrases=req.must_phrases, must_not_phrases=req.must_not_phrases)
+            specs = [p for ps in (req.must_phrases, req.must_not_phrases) for p in ps or () if isinstance(p, NearSpec)]
+            near = req.proximity or bool(specs)      # a proximity condition the engine cannot hold is the caller's error: 400
             try:
+                if near:
+                    from .text import Near
+                    cond = lambda ps: None if ps is None else [Near(p.phrase, p.slop, p.ordered) if isinstance(p, NearSpec) else p
+                                                               for p in ps]
+                    kw.update(phrases=req.phrases, proximity=req.proximity, must_phrases=cond(req.must_phrases),
+                              must_not_phrases=cond(req.must_not_phrases))
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
-                if req.mode == "lexical":
+                if req.mode == "lexical" and not near:
                     raise
                 return JSONResponse(status_code=400, content={"error": str(e)})      # a dense_k the engine cannot hold
             llm_response = ""

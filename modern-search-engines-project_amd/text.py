@@ -7,6 +7,8 @@ Mirrors, by behaviour, /root/reference/search_api.py:155-166 (preprocess_query),
 import re
 from urllib.parse import urlparse
 
+from ._abi import MSR_PHRASE_MAX_TERMS, MSR_PROX_MAX_SPAN
+
 CITY = "tübingen"
 
 
@@ -110,6 +112,96 @@ def parse_phrases(processed_query: str):
                 must.append(inner)
             out.append(" " + inner + " ")
         pos = b + 1
+    out.append(processed_query[pos:])
+    return " ".join("".join(out).split()), must, must_not
+
+
+class Near:
+    """A proximity condition (DESIGN K13): the terms stand within a window of the page's indexed token stream.  terms: a
+    string (tokenised like the query by the facade that takes it), a list of term strings, or at engine level a list of term
+    ids.  ordered=False: one occurrence of every distinct term inside a window of (number of distinct terms + slop) tokens,
+    in any order -- up to `slop` other tokens among them; ordered=True: the terms in this order, the first and the last at
+    most (number of terms + slop) tokens apart -- slop 0 is the exact phrase.  An immutable value; equal conditions compare
+    and hash equal.  ValueError: a negative slop; a list of more than MSR_PHRASE_MAX_TERMS terms; a window of more than
+    MSR_PROX_MAX_SPAN tokens (both known once the terms are a list: with_terms checks what a string could not)."""
+    __slots__ = ("terms", "slop", "ordered")
+
+    def __init__(self, terms, slop=0, ordered=False):
+        if isinstance(slop, bool) or int(slop) != slop or slop < 0:
+            raise ValueError(f"Near: slop must be a whole number >= 0, got {slop!r}")
+        set_ = object.__setattr__
+        set_(self, "terms", terms if isinstance(terms, str) else tuple(terms))
+        set_(self, "slop", int(slop))
+        set_(self, "ordered", bool(ordered))
+        if not isinstance(terms, str):
+            if len(self.terms) > MSR_PHRASE_MAX_TERMS:
+                raise ValueError(f"a proximity condition may hold at most {MSR_PHRASE_MAX_TERMS} terms (MSR_PHRASE_MAX_TERMS), "
+                                 f"got {len(self.terms)}")
+            if self.span > MSR_PROX_MAX_SPAN:
+                raise ValueError(f"a proximity window may span at most {MSR_PROX_MAX_SPAN} tokens (MSR_PROX_MAX_SPAN), got "
+                                 f"{self.span} = {self.span - self.slop} terms + slop {self.slop}")
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Near is immutable")
+
+    @property
+    def span(self):
+        """The window in tokens: L + slop when ordered, the number of distinct terms + slop otherwise (terms as a list)."""
+        if isinstance(self.terms, str):
+            raise ValueError("Near.span: the terms are still a string (tokenise them first: with_terms)")
+        return (len(self.terms) if self.ordered else len(set(self.terms))) + self.slop
+
+    def with_terms(self, terms):
+        """The same condition over other terms (the tokens of the string, the ids of the terms)."""
+        return Near(terms, self.slop, self.ordered)
+
+    def __len__(self):
+        return len(self.terms)
+
+    def _key(self):
+        return (self.terms, self.slop, self.ordered)
+
+    def __eq__(self, other):
+        return isinstance(other, Near) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        terms = self.terms if isinstance(self.terms, str) else list(self.terms)
+        return f"Near({terms!r}, slop={self.slop}, ordered={self.ordered})"
+
+
+_SLOP = re.compile(r"~(>?)(\d+)(?=\s|$)")
+
+
+def parse_proximity(processed_query: str):
+    """parse_phrases with one addition -> (text_without_quotes, must, must_not): a closing quote DIRECTLY followed by `~N` or
+    `~>N` (digits only, then whitespace or the end of the text) turns that phrase into a proximity condition, and the suffix
+    is removed from the text.  `"a b"~N` -> Near("a b", N, ordered=False): the words within a window, in any order, with up
+    to N other tokens among them; `"a b"~>N` -> Near("a b", N, ordered=True): the words in this order, with up to N other
+    tokens between the first and the last.  A `~` followed by anything else is left in the text and the phrase stays exact.
+    Entries without a suffix come back as plain strings; pairing of the quotes, the sign in front and what stays in the scoring
+    text are parse_phrases' (a text without a suffix gives exactly its output).  A slop too wide for the words (Near's
+    ValueError) shows once the phrase is tokenised."""
+    at = [i for i, ch in enumerate(processed_query) if ch == '"']
+    if len(at) < 2:
+        return processed_query, [], []
+    out, must, must_not, pos = [], [], [], 0
+    for a, b in zip(at[0::2], at[1::2]):
+        inner = processed_query[a + 1:b].strip()
+        sign = processed_query[a - 1] if a >= 1 and processed_query[a - 1] in "+-" and (a == 1 or processed_query[a - 2].isspace()) else ""
+        out.append(processed_query[pos:a - len(sign)])
+        m = _SLOP.match(processed_query, b + 1)
+        entry = Near(inner, int(m.group(2)), ordered=m.group(1) == ">") if m else inner
+        if sign == "-":
+            if inner:
+                must_not.append(entry)
+        else:
+            if inner:
+                must.append(entry)
+            out.append(" " + inner + " ")
+        pos = m.end() if m else b + 1
     out.append(processed_query[pos:])
     return " ".join("".join(out).split()), must, must_not
 
