@@ -35,18 +35,20 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 14        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 15        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
                                      tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets;
-                                     13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets */
+                                     13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets;
+                                     15: msr_best_windows */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
 #define MSR_RERANK_MAX_CHUNKS 10  /* reranker_api.py:58 */
 #define MSR_TERMSET_SPAN_DOCS 8192 /* msr_term_sets: consecutive documents one work item of its kernel owns (a multiple of 1024) */
 #define MSR_PHRASE_MAX_TERMS 16    /* msr_phrase_sets / msr_proximity_sets: most term ids a row may hold */
-#define MSR_PROX_MAX_SPAN 64       /* msr_proximity_sets: the widest window, in tokens */
+#define MSR_PROX_MAX_SPAN 64       /* msr_proximity_sets / msr_best_windows: the widest window, in tokens */
+#define MSR_SNIPPET_MAX_WEIGHT (1 << 20) /* msr_best_windows: the largest weight of a term (16 of them sum to 2^24 exactly) */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -278,6 +280,35 @@ int msr_proximity_sets(msr_engine* e, int32_t n_rows, const int32_t* phrase_off,
                        const int32_t* row_span, const int32_t* row_ordered,
                        const uint32_t* cand_bits, int32_t n_cand, int64_t cand_stride, const int32_t* row_cand,
                        uint32_t* out_bits, int64_t out_stride, void* stream);
+
+/* Query-biased snippets: the best window of a document for a weighted list of terms.
+ *   ROW r is (p[0 .. L), w[0 .. L), span): p = row_terms[row_off[r] .. row_off[r + 1]), w = row_weights[same range],
+ *   span = row_span[r] (row_off int32 [n_rows + 1], row_span int32 [n_rows]), with 1 <= L <= MSR_PHRASE_MAX_TERMS,
+ *   0 <= w[j] <= MSR_SNIPPET_MAX_WEIGHT and 1 <= span <= MSR_PROX_MAX_SPAN.  A repeated id counts once, with the weight and
+ *   the bit of its first occurrence.
+ *   PAIR i is (pair_doc[i], pair_row[i]).  Let s = tok[d][0 .. n) be the document's own stream (n < 2^31).  For every start a
+ *   in [0, n) the window is s[a .. min(a + span, n)); hits(a) = the number of positions of the window whose token is a term of
+ *   the row; cover(a) = the sum of w[j] over the DISTINCT ids present in the window.  The pair's answer is the start with the
+ *   largest (cover, hits), compared lexicographically; among equal ones the SMALLEST a.  If no position of the document
+ *   holds a term of the row (an empty document included) the pair has no window.  Entry i of the five outputs:
+ *     out_start int32   the position inside the document, or -1
+ *     out_cover int32   cover(start)
+ *     out_hits  int32   hits(start)
+ *     out_mask  uint64  bit k = the token at start + k is a term of the row; bits at or above the window's length are 0
+ *     out_terms uint32  bit j = p[j] stands in the window; a repeated id sets only the bit of its first occurrence
+ *   NO WINDOW is (-1, 0, 0, 0, 0).  The kernel writes the same five values, without a host round trip, for a pair_doc outside
+ *   [0, n_docs), a pair_row outside [0, n_rows), and a row with L < 1, L > MSR_PHRASE_MAX_TERMS, an id outside [0, n_terms),
+ *   a weight outside [0, MSR_SNIPPET_MAX_WEIGHT] or a span outside 1 .. MSR_PROX_MAX_SPAN.  A window never uses a token of a
+ *   neighbouring document: the bound of every read is the document's end.  All arithmetic is integer.
+ *   All pointers are device pointers.  The call only enqueues (one launch, one wave per pair) and uses no engine scratch;
+ *   repeated calls give the same bytes; entries at or above n_pairs are not touched.  Refused before any launch, outputs
+ *   untouched: MSR_ERR_NOT_BOUND without tokens (msr_bind_tokens); MSR_ERR_INVALID for a NULL pointer with n_pairs > 0, a
+ *   negative count, or n_rows == 0 with n_pairs > 0.  n_pairs == 0 succeeds and launches nothing.  Cost per pair: every token
+ *   of the document is read once, 4 bytes; there is no early exit. */
+int msr_best_windows(msr_engine* e, int32_t n_pairs, const int32_t* pair_doc, const int32_t* pair_row,
+                     int32_t n_rows, const int32_t* row_off, const int32_t* row_terms, const int32_t* row_weights,
+                     const int32_t* row_span, int32_t* out_start, int32_t* out_cover, int32_t* out_hits, uint64_t* out_mask,
+                     uint32_t* out_terms, void* stream);
 
 /* msr_combine_sets: out[r] = AND of in[s] for s in and_rows[and_off[r] .. and_off[r + 1])  AND NOT  OR of in[s] for s in
  *   not_rows[not_off[r] .. not_off[r + 1]), rows of in_bits (n_in rows in_stride words apart) in the layout above.  An empty

@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 14
+MSR_ABI_VERSION = 15
 MSR_CFG_NO_ROW_COPY = 1
 MSR_DIM = 768
 MSR_MAX_K = 1024
@@ -16,6 +16,7 @@ MSR_MERGE_MAX_ENTRIES = 8192
 MSR_TERMSET_SPAN_DOCS = 8192
 MSR_PHRASE_MAX_TERMS = 16
 MSR_PROX_MAX_SPAN = 64
+MSR_SNIPPET_MAX_WEIGHT = 1 << 20
 MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
 
 
@@ -78,6 +79,7 @@ _SIGNATURES = {
     "msr_bind_tokens": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
     "msr_phrase_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "msr_proximity_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
+    "msr_best_windows": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "msr_combine_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,

@@ -35,6 +35,7 @@ UNITS = {
     "msr_termset.hip": [],
     "msr_phrase.hip": [],
     "msr_proximity.hip": [],
+    "msr_snippet.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)

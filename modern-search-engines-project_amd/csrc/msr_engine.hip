@@ -959,6 +959,30 @@ extern "C" int msr_proximity_sets(msr_engine* e, int32_t n_rows, const int32_t* 
     return MSR_OK;
 }
 
+// ---- K14: query-biased snippets (msr_snippet.hip) -------------------------------------------------------------------------------
+extern "C" int msr_best_windows(msr_engine* e, int32_t n_pairs, const int32_t* pair_doc, const int32_t* pair_row, int32_t n_rows,
+                                const int32_t* row_off, const int32_t* row_terms, const int32_t* row_weights,
+                                const int32_t* row_span, int32_t* out_start, int32_t* out_cover, int32_t* out_hits,
+                                uint64_t* out_mask, uint32_t* out_terms, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_tokens)
+        return fail(e, MSR_ERR_NOT_BOUND, "msr_best_windows: tokens not bound (msr_bind_tokens: the index has no forward index)");
+    if (n_pairs < 0 || n_rows < 0)
+        return fail(e, MSR_ERR_INVALID, "msr_best_windows: bad argument (n_pairs=%d, n_rows=%d)", n_pairs, n_rows);
+    if (n_pairs == 0) return MSR_OK;
+    if (n_rows == 0) return fail(e, MSR_ERR_INVALID, "msr_best_windows: bad argument (n_rows=0 with n_pairs=%d)", n_pairs);
+    if (!pair_doc || !pair_row || !row_off || !row_terms || !row_weights || !row_span)
+        return fail(e, MSR_ERR_INVALID, "msr_best_windows: bad argument (pair_doc, pair_row, row_off, row_terms, row_weights or "
+                    "row_span is NULL with n_pairs=%d)", n_pairs);
+    if (!out_start || !out_cover || !out_hits || !out_mask || !out_terms)
+        return fail(e, MSR_ERR_INVALID, "msr_best_windows: bad argument (an output pointer is NULL with n_pairs=%d)", n_pairs);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_best_windows_run(e->tok_off, e->tok_ids, e->bm25.n_docs, e->bm25.n_terms, n_pairs, pair_doc, pair_row, n_rows,
+                                    row_off, row_terms, row_weights, row_span, out_start, out_cover, out_hits, out_mask, out_terms,
+                                    (hipStream_t)stream));
+    return MSR_OK;
+}
+
 extern "C" int msr_combine_sets(msr_engine* e, int32_t n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int32_t n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, void* stream) {

@@ -193,6 +193,12 @@ hipError_t msr_proximity_sets_run(const int64_t* tok_off, const int32_t* tok_ids
                                   const int32_t* phrase_off, const int32_t* phrase_terms, const int32_t* row_span,
                                   const int32_t* row_ordered, const uint32_t* cand_bits, int n_cand, int64_t cand_stride,
                                   const int32_t* row_cand, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);
+// K14 (msr_snippet.hip): the best window of a document for a weighted row of terms (see msretr.h; arguments checked by the caller).
+hipError_t msr_best_windows_run(const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_terms, int n_pairs,
+                                const int32_t* pair_doc, const int32_t* pair_row, int n_rows, const int32_t* row_off,
+                                const int32_t* row_terms, const int32_t* row_weights, const int32_t* row_span, int32_t* out_start,
+                                int32_t* out_cover, int32_t* out_hits, uint64_t* out_mask, uint32_t* out_terms,
+                                hipStream_t stream);
 hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);

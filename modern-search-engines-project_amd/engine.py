@@ -475,6 +475,53 @@ class DeviceEngine:
         out.n_near = Pn
         return out
 
+    def best_windows(self, pair_doc, pair_row, rows, weights, spans):
+        """Query-biased snippets (msr_best_windows, DESIGN K14): per pair (pair_doc[i], pair_row[i]) the window of the
+        document's token stream that covers the most weight of row pair_row[i] -> five device tensors of len(pair_doc)
+        entries: start int32 (-1: no window), cover int32, hits int32, mask int64 (the uint64 position mask's bits), terms
+        int32 (the uint32 term bits).  rows: lists of term ids, weights: lists of ints (one per id), spans: an int or one per
+        row.  pair_doc / pair_row: host arrays or device tensors of document indices and row numbers.  Every list travels in
+        ONE upload (host pairs with them), ONE launch follows and nothing synchronises: the caller copies back.  What the
+        ABI turns into "no window" (an id, weight, span, document or row out of range) is not checked here.  Raises MsrError
+        when the index has no forward index."""
+        if not self.has_tokens:
+            raise _abi.MsrError(-2, "best_windows: the index has no forward index (tok_off / tok_ids): build it with "
+                                    "keep_tokens=True or attach the token streams with index_build.attach_tokens, then rebind")
+        R = len(rows)
+        if len(weights) != R:
+            raise ValueError(f"best_windows: {len(weights)} weight lists for {R} rows")
+        spans = [int(spans)] * R if np.ndim(spans) == 0 else [int(v) for v in spans]
+        if len(spans) != R:
+            raise ValueError(f"best_windows: {len(spans)} spans for {R} rows")
+        off, terms, wts = [0], [], []
+        for p, w in zip(rows, weights):
+            if len(p) != len(w):
+                raise ValueError(f"best_windows: a row of {len(p)} terms with {len(w)} weights")
+            terms += [int(t) for t in p]; wts += [int(v) for v in w]; off.append(len(terms))
+        on_dev = torch.is_tensor(pair_doc) and pair_doc.is_cuda
+        if on_dev != (torch.is_tensor(pair_row) and pair_row.is_cuda):
+            raise ValueError("best_windows: pair_doc and pair_row are both host arrays or both device tensors")
+        n = int(pair_doc.numel()) if on_dev else len(pair_doc)
+        if (int(pair_row.numel()) if on_dev else len(pair_row)) != n:
+            raise ValueError("best_windows: pair_doc and pair_row differ in length")
+        parts = [off, terms or [0], wts or [0], spans or [0]]     # (an empty list keeps a word, so that no pointer is NULL)
+        if not on_dev:
+            parts += [np.asarray(pair_doc, np.int64).astype(np.int32).reshape(-1) if n else [0],
+                      np.asarray(pair_row, np.int64).astype(np.int32).reshape(-1) if n else [0]]
+        cut = np.cumsum([0] + [len(p) for p in parts])
+        dev = self._dev(np.concatenate([np.asarray(p, np.int32) for p in parts]), torch.int32)
+        d_off, d_terms, d_wts, d_span = [dev[cut[i]:cut[i + 1]] for i in range(4)]
+        if on_dev:
+            d_doc, d_row = self._dev(pair_doc, torch.int32).reshape(-1), self._dev(pair_row, torch.int32).reshape(-1)
+        else:
+            d_doc, d_row = dev[cut[4]:cut[5]], dev[cut[5]:cut[6]]
+        i32 = lambda: torch.empty(n, dtype=torch.int32, device=self.device)
+        out = (i32(), i32(), i32(), torch.empty(n, dtype=torch.int64, device=self.device), i32())
+        if n:
+            self._check(self.lib.msr_best_windows(self.handle, n, _ptr(d_doc), _ptr(d_row), R, _ptr(d_off), _ptr(d_terms),
+                                                  _ptr(d_wts), _ptr(d_span), *[_ptr(t) for t in out], self._stream()))
+        return out
+
     def bm25_topk(self, term_lists, k=1000, min_score=0.0, packed=None, within=None):
         """-> (doc index int32 [Q, k], score float64 [Q, k], n int32 [Q]) device tensors.  within: None, a DocSet (every
         query) or a list of DocSet / None per query -- the top k of each query's set (msr_bm25_topk_within)."""

@@ -16,6 +16,7 @@ from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .reranker import Reranker
+from .snippets import SNIPPET_TOKENS, query_row, render, term_weights
 from .text import (LineFormatter, Near, extract_domain, extract_domain_topic, format_result_line, parse_operators, parse_phrases,
                    parse_proximity,
                    preprocess_query, read_queries_file)
@@ -45,7 +46,11 @@ def _check_mode(mode):
 
 
 class Retriever:
-    def __init__(self, embedder=None, indexer=None, db_path=None, tokenizer=None, device=0, freeze_gc=False, **engine_kw):
+    def __init__(self, embedder=None, indexer=None, db_path=None, tokenizer=None, device=0, freeze_gc=False,
+                 span_tokenizer=None, **engine_kw):
+        """span_tokenizer: `tokenizer` with each token's place -- a callable text -> iterable of (term, begin, end) over the
+        same tokens in the same order (text.simple_tokenize_spans is simple_tokenize's); snippets=True needs it beside a
+        custom tokenizer (DESIGN K14)."""
         if isinstance(indexer, DeviceEngine):
             self.engine = indexer
         else:
@@ -60,6 +65,8 @@ class Retriever:
         self._domains_bound = False
         self._formatter = None
         self._pinned = {}
+        self._tokenizer, self._span_tokenizer = tokenizer, span_tokenizer
+        self._term_names = None
         if freeze_gc:
             # The corpus side of a retriever is millions of long-lived Python objects (URL / title / text strings, the id maps):
             # every full garbage collection walks them -- tens of milliseconds, in the middle of a 10 ms batch.  They never
@@ -84,6 +91,7 @@ class Retriever:
         self._ids = ids.cpu().numpy() if hasattr(ids, "cpu") else np.asarray(ids)
         self._domains_bound = False
         self._formatter = None
+        self._term_names = None
         if ix.term_off is None:
             self.bm25 = None
         elif self.bm25 is None:
@@ -534,9 +542,61 @@ class Retriever:
                            for i in range(len(queries))]) if len(queries) else np.zeros((0, 768), np.float32)
         return ids, qv
 
+    # ------------------------------------------------------------------ query-biased snippets (msr_best_windows, DESIGN K14)
+    def _check_snippets(self, snippet_tokens):
+        """What snippets=True needs, checked before any device work: a window of 1 .. MSR_PROX_MAX_SPAN tokens and the spans of a
+        custom tokenizer (ValueError); an index with a forward index and texts (MsrError, as phrase search)."""
+        from ._abi import MSR_PROX_MAX_SPAN, MsrError
+        if isinstance(snippet_tokens, bool) or not isinstance(snippet_tokens, (int, np.integer)) or \
+                not 1 <= int(snippet_tokens) <= MSR_PROX_MAX_SPAN:
+            raise ValueError(f"snippet_tokens must be 1 .. MSR_PROX_MAX_SPAN = {MSR_PROX_MAX_SPAN} (got {snippet_tokens!r})")
+        if self._tokenizer is not None and self._span_tokenizer is None:
+            raise ValueError("snippets=True with a custom tokenizer needs Retriever(span_tokenizer=...): the tokenizer's "
+                             "(term, begin, end) form (text.simple_tokenize_spans is simple_tokenize's)")
+        if not self.engine.has_tokens:
+            raise MsrError(-2, "snippets: the index has no forward index (tok_off / tok_ids): build it with keep_tokens=True "
+                               "or attach the token streams with index_build.attach_tokens, then update_index")
+        if self.index.texts is None:
+            raise MsrError(-2, "snippets: the index has no texts to cut a passage from")
+
+    def _term_name(self, t):
+        if self._term_names is None:
+            self._term_names = {v: k for k, v in (self.index.vocab or {}).items()}
+        return self._term_names.get(t, str(t))
+
+    def _snippets(self, ids, doc, n, snippet_tokens):
+        """-> {(query, rank index): (snippet, highlights, missing)} for the returned documents that have a window, and per
+        query its row's term strings (None: no row).  ONE best_windows call for all pairs of the call: the row of a query is
+        snippets.query_row of its term ids, the weights term_weights, the span snippet_tokens."""
+        ix, span = self.index, int(snippet_tokens)
+        rows, row_of = [], []
+        for q in range(len(ids)):
+            row = query_row(ix, ids[q]) if int(n[q]) else None
+            row_of.append(None if row is None else len(rows))
+            if row is not None:
+                rows.append(row)
+        names = [None if r is None else [self._term_name(t) for t in rows[r]] for r in row_of]
+        pq = [q for q in range(len(ids)) if row_of[q] is not None for _ in range(int(n[q]))]
+        pr = [r for q in range(len(ids)) if row_of[q] is not None for r in range(int(n[q]))]
+        if not pq:
+            return {}, names
+        pair_doc = doc[pq, pr]
+        out = self.engine.best_windows(pair_doc, [row_of[q] for q in pq], rows, [term_weights(ix, row) for row in rows], span)
+        start, _, _, mask, terms = [x.cpu().numpy() for x in out]
+        mask, terms = mask.view(np.uint64), terms.view(np.uint32)
+        titles, texts, got = ix.titles, ix.texts, {}
+        for i, (q, r) in enumerate(zip(pq, pr)):
+            if start[i] < 0:
+                continue
+            d = int(pair_doc[i])
+            snippet, highlights = render(titles[d] if titles is not None else None, texts[d], int(start[i]), int(mask[i]), span,
+                                         self._span_tokenizer)
+            got[q, r] = (snippet, highlights, [w for j, w in enumerate(names[q]) if not int(terms[i]) >> j & 1])
+        return got, names
+
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
-                     must_phrases=None, must_not_phrases=None, proximity=False):
+                     must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
@@ -556,8 +616,19 @@ class Retriever:
         proximity=True: phrases=True, and `"a b"~N` / `"a b"~>N` are proximity conditions (text.parse_proximity): the words
         within a window with up to N other tokens among them, in any order / in this order.  A text.Near in must_phrases /
         must_not_phrases (terms: a string or a list of term strings) is such a condition without the text syntax.  A slop
-        below 0, more than 16 terms or a window of more than 64 tokens raises ValueError.  Off by default."""
+        below 0, more than 16 terms or a window of more than 64 tokens raises ValueError.  Off by default.
+        snippets=True (DESIGN K14): every row's "snippet" is the passage of the page that holds the most of the query -- the
+        window of snippet_tokens (1 .. 64) tokens of its indexed stream with the largest summed weight of distinct query terms
+        (snippets.term_weights: the idf; then the most occurrences, then the earliest), found by ONE DeviceEngine.best_windows
+        call for all returned documents of the call and cut from the page by snippets.render -- and the row gains
+        "highlights" ([begin, end) offsets of the query's terms in the snippet) and "missing" (the query's terms the passage
+        lacks).  Documents, ranks and scores are unchanged.  A page without a query term (a dense-only hybrid hit) and a
+        query of unknown words keep the reference's snippet, with "highlights": [] and every term of the row missing.  A
+        custom tokenizer needs Retriever(span_tokenizer=...) (ValueError); the index needs a forward index and texts
+        (MsrError).  Off by default: without it the call uploads, launches and returns exactly what it did."""
         _check_mode(mode)
+        if snippets:
+            self._check_snippets(snippet_tokens)
         ids, qv, ops = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not, phrases, must_phrases,
                                          must_not_phrases, proximity)
         src = None
@@ -567,6 +638,7 @@ class Retriever:
         else:
             doc, score, _, n = self.final_lists(ids, qv, top_k, within=within, **ops)
         ix = self.index
+        passages, row_names = self._snippets(ids, doc, n, snippet_tokens) if snippets else (None, None)
         out = []
         for q in range(len(queries)):
             rows = []
@@ -582,37 +654,49 @@ class Retriever:
                              "domain": extract_domain_topic(url), "doc_id": str(int(self._ids[i]))})
                 if src is not None:
                     rows[-1]["matched_by"] = MATCHED_BY[int(src[q, r])]
+                if snippets:
+                    hit = passages.get((q, r))
+                    if hit is not None:
+                        rows[-1]["snippet"] = hit[0]
+                    rows[-1]["highlights"] = hit[1] if hit is not None else []
+                    rows[-1]["missing"] = hit[2] if hit is not None else list(row_names[q] or [])
             out.append(rows)
         return out
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-               must_not_phrases=None, proximity=False):
+               must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS):
         """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
-        list of phrases (or text.Near conditions) each."""
+        list of phrases (or text.Near conditions) each; snippets / snippet_tokens: search_batch."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
                                  mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
                                  must_not=None if must_not is None else [must_not], phrases=phrases,
                                  must_phrases=None if must_phrases is None else [must_phrases],
                                  must_not_phrases=None if must_not_phrases is None else [must_not_phrases],
-                                 proximity=proximity)[0]
+                                 proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens)[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-                     must_not_phrases=None, proximity=False):
+                     must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
         search_batch (the entries keep the reference's keys in either mode); operators / must / must_not / phrases /
-        must_phrases / must_not_phrases / proximity: search_batch."""
+        must_phrases / must_not_phrases / proximity: search_batch.  snippets=True: every entry gains "snippet" (None where the
+        page has no window), "highlights" and "missing" as in search_batch; the formatted lines are what they were."""
         _check_mode(mode)
+        if snippets:
+            self._check_snippets(snippet_tokens)
         ids, qv, ops = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators, must, must_not,
                                          phrases, must_phrases, must_not_phrases, proximity)
         doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
-        return BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
+        lines = BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
+        if snippets:
+            lines.passages, lines.row_names = self._snippets(ids, doc, n, snippet_tokens)
+        return lines
 
     def batch_search_to_file(self, queries_path, out_path, query_embeddings=None, term_lists=None, chunk=None):
         """search_api.py:331-367: queries.txt -> one formatted line per result in out_path; -> number of lines.  (Quotes and
@@ -669,6 +753,7 @@ class BatchLines:
         self.query_nums, self.doc, self.score, self.n, self.urls, self._fmt = query_nums, doc, score, n, urls, formatter
         self._start = np.zeros(len(n) + 1, np.int64)
         np.cumsum(n, out=self._start[1:])
+        self.passages = self.row_names = None                # Retriever.batch_search(snippets=True) fills them
 
     def __len__(self):
         return int(self._start[-1])
@@ -678,8 +763,13 @@ class BatchLines:
         url = (self.urls[i] if self.urls is not None else "") or ""
         sc = float(self.score[q, r])
         qn = self.query_nums[q]
-        return {"query_num": qn, "rank": r + 1, "url": url, "score": f"{sc:.3f}",
-                "formatted_line": format_result_line(qn, r + 1, url, sc)}
+        entry = {"query_num": qn, "rank": r + 1, "url": url, "score": f"{sc:.3f}",
+                 "formatted_line": format_result_line(qn, r + 1, url, sc)}
+        if self.passages is not None:
+            hit = self.passages.get((q, r))
+            entry.update(snippet=hit[0] if hit else None, highlights=hit[1] if hit else [],
+                         missing=hit[2] if hit else list(self.row_names[q] or []))
+        return entry
 
     def __getitem__(self, k):
         if isinstance(k, slice):

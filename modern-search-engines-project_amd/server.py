@@ -71,6 +71,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         must_phrases: Optional[List[Union[str, NearSpec]]] = None
         must_not_phrases: Optional[List[Union[str, NearSpec]]] = None
         proximity: bool = False       # phrases, and `"a b"~N` / `"a b"~>N`: the words within a window (text.parse_proximity)
+        snippets: bool = False        # every row's snippet is the page's best passage for the query, with "highlights" and
+        snippet_tokens: int = 30      # "missing" (Retriever.search, DESIGN K14); the passage's width in tokens, 1 .. 64
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -139,10 +141,12 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                                                                for p in ps]
                     kw.update(phrases=req.phrases, proximity=req.proximity, must_phrases=cond(req.must_phrases),
                               must_not_phrases=cond(req.must_not_phrases))
+                if req.snippets:
+                    kw.update(snippets=True, snippet_tokens=req.snippet_tokens)
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
-                if req.mode == "lexical" and not near:
+                if req.mode == "lexical" and not near and not req.snippets:
                     raise
                 return JSONResponse(status_code=400, content={"error": str(e)})      # a dense_k the engine cannot hold
             llm_response = ""

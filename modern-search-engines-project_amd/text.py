@@ -65,6 +65,14 @@ def simple_tokenize(text: str):
     return [m.group(0).lower() for m in _WORD.finditer(text)]
 
 
+def simple_tokenize_spans(text: str):
+    """simple_tokenize with each token's place: a generator of (term, begin, end), text[begin:end] being the match the term
+    came from -- the same matches in the same order, so token i of a document's indexed stream is the i-th item.  Lazy: the
+    snippet renderer (snippets.render) stops at its window's end and a long page is never tokenised whole."""
+    for m in _WORD.finditer(text):
+        yield m.group(0).lower(), m.start(), m.end()
+
+
 def parse_operators(processed_query: str):
     """Search-box operators of a query that has been through preprocess_query -> (scoring_text, must_words, not_words).
     A whitespace-delimited token that starts with `+` or `-` FOLLOWED BY A LETTER is an operator token: `+word` -- the page
