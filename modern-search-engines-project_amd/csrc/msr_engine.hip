@@ -850,23 +850,42 @@ extern "C" int msr_bm25_topk_within(msr_engine* e, const int32_t* q_term_off, co
                           out_n, stream, set_bits, n_sets, set_stride, q_set);
 }
 
+// K12 - K14 read the forward index: refused until msr_bind_tokens has bound one to the bound postings.
+static int tokens_bound(msr_engine* e, const char* fn) {
+    if (e->have_postings && e->have_tokens) return MSR_OK;
+    return fail(e, MSR_ERR_NOT_BOUND, "%s: tokens not bound (msr_bind_tokens: the index has no forward index)", fn);
+}
+
+// The refusals that the calls writing bitset rows share (K11 - K13, msr_combine_sets): n_rows rows out, described by arrays of
+// the call's own (rows_ok: out_bits and they are non-NULL; rows_what names them), and n_in rows in -- base, candidate or input
+// rows (in_ok: their pointers are non-NULL).  Checked as the header says, before anything is launched (outputs untouched).
+static int set_rows_args_ok(msr_engine* e, const char* fn, int32_t n_rows, bool rows_ok, const char* rows_what, int64_t out_stride,
+                            const char* n_in_name, int32_t n_in, bool in_ok, const char* in_what, const char* in_stride_name,
+                            int64_t in_stride) {
+    const int64_t W = (e->bm25.n_docs + 31) / 32;
+    if (n_rows < 0 || n_in < 0) return fail(e, MSR_ERR_INVALID, "%s: bad argument (n_rows=%d, %s=%d)", fn, n_rows, n_in_name, n_in);
+    if (n_rows > 0 && !rows_ok)
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (%s is NULL with n_rows=%d)", fn, rows_what, n_rows);
+    if (out_stride < W)
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)", fn, (long long)out_stride,
+                    (long long)W);
+    if (n_in > 0 && !in_ok)
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (%s is NULL with %s=%d)", fn, in_what, n_in_name, n_in);
+    if (n_in > 0 && in_stride < W)
+        return fail(e, MSR_ERR_INVALID, "%s: bad argument (%s=%lld < ceil(n_docs / 32) = %lld)", fn, in_stride_name,
+                    (long long)in_stride, (long long)W);
+    return MSR_OK;
+}
+
 extern "C" int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_off, const int32_t* must_terms,
                              const int32_t* not_off, const int32_t* not_terms, const uint32_t* base_bits, int32_t n_base,
                              int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride, void* stream) {
     if (!e) return MSR_ERR_INVALID;
     if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_term_sets: postings not bound");
-    const int64_t W = (e->bm25.n_docs + 31) / 32;
-    if (n_rows < 0 || n_base < 0) return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (n_rows=%d, n_base=%d)", n_rows, n_base);
-    if (n_rows > 0 && (!out_bits || !must_off || !not_off))
-        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (out_bits, must_off or not_off is NULL with n_rows=%d)", n_rows);
-    if (out_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)out_stride, (long long)W);
-    if (n_base > 0 && (!base_bits || !row_base))
-        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (base_bits or row_base is NULL with n_base=%d)", n_base);
-    if (n_base > 0 && base_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_term_sets: bad argument (base_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)base_stride, (long long)W);
+    const int rc = set_rows_args_ok(e, "msr_term_sets", n_rows, out_bits && must_off && not_off, "out_bits, must_off or not_off",
+                                    out_stride, "n_base", n_base, base_bits && row_base, "base_bits or row_base", "base_stride",
+                                    base_stride);
+    if (rc) return rc;
     if (n_rows == 0) return MSR_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_term_sets_run(e->bm25, n_rows, must_off, must_terms, not_off, not_terms, base_bits, n_base, base_stride,
@@ -908,20 +927,11 @@ extern "C" int msr_phrase_sets(msr_engine* e, int32_t n_rows, const int32_t* phr
                                const uint32_t* cand_bits, int32_t n_cand, int64_t cand_stride, const int32_t* row_cand,
                                uint32_t* out_bits, int64_t out_stride, void* stream) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_postings || !e->have_tokens)
-        return fail(e, MSR_ERR_NOT_BOUND, "msr_phrase_sets: tokens not bound (msr_bind_tokens: the index has no forward index)");
-    const int64_t W = (e->bm25.n_docs + 31) / 32;
-    if (n_rows < 0 || n_cand < 0) return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (n_rows=%d, n_cand=%d)", n_rows, n_cand);
-    if (n_rows > 0 && (!out_bits || !phrase_off))
-        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (out_bits or phrase_off is NULL with n_rows=%d)", n_rows);
-    if (out_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)out_stride, (long long)W);
-    if (n_cand > 0 && (!cand_bits || !row_cand))
-        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (cand_bits or row_cand is NULL with n_cand=%d)", n_cand);
-    if (n_cand > 0 && cand_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_phrase_sets: bad argument (cand_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)cand_stride, (long long)W);
+    int rc = tokens_bound(e, "msr_phrase_sets");
+    if (rc) return rc;
+    rc = set_rows_args_ok(e, "msr_phrase_sets", n_rows, out_bits && phrase_off, "out_bits or phrase_off", out_stride, "n_cand", n_cand,
+                          cand_bits && row_cand, "cand_bits or row_cand", "cand_stride", cand_stride);
+    if (rc) return rc;
     if (n_rows == 0) return MSR_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_phrase_sets_run(e->tok_off, e->tok_ids, e->bm25.n_docs, e->bm25.n_terms, n_rows, phrase_off, phrase_terms,
@@ -935,22 +945,12 @@ extern "C" int msr_proximity_sets(msr_engine* e, int32_t n_rows, const int32_t* 
                                   int64_t cand_stride, const int32_t* row_cand, uint32_t* out_bits, int64_t out_stride,
                                   void* stream) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_postings || !e->have_tokens)
-        return fail(e, MSR_ERR_NOT_BOUND, "msr_proximity_sets: tokens not bound (msr_bind_tokens: the index has no forward index)");
-    const int64_t W = (e->bm25.n_docs + 31) / 32;
-    if (n_rows < 0 || n_cand < 0)
-        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (n_rows=%d, n_cand=%d)", n_rows, n_cand);
-    if (n_rows > 0 && (!out_bits || !phrase_off || !row_span || !row_ordered))
-        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (out_bits, phrase_off, row_span or row_ordered is NULL "
-                    "with n_rows=%d)", n_rows);
-    if (out_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)out_stride, (long long)W);
-    if (n_cand > 0 && (!cand_bits || !row_cand))
-        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (cand_bits or row_cand is NULL with n_cand=%d)", n_cand);
-    if (n_cand > 0 && cand_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_proximity_sets: bad argument (cand_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)cand_stride, (long long)W);
+    int rc = tokens_bound(e, "msr_proximity_sets");
+    if (rc) return rc;
+    rc = set_rows_args_ok(e, "msr_proximity_sets", n_rows, out_bits && phrase_off && row_span && row_ordered,
+                          "out_bits, phrase_off, row_span or row_ordered", out_stride, "n_cand", n_cand, cand_bits && row_cand,
+                          "cand_bits or row_cand", "cand_stride", cand_stride);
+    if (rc) return rc;
     if (n_rows == 0) return MSR_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_proximity_sets_run(e->tok_off, e->tok_ids, e->bm25.n_docs, e->bm25.n_terms, n_rows, phrase_off, phrase_terms,
@@ -965,8 +965,8 @@ extern "C" int msr_best_windows(msr_engine* e, int32_t n_pairs, const int32_t* p
                                 const int32_t* row_span, int32_t* out_start, int32_t* out_cover, int32_t* out_hits,
                                 uint64_t* out_mask, uint32_t* out_terms, void* stream) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_postings || !e->have_tokens)
-        return fail(e, MSR_ERR_NOT_BOUND, "msr_best_windows: tokens not bound (msr_bind_tokens: the index has no forward index)");
+    const int rc = tokens_bound(e, "msr_best_windows");
+    if (rc) return rc;
     if (n_pairs < 0 || n_rows < 0)
         return fail(e, MSR_ERR_INVALID, "msr_best_windows: bad argument (n_pairs=%d, n_rows=%d)", n_pairs, n_rows);
     if (n_pairs == 0) return MSR_OK;
@@ -988,16 +988,9 @@ extern "C" int msr_combine_sets(msr_engine* e, int32_t n_rows, const int32_t* an
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, void* stream) {
     if (!e) return MSR_ERR_INVALID;
     if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_combine_sets: postings not bound");
-    const int64_t W = (e->bm25.n_docs + 31) / 32;
-    if (n_rows < 0 || n_in < 0) return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (n_rows=%d, n_in=%d)", n_rows, n_in);
-    if (n_rows > 0 && (!out_bits || !and_off || !not_off))
-        return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (out_bits, and_off or not_off is NULL with n_rows=%d)", n_rows);
-    if (out_stride < W)
-        return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (out_stride=%lld < ceil(n_docs / 32) = %lld)",
-                    (long long)out_stride, (long long)W);
-    if (n_in > 0 && (!in_bits || in_stride < W))
-        return fail(e, MSR_ERR_INVALID, "msr_combine_sets: bad argument (in_bits is NULL or in_stride=%lld < ceil(n_docs / 32) = %lld "
-                    "with n_in=%d)", (long long)in_stride, (long long)W, n_in);
+    const int rc = set_rows_args_ok(e, "msr_combine_sets", n_rows, out_bits && and_off && not_off, "out_bits, and_off or not_off",
+                                    out_stride, "n_in", n_in, in_bits != nullptr, "in_bits", "in_stride", in_stride);
+    if (rc) return rc;
     if (n_rows == 0) return MSR_OK;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_combine_sets_run(e->bm25.n_docs, n_rows, and_off, and_rows, not_off, not_rows, in_bits, n_in, in_stride,

@@ -4,10 +4,11 @@
 // msr_phrase_sets is the documents of a candidate set whose OWN stream holds the row's phrase at consecutive positions, as a
 // bitset in the layout of K8 / K11 (document d = bit d & 31 of word d >> 5).
 //
-// One workgroup owns (row, span of MSR_TERMSET_SPAN_DOCS consecutive documents): one 32-bit word per thread, K11's ownership.
-// Thread j loads candidate word j; a span without a candidate stores zeros and leaves (a phrase's intersection leaves most
-// spans empty).  Otherwise the candidates are compacted into an LDS list with popcount prefixes and the four waves take
-// documents from it, one wave per document: the lanes stride the stream 64 tokens at a time (one coalesced 256-byte load),
+// One workgroup owns (row, span of MSR_TERMSET_SPAN_DOCS consecutive documents): one 32-bit word per thread, K11's ownership
+// (msr_tokscan.h: the rule, the candidate word and the compaction, shared with K11 and K13).  Thread j loads candidate word j;
+// a span without a candidate stores zeros and leaves (a phrase's intersection leaves most spans empty).  Otherwise the
+// candidates are compacted into an LDS list and the four waves take documents from it, one wave per document: the lanes
+// stride the stream 64 tokens at a time (one coalesced 256-byte load),
 // a lane whose token equals the phrase's first id reads the following ids (lines the wave has just loaded) and leaves at the
 // first mismatch.  THE BOUND OF EVERY READ IS THE DOCUMENT'S END tok_off[d + 1]: a lane at position i tests only if
 // i + L <= len(d), so a match never crosses into the next document and the last document never reads past the buffer.  The
@@ -20,15 +21,11 @@
 
 #include "../../include/msretr.h"
 #include "msr_internal.h"
+#include "msr_tokscan.h"
 
 namespace {
 
-constexpr int PH_SPAN = MSR_TERMSET_SPAN_DOCS;
-constexpr int PH_THREADS = PH_SPAN / 32;                 // one word of the span per thread
-constexpr int PH_WAVES = PH_THREADS / 64;
-constexpr int PH_MAX = MSR_PHRASE_MAX_TERMS;
-static_assert(PH_THREADS == 256, "the candidate compaction assumes four waves of 64");
-static_assert(PH_SPAN <= 65536, "a candidate's offset in its span is kept in 16 bits");
+using namespace tokscan;
 
 struct PhraseArgs {
     const int64_t* tok_off;
@@ -40,33 +37,21 @@ struct PhraseArgs {
     int32_t row0;
 };
 
-// the words of row_sel's set below n_docs: -1 (or no rows at all) = every document, a row of `bits`, anything else = empty
-__device__ __forceinline__ uint32_t set_word(const uint32_t* bits, int32_t n_rows, int64_t stride, int32_t sel, int64_t w,
-                                             int64_t W, int64_t n_docs) {
-    if (w >= W) return 0;
-    uint32_t acc = (w == W - 1 && (n_docs & 31)) ? (1u << (n_docs & 31)) - 1u : 0xFFFFFFFFu;
-    if (n_rows > 0) {
-        if (sel >= 0 && sel < n_rows) acc &= bits[(int64_t)sel * stride + w];
-        else if (sel != -1) acc = 0;
-    }
-    return acc;
-}
-
-__global__ __launch_bounds__(PH_THREADS) void phrase_sets_kernel(const PhraseArgs a) {
-    __shared__ uint32_t found[PH_THREADS];
-    __shared__ uint16_t list[PH_SPAN];                   // the span's candidate documents (offset in the span), ascending
-    __shared__ int32_t ph[PH_MAX];
-    __shared__ int32_t wave_cnt[PH_WAVES];
+__global__ __launch_bounds__(THREADS) void phrase_sets_kernel(const PhraseArgs a) {
+    __shared__ uint32_t found[THREADS];
+    __shared__ uint16_t list[SPAN];                      // the span's candidate documents (offset in the span), ascending
+    __shared__ int32_t ph[MAX_TERMS];
+    __shared__ int32_t wave_cnt[WAVES];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = a.row0 + (int)blockIdx.y;
-    const int64_t d0 = (int64_t)blockIdx.x * PH_SPAN;
+    const int64_t d0 = (int64_t)blockIdx.x * SPAN;
     const int64_t W = (a.n_docs + 31) >> 5;
     const int64_t w = (d0 >> 5) + tid;                   // this thread's word of the row
     uint32_t acc = set_word(a.cand_bits, a.n_cand, a.cand_stride, a.n_cand > 0 ? a.row_cand[r] : -1, w, W, a.n_docs);
 
-    // the phrase: 1 .. PH_MAX ids inside [0, n_terms), else the row is empty
+    // the phrase: 1 .. MAX_TERMS ids inside [0, n_terms), else the row is empty
     const int p0 = a.phrase_off[r], L = a.phrase_off[r + 1] - p0;
-    int bad = (L < 1 || L > PH_MAX);
+    int bad = (L < 1 || L > MAX_TERMS);
     if (!bad && tid < L) {
         const int32_t t = a.phrase_terms[p0 + tid];
         ph[tid] = t;
@@ -78,26 +63,10 @@ __global__ __launch_bounds__(PH_THREADS) void phrase_sets_kernel(const PhraseArg
         return;
     }
 
-    // compact the candidates: exclusive prefix of the words' popcounts (wave scan, then the four wave totals)
-    const int cnt = __popc(acc);
-    int incl = cnt;
-    for (int s = 1; s < 64; s <<= 1) {
-        const int v = __shfl_up(incl, s);
-        if (lane >= s) incl += v;
-    }
-    if (lane == 63) wave_cnt[wave] = incl;
-    found[tid] = 0;
-    __syncthreads();
-    int base = incl - cnt, total = 0;
-    for (int i = 0; i < PH_WAVES; ++i) {
-        if (i < wave) base += wave_cnt[i];
-        total += wave_cnt[i];
-    }
-    for (uint32_t m = acc; m; m &= m - 1) list[base++] = (uint16_t)(tid * 32 + (__ffs(m) - 1));   // base + cnt <= PH_SPAN
-    __syncthreads();
+    const int total = compact_candidates(acc, tid, lane, wave, found, list, wave_cnt);
 
     const int32_t first = ph[0];
-    for (int c = wave; c < total; c += PH_WAVES) {       // one wave per candidate document (c is uniform in the wave)
+    for (int c = wave; c < total; c += WAVES) {          // one wave per candidate document (c is uniform in the wave)
         const int dl = list[c];
         const int64_t d = d0 + dl;                       // < n_docs: the candidate word was masked
         const int64_t s = a.tok_off[d], e = a.tok_off[d + 1];
@@ -134,7 +103,7 @@ __global__ __launch_bounds__(256) void combine_sets_kernel(const CombineArgs a) 
     const int64_t W = (a.n_docs + 31) >> 5;
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= W) return;
-    uint32_t acc = (w == W - 1 && (a.n_docs & 31)) ? (1u << (a.n_docs & 31)) - 1u : 0xFFFFFFFFu;
+    uint32_t acc = tail_mask(w, W, a.n_docs);
     for (int i = a.and_off[r]; i < a.and_off[r + 1]; ++i) {
         const int32_t s = a.and_rows[i];
         if (s >= 0 && s < a.n_in) acc &= a.in_bits[(int64_t)s * a.in_stride + w];
@@ -164,8 +133,6 @@ __global__ void tokens_validate_kernel(const int64_t* tok_off, const int32_t* to
     if (code) atomicMax(flag, code);
 }
 
-constexpr int ROWS_PER_LAUNCH = 32768;                   // (the grid's y extent is 16 bits)
-
 }  // namespace
 
 hipError_t msr_tokens_validate(const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_tokens, int64_t n_terms,
@@ -180,34 +147,14 @@ hipError_t msr_phrase_sets_run(const int64_t* tok_off, const int32_t* tok_ids, i
                                const int32_t* phrase_off, const int32_t* phrase_terms, const uint32_t* cand_bits, int n_cand,
                                int64_t cand_stride, const int32_t* row_cand, uint32_t* out_bits, int64_t out_stride,
                                hipStream_t stream) {
-    if (n_rows <= 0) return hipSuccess;
-    const int64_t n_spans = (n_docs + PH_SPAN - 1) / PH_SPAN;
-    if (n_spans <= 0) return hipSuccess;
-    PhraseArgs a{tok_off, tok_ids, n_docs, n_terms, phrase_off, phrase_terms, cand_bits, n_cand, cand_stride, row_cand,
-                 out_bits, out_stride, 0};
-    for (int r0 = 0; r0 < n_rows; r0 += ROWS_PER_LAUNCH) {
-        a.row0 = r0;
-        const dim3 grid((unsigned)n_spans, (unsigned)std::min(ROWS_PER_LAUNCH, n_rows - r0));
-        hipLaunchKernelGGL(phrase_sets_kernel, grid, dim3(PH_THREADS), 0, stream, a);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
+    const PhraseArgs a{tok_off, tok_ids, n_docs, n_terms, phrase_off, phrase_terms, cand_bits, n_cand, cand_stride, row_cand,
+                       out_bits, out_stride, 0};
+    return launch_rows(phrase_sets_kernel, span_count(n_docs), THREADS, n_rows, a, stream);
 }
 
 hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream) {
-    if (n_rows <= 0) return hipSuccess;
-    const int64_t W = (n_docs + 31) / 32;
-    if (W <= 0) return hipSuccess;
-    CombineArgs a{and_off, and_rows, not_off, not_rows, in_bits, n_in, in_stride, out_bits, out_stride, n_docs, 0};
-    for (int r0 = 0; r0 < n_rows; r0 += ROWS_PER_LAUNCH) {
-        a.row0 = r0;
-        const dim3 grid((unsigned)((W + 255) / 256), (unsigned)std::min(ROWS_PER_LAUNCH, n_rows - r0));
-        hipLaunchKernelGGL(combine_sets_kernel, grid, dim3(256), 0, stream, a);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
+    const CombineArgs a{and_off, and_rows, not_off, not_rows, in_bits, n_in, in_stride, out_bits, out_stride, n_docs, 0};
+    return launch_rows(combine_sets_kernel, ((n_docs + 31) / 32 + 255) / 256, 256, n_rows, a, stream);
 }

@@ -9,30 +9,25 @@
 // without a pair or with an invalid one writes its answer and leaves.  Lane j loads term j and weight j of the row; a repeated
 // id loses its weight and its bit before the scan (lane j compares its id with the lanes below it).
 //
-// The scan is K13's (msr_proximity.hip, restated here so that that kernel and its recorded resources stay what they are) with
-// another evaluation: the wave walks the document in chunks of 64 tokens, lane l = position b0 + l, one coalesced 256-byte
-// load per chunk, the chunk after the next in flight.  THE BOUND OF EVERY READ IS THE DOCUMENT'S END tok_off[d + 1]: a lane at
-// or past it loads nothing and holds -1, which equals no term of a valid row, so a window never leaves the document and the
-// last document never reads past the buffer.  Per chunk and term j one __ballot(tok == p[j]) gives a wave-uniform 64-bit mask;
-// the masks of the current and of the next chunk are kept (span <= 64).  Lane l's view of term j is the 128-bit pair shifted
-// right by l and cut to `span` bits; cover = the sum of w[j] over non-zero views, hits = the popcount of the OR of the views
-// (a position holds one token: the union counts every hit once), and that OR is the window's mask.  Every lane keeps the best
-// key of the starts it has seen, packed (cover, hits, -start) into one 64-bit integer, with that start's mask and term bits;
-// ONE wave reduction at the document's end picks the winner, and lane 0 stores the five values.  Every chunk is read: there
-// is no early exit.
+// The scan is the chunk walker of msr_tokscan.h (shared with K13; the read bound, the ballots and a lane's 128-bit view of a
+// term are explained there) with another evaluation.  Lane l's view of term j is cut to `span` bits; cover = the sum of w[j]
+// over non-zero views, hits = the popcount of the OR of the views (a position holds one token: the union counts every hit
+// once), and that OR is the window's mask.  Every lane keeps the best key of the starts it has seen, packed (cover, hits,
+// -start) into one 64-bit integer, with that start's mask and term bits; ONE wave reduction at the document's end picks the
+// winner, and lane 0 stores the five values.  Every chunk is read: there is no early exit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/msretr.h"
 #include "msr_internal.h"
+#include "msr_tokscan.h"
 
 namespace {
 
 constexpr int SN_WAVES = 4;
 constexpr int SN_THREADS = SN_WAVES * 64;
-constexpr int SN_MAX = MSR_PHRASE_MAX_TERMS;
+constexpr int SN_MAX = tokscan::MAX_TERMS;
 static_assert(SN_MAX <= 32, "lane j of a wave holds term j, and out_terms has a bit per term");
-static_assert(MSR_PROX_MAX_SPAN == 64, "a window spans at most the current chunk and the next");
 // the key: cover in bits 38 .. 62, hits in bits 31 .. 37, 0x7FFFFFFF - start in bits 0 .. 30
 static_assert((int64_t)SN_MAX * MSR_SNIPPET_MAX_WEIGHT < (1ll << 25), "cover has 25 bits of the key");
 static_assert(MSR_PROX_MAX_SPAN < (1 << 7), "hits has 7 bits of the key");
@@ -47,11 +42,6 @@ struct SnipArgs {
     int32_t n_rows; const int32_t* row_off; const int32_t* row_terms; const int32_t* row_weights; const int32_t* row_span;
     int32_t* out_start; int32_t* out_cover; int32_t* out_hits; uint64_t* out_mask; uint32_t* out_terms;
 };
-
-// this lane's view of a term: bit k = the term stands at (chunk start + lane + k); a shift by 64 is undefined, lane 0 takes cur
-__device__ __forceinline__ uint64_t view(uint64_t cur, uint64_t nxt, int lane) {
-    return lane ? (cur >> lane) | (nxt << (64 - lane)) : cur;
-}
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
@@ -68,33 +58,26 @@ __device__ __forceinline__ void store(const SnipArgs& a, int i, int32_t start, i
     a.out_start[i] = start; a.out_cover[i] = cover; a.out_hits[i] = hits; a.out_mask[i] = mask; a.out_terms[i] = terms;
 }
 
-// One wave's walk of document [s, e), a row of at most LM terms (the loops over j are unrolled to LM, so that every mask has
-// a register of its own: 2 LM wave-uniform 64-bit masks are alive at once).  mine / myw: lane j's id and weight, a lane
-// without a term (or with a repeated one) holds -2 and 0.
+// One wave's walk of document [s, e), a row of at most LM terms.  mine / myw: lane j's id and weight, a lane without a term (or
+// with a repeated one) holds -2 and 0.
 template <int LM>
 __device__ __forceinline__ void scan_document(const SnipArgs& a, int i, int64_t s, int64_t e, int lane, int32_t mine, int32_t myw,
                                               int L, int span) {
-    const uint64_t cut = span == 64 ? ~0ull : (1ull << span) - 1ull;
-    int64_t pos = s + lane;
-    const int32_t t_cur = pos < e ? a.tok_ids[pos] : -1;     // chunk 0 ...
-    pos += 64;
-    int32_t t_nxt = pos < e ? a.tok_ids[pos] : -1;           // ... and chunk 1: both loads are issued before the first ballot
-    uint64_t cur[LM], nxt[LM];
-#pragma unroll
-    for (int j = 0; j < LM; ++j) {
-        cur[j] = 0; nxt[j] = 0;
-        if (j < L) cur[j] = __ballot(t_cur == __builtin_amdgcn_readlane(mine, j));
-    }
+    using namespace tokscan;
+    const uint64_t cut = window_cut(span);
+    uint64_t cur[LM], nxt[LM];                               // (never members of a struct: msr_tokscan.h)
+    int64_t pos;
+    int32_t t_nxt;
+    walk_start<LM>(a.tok_ids, s, e, lane, mine, L, cur, nxt, pos, t_nxt);
     uint64_t best = 0, best_mask = 0;                        // 0: no start with a hit seen yet
     uint32_t best_terms = 0;
     for (int64_t b0 = s; b0 < e; b0 += 64) {
-        pos += 64;
-        const int32_t t_far = pos < e ? a.tok_ids[pos] : -1; // the chunk after the next: in flight during the evaluation
+        const int32_t t_far = load_token(a.tok_ids, pos += 64, e);   // the chunk after the next
         uint64_t any = 0;
 #pragma unroll
         for (int j = 0; j < LM; ++j)
             if (j < L) {
-                nxt[j] = __ballot(t_nxt == __builtin_amdgcn_readlane(mine, j));
+                nxt[j] = term_mask(t_nxt, mine, j);
                 any |= cur[j] | nxt[j];
             }
         if (any) {                                           // (a start of this chunk sees a hit only in these two chunks)
@@ -115,9 +98,7 @@ __device__ __forceinline__ void scan_document(const SnipArgs& a, int i, int64_t 
                                  (uint64_t)(KEY_START - (uint32_t)start);
             if (b0 + lane < e && hits > 0 && key > best) { best = key; best_mask = un; best_terms = tb; }
         }
-#pragma unroll
-        for (int j = 0; j < LM; ++j) cur[j] = nxt[j];
-        t_nxt = t_far;
+        walk_roll<LM>(cur, nxt, t_nxt, t_far);
     }
     uint64_t top = best;
     for (int m = 32; m; m >>= 1) {

@@ -3,8 +3,9 @@
 // Row r of the output is  base(r)  AND  D(t) for every must term t  AND NOT  D(t) for every not term t,  as a bitset in the
 // layout of K8 (document d = bit d & 31 of word d >> 5): the producer of the rows that msr_*_topk_within consume.
 //
-// One workgroup owns (row, span of MSR_TERMSET_SPAN_DOCS consecutive documents): one 32-bit word per thread.  The row's
-// accumulator word lives in a register of its thread, the bits of ONE posting list (or of all not lists together) in LDS.
+// One workgroup owns (row, span of MSR_TERMSET_SPAN_DOCS consecutive documents): one 32-bit word per thread (the ownership
+// rule, its constants and the base word of a row stand in msr_tokscan.h, which K12 and K13 share).  The row's accumulator word
+// lives in a register of its thread, the bits of ONE posting list (or of all not lists together) in LDS.
 // Per term one thread finds the postings of the span -- two loads of the BM25 skip table for a long list, a binary search
 // on post_doc otherwise; up to 256 terms' searches run side by side -- then the workgroup streams post_doc (4 bytes per
 // posting) and ORs a bit per posting into LDS: an OR is order-independent, so the words do not depend on the schedule.
@@ -13,17 +14,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "../../include/msretr.h"
 #include "msr_internal.h"
+#include "msr_tokscan.h"
 
 namespace {
 
-constexpr int TS_SPAN = MSR_TERMSET_SPAN_DOCS;
-constexpr int TS_THREADS = TS_SPAN / 32;                 // one word of the span per thread
-static_assert(TS_SPAN % MSR_BM25_TILE == 0, "a span is a whole number of skip-table tiles");
-static_assert(TS_THREADS >= 64 && TS_THREADS <= 1024 && TS_THREADS % 64 == 0, "one workgroup of whole waves per span");
+using namespace tokscan;
+static_assert(SPAN % MSR_BM25_TILE == 0, "a span is a whole number of skip-table tiles");
 
 struct TermSetArgs {
     const int64_t* term_off;
@@ -39,27 +37,27 @@ struct TermSetArgs {
     int32_t row0;
 };
 
-// [*lo, *hi): the postings of term t (a valid id) whose document lies in [d0, d0 + TS_SPAN).
+// [*lo, *hi): the postings of term t (a valid id) whose document lies in [d0, d0 + SPAN).
 __device__ __forceinline__ void span_postings(const TermSetArgs& a, int32_t t, int64_t d0, int64_t* lo, int64_t* hi) {
     const int64_t p0 = a.term_off[t], p1 = a.term_off[t + 1];
     const int32_t h = a.heavy_id ? a.heavy_id[t] : -1;
     if (h >= 0) {
         const uint32_t* row = a.tile_off + (int64_t)h * (a.n_tiles + 1);
         const int32_t t0 = (int32_t)(d0 / MSR_BM25_TILE);
-        const int32_t t1 = min(t0 + TS_SPAN / MSR_BM25_TILE, a.n_tiles);
+        const int32_t t1 = min(t0 + SPAN / MSR_BM25_TILE, a.n_tiles);
         *lo = p0 + row[t0];
         *hi = p0 + row[t1];
         return;
     }
-    // first posting with document >= d0, then (from there on) the first with document >= d0 + TS_SPAN
+    // first posting with document >= d0, then (from there on) the first with document >= d0 + SPAN
     int64_t l = p0, r = p1;
     while (l < r) {
         const int64_t m = l + ((r - l) >> 1);
         if (a.post_doc[m] < d0) l = m + 1; else r = m;
     }
     *lo = l;
-    r = min(p1, l + TS_SPAN);                            // documents ascend strictly: a span holds at most TS_SPAN postings
-    const int64_t d1 = d0 + TS_SPAN;
+    r = min(p1, l + SPAN);                               // documents ascend strictly: a span holds at most SPAN postings
+    const int64_t d1 = d0 + SPAN;
     while (l < r) {
         const int64_t m = l + ((r - l) >> 1);
         if (a.post_doc[m] < d1) l = m + 1; else r = m;
@@ -70,35 +68,27 @@ __device__ __forceinline__ void span_postings(const TermSetArgs& a, int32_t t, i
 // bits |= the documents of postings [lo, hi) (all inside the span; the range test keeps a malformed table out of LDS)
 __device__ __forceinline__ void or_postings(const int32_t* __restrict__ post_doc, int64_t lo, int64_t hi, int64_t d0,
                                             uint32_t* bits) {
-    for (int64_t p = lo + threadIdx.x; p < hi; p += TS_THREADS) {
+    for (int64_t p = lo + threadIdx.x; p < hi; p += THREADS) {
         const int64_t d = (int64_t)post_doc[p] - d0;
-        if (d >= 0 && d < TS_SPAN) atomicOr(&bits[d >> 5], 1u << (d & 31));
+        if (d >= 0 && d < SPAN) atomicOr(&bits[d >> 5], 1u << (d & 31));
     }
 }
 
-__global__ __launch_bounds__(TS_THREADS) void term_sets_kernel(const TermSetArgs a) {
-    __shared__ uint32_t bits[TS_THREADS];
-    __shared__ int64_t r_lo[TS_THREADS], r_hi[TS_THREADS];   // the span's postings of up to TS_THREADS terms, found side by side
+__global__ __launch_bounds__(THREADS) void term_sets_kernel(const TermSetArgs a) {
+    __shared__ uint32_t bits[THREADS];
+    __shared__ int64_t r_lo[THREADS], r_hi[THREADS];         // the span's postings of up to THREADS terms, found side by side
     const int tid = (int)threadIdx.x;
     const int r = a.row0 + (int)blockIdx.y;
-    const int64_t d0 = (int64_t)blockIdx.x * TS_SPAN;
+    const int64_t d0 = (int64_t)blockIdx.x * SPAN;
     const int64_t W = (a.n_docs + 31) >> 5;
     const int64_t w = (d0 >> 5) + tid;                   // this thread's word of the row
     const int m0 = a.must_off[r], m1 = a.must_off[r + 1], x0 = a.not_off[r], x1 = a.not_off[r + 1];
 
     // base(r), without the bits at or above n_docs
-    uint32_t acc = 0;
-    if (w < W) {
-        acc = (w == W - 1 && (a.n_docs & 31)) ? (1u << (a.n_docs & 31)) - 1u : 0xFFFFFFFFu;
-        if (a.n_base > 0) {
-            const int32_t b = a.row_base[r];
-            if (b >= 0 && b < a.n_base) acc &= a.base_bits[(int64_t)b * a.base_stride + w];
-            else if (b != -1) acc = 0;
-        }
-    }
+    uint32_t acc = set_word(a.base_bits, a.n_base, a.base_stride, a.n_base > 0 ? a.row_base[r] : -1, w, W, a.n_docs);
     // a must term the index lacks (or whose list is empty) empties the row whatever the others hold
     int lacks = 0;
-    for (int i = m0 + tid; i < m1; i += TS_THREADS) {
+    for (int i = m0 + tid; i < m1; i += THREADS) {
         const int32_t t = a.must_terms[i];
         if (t < 0 || t >= a.n_terms || a.term_off[t] == a.term_off[t + 1]) lacks = 1;
     }
@@ -107,8 +97,8 @@ __global__ __launch_bounds__(TS_THREADS) void term_sets_kernel(const TermSetArgs
 
     // must terms: thread j finds the span's postings of the round's j-th term (the searches' dependent loads run side by side
     // instead of one term after the other), then the lists are folded in one at a time
-    for (int i0 = m0; i0 < m1 && alive; i0 += TS_THREADS) {
-        const int cnt = min(TS_THREADS, m1 - i0);
+    for (int i0 = m0; i0 < m1 && alive; i0 += THREADS) {
+        const int cnt = min(THREADS, m1 - i0);
         if (tid < cnt) span_postings(a, a.must_terms[i0 + tid], d0, &r_lo[tid], &r_hi[tid]);   // (alive: every must id is valid)
         __syncthreads();
         for (int k = 0; k < cnt && alive; ++k) {
@@ -122,8 +112,8 @@ __global__ __launch_bounds__(TS_THREADS) void term_sets_kernel(const TermSetArgs
     }
     if (alive && x0 < x1) {                              // the not lists share one OR
         bits[tid] = 0;
-        for (int i0 = x0; i0 < x1; i0 += TS_THREADS) {
-            const int cnt = min(TS_THREADS, x1 - i0);
+        for (int i0 = x0; i0 < x1; i0 += THREADS) {
+            const int cnt = min(THREADS, x1 - i0);
             if (tid < cnt) {
                 const int32_t t = a.not_terms[i0 + tid];
                 int64_t lo = 0, hi = 0;
@@ -145,18 +135,7 @@ hipError_t msr_term_sets_run(const Bm25Index& ix, int n_rows, const int32_t* mus
                              const int32_t* not_off, const int32_t* not_terms, const uint32_t* base_bits, int n_base,
                              int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride,
                              hipStream_t stream) {
-    if (n_rows <= 0) return hipSuccess;
-    const int64_t n_spans = (ix.n_docs + TS_SPAN - 1) / TS_SPAN;
-    if (n_spans <= 0) return hipSuccess;
-    TermSetArgs a{ix.term_off, ix.post_doc, ix.heavy_id, ix.tile_off, ix.n_terms, ix.n_docs, ix.n_tiles,
-                  must_off, must_terms, not_off, not_terms, base_bits, n_base, base_stride, row_base, out_bits, out_stride, 0};
-    constexpr int ROWS_PER_LAUNCH = 32768;               // (the grid's y extent is 16 bits)
-    for (int r0 = 0; r0 < n_rows; r0 += ROWS_PER_LAUNCH) {
-        a.row0 = r0;
-        const dim3 grid((unsigned)n_spans, (unsigned)std::min(ROWS_PER_LAUNCH, n_rows - r0));
-        hipLaunchKernelGGL(term_sets_kernel, grid, dim3(TS_THREADS), 0, stream, a);
-        const hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
+    const TermSetArgs a{ix.term_off, ix.post_doc, ix.heavy_id, ix.tile_off, ix.n_terms, ix.n_docs, ix.n_tiles, must_off,
+                        must_terms, not_off, not_terms, base_bits, n_base, base_stride, row_base, out_bits, out_stride, 0};
+    return launch_rows(term_sets_kernel, span_count(ix.n_docs), THREADS, n_rows, a, stream);
 }
