@@ -40,7 +40,9 @@ extern "C" {
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
                                      tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets;
                                      13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets;
-                                     15: msr_best_windows */
+                                     15: msr_best_windows; also 15 (calls added, none changed: a library
+                                     that lacks them fails to load by symbol): msr_bind_vocab, msr_fuzzy_scratch_bytes,
+                                     msr_fuzzy_terms */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -49,6 +51,11 @@ extern "C" {
 #define MSR_PHRASE_MAX_TERMS 16    /* msr_phrase_sets / msr_proximity_sets: most term ids a row may hold */
 #define MSR_PROX_MAX_SPAN 64       /* msr_proximity_sets / msr_best_windows: the widest window, in tokens */
 #define MSR_SNIPPET_MAX_WEIGHT (1 << 20) /* msr_best_windows: the largest weight of a term (16 of them sum to 2^24 exactly) */
+#define MSR_FUZZY_MAX_LEN 32       /* msr_fuzzy_terms: the longest word and the longest term, in code points */
+#define MSR_FUZZY_MAX_WORDS 1024   /* msr_fuzzy_terms: most words of one call */
+#define MSR_FUZZY_MAX_LIMIT 16     /* msr_fuzzy_terms: most candidates returned per word */
+#define MSR_FUZZY_SPAN_TERMS 1024  /* msr_fuzzy_terms: consecutive vocabulary terms one workgroup of its first kernel owns */
+#define MSR_FUZZY_WORD_GROUP 16    /* msr_fuzzy_terms: words that kernel stages in LDS at a time */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -309,6 +316,42 @@ int msr_best_windows(msr_engine* e, int32_t n_pairs, const int32_t* pair_doc, co
                      int32_t n_rows, const int32_t* row_off, const int32_t* row_terms, const int32_t* row_weights,
                      const int32_t* row_span, int32_t* out_start, int32_t* out_cover, int32_t* out_hits, uint64_t* out_mask,
                      uint32_t* out_terms, void* stream);
+
+/* Typo-tolerant lookup: the vocabulary terms nearest to a word.
+ *   DISTANCE d(w, t): optimal string alignment (restricted Damerau-Levenshtein) over 16-bit code points: an insertion, a
+ *   deletion, a substitution and a swap of two ADJACENT code points cost 1 each, and no substring is edited twice:
+ *   d("ca", "abc") = 3, d("ab", "ba") = 1.
+ *   CANDIDATES of word w with tolerance m in {0, 1, 2}: the terms t with weight[t] > 0, at most MSR_FUZZY_MAX_LEN code points
+ *   and d(w, t) <= m, ORDERED by distance ascending, then weight descending, then term id ascending (a total order).
+ *
+ * msr_bind_vocab: term t's code points are chars[char_off[t] .. char_off[t + 1]) (char_off int64 [n_terms + 1], chars uint16
+ *   [n_chars], weight uint32 [n_terms]).  Device pointers, caller-owned; the engine keeps the pointers, as it does for the
+ *   tokens.  Checked once on the device (the call synchronises the stream), MSR_ERR_INVALID otherwise: char_off[0] == 0,
+ *   non-decreasing, char_off[n_terms] == n_chars; every weight below 2^31; n_terms equal to the bound postings' term count.
+ *   chars may be NULL when n_chars == 0.  MSR_ERR_NOT_BOUND without postings.  The call builds one table of 8 bytes per term
+ *   (a 64-bit signature of the term's character set, the lookup's filter), owned by the engine, counted by msr_owned_bytes
+ *   and released, with the binding, by msr_unbind and msr_bind_postings.  A failed call leaves no vocabulary bound.
+ *
+ * msr_fuzzy_scratch_bytes: bytes of scratch one msr_fuzzy_terms call over a vocabulary of n_terms terms needs for n_words
+ *   words and `limit` candidates (-1 for arguments the call would refuse; 0 for n_words == 0).  The caller supplies the
+ *   scratch (8-byte aligned); the engine keeps none.
+ *
+ * msr_fuzzy_terms: word i's code points are word_chars[word_off[i] .. word_off[i + 1]) (int32 offsets), its tolerance
+ *   word_max[i].  Row i of out_term / out_dist (int32 [n_words][limit]) receives the first out_n[i] = min(out_total[i], limit)
+ *   candidates in the order above (term id, distance), the remaining slots of the row -1; out_total[i] = the number of ALL
+ *   candidates.  The kernel itself writes the row empty (out_n = out_total = 0, every slot -1) for a word of length 0 or of
+ *   more than MSR_FUZZY_MAX_LEN code points and for a tolerance outside {0, 1, 2}.  All pointers are device pointers.  The
+ *   call only enqueues (two launches); repeated calls give the same bytes (no atomics); nothing is written at or beyond row
+ *   n_words.  Refused before any launch, outputs untouched: MSR_ERR_NOT_BOUND without a vocabulary; MSR_ERR_INVALID for
+ *   n_words < 0 or > MSR_FUZZY_MAX_WORDS, limit outside [1, MSR_FUZZY_MAX_LIMIT], and with n_words > 0 a NULL pointer, a
+ *   scratch that is not 8-byte aligned or scratch_bytes < msr_fuzzy_scratch_bytes(n_terms, n_words, limit).  n_words == 0
+ *   succeeds and launches nothing. */
+int msr_bind_vocab(msr_engine* e, const int64_t* char_off, const uint16_t* chars, const uint32_t* weight, int64_t n_terms,
+                   int64_t n_chars, void* stream);
+int64_t msr_fuzzy_scratch_bytes(int64_t n_terms, int32_t n_words, int32_t limit);
+int msr_fuzzy_terms(msr_engine* e, int32_t n_words, const int32_t* word_off, const uint16_t* word_chars, const int32_t* word_max,
+                    int32_t limit, int32_t* out_term, int32_t* out_dist, int32_t* out_n, int32_t* out_total, void* scratch,
+                    int64_t scratch_bytes, void* stream);
 
 /* msr_combine_sets: out[r] = AND of in[s] for s in and_rows[and_off[r] .. and_off[r + 1])  AND NOT  OR of in[s] for s in
  *   not_rows[not_off[r] .. not_off[r + 1]), rows of in_bits (n_in rows in_stride words apart) in the layout above.  An empty

@@ -17,6 +17,11 @@ MSR_TERMSET_SPAN_DOCS = 8192
 MSR_PHRASE_MAX_TERMS = 16
 MSR_PROX_MAX_SPAN = 64
 MSR_SNIPPET_MAX_WEIGHT = 1 << 20
+MSR_FUZZY_MAX_LEN = 32
+MSR_FUZZY_MAX_WORDS = 1024
+MSR_FUZZY_MAX_LIMIT = 16
+MSR_FUZZY_SPAN_TERMS = 1024
+MSR_FUZZY_WORD_GROUP = 16
 MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
 
 
@@ -80,6 +85,9 @@ _SIGNATURES = {
     "msr_phrase_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "msr_proximity_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "msr_best_windows": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "msr_bind_vocab": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
+    "msr_fuzzy_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "msr_fuzzy_terms": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "msr_combine_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,

@@ -9,6 +9,7 @@ in the reference too: tokenising the query string and formatting the snippet.
 """
 from typing import Callable, List, Optional, Sequence, Union
 
+from . import fuzzy as _fuzzy
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .text import Near, parse_operators, parse_phrases, parse_proximity, simple_tokenize
@@ -30,6 +31,32 @@ class BM25:
         self.index = index
         self.k1, self.b = index.k1, index.b
         self._pos = None
+        self._names = None
+
+    def _name_of(self, t):
+        if self._names is None:
+            self._names = {v: k for k, v in (self.index.vocab or {}).items()}
+        return self._names.get(int(t), str(t))
+
+    def _check_fuzzy(self):
+        if not self.engine.has_vocab:
+            raise ValueError("fuzzy: the index has no vocabulary (CorpusIndex.vocab: term strings); a term-id-only index cannot "
+                             "correct a word")
+
+    def _lookup(self, words):
+        """fuzzy.correct's lookup: per word the id of its first candidate or -1 (ONE DeviceEngine.fuzzy_terms call)."""
+        return [c[0][0] if c else -1 for c, _ in self.engine.fuzzy_terms(words, limit=1)]
+
+    def fuzzy_terms(self, words, limit=5):
+        """Which vocabulary words are near these?  -> per word a list of (term, distance, doc_freq), nearest first (distance,
+        then document frequency descending), at most `limit` of them, within the AUTO tolerance of the word's length (0 edits
+        below 3 code points, 1 for 3 .. 5, 2 from 6 up); a word of the vocabulary comes first in its own list, at distance
+        0.  One DeviceEngine.fuzzy_terms call (msr_fuzzy_terms, DESIGN K15)."""
+        import numpy as np
+        from .index import _np
+        self._check_fuzzy()
+        df = np.diff(_np(self.index.term_off).astype(np.int64))
+        return [[(self._name_of(t), d, int(df[t])) for t, d in cands] for cands, _ in self.engine.fuzzy_terms(list(words), limit=limit)]
 
     # -- engine-level entry points (usable without spaCy: pre-tokenised terms or term ids) ----------
     def search_terms(self, terms: Sequence[Union[str, int]], top_k: int = 1000, min_score: float = 0.0, within=None):
@@ -72,8 +99,14 @@ class BM25:
     # -- the reference's method ------------------------------------------------------------------------
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
                must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None,
-               proximity: bool = False):
-        """operators=True: `+word` / `-word` tokens of the query are required / excluded words (text.parse_operators; the
+               proximity: bool = False, fuzzy: bool = False):
+        """fuzzy=True (DESIGN K15): a query word (or must word) the vocabulary lacks is replaced by its nearest vocabulary term
+        -- optimal string alignment distance within the AUTO tolerance of its length, then the largest document frequency
+        (fuzzy.py) -- before scoring; the result is a fuzzy.Results list whose `corrections` maps typed to used terms (`corrected_query`: the scoring text with them, or None).  Words
+        of the vocabulary are never touched; must_not words, phrases and proximity conditions are NOT corrected (excluding
+        or quoting a guessed word is wrong more often than right).  Needs an index with term strings (ValueError).  Off by
+        default.
+        operators=True: `+word` / `-word` tokens of the query are required / excluded words (text.parse_operators; the
         query is taken as it is -- no city is appended here); must / must_not: further term strings (or ids) every result
         must / must not contain.  Both restrict the documents on the device (DeviceEngine.term_sets), inside `within`.
         phrases=True: `"a b"` / `-"a b"` in the query are required / excluded phrases (text.parse_phrases, before the
@@ -103,13 +136,19 @@ class BM25:
             xp += [as_terms(p) for p in x_ph]
         mp, xp = [p for p in mp if p], [p for p in xp if p]
         ids = self.index.term_ids
+        corrections = None
+        if fuzzy:
+            self._check_fuzzy()
+            new_ids, new_must, corr = _fuzzy.correct(self._lookup, self._name_of, [query_terms], [ids(query_terms)], [m], [ids(m)])
+            query_terms, m, corrections = new_ids[0], new_must[0], corr[0]
         ph_ids = lambda p: p.with_terms(ids(list(p.terms))) if isinstance(p, Near) else ids(p)
         if mp or xp:
             within = self.engine.phrase_sets([[ph_ids(p) for p in mp]], [[ph_ids(p) for p in xp]], [ids(m)], [ids(x)],
                                              within=None if within is None else [within])
         elif m or x:
             within = self.engine.term_sets([ids(m)], [ids(x)], within=None if within is None else [within])
-        return self._finish(self.search_terms(query_terms, top_k, min_score, within=within))
+        rows = self._finish(self.search_terms(query_terms, top_k, min_score, within=within))
+        return rows if corrections is None else _fuzzy.Results(rows, corrections, _fuzzy.corrected_text(query, corrections))
 
     def _finish(self, ranked):
         """urlsDB join after the cut: documents without a row are dropped, snippet = title + 200 chars

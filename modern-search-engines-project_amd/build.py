@@ -36,6 +36,7 @@ UNITS = {
     "msr_phrase.hip": [],
     "msr_proximity.hip": [],
     "msr_snippet.hip": [],
+    "msr_fuzzy.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)

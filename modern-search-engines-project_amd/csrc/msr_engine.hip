@@ -36,6 +36,11 @@ struct msr_engine {
     const int32_t* tok_ids = nullptr;
     int64_t n_tokens = 0;
     bool have_tokens = false;
+    const int64_t* voc_char_off = nullptr; // msr_bind_vocab (borrowed): the bound postings' terms as code points, their weights
+    const uint16_t* voc_chars = nullptr;
+    const uint32_t* voc_weight = nullptr;
+    int64_t voc_n_chars = 0;
+    bool have_vocab = false;
     DenseIndex dense{};
     bool have_chunks = false;
     const int32_t* url_group = nullptr;
@@ -70,6 +75,7 @@ struct msr_engine {
     uint32_t* bm_tile_off = nullptr;
     int32_t* bm_cand_n = nullptr;      // [max_queries][tiles] candidates per (query, segment) of the candidate rows
     uint64_t* bm_win = nullptr;        // [max_queries] anchor of the select's window pass (msr_bm25_window)
+    uint64_t* voc_sig = nullptr;       // [n_terms] character-set signatures of the bound vocabulary (msr_bind_vocab, K15)
     // mem_engine: candidate scratch of the batched bf16 path (allocated by the first msr_enable_bf16, kept across re-binds)
     int32_t* bt_top_doc = nullptr; float* bt_top_score = nullptr; int32_t* bt_top_n = nullptr;
     int32_t* bt_cand_doc = nullptr; float* bt_cand_score = nullptr; int32_t* bt_cand_chunk = nullptr;
@@ -148,9 +154,15 @@ static int fail(msr_engine* e, int code, const char* fmt, ...) {
 
 // How a binding goes away, in msr_unbind, in msr_destroy and in each bind where it starts to replace state: the flags and the
 // index structs first, then the memory, so that nothing is left pointing at what is freed.
+static void drop_vocab(msr_engine* e) {
+    e->have_vocab = false;
+    e->voc_char_off = nullptr; e->voc_chars = nullptr; e->voc_weight = nullptr; e->voc_n_chars = 0;
+    e->mem_postings.free_one(&e->voc_sig);
+}
 static void drop_postings(msr_engine* e) {
     e->have_postings = e->have_tokens = false;
     e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
+    drop_vocab(e);
     e->bm25 = Bm25Index{};
     e->mem_postings.release();
 }
@@ -980,6 +992,73 @@ extern "C" int msr_best_windows(msr_engine* e, int32_t n_pairs, const int32_t* p
     HIP_TRY(e, msr_best_windows_run(e->tok_off, e->tok_ids, e->bm25.n_docs, e->bm25.n_terms, n_pairs, pair_doc, pair_row, n_rows,
                                     row_off, row_terms, row_weights, row_span, out_start, out_cover, out_hits, out_mask, out_terms,
                                     (hipStream_t)stream));
+    return MSR_OK;
+}
+
+// ---- K15: typo-tolerant lookup (msr_fuzzy.hip) ---------------------------------------------------------------------------------
+extern "C" int msr_bind_vocab(msr_engine* e, const int64_t* char_off, const uint16_t* chars, const uint32_t* weight,
+                              int64_t n_terms, int64_t n_chars, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_bind_vocab: postings not bound");
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    drop_vocab(e);
+    if (!char_off || !weight || n_chars < 0 || (n_chars > 0 && !chars)) return fail(e, MSR_ERR_INVALID, "msr_bind_vocab: bad argument");
+    if (n_terms != e->bm25.n_terms)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_vocab: n_terms %lld differs from bound postings (%lld)", (long long)n_terms,
+                    (long long)e->bm25.n_terms);
+    hipStream_t st = (hipStream_t)stream;
+    if (!e->sim_flag) ALLOC(e, e->mem_engine, e->sim_flag, 64);
+    // one kernel checks the offsets and the weights; it reads char_off[0 .. n_terms] and weight[0 .. n_terms), which the
+    // caller vouches for, and never follows an offset; the signatures are built from offsets that have passed
+    int32_t flag = 0;
+    HIP_TRY(e, hipMemsetAsync(e->sim_flag, 0, sizeof(int32_t), st));
+    HIP_TRY(e, msr_vocab_validate(char_off, weight, n_terms, n_chars, e->sim_flag, st));
+    HIP_TRY(e, hipMemcpyAsync(&flag, e->sim_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (flag) {
+        static const char* why[] = {"", "char_off does not run from 0 to n_chars", "char_off descends",
+                                    "a weight is 2^31 or more"};
+        return fail(e, MSR_ERR_INVALID, "msr_bind_vocab: malformed vocabulary: %s", why[std::min(std::max(flag, 0), 3)]);
+    }
+    ALLOC(e, e->mem_postings, e->voc_sig, (size_t)std::max<int64_t>(n_terms, 1) * sizeof(uint64_t));
+    hipError_t err = msr_vocab_signatures(char_off, chars, n_terms, e->voc_sig, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (err != hipSuccess) {
+        e->mem_postings.free_one(&e->voc_sig);
+        return fail(e, MSR_ERR_HIP, "msr_bind_vocab: %s", hipGetErrorString(err));
+    }
+    e->voc_char_off = char_off; e->voc_chars = chars; e->voc_weight = weight; e->voc_n_chars = n_chars;
+    e->have_vocab = true;
+    return MSR_OK;
+}
+
+extern "C" int64_t msr_fuzzy_scratch_bytes(int64_t n_terms, int32_t n_words, int32_t limit) {
+    if (n_terms < 0 || n_terms >= (1ll << 31) || n_words < 0 || n_words > MSR_FUZZY_MAX_WORDS || limit < 1 ||
+        limit > MSR_FUZZY_MAX_LIMIT)
+        return -1;
+    return (int64_t)n_words * msr_fuzzy_spans(n_terms) * ((int64_t)limit * 8 + 4);
+}
+
+extern "C" int msr_fuzzy_terms(msr_engine* e, int32_t n_words, const int32_t* word_off, const uint16_t* word_chars,
+                               const int32_t* word_max, int32_t limit, int32_t* out_term, int32_t* out_dist, int32_t* out_n,
+                               int32_t* out_total, void* scratch, int64_t scratch_bytes, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_vocab)
+        return fail(e, MSR_ERR_NOT_BOUND, "msr_fuzzy_terms: vocabulary not bound (msr_bind_vocab: the index has no term strings)");
+    if (n_words < 0 || n_words > MSR_FUZZY_MAX_WORDS || limit < 1 || limit > MSR_FUZZY_MAX_LIMIT)
+        return fail(e, MSR_ERR_INVALID, "msr_fuzzy_terms: bad argument (n_words=%d, at most %d; limit=%d, 1 .. %d)", n_words,
+                    MSR_FUZZY_MAX_WORDS, limit, MSR_FUZZY_MAX_LIMIT);
+    if (n_words == 0) return MSR_OK;
+    if (!word_off || !word_chars || !word_max || !out_term || !out_dist || !out_n || !out_total || !scratch)
+        return fail(e, MSR_ERR_INVALID, "msr_fuzzy_terms: bad argument (a NULL pointer with n_words=%d)", n_words);
+    const int64_t need = msr_fuzzy_scratch_bytes(e->bm25.n_terms, n_words, limit);
+    if (need < 0 || scratch_bytes < need || ((uintptr_t)scratch & 7))
+        return fail(e, MSR_ERR_INVALID, "msr_fuzzy_terms: bad argument (scratch_bytes=%lld, needed %lld, 8-byte aligned)",
+                    (long long)scratch_bytes, (long long)need);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_fuzzy_terms_run(e->voc_char_off, e->voc_chars, e->voc_weight, e->voc_sig, e->bm25.n_terms, n_words, word_off,
+                                   word_chars, word_max, limit, out_term, out_dist, out_n, out_total, scratch,
+                                   (hipStream_t)stream));
     return MSR_OK;
 }
 

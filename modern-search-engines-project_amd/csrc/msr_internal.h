@@ -199,6 +199,19 @@ hipError_t msr_best_windows_run(const int64_t* tok_off, const int32_t* tok_ids, 
                                 const int32_t* row_terms, const int32_t* row_weights, const int32_t* row_span, int32_t* out_start,
                                 int32_t* out_cover, int32_t* out_hits, uint64_t* out_mask, uint32_t* out_terms,
                                 hipStream_t stream);
+// K15 (msr_fuzzy.hip): the vocabulary terms nearest to a word (see msretr.h; arguments checked by the caller).
+// *flag <- max(*flag, code): 1 char_off does not run from 0 to n_chars, 2 it descends, 3 a weight of 2^31 or more
+hipError_t msr_vocab_validate(const int64_t* char_off, const uint32_t* weight, int64_t n_terms, int64_t n_chars, int32_t* flag,
+                              hipStream_t stream);
+// sig[t] <- the 64-bit character-set signature of term t (validated offsets)
+hipError_t msr_vocab_signatures(const int64_t* char_off, const uint16_t* chars, int64_t n_terms, uint64_t* sig,
+                                hipStream_t stream);
+int64_t msr_fuzzy_spans(int64_t n_terms);                   // workgroups of the scan: ceil(n_terms / MSR_FUZZY_SPAN_TERMS)
+// scratch: n_words * spans * limit keys of 8 bytes, then n_words * spans counts of 4
+hipError_t msr_fuzzy_terms_run(const int64_t* char_off, const uint16_t* chars, const uint32_t* weight, const uint64_t* sig,
+                               int64_t n_terms, int n_words, const int32_t* word_off, const uint16_t* word_chars,
+                               const int32_t* word_max, int limit, int32_t* out_term, int32_t* out_dist, int32_t* out_n,
+                               int32_t* out_total, void* scratch, hipStream_t stream);
 hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);

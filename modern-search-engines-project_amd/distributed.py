@@ -314,10 +314,16 @@ class ShardedEngine:
 
     # ------------------------------------------------------------------ the sharded hot path
     def search(self, term_lists, qvec, k1=1000, k2=100, min_score=0.0, max_chunks_per_doc=0, rerank=True,
-               packed=None, dense_batched=False, rerank_keep=None, **rerank_params):
+               packed=None, dense_batched=False, rerank_keep=None, fuzzy=False, **rerank_params):
         """-> dict(bm25=(doc, score, n), dense=(doc, score, chunk, n), rerank=(doc, score, orig, chunk, n, rows)); documents
         and chunk rows are GLOBAL indices; every rank returns the same tensors.  rerank_keep: entries per query of the fused
-        lists to return (None: all k1; the reranker facade's diversification wants them all, a top-100 service k2)."""
+        lists to return (None: all k1; the reranker facade's diversification wants them all, a top-100 service k2).
+        fuzzy=True is refused: a shard knows only its own document frequencies, so the ranks would pick different nearest
+        terms and their lists would disagree (DESIGN K15); correct the words on an unsharded engine and pass the ids."""
+        if fuzzy:
+            raise ValueError("fuzzy=True is not available on a sharded engine: shard-local document frequencies would make the "
+                             "ranks choose different corrections and their ranks disagree; look the words up on an unsharded "
+                             "index (DeviceEngine.fuzzy_terms) and pass the corrected term ids")
         e = self.engine
         keep = k1 if rerank_keep is None else min(int(rerank_keep), k1)
         max_chunks = rerank_params.get("max_chunks", 10)

@@ -21,7 +21,8 @@ def _ptr(t):
 
 
 STREAM_MIN_BYTES = 64 << 20
-_NP_OF = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int64: np.int64}
+_NP_OF = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int64: np.int64,
+          torch.int16: np.int16}
 
 
 def stream_to_device(arr, device, block_bytes=128 << 20):
@@ -128,6 +129,14 @@ class DeviceEngine:
                     self._check(self.lib.msr_bind_tokens(self.handle, _ptr(tok_off), _ptr(tok_ids) if tok_ids.numel() else
                                                          C.c_void_p(0), ix.n_docs, int(tok_ids.numel()), self._stream()))
                     t["tok_off"], t["tok_ids"] = tok_off, tok_ids
+                if ix.vocab:                                 # the term strings (typo-tolerant lookup, msr_bind_vocab)
+                    char_off, chars, weight = ix.vocab_image()
+                    v_off, v_w = self._dev(char_off, torch.int64), self._dev(weight.view(np.int32), torch.int32)
+                    v_chars = self._dev(chars.view(np.int16), torch.int16)
+                    self._check(self.lib.msr_bind_vocab(self.handle, _ptr(v_off), _ptr(v_chars) if v_chars.numel() else
+                                                        C.c_void_p(0), _ptr(v_w), ix.n_terms, int(v_chars.numel()),
+                                                        self._stream()))
+                    t["voc_off"], t["voc_chars"], t["voc_weight"] = v_off, v_chars, v_w
             if ix.doc_off is not None and ix.emb is not None:
                 t["doc_off"] = self._dev(ix.doc_off, torch.int32)
                 emb = self._dev(ix.emb, torch.float32)
@@ -172,6 +181,60 @@ class DeviceEngine:
     def has_tokens(self):
         """True if the bound index came with a forward index (CorpusIndex.tok_off / tok_ids): phrase_sets works."""
         return "tok_off" in self._t
+
+    @property
+    def has_vocab(self):
+        """True if the bound index came with its term strings (CorpusIndex.vocab): fuzzy_terms works."""
+        return "voc_off" in self._t
+
+    def fuzzy_terms(self, words, max_edits=None, limit=1):
+        """The vocabulary terms nearest to each word (msr_fuzzy_terms, DESIGN K15) -> per word ([(term id, distance), ...],
+        total): the first `limit` (1 .. 16) candidates -- terms with a document frequency above 0 within the word's tolerance
+        by optimal string alignment distance (insertion, deletion, substitution, swap of two adjacent code points), ordered by
+        distance, then document frequency descending, then term id -- and the number of all candidates.  max_edits: None (the
+        AUTO rule per word, fuzzy.auto_edits), an int for every word or one per word, each 0 .. 2.  A word that cannot be
+        looked up (empty, more than 32 code points, a code point above 0xFFFE) gets ([], 0).  ONE upload, two launches, one
+        copy back for up to MSR_FUZZY_MAX_WORDS words; longer lists go in slices.  Raises MsrError without a vocabulary."""
+        from .fuzzy import auto_edits, encode_words, lookable
+        if not self.has_vocab:
+            raise _abi.MsrError(-2, "fuzzy_terms: the index has no vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
+                                    "index cannot suggest words")
+        limit = int(limit)
+        if not 1 <= limit <= _abi.MSR_FUZZY_MAX_LIMIT:
+            raise ValueError(f"fuzzy_terms: limit must be 1 .. MSR_FUZZY_MAX_LIMIT = {_abi.MSR_FUZZY_MAX_LIMIT} (got {limit})")
+        words = list(words)
+        W = len(words)
+        if max_edits is None:
+            maxes = [auto_edits(len(w)) if isinstance(w, str) else 0 for w in words]
+        else:
+            maxes = [int(max_edits)] * W if np.ndim(max_edits) == 0 else [int(v) for v in max_edits]
+            if len(maxes) != W or any(not 0 <= m <= 2 for m in maxes):
+                raise ValueError("fuzzy_terms: max_edits is None, or 0 .. 2 for every word")
+        out = [([], 0)] * W
+        ask = [i for i in range(W) if lookable(words[i])]
+        step = _abi.MSR_FUZZY_MAX_WORDS
+        for a in range(0, len(ask), step):
+            part = ask[a:a + step]
+            n = len(part)
+            off, chars = encode_words([words[i] for i in part])
+            # ONE upload: offsets, tolerances, then the code points two to a word
+            chars32 = np.zeros((len(chars) + 1) // 2 + 1, np.int32)
+            chars32.view(np.uint16)[:len(chars)] = chars
+            up = self._dev(np.concatenate([off, np.asarray([maxes[i] for i in part], np.int32), chars32]), torch.int32)
+            d_off, d_max, d_chars = up[:n + 1], up[n + 1:2 * n + 1], up[2 * n + 1:]
+            res = torch.empty((2 * n * limit + 2 * n,), dtype=torch.int32, device=self.device)
+            need = int(self.lib.msr_fuzzy_scratch_bytes(self.index.n_terms, n, limit))
+            scratch = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=self.device)
+            r_term, r_dist = res[:n * limit], res[n * limit:2 * n * limit]
+            r_n, r_total = res[2 * n * limit:2 * n * limit + n], res[2 * n * limit + n:]
+            self._check(self.lib.msr_fuzzy_terms(self.handle, n, _ptr(d_off), _ptr(d_chars), _ptr(d_max), limit, _ptr(r_term),
+                                                 _ptr(r_dist), _ptr(r_n), _ptr(r_total), _ptr(scratch), need, self._stream()))
+            host = res.cpu().numpy()
+            term, dist = host[:n * limit].reshape(n, limit), host[n * limit:2 * n * limit].reshape(n, limit)
+            cnt, total = host[2 * n * limit:2 * n * limit + n], host[2 * n * limit + n:]
+            for j, i in enumerate(part):
+                out[i] = ([(int(term[j, c]), int(dist[j, c])) for c in range(int(cnt[j]))], int(total[j]))
+        return out
 
     def scan_arith(self):
         """'f32' (exact f32 MFMA) or 'f16x2' (f32 rows split into two f16 pieces, f32 accumulation)."""

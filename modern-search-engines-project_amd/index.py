@@ -53,6 +53,7 @@ class CorpusIndex:
     tok_off: object = None              # int64 [N+1]
     tok_ids: object = None              # int32 [T]
     _url_group: object = field(default=None, repr=False)
+    _vocab_image: object = field(default=None, repr=False)
 
     # ------------------------------------------------------------------ basic properties
     @property
@@ -76,6 +77,20 @@ class CorpusIndex:
             else:
                 out.append(self.vocab.get(t, -1) if self.vocab else -1)
         return out
+
+    def vocab_image(self):
+        """-> (char_off int64 [V + 1], chars uint16, weight uint32 [V]): the vocabulary as the typo-tolerant lookup reads it
+        (msr_bind_vocab, DESIGN K15; fuzzy.vocab_image) -- term id t's code points chars[char_off[t]:char_off[t + 1]] and its
+        weight, the document frequency term_off[t + 1] - term_off[t]; weight 0 (never suggested) for a term of more than 32
+        code points or holding a code point above 0xFFFE.  Built once per (vocab, term_off) and kept on the index.  Raises
+        ValueError without a vocab or postings."""
+        if not self.vocab or self.term_off is None:
+            raise ValueError("vocab_image: the index has no vocabulary (term strings) or no postings")
+        got = self._vocab_image
+        if got is None or got[0] is not self.vocab or got[1] is not self.term_off:
+            from .fuzzy import vocab_image
+            got = self._vocab_image = (self.vocab, self.term_off, vocab_image(self.vocab, _np(self.term_off)))
+        return got[2]
 
     def url_group(self):
         """int32[N]: id of the URL with its query string removed (reranker_api.py:43-46); -1 if the

@@ -12,6 +12,7 @@ import weakref
 import numpy as np
 
 from .bm25 import BM25
+from . import fuzzy as _fuzzy
 from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
@@ -374,7 +375,7 @@ class Retriever:
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
-                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False):
+                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
@@ -397,10 +398,21 @@ class Retriever:
         MsrError otherwise; a phrase of more than MSR_PHRASE_MAX_TERMS terms raises ValueError.  phrases=True is refused like
         operators=True (text.parse_phrases needs the text).
         A text.Near in must_phrases / must_not_phrases is a proximity condition (DESIGN K13): its terms within a window, in
-        order or in any order; proximity=True is refused like phrases=True (text.parse_proximity needs the text)."""
+        order or in any order; proximity=True is refused like phrases=True (text.parse_proximity needs the text).
+        fuzzy (DESIGN K15): None, or a dict {"terms": per query the term STRINGS that term_id_lists was mapped from}: per chunk
+        ONE DeviceEngine.fuzzy_terms call over all its unknown words, in front of stage 1 (the place term_sets has), replaces
+        each -1 of the chunk's term ids and must ids by the word's nearest vocabulary term (fuzzy.correct); must_not and the
+        phrases are not corrected.  The generator fills fuzzy["corrections"] (per query {typed: used}) and fuzzy["ids"] (the
+        term ids that were scored).  The lookup's answer comes back to the host before the chunk is enqueued: with fuzzy the
+        host does not run ahead of the device.  Needs an index with term strings (ValueError); not with prepare=."""
         import torch
         eng = self.engine
         _check_mode(mode)
+        if fuzzy is not None:
+            self._check_fuzzy()
+            if prepare is not None or len(fuzzy["terms"]) != len(term_id_lists):
+                raise ValueError("fuzzy: needs the term strings of every query (not with prepare=)")
+            fuzzy["corrections"], fuzzy["ids"] = [], []
         if operators:
             raise ValueError("operators=True needs the query text: use search / search_batch / batch_search, or parse with "
                              "text.parse_operators and pass must= / must_not=")
@@ -434,7 +446,13 @@ class Retriever:
             qv = eng._dev(np.asarray(qv, np.float32) if not torch.is_tensor(qv) else qv, torch.float32).reshape(-1, 768)
             w = (list(within[a:b]) if isinstance(within, (list, tuple))
                  else within.queries(a, b) if isinstance(within, DeviceSets) else within)
-            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=op_ids(must, a, b),
+            m_ids = op_ids(must, a, b)
+            if fuzzy is not None:
+                ids, m_ids, corr = _fuzzy.correct(self.bm25._lookup, self.bm25._name_of, fuzzy["terms"][a:b], ids,
+                                                  None if must is None else must[a:b], m_ids)
+                fuzzy["corrections"] += corr
+                fuzzy["ids"] += ids
+            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=m_ids,
                                       must_not=op_ids(must_not, a, b), must_phrases=ph_ids(must_phrases, a, b),
                                       must_not_phrases=ph_ids(must_not_phrases, a, b))
             if pending is not None:
@@ -442,6 +460,12 @@ class Retriever:
             pending = (a, job)
         if pending is not None:
             yield (pending[0],) + self._collect(pending[1])
+
+    def _check_fuzzy(self):
+        """What fuzzy=True needs, checked before any device work: an index with term strings (ValueError)."""
+        if self.bm25 is None or not self.engine.has_vocab:
+            raise ValueError("fuzzy=True needs an index with a vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
+                             "index cannot correct a word")
 
     def _phrase_ids(self, p):
         """A phrase's term ids; a text.Near keeps its slop and mode (a Near of a string is tokenised like the query)."""
@@ -456,18 +480,19 @@ class Retriever:
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
-                    must_phrases=None, must_not_phrases=None, proximity=False):
+                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
         with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
-        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity: final_list_chunks."""
+        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity / fuzzy: final_list_chunks."""
         _check_mode(mode)
         if with_source and mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
         parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
                                             operators=operators, must=must, must_not=must_not, phrases=phrases,
-                                            must_phrases=must_phrases, must_not_phrases=must_not_phrases, proximity=proximity))
+                                            must_phrases=must_phrases, must_not_phrases=must_not_phrases, proximity=proximity,
+                                            fuzzy=fuzzy))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -518,7 +543,7 @@ class Retriever:
         return processed, m, x, mp, xp
 
     def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not, phrases=False, must_phrases=None,
-                     must_not_phrases=None, proximity=False):
+                     must_not_phrases=None, proximity=False, keep=None):
         """_prepare with operators and phrases: -> (term ids, vectors, keyword arguments of final_lists: must / must_not /
         must_phrases / must_not_phrases where there are any).  The scoring text (excluded words and phrases removed, quotes
         gone) is what gets tokenised and embedded."""
@@ -527,13 +552,16 @@ class Retriever:
         ops = {} if m is None else {"must": m, "must_not": x}
         if mp is not None:
             ops.update(must_phrases=mp, must_not_phrases=xp)
-        return self._prepare(queries, query_embeddings, term_lists, processed) + (ops,)
+        return self._prepare(queries, query_embeddings, term_lists, processed, keep) + (ops,)
 
-    def _prepare(self, queries, query_embeddings, term_lists, processed=None):
+    def _prepare(self, queries, query_embeddings, term_lists, processed=None, keep=None):
+        """keep (a dict, optional) receives "processed" (the scoring texts) and "terms" (the term lists the ids came from)."""
         if processed is None:
             processed = [preprocess_query(q) for q in queries]
         if term_lists is None:
             term_lists = [self.bm25._tokenize(q) for q in processed]
+        if keep is not None:
+            keep.update(processed=list(processed), terms=[list(t) for t in term_lists])
         ids = [self.index.term_ids(t) for t in term_lists]
         if isinstance(query_embeddings, np.ndarray) and query_embeddings.ndim == 2:
             qv = np.ascontiguousarray(query_embeddings, np.float32)             # (a matrix of vectors: taken as it is)
@@ -596,7 +624,8 @@ class Retriever:
 
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
-                     must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS):
+                     must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS,
+                     fuzzy=False):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
@@ -625,12 +654,28 @@ class Retriever:
         lacks).  Documents, ranks and scores are unchanged.  A page without a query term (a dense-only hybrid hit) and a
         query of unknown words keep the reference's snippet, with "highlights": [] and every term of the row missing.  A
         custom tokenizer needs Retriever(span_tokenizer=...) (ValueError); the index needs a forward index and texts
-        (MsrError).  Off by default: without it the call uploads, launches and returns exactly what it did."""
+        (MsrError).  Off by default: without it the call uploads, launches and returns exactly what it did.
+        fuzzy=True (DESIGN K15): a query word the vocabulary lacks -- today silently dropped -- is replaced by its nearest
+        vocabulary term before stage 1: optimal string alignment distance (insertion, deletion, substitution, swap of two
+        adjacent code points) within the AUTO tolerance of the word's length (0 edits below 3 code points, 1 for 3 .. 5, 2
+        from 6 up), then the largest document frequency, then the smallest term id; ONE DeviceEngine.fuzzy_terms call per
+        chunk of queries.  Words of the vocabulary are never touched; must= / `+word` terms are corrected the same way;
+        must_not / `-word` terms, phrases and proximity conditions are NOT (excluding or quoting a guessed word is wrong more
+        often than right).  Correction is lexical: the dense stage and the reranker use the embedding of the query AS TYPED.
+        Each query's result is then a fuzzy.Results list -- the same rows, plus `corrections` ({typed term: used term}, empty if
+        none) and `corrected_query` (the processed query with the replacements, or None).  Needs an index with term strings
+        (ValueError).  Off by default: without it every row and every list is what it was."""
         _check_mode(mode)
         if snippets:
             self._check_snippets(snippet_tokens)
+        fz = None
+        if fuzzy:
+            self._check_fuzzy()
+            fz = {}
         ids, qv, ops = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not, phrases, must_phrases,
-                                         must_not_phrases, proximity)
+                                         must_not_phrases, proximity, keep=fz)
+        if fz is not None:
+            ops["fuzzy"] = fz
         src = None
         if mode == "hybrid":
             doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
@@ -638,6 +683,8 @@ class Retriever:
         else:
             doc, score, _, n = self.final_lists(ids, qv, top_k, within=within, **ops)
         ix = self.index
+        if fz is not None:
+            ids = fz["ids"]                                  # (the snippets look for the words that were scored)
         passages, row_names = self._snippets(ids, doc, n, snippet_tokens) if snippets else (None, None)
         out = []
         for q in range(len(queries)):
@@ -660,40 +707,56 @@ class Retriever:
                         rows[-1]["snippet"] = hit[0]
                     rows[-1]["highlights"] = hit[1] if hit is not None else []
                     rows[-1]["missing"] = hit[2] if hit is not None else list(row_names[q] or [])
+            if fz is not None:
+                rows = _fuzzy.Results(rows, fz["corrections"][q], _fuzzy.corrected_text(fz["processed"][q], fz["corrections"][q]))
             out.append(rows)
         return out
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-               must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS):
+               must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False):
         """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
-        list of phrases (or text.Near conditions) each; snippets / snippet_tokens: search_batch."""
+        list of phrases (or text.Near conditions) each; snippets / snippet_tokens / fuzzy: search_batch (fuzzy=True: the
+        result is a fuzzy.Results list with `corrections` and `corrected_query`)."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
                                  mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
                                  must_not=None if must_not is None else [must_not], phrases=phrases,
                                  must_phrases=None if must_phrases is None else [must_phrases],
                                  must_not_phrases=None if must_not_phrases is None else [must_not_phrases],
-                                 proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens)[0]
+                                 proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens, fuzzy=fuzzy)[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-                     must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS):
+                     must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
         search_batch (the entries keep the reference's keys in either mode); operators / must / must_not / phrases /
         must_phrases / must_not_phrases / proximity: search_batch.  snippets=True: every entry gains "snippet" (None where the
-        page has no window), "highlights" and "missing" as in search_batch; the formatted lines are what they were."""
+        page has no window), "highlights" and "missing" as in search_batch; the formatted lines are what they were.
+        fuzzy=True: unknown words are corrected as in search_batch; the returned BatchLines then carries `corrections` (per
+        query {typed term: used term}) and `corrected_queries` (per query the corrected text or None); the entries keep
+        their keys."""
         _check_mode(mode)
         if snippets:
             self._check_snippets(snippet_tokens)
+        fz = None
+        if fuzzy:
+            self._check_fuzzy()
+            fz = {}
         ids, qv, ops = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators, must, must_not,
-                                         phrases, must_phrases, must_not_phrases, proximity)
+                                         phrases, must_phrases, must_not_phrases, proximity, keep=fz)
+        if fz is not None:
+            ops["fuzzy"] = fz
         doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         lines = BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
+        if fz is not None:
+            ids = fz["ids"]
+            lines.corrections = fz["corrections"]
+            lines.corrected_queries = [_fuzzy.corrected_text(p, c) for p, c in zip(fz["processed"], fz["corrections"])]
         if snippets:
             lines.passages, lines.row_names = self._snippets(ids, doc, n, snippet_tokens)
         return lines
@@ -754,6 +817,7 @@ class BatchLines:
         self._start = np.zeros(len(n) + 1, np.int64)
         np.cumsum(n, out=self._start[1:])
         self.passages = self.row_names = None                # Retriever.batch_search(snippets=True) fills them
+        self.corrections = self.corrected_queries = None     # ... and fuzzy=True these
 
     def __len__(self):
         return int(self._start[-1])

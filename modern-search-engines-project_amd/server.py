@@ -73,6 +73,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         proximity: bool = False       # phrases, and `"a b"~N` / `"a b"~>N`: the words within a window (text.parse_proximity)
         snippets: bool = False        # every row's snippet is the page's best passage for the query, with "highlights" and
         snippet_tokens: int = 30      # "missing" (Retriever.search, DESIGN K14); the passage's width in tokens, 1 .. 64
+        fuzzy: bool = False           # a word the vocabulary lacks is replaced by its nearest term (Retriever.search, DESIGN K15);
+        #                               the response then carries "corrected_query" and "corrections"
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -143,15 +145,21 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                               must_not_phrases=cond(req.must_not_phrases))
                 if req.snippets:
                     kw.update(snippets=True, snippet_tokens=req.snippet_tokens)
+                if req.fuzzy:
+                    kw.update(fuzzy=True)
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
-                if req.mode == "lexical" and not near and not req.snippets:
+                if req.mode == "lexical" and not near and not req.snippets and not req.fuzzy:
                     raise
-                return JSONResponse(status_code=400, content={"error": str(e)})      # a dense_k the engine cannot hold
+                # a dense_k the engine cannot hold; fuzzy on an index without term strings
+                return JSONResponse(status_code=400, content={"error": str(e)})
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
+            if req.fuzzy:
+                return {"llm_response": llm_response, "documents": list(docs), "corrected_query": docs.corrected_query,
+                        "corrections": docs.corrections}
             return {"llm_response": llm_response, "documents": docs}
         except Exception:
             return JSONResponse(status_code=500, content={"error": "Internal server error"})
