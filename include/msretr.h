@@ -42,7 +42,7 @@ extern "C" {
                                      13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets;
                                      15: msr_best_windows; also 15 (calls added, none changed: a library
                                      that lacks them fails to load by symbol): msr_bind_vocab, msr_fuzzy_scratch_bytes,
-                                     msr_fuzzy_terms */
+                                     msr_fuzzy_terms; msr_debug_chunk_layout */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -715,6 +715,13 @@ int msr_compact_postings(const int64_t* term_off, int64_t n_terms, const int32_t
  * behind out[n - 1] is written); *total (device pointer, nullable) <- the sum of all n elements (0 for n = 0).  in / out are
  * device pointers to n elements and may not overlap.  MSR_ERR_INVALID for n < 0 or, with n > 0, a NULL in or out. */
 int msr_debug_exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int64_t* total, void* stream);
+
+/* Test hook, host only (no device call, no engine): what msr_bind_chunks derives from the document offsets doc_off
+ * [n_docs + 1] (HOST pointer).  On entry out[3] holds the CU count to cut the spans for (<= 0: 256).  On return out[0] = 1 if
+ * the corpus may take the K-split sweeps (msr_scan_width() 64 and up), out[1] = 1 if also the 128-query bf16 sweep
+ * (msr_batch_width() 128), out[2] = 1 if every document fits a 256-row tile, out[3] = the number of spans of the K-split
+ * kernels.  MSR_ERR_INVALID for offsets msr_bind_chunks would refuse (text in msr_last_error(NULL)). */
+int msr_debug_chunk_layout(const int32_t* doc_off, int64_t n_docs, int32_t out[4]);
 
 /* Timing hooks for bench.py: while enabled, every launch of the dominant kernels is bracketed by a
  * hipEvent pair recorded on the caller's stream (ring of 256 launches per kernel).  msr_kernel_time_ms

@@ -126,6 +126,7 @@ _SIGNATURES = {
                                      C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "msr_compact_postings": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64), _P]),
     "msr_debug_exclusive_scan": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "msr_debug_chunk_layout": (C.c_int, [_P, C.c_int64, C.POINTER(C.c_int32)]),
     "msr_set_timing": (C.c_int, [_P, C.c_int32]),
     "msr_tune": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "msr_kernel_time_ms": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

@@ -19,8 +19,10 @@
 //   their ring slots reset to -inf, which is also what a chunk-less document reports.
 //
 // The ring holds 128 documents; it never wraps onto live slots if any 32 consecutive rows (on 16-row group
-// boundaries) span fewer than 96 documents, which the engine checks when the chunks are bound (DenseIndex.wide_ok;
-// otherwise the narrow kernel runs).  max_chunks > 0 (a per-document row limit) also stays on the narrow kernel.
+// boundaries) span at most 96 documents AND the retirement below (two blocks per unit) never falls a whole ring behind
+// the rows -- both checked when the chunks are bound, the second by walking this kernel's next_b / next_end bookkeeping
+// on the host (DenseIndex.wide_ok, chunk_layout in msr_engine.hip; otherwise the narrow kernel runs).  max_chunks > 0
+// (a per-document row limit) also stays on the narrow kernel.
 //
 // The workgroups are persistent, one per CU, each with its own span of rows cut at a document boundary, so there
 // is no traffic between workgroups.  Bytes per launch are those of the narrow kernel (E once, 15.36 GB at 5 M
@@ -122,7 +124,9 @@ __global__ __launch_bounds__(NWAVES * 64) void dense_ksplit_kernel(DenseIndex ix
     };
     // Inside the loop at most two blocks become complete per unit (the engine admits the kernel only if a 16-row group
     // spans <= 32 documents), so two plain ifs do: a loop with stores in it would make the compiler wait for ALL
-    // outstanding loads, prefetches included, at the next use of a row register.
+    // outstanding loads, prefetches included, at the next use of a row register.  Two per unit is also all that is
+    // retired of blocks that were complete EARLIER: chunk_layout walks exactly this bookkeeping and refuses a corpus on
+    // which next_b would fall a ring behind (keep the two in step: tests/dense_geometry_cases.py restates both).
     auto flush_step = [&](int64_t rows_done) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)

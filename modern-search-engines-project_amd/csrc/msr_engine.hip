@@ -430,7 +430,9 @@ struct ChunkLayout {
 };
 
 // Checks the document offsets (host copy) and works out everything the bind derives from them.  No device calls.
-static int chunk_layout(msr_engine* e, const std::vector<int32_t>& h_off, int64_t n_chunks, int64_t n_docs, ChunkLayout& L) {
+// (e: whose error text a refusal writes, null for the handle-less debug call; n_cus: workgroups of the K-split kernels.)
+static int chunk_layout(msr_engine* e, int n_cus, const std::vector<int32_t>& h_off, int64_t n_chunks, int64_t n_docs,
+                        ChunkLayout& L) {
     if (h_off[0] != 0 || (int64_t)h_off[n_docs] != n_chunks)
         return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: doc_off[0]=%d, doc_off[n_docs]=%d, n_chunks=%lld",
                     h_off[0], h_off[n_docs], (long long)n_chunks);
@@ -450,9 +452,9 @@ static int chunk_layout(msr_engine* e, const std::vector<int32_t>& h_off, int64_
         if (sp.back() != (int32_t)n_docs) sp.push_back((int32_t)n_docs);
         return sp;
     };
-    L.spans = make_spans(e->n_cus, 256);
-    L.wspans = make_spans(e->n_cus * 8, 64);
-    L.wspans12 = make_spans(e->n_cus * 12, 64);
+    L.spans = make_spans(n_cus, 256);
+    L.wspans = make_spans(n_cus * 8, 64);
+    L.wspans12 = make_spans(n_cus * 12, 64);
     // K-split kernels: documents spanned by any two consecutive 16-row groups must fit the LDS ring with a block to spare
     {
         const int64_t n_groups = (n_chunks + 15) / 16;
@@ -470,6 +472,32 @@ static int chunk_layout(msr_engine* e, const std::vector<int32_t>& h_off, int64_
             while (h_off[dm + 1] <= glast) ++dm;
             if (dm - dl > 32) L.wide_ok = L.wide_ok64 = 0;
         }
+    }
+    // ... and the kernel's retirement must keep up.  It retires at most two blocks of 32 documents per unit, and only blocks
+    // that were complete before the unit, so where the documents under the units advance by more than 64 per unit for several
+    // units in a row (sustained runs of chunk-less documents; the windows above allow up to 96) the first block not yet retired
+    // falls further behind each unit, until a document being folded lies a whole ring ahead of it and shares a slot with a
+    // document still waiting to be written.  Walk the kernel's own bookkeeping (next_b, next_end, flush_step in
+    // msr_dense_ks.hip) over every span, O(n_docs + n_chunks / 16), and refuse such a corpus: it takes the narrow kernel.
+    if (L.wide_ok || L.wide_ok64) {
+        int64_t lag = 0;                                     // most documents between next_b and a document being folded
+        for (size_t s = 0; s + 1 < L.spans.size(); ++s) {
+            const int64_t d0 = L.spans[s], d1 = L.spans[s + 1];
+            const int64_t c0 = h_off[d0], c1 = h_off[d1];
+            if (c1 <= c0) continue;
+            auto block_end = [&](int64_t b) -> int64_t { return h_off[std::min(b + 32, d1)]; };
+            int64_t next_b = d0 & ~(int64_t)31;
+            while (next_b < d1 && block_end(next_b) <= c0) next_b += 32;            // flush_done(c0)
+            int64_t d = d0;                                  // document of the unit's last row
+            for (int64_t g = c0 >> 4; g < (c1 + 15) >> 4; ++g) {
+                const int64_t last = std::min(16 * g + 16, c1) - 1;
+                while (h_off[d + 1] <= last) ++d;
+                lag = std::max(lag, d - next_b);
+                for (int i = 0; i < 2 && next_b < d1 && block_end(next_b) <= 16 * g; ++i) next_b += 32;   // flush_step(16 g)
+            }
+        }
+        if (lag >= MSR_WIDE_RING) L.wide_ok = 0;
+        if (lag >= 64) L.wide_ok64 = 0;
     }
     // row tiles for the GEMM paths: <= 256 rows, cut at document boundaries
     int32_t start = 0;
@@ -661,7 +689,7 @@ extern "C" int msr_bind_chunks(msr_engine* e, const float* emb, int64_t n_chunks
     HIP_TRY(e, hipMemcpyAsync(h_off.data(), doc_off, (size_t)(n_docs + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(e, hipStreamSynchronize(st));
     ChunkLayout L;
-    int rc = chunk_layout(e, h_off, n_chunks, n_docs, L);
+    int rc = chunk_layout(e, e->n_cus, h_off, n_chunks, n_docs, L);
     if (rc) return rc;                                       // (a malformed doc_off: the previous binding keeps serving)
     // from here on the previous binding is being replaced -- its tables, the bf16 image, a pending msr_dense_topk_begin: the
     // engine counts as unbound until this call succeeds
@@ -672,6 +700,18 @@ extern "C" int msr_bind_chunks(msr_engine* e, const float* emb, int64_t n_chunks
     if (rc) drop_chunks(e);                                  // (nothing half-built stays behind)
     e->have_chunks = rc == MSR_OK;
     return rc;
+}
+
+extern "C" int msr_debug_chunk_layout(const int32_t* doc_off, int64_t n_docs, int32_t out[4]) {
+    if (!doc_off || !out || n_docs < 0 || n_docs >= ((int64_t)1 << 31))
+        return fail(nullptr, MSR_ERR_INVALID, "msr_debug_chunk_layout: bad argument");
+    const int n_cus = out[3] > 0 ? out[3] : 256;
+    const std::vector<int32_t> h_off(doc_off, doc_off + n_docs + 1);
+    ChunkLayout L;
+    const int rc = chunk_layout(nullptr, n_cus, h_off, h_off[n_docs], n_docs, L);
+    if (rc) return rc;
+    out[0] = L.wide_ok; out[1] = L.wide_ok && L.wide_ok64; out[2] = L.tiles_ok; out[3] = (int32_t)L.spans.size() - 1;
+    return MSR_OK;
 }
 
 extern "C" int msr_unbind(msr_engine* e) {

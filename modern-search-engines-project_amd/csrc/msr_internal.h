@@ -243,7 +243,12 @@ struct DenseIndex {
                                // one load per unit for the K-split kernels; null when !wide_ok
     int32_t wide_ok;           // any 32 consecutive rows (on 16-row group boundaries) span <= MSR_WIDE_RING - 32 documents
                                // (the K-split kernels' ring of per-document maxima cannot wrap onto live slots) and any
-                               // 16-row group <= 32 documents (at most two finished blocks per unit)
+                               // 16-row group <= 32 documents (at most two finished blocks per unit), and -- walked over every span
+                               // with the kernel's own bookkeeping at bind (chunk_layout) -- no document is folded MSR_WIDE_RING
+                               // or more documents ahead of the first block not yet written.  The windows alone allow an advance
+                               // of 96 documents per unit against 64 retired: sustained runs of chunk-less documents made ring
+                               // slots alias.  The rule was tightened rather than the kernel given a third retirement per unit:
+                               // the refused layouts are degenerate and the sweep's measured inner loop stays as it is
     int32_t wide_ok64;         // the same with a ring of 64 documents (128-query bf16 sweeps)
     const int32_t* gate;       // optional device word: when non-null and *gate == 0 the scan / best-chunk kernels return at once
     int32_t variant;           // scan kernel: 14 = K-split kernel, f16-split products, <= 64 queries per sweep (default when

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from dense_geometry_cases import check_dense as _check_dense      # (shared with tests/test_gpu_dense_geometry.py)
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
@@ -253,35 +255,6 @@ def _rand_chunked(rng, n_docs, max_ch, big=()):
     emb = rng.standard_normal((C, 768)).astype(np.float32)
     emb /= np.linalg.norm(emb, axis=1, keepdims=True)
     return doc_off, emb
-
-
-def _check_dense(mods, eng, doc_off, emb, q, k, mc, got):
-    doc, score, chunk, n = [x.cpu().numpy() for x in got]
-    for i in range(q.shape[0]):
-        best, arg = mods["dense_ref"].doc_scores(emb, doc_off, q[i], mc)
-        oi, os_, oa = mods["dense_ref"].quick_search(emb, doc_off, q[i], k, mc)
-        assert n[i] == len(oi)
-        np.testing.assert_allclose(score[i, :n[i]], os_, rtol=0, atol=1e-5)        # north_star: 1e-5 fp32
-        np.testing.assert_allclose(score[i, :n[i]], best[doc[i, :n[i]]], rtol=0, atol=1e-5)
-        assert np.all(np.diff(score[i, :n[i]]) <= 0)
-        # same documents, except for swaps among scores closer than the tolerance
-        diff = set(doc[i, :n[i]].tolist()) ^ set(oi.tolist())
-        for d in diff:
-            assert abs(best[d] - os_[-1]) <= 2e-5
-        # ties broken by ascending index where the scores are exactly equal
-        for j in range(1, n[i]):
-            if score[i, j] == score[i, j - 1]:
-                assert doc[i, j] > doc[i, j - 1]
-        # arg-max chunk row
-        for j in range(n[i]):
-            d = doc[i, j]
-            c = chunk[i, j]
-            lo, hi = doc_off[d], doc_off[d + 1]
-            if mc:
-                hi = min(hi, lo + mc)
-            assert lo <= c < hi
-            cos_c = float(mods["rerank_ref"].cosine_f32(q[i], emb[c:c + 1])[0])
-            assert abs(cos_c - best[d]) <= 2e-5
 
 
 @pytest.mark.parametrize("layout,variant", [(0, 0), (1, 0), (0, 2), (1, 2), (0, 7), (1, 7), (0, 14), (0, 15)])
