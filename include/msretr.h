@@ -42,7 +42,7 @@ extern "C" {
                                      13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets;
                                      15: msr_best_windows; also 15 (calls added, none changed: a library
                                      that lacks them fails to load by symbol): msr_bind_vocab, msr_fuzzy_scratch_bytes,
-                                     msr_fuzzy_terms; msr_debug_chunk_layout */
+                                     msr_fuzzy_terms; msr_debug_chunk_layout; msr_dense_pass_info */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -88,6 +88,10 @@ typedef struct msr_config {
                                  pass then reads the caller's row-major matrix (same results bit for bit, ~13 % slower pass,
                                  half the embedding footprint); also declines the f16 image of the rows that launches of
                                  several query groups read (max_queries >= 512; msr_row_image_state) */
+#define MSR_CFG_SINGLE_EMIT 2 /* the streaming pass of msr_dense_topk emits in ONE launch per query group, with thresholds from
+                                 the sample pass alone, instead of cutting the emit pass into segments and raising the
+                                 thresholds between them (same results bit for bit, more entries written and filtered: the
+                                 reference form for tests and measurements; msr_dense_pass_info) */
 
 /* BM25 parameters travel with the postings (bm25_indexer.py:57 k1=1.2, b=0.75). */
 typedef struct msr_rerank_params {
@@ -168,6 +172,13 @@ int msr_scan_width(const msr_engine* e);
  * 64 / 32: the sweeps -- also what a call takes whose k or max_chunks_per_doc the streaming pass does not serve); 0 before
  * the first call.  For whoever attributes a measured kernel time to a kernel (bench.py). */
 int msr_dense_path(const msr_engine* e);
+/* What the streaming pass of the MOST RECENT msr_dense_topk / msr_dense_topk_begin call did (its last slice of queries, when a
+ * call is served in several): *segments = emit launches per query group -- 1: one launch over all row tiles (a small corpus,
+ * or MSR_CFG_SINGLE_EMIT), 2: the pass was cut after the first T1 tiles and the emission thresholds raised to what their tile
+ * maxima vouch for; 0: the call ran on the sweeps (then *entries = 0) --, *entries = (row, query, score) entries the pass
+ * appended to its per-wave buffers, summed over the waves (counted past a buffer's capacity when one overflowed).  DIAGNOSTIC:
+ * waits for the device and copies the counters to the host; it belongs in tests and measurements, never on a serving path. */
+int msr_dense_pass_info(msr_engine* e, int32_t* segments, int64_t* entries);
 /* The same for the <= 128-query sweeps of msr_dense_topk_bf16 (after msr_enable_bf16): 128, 64, or -1. */
 int msr_batch_width(const msr_engine* e);
 /* 1 if calls of msr_dense_topk_bf16 with more than 128 queries run as the tiled matrix-core GEMM (every document fits a

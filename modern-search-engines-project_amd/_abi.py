@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
 MSR_ABI_VERSION = 15
 MSR_CFG_NO_ROW_COPY = 1
+MSR_CFG_SINGLE_EMIT = 2
 MSR_DIM = 768
 MSR_MAX_K = 1024
 MSR_RERANK_MAX_CHUNKS = 10
@@ -61,6 +62,7 @@ _SIGNATURES = {
     "msr_scan_arith": (C.c_int, [_P]),
     "msr_scan_width": (C.c_int, [_P]),
     "msr_dense_path": (C.c_int, [_P]),
+    "msr_dense_pass_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "msr_row_copy_state": (C.c_int, [_P]),
     "msr_row_image_state": (C.c_int, [_P]),
     "msr_owned_bytes": (C.c_int64, [_P]),

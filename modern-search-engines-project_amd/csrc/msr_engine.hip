@@ -110,6 +110,7 @@ struct msr_engine {
                                        // msr_config.flags, 3 allocation failed (the row-major instantiation of the kernel runs)
     int row_image_state = 0;           // f16 image of the rows (launches of several query groups): the same four states
     int last_dense_width = 0;          // queries per pass over the matrix of the most recent msr_dense_topk call (msr_dense_path)
+    int last_dense_segments = 0;       // emit launches per query group of the most recent streaming call (msr_dense_pass_info)
     // mem_engine: msr_gather_rows / msr_dense_topk_grouped (grown on demand, kept until msr_destroy): a check flag, the per-row
     // lists, the per-row set indices and the merge's overflow records
     int32_t* sim_flag = nullptr;
@@ -258,7 +259,7 @@ extern "C" int msr_create(const msr_config* cfg, msr_engine** out) {
     if (cfg->scan_variant != 0 && cfg->scan_variant != 2 && cfg->scan_variant != 7 && cfg->scan_variant != 14 &&
         cfg->scan_variant != 15)
         return fail(nullptr, MSR_ERR_INVALID, "msr_create: scan_variant must be 0, 2, 7, 14 or 15");
-    if (cfg->flags & ~(int32_t)MSR_CFG_NO_ROW_COPY)
+    if (cfg->flags & ~(int32_t)(MSR_CFG_NO_ROW_COPY | MSR_CFG_SINGLE_EMIT))
         return fail(nullptr, MSR_ERR_INVALID, "msr_create: unknown flag bits 0x%x", cfg->flags);
     int ndev = 0;
     hipError_t herr = hipGetDeviceCount(&ndev);
@@ -595,6 +596,7 @@ static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st)
     const int max_nt = std::max(1, std::min(4, groups / 2));      // 256-query groups that share the rows of one launch
     GemmF32Index& g = e->gf;
     g.n_tiles = n_tiles; g.n_cus = e->n_cus; g.max_groups = groups; g.tmax_stride = stride; g.wv_cap = GF_WV_CAP; g.max_nt = max_nt;
+    g.single_emit = (e->cfg.flags & MSR_CFG_SINGLE_EMIT) ? 1 : 0;
     ALLOC(e, e->mem_chunks, e->gf_inv_pad, (size_t)(n_chunks + 512) * 4);
     ALLOC(e, e->mem_chunks, g.qimg, (size_t)groups * 24 * 8192);
     ALLOC(e, e->mem_chunks, e->gf_qn, (QM + 64) * MSR_DIM * 4);
@@ -722,6 +724,7 @@ extern "C" int msr_unbind(msr_engine* e) {
     e->url_group = nullptr; e->url_group_n = 0;
     e->doc_domain = nullptr; e->doc_domain_n = 0;
     e->last_dense_width = 0;
+    e->last_dense_segments = 0;
     // scratch sized by the corpus (the per-query scratch of msr_create stays)
     e->mem_corpus.release();
     e->score_rows_bytes = e->bm_cand_bytes = 0;
@@ -790,6 +793,23 @@ extern "C" int msr_scan_width(const msr_engine* e) {
 }
 
 extern "C" int msr_dense_path(const msr_engine* e) { return e ? e->last_dense_width : -1; }
+
+// Diagnostic (never on the hot path): waits for the device and reads the per-wave emission counters of the last streaming call.
+extern "C" int msr_dense_pass_info(msr_engine* e, int32_t* segments, int64_t* entries) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!segments || !entries) return fail(e, MSR_ERR_INVALID, "msr_dense_pass_info: null argument");
+    *segments = e->last_dense_segments;
+    *entries = 0;
+    if (!e->have_chunks || !e->gf_ok || e->last_dense_segments == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, hipDeviceSynchronize());
+    std::vector<int32_t> cnt((size_t)e->gf.n_cus * 8);
+    HIP_TRY(e, hipMemcpy(cnt.data(), e->gf.wv_count, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    int64_t sum = 0;
+    for (int32_t c : cnt) sum += c;
+    *entries = sum;
+    return MSR_OK;
+}
 
 extern "C" int64_t msr_owned_bytes(const msr_engine* e) {
     if (!e) return -1;
@@ -1284,8 +1304,10 @@ extern "C" int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_que
     hipEvent_t ev_buf[4];
     hipEvent_t* ev = pass_events(e, 0, ev_buf);
     int width = 0;
-    HIP_TRY(e, msr_gemm_f32_pass(e->gf, e->dense, e->gf_qn, n_queries, k, k_part, out_part, ev, &width, st));
+    int segs = 0;
+    HIP_TRY(e, msr_gemm_f32_pass(e->gf, e->dense, e->gf_qn, n_queries, k, k_part, out_part, ev, &width, &segs, st));
     e->last_dense_width = width;
+    e->last_dense_segments = segs;
     pass_events_used(e, 0, ev);
     e->split_pending = n_queries;
     return MSR_OK;
@@ -1363,6 +1385,7 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
     const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
     const bool gemm = wide && dense_stream_ok(e, k);
     e->last_dense_width = gemm && n_queries > 64 ? 0 : (wide ? 64 : 32);       // (the streaming path reports its own width below)
+    e->last_dense_segments = 0;
     int q0 = 0;
     while (q0 < n_queries) {
         const int left = n_queries - q0;
@@ -1373,11 +1396,12 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
             HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
             hipEvent_t ev_buf[4];
             hipEvent_t* ev = pass_events(e, 0, ev_buf);
-            int width = 0;
+            int width = 0, segs = 0;
             HIP_TRY(e, msr_gemm_f32_topk(e->gf, e->dense, e->gf_qn, nq, k, out_doc + (int64_t)q0 * k,
                                          out_score + (int64_t)q0 * k, out_chunk ? out_chunk + (int64_t)q0 * k : nullptr,
-                                         out_n + q0, e->gf_gate, ev, &width, st));
+                                         out_n + q0, e->gf_gate, ev, &width, &segs, st));
             e->last_dense_width = std::max(e->last_dense_width, width);
+            e->last_dense_segments = segs;
             pass_events_used(e, 0, ev);
             {
                 int rcf = dense_gated_fallback(e, nq, k, out_doc + (int64_t)q0 * k, out_score + (int64_t)q0 * k,
@@ -1417,6 +1441,7 @@ extern "C" int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_qu
     // every query on the sweeps (the kernels an unrestricted call of <= 64 queries runs), the restriction in the select
     const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
     e->last_dense_width = wide ? 64 : 32;
+    e->last_dense_segments = 0;
     const MsrSetView set{set_bits, set_stride, q_set, n_sets};
     return dense_sweeps(e, q, 0, n_queries, k, max_chunks_per_doc, wide, nullptr, out_doc, out_score, out_chunk, out_n, st, &set);
 }

@@ -18,7 +18,8 @@
 // MAXIMUM is attained by k different documents -- a lower bound of t^.  Pass 1 (every ss-th tile) computes tile maxima
 // only and gives the emission threshold; pass 2 (all tiles) stores the maxima of ALL tiles (a tighter bound afterwards)
 // and appends every (row, query, score) at or above the threshold to a buffer private to the WAVE (scalar counter +
-// lane prefix count, plain 16 B stores: no atomics).  Finish: entries above the tighter bound are bucketed per query
+// lane prefix count, plain 16 B stores: no atomics).  Pass 2 runs in two segments on corpora large enough for it: the tile
+// maxima of the first raise the threshold of the second (pass_shape below).  Finish: entries above the tighter bound are bucketed per query
 // (msr_gemm_bucket), reduced to distinct documents (gemm_f32_cand_kernel), rescored and sorted.  A query whose entries do
 // not fit anywhere on the way (huge tie groups) raises a device-side gate; the engine's sweeps, always enqueued behind
 // this path, run only when that gate is up (no host round trip).
@@ -31,6 +32,7 @@
 // freely, so one wave's memory wait hides behind the others' MFMAs.  (The first version staged the rows through LDS with
 // a barrier per K step: 3.6 ms per pass with the split arithmetic, 3.1 ms with one product; this form: 2.7 ms =
 // 5.7 TB/s on the same box, profiles/r02_gemm_knockout.md.)
+#include <cmath>
 #include <type_traits>
 
 #include "msr_common.h"
@@ -1101,16 +1103,83 @@ hipError_t msr_f16_row_error(const float* emb, const float* inv_norm, int64_t n_
     return hipGetLastError();
 }
 
+namespace {
+// The shape of a streaming call: which tiles the sample pass visits and where the emit pass is cut into segments.  Host
+// arithmetic only (restated in numpy by tests/test_dense_segments_host.py).
+//
+// Sample: every ss-th tile bounds the k-th score from below; >= 3 k sampled tiles, ss <= 64 (the weaker the bound, the more
+// entries the emit pass writes: ~150 ss per query).
+//
+// Segments: tile maxima are by-products of the emit pass itself, and ANY set of >= k distinct tiles bounds the k-th
+// document score from below (documents never straddle tiles).  So the pass emits over the first T1 tiles with the sample's
+// threshold, takes the k-th largest of THOSE T1 maxima (gemm_kth_kernel, raise mode: thr = max(thr, k-th - margin)) and
+// emits over the rest with the raised threshold.  With entries ~ c (T1 / n_s + (T - T1) / T1) the optimum is
+// T1 = sqrt(T n_s); T1 is the multiple of the grid nearest to that, so that both segments run whole rounds of the persistent
+// grid, and the cut is made only where T1 >= max(grid, 2 k) and T - T1 >= grid: smaller corpora keep the one-launch pass.
+// thr(sample) <= thr(first T1) <= thr2(all tiles) -- subsets of the same maxima, the same margin --, so what the bucket
+// keeps (score >= thr2) is the same set of entries either way: results do not move, the wave buffers only get fewer entries.
+// (Three segments, bounds at n_s r and n_s r^2 with r = (T / n_s)^(1/3), were measured too: profiles/dense_emit_segments.md.)
+struct PassShape {
+    int ss, n_s;               // sample: tiles ss / 2, ss / 2 + ss, ...: n_s of them
+    int n_seg;                 // emit launches per group
+    int bound[4];              // segment s covers tiles [bound[s], bound[s + 1])
+};
+PassShape pass_shape(int T, int k, int grid, bool single, int dbg) {
+    PassShape p{};
+    int ss = T / (3 * k);
+    ss = ss < 1 ? 1 : (ss > 64 ? 64 : ss);
+    p.ss = ss;
+    p.n_s = (T - ss / 2 + ss - 1) / ss;
+    p.n_seg = 1; p.bound[0] = 0; p.bound[1] = T;
+    if (single) return p;
+    (void)dbg;
+#ifdef MSR_DIAG
+    // timing experiments of the diagnostic build: 2097152 three segments, 4194304 / 8388608 T1 at half / double the rule's
+    // value, 16777216 the sample in whole rounds of the grid
+    if ((dbg & 16777216) && grid >= 2 * k && p.n_s > grid) {
+        p.n_s = p.n_s / grid * grid;
+        p.ss = T / p.n_s;
+    }
+#endif
+    const double root = std::sqrt((double)T * (double)p.n_s);
+    int want3 = 0;
+#ifdef MSR_DIAG
+    want3 = dbg & 2097152;
+#endif
+    if (want3) {
+        const double r = std::cbrt((double)T / (double)p.n_s);
+        const int m1 = (int)std::floor(p.n_s * r / grid + 0.5), m2 = (int)std::floor(p.n_s * r * r / grid + 0.5);
+        const int64_t t1 = (int64_t)m1 * grid, t2 = (int64_t)m2 * grid;
+        if (m1 >= 1 && m2 > m1 && t1 >= 2 * k && T - t2 >= grid) {
+            p.n_seg = 3; p.bound[1] = (int)t1; p.bound[2] = (int)t2; p.bound[3] = T;
+            return p;
+        }
+    }
+    int64_t t1 = (int64_t)std::floor(root / grid + 0.5) * grid;
+#ifdef MSR_DIAG
+    if (dbg & 4194304) t1 = std::max<int64_t>(grid, t1 / 2 / grid * grid);
+    if (dbg & 8388608) t1 = 2 * t1;
+#endif
+    if (t1 >= std::max(grid, 2 * k) && T - t1 >= grid) {
+        p.n_seg = 2; p.bound[1] = (int)t1; p.bound[2] = T;
+    }
+    return p;
+}
+
+}  // namespace
+
 // Exact f32 top-k of up to 128 x g.max_groups queries; see the header of this file.  nq <= 128: one pass of the 128-query
 // kernel; more: groups of 256 queries, one pass of the 256-query kernel each (a last group that is not full is padded with
 // zero queries: the bytes are the same).  The passes of all groups are queued back to back; everything between and after
-// them (the two selects over tile maxima, bucketing, candidate lists, rescoring, final sort) runs ONCE for all queries of
+// them (the selects over tile maxima, bucketing, candidate lists, rescoring, final sort) runs ONCE for all queries of
 // the call.
 // qn: [nq][768] normalised queries.  gate[s] != 0 (one word per 64 queries, zero on entry) when a query of slice s overflowed
 // (the caller falls back for that slice).  ev (nullable): events around the sample pass (0, 1) and the emit pass (2, 3) of
-// the first group.  *width_out (nullable): queries per pass of the kernel that ran.
+// the first group -- 2 before its first segment, 3 behind its last, the threshold refresh in between included: the time of a
+// WHOLE pass over the rows.  *width_out (nullable): queries per pass of the kernel that ran; *seg_out (nullable): emit
+// launches per group.
 hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k, int k_part,
-                             float* out_part, hipEvent_t* ev, int* width_out, hipStream_t stream) {
+                             float* out_part, hipEvent_t* ev, int* width_out, int* seg_out, hipStream_t stream) {
     const int W = nq > 128 ? 256 : 128;                 // queries per pass
     const int waves = 8;                                // waves per workgroup = emission buffers per workgroup (both kernels)
     const int G = (nq + W - 1) / W;
@@ -1131,10 +1200,10 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
     else build_qimg1_kernel<<<dim3((GF_KT * 128 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg);
     f16_margin_kernel<<<(nq + 3) / 4, 256, 0, stream>>>(qn, nq, g.err_max, g.margin);
     const float* margin = g.margin;
-    int ss = g.n_tiles / (3 * k);                       // every ss-th tile bounds the k-th score from below: >= 3 k sampled tiles
-    ss = ss < 1 ? 1 : (ss > 64 ? 64 : ss);          // (the weaker the bound, the more entries pass 2 emits: ~150 ss per query)
-    const int n_s = (g.n_tiles - ss / 2 + ss - 1) / ss;
     const int grid = g.n_cus;
+    const PassShape shape = pass_shape(g.n_tiles, k, grid, g.single_emit != 0, g_f32_dbg);
+    const int ss = shape.ss, n_s = shape.n_s;
+    if (seg_out) *seg_out = shape.n_seg;
     const size_t qimg_bytes = (size_t)GF_KT * W * 64;   // one group's image
     // 256-query kernel: up to 4 groups per launch walk the same tile sequence on CUs of one XCD -- the rows come from HBM
     // once per launch and from that XCD's L2 for the other groups (the bytes per query are what the pass costs)
@@ -1155,7 +1224,7 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
     if (image16) a.E = (const char*)g.emb_f16;
     const int tmax_parts = image16 ? 1 : waves;         // (the 16-bit image's data path joins the waves' tile maxima in LDS: one row per tile)
     a.n_rows = ix.n_chunks; a.tmax_t = g.tmax_t;
-    // ---- pass 1 of every group: maxima of every ss-th tile -> emission thresholds ----
+    // ---- sample pass of every group: maxima of every ss-th tile -> emission thresholds ----
     a.t_first = ss / 2; a.t_stride = ss; a.t_count = n_s;
     for (int gi = 0; gi < G; gi += NT) {
         a.nt = std::min(NT, G - gi);
@@ -1166,17 +1235,28 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
         if ((err = msr_gemm_tmax(g.tmax_t, n_s, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride, g.tmax_stride, stream)) != hipSuccess) return err;
     }
     if ((err = msr_gemm_kth(g.tmax, n_s, g.tmax_stride, nq, W * G, k, margin, g.thr, g.flag, stream)) != hipSuccess) return err;
-    // ---- pass 2 of every group: maxima of all tiles + the entries at or above the threshold (one set of wave buffers) ----
-    a.t_first = 0; a.t_stride = 1; a.t_count = g.n_tiles;
+    // ---- emit pass, segment by segment (pass_shape above): every group's launch over the segment's tiles -- their maxima
+    //      (the launch numbers its tiles from 0: tmax_t is joined into the segment's columns of g.tmax before the next launch
+    //      overwrites it) + the entries at or above the threshold, appended to one set of wave buffers --, then the thresholds
+    //      of ALL queries are raised to what the tiles seen so far vouch for.  The refresh never writes g.flag, never lowers a
+    //      threshold and leaves the padding queries at +inf (gemm_kth_kernel, raise mode). ----
+    a.t_stride = 1;
     a.wvbuf = g.wvbuf; a.wv_cap = g.wv_cap * (8 / waves); a.wv_count = g.wv_count;
-    for (int gi = 0; gi < G; gi += NT) {
-        a.nt = std::min(NT, G - gi);
-        a.qimg = (const char*)g.qimg + gi * qimg_bytes;
-        a.thr = g.thr + gi * W; a.q_base = gi * W; a.append = gi > 0;
-        if (ev && gi == 0 && (err = hipEventRecord(ev[2], stream)) != hipSuccess) return err;
-        if ((err = launch_f32(W, true, a, grid, stream, tiled, image16)) != hipSuccess) return err;
-        if (ev && gi == 0 && (err = hipEventRecord(ev[3], stream)) != hipSuccess) return err;
-        if ((err = msr_gemm_tmax(g.tmax_t, g.n_tiles, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride, g.tmax_stride, stream)) != hipSuccess) return err;
+    for (int s = 0; s < shape.n_seg; ++s) {
+        const int t0 = shape.bound[s], t1 = shape.bound[s + 1];
+        a.t_first = t0; a.t_count = t1 - t0;
+        for (int gi = 0; gi < G; gi += NT) {
+            a.nt = std::min(NT, G - gi);
+            a.qimg = (const char*)g.qimg + gi * qimg_bytes;
+            a.thr = g.thr + gi * W; a.q_base = gi * W; a.append = (s > 0 || gi > 0);
+            if (ev && gi == 0 && s == 0 && (err = hipEventRecord(ev[2], stream)) != hipSuccess) return err;
+            if ((err = launch_f32(W, true, a, grid, stream, tiled, image16)) != hipSuccess) return err;
+            if (ev && gi == 0 && s == shape.n_seg - 1 && (err = hipEventRecord(ev[3], stream)) != hipSuccess) return err;
+            if ((err = msr_gemm_tmax(g.tmax_t, t1 - t0, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride + t0, g.tmax_stride, stream)) != hipSuccess) return err;
+        }
+        if (s + 1 < shape.n_seg &&
+            (err = msr_gemm_kth(g.tmax, t1, g.tmax_stride, nq, W * G, k, margin, g.thr, nullptr, stream, __builtin_inff(), 1.0f, true)) != hipSuccess)
+            return err;
     }
     if ((err = msr_gemm_kth(g.tmax, g.n_tiles, g.tmax_stride, nq, W * G, k, margin, g.thr2, nullptr, stream)) != hipSuccess) return err;
     // (sharded callers: what this shard can vouch for towards the k-th score over all shards, see msr_internal.h)
@@ -1219,8 +1299,8 @@ hipError_t msr_gemm_f32_finish(const GemmF32Index& g, const DenseIndex& ix, cons
 
 hipError_t msr_gemm_f32_topk(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k,
                              int32_t* out_doc, float* out_score, int32_t* out_chunk,
-                             int32_t* out_n, int32_t* gate, hipEvent_t* ev, int* width_out, hipStream_t stream) {
-    hipError_t err = msr_gemm_f32_pass(g, ix, qn, nq, k, k, nullptr, ev, width_out, stream);
+                             int32_t* out_n, int32_t* gate, hipEvent_t* ev, int* width_out, int* seg_out, hipStream_t stream) {
+    hipError_t err = msr_gemm_f32_pass(g, ix, qn, nq, k, k, nullptr, ev, width_out, seg_out, stream);
     if (err != hipSuccess) return err;
     return msr_gemm_f32_finish(g, ix, qn, nq, k, nullptr, out_doc, out_score, out_chunk, out_n, gate, stream);
 }

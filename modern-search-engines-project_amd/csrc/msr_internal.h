@@ -385,9 +385,11 @@ int msr_gemm_pair_cap();
 hipError_t msr_gemm_tmax(const float* tmax_t, int n_j, int parts, int nq_pad, float* out, int out_stride, hipStream_t stream);
 // thr[q] = k-th largest valid value of row q of tmax ([nq][stride], n values per row) - margin[q]; one launch
 hipError_t msr_gemm_kth(const float* tmax, int n, int stride, int nq, int nq_pad, int k, const float* margin, float* thr,
-                        int32_t* flag, hipStream_t stream, float short_val = __builtin_inff(), float margin_scale = 1.0f);
+                        int32_t* flag, hipStream_t stream, float short_val = __builtin_inff(), float margin_scale = 1.0f,
+                        bool raise = false);
 // (short_val: what thr[q] becomes when row q holds fewer than k valid values -- and for the padding rows q >= nq;
-// margin_scale: thr = k-th value - margin_scale * margin[q])
+// margin_scale: thr = k-th value - margin_scale * margin[q]; raise: thr[q] = max(thr[q], that value) instead -- rows with
+// fewer than k valid values and padding rows keep what they hold, flag is not written)
 hipError_t msr_gemm_bucket(const void* wvbuf, int wv_cap, const int32_t* wv_count, int n_waves, const float* thr2,
                            void* pairs, int32_t* pair_n, hipStream_t stream);
 void msr_bm25_set_dbg(int v);       // honoured by -DMSR_DIAG builds only
@@ -455,6 +457,7 @@ struct GemmF32Index {
     const int32_t* tile_trow;  // [n_tiles] first row of each tile in that copy
     const void* emb_f16;       // row-major f16 image of the rows (as the pass converts them; [n_chunks + 512][768], zero padded)
                                // for launches of several query groups (nullptr: none), see msr_f16_rows
+    int32_t single_emit;       // MSR_CFG_SINGLE_EMIT: the emit pass as ONE launch per group, thresholds from the sample alone
 };
 // emb_tiled <- fragment-order copy of emb: tile t's rows at tile_trow[t] (multiples of 16), 16-row groups x 24 K steps x 2 KB
 hipError_t msr_f16_rows(const float* emb, int64_t n_rows, int64_t n_pad, void* out, hipStream_t stream);
@@ -465,10 +468,11 @@ void msr_gemm_f32_set_dbg(int v);   // honoured by -DMSR_DIAG builds only
 hipError_t msr_pad_inv_norm(const float* inv, int64_t n, int64_t n_pad, float* out, hipStream_t stream);
 // Top-k of up to 128 normalised queries qn in one pass over the f32 rows; out_n[q] = -1 and *gate |= 1 for a query whose
 // entries overflowed (caller: rerun the batch on the sweeps, gated on *gate).  ev (nullable): events around the sample
-// pass (0, 1) and the emit pass (2, 3).
+// pass (0, 1) and the emit pass (2, 3: all its segments and the threshold refresh between them).  *seg_out (nullable): emit
+// launches per query group (1: the corpus is too small to cut the pass, or g.single_emit).
 hipError_t msr_gemm_f32_topk(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k,
                              int32_t* out_doc, float* out_score, int32_t* out_chunk,
-                             int32_t* out_n, int32_t* gate, hipEvent_t* ev, int* width_out, hipStream_t stream);
+                             int32_t* out_n, int32_t* gate, hipEvent_t* ev, int* width_out, int* seg_out, hipStream_t stream);
 // The same in two halves, for a doc-sharded index (msr_dense_topk_begin / _end).  _pass: everything up to the thresholds of
 // this shard's own tile maxima; out_part[q] (nullable) <- (k_part-th largest tile maximum of query q) - margin[q] / 2, -inf
 // when the shard has fewer than k_part row tiles: k_part documents of this shard have EXACT cosines >= that value (a filter
@@ -477,7 +481,7 @@ hipError_t msr_gemm_f32_topk(const GemmF32Index& g, const DenseIndex& ix, const 
 // document of the global top-k has exact cosine >= A, so filter score >= A - eps: entries below bound - margin / 2 are dropped before
 // bucketing, candidate lists and exact rescoring -- the shard then returns fewer than k documents, all it can contribute.
 hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k, int k_part,
-                             float* out_part, hipEvent_t* ev, int* width_out, hipStream_t stream);
+                             float* out_part, hipEvent_t* ev, int* width_out, int* seg_out, hipStream_t stream);
 hipError_t msr_gemm_f32_finish(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k, const float* bound,
                                int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, int32_t* gate,
                                hipStream_t stream);

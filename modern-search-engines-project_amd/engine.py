@@ -57,9 +57,11 @@ def stream_to_device(arr, device, block_bytes=128 << 20):
 
 class DeviceEngine:
     def __init__(self, index: CorpusIndex, device=0, max_queries=32, max_k=1000, rerank_max_docs=1000,
-                 scan_layout=0, scan_variant=0, row_copy=True):
+                 scan_layout=0, scan_variant=0, row_copy=True, single_emit=False):
         """row_copy=False: MSR_CFG_NO_ROW_COPY -- the 256-query pass reads the row-major matrix instead of an engine-owned
-        fragment-order copy of it (half the embedding footprint, a slower pass, the same results)."""
+        fragment-order copy of it (half the embedding footprint, a slower pass, the same results).
+        single_emit=True: MSR_CFG_SINGLE_EMIT -- the streaming pass emits in one launch per query group with the sample's
+        thresholds (the reference form of the segmented pass: the same results, more entries; dense_pass_info())."""
         if not torch.cuda.is_available():
             raise _abi.MsrError(-102, "no GPU visible: the retrieval path runs on MI355X only (no CPU fallback)")
         self.lib = _abi.load()
@@ -71,7 +73,7 @@ class DeviceEngine:
         self.rerank_max_docs = int(rerank_max_docs)
         cfg = _abi.MsrConfig(C.sizeof(_abi.MsrConfig), self.device.index or 0, DIM, int(max_queries), int(max_k),
                              int(rerank_max_docs), int(scan_layout), int(scan_variant),
-                             0 if row_copy else _abi.MSR_CFG_NO_ROW_COPY)
+                             (0 if row_copy else _abi.MSR_CFG_NO_ROW_COPY) | (_abi.MSR_CFG_SINGLE_EMIT if single_emit else 0))
         self.handle = C.c_void_p()
         rc = self.lib.msr_create(C.byref(cfg), C.byref(self.handle))
         if rc != 0:
@@ -270,6 +272,14 @@ class DeviceEngine:
     def dense_path(self):
         """Queries per pass of the kernel the most recent dense_topk call ran (256 / 128 / 64 / 32; 0 before the first)."""
         return int(self.lib.msr_dense_path(self.handle))
+
+    def dense_pass_info(self):
+        """(segments, entries) of the streaming pass of the most recent dense_topk / dense_begin call: emit launches per query
+        group (1: one launch over all tiles; 2: cut once, thresholds raised in between; 0: the call ran on the sweeps) and the
+        entries it appended to its wave buffers.  Diagnostic: waits for the device."""
+        seg, ent = C.c_int32(0), C.c_int64(0)
+        self._check(self.lib.msr_dense_pass_info(self.handle, C.byref(seg), C.byref(ent)))
+        return int(seg.value), int(ent.value)
 
     def pack_queries(self, term_lists):
         """list of term-id lists (repeats allowed, any unknown id < 0) -> device CSR of UNIQUE terms in
