@@ -5,10 +5,12 @@ two-stage path and write `qnum<TAB>rank<TAB>url<TAB>score` lines, like POST /api
 is generated: documents are bags of words from a vocabulary that contains the query words, indexed with
 msretr.index_build (the reference's BM25.build_index semantics) and given random unit-norm chunk embeddings.
 
-    python examples/run_queries_txt.py [--fuzzy] [queries.txt] [out.txt]
+    python examples/run_queries_txt.py [--fuzzy] [--wildcards] [queries.txt] [out.txt]
 
 --fuzzy: words the vocabulary lacks are replaced by their nearest term (Retriever.batch_search(fuzzy=True)) and every
 correction is printed.
+--wildcards: `bibliothek*`, `*bibliothek`, `t?bingen` are expanded over the vocabulary
+(Retriever.batch_search(wildcards=True)) and every expansion is printed.
 """
 import os
 import sys
@@ -63,19 +65,22 @@ def fake_encoder(dim=768):
 
 def main():
     from msretr.retriever import Retriever
-    argv = [a for a in sys.argv[1:] if a != "--fuzzy"]
-    fuzzy = "--fuzzy" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--fuzzy", "--wildcards")]
+    fuzzy, wildcards = "--fuzzy" in sys.argv[1:], "--wildcards" in sys.argv[1:]
     qfile = argv[0] if len(argv) > 0 else None
     out = argv[1] if len(argv) > 1 else "batch_search_results.txt"
     queries = read_queries_file(qfile) if qfile else [(str(i + 1), q) for i, q in enumerate(DEFAULT_QUERIES)]
     ix = synthetic_crawl()
     rt = Retriever(embedder=fake_encoder(), indexer=ix, tokenizer=simple_tokenize, max_queries=8, max_k=1000)
-    res = rt.batch_search(queries, fuzzy=fuzzy)     # the reference's `results` list (dicts built on access) ...
+    res = rt.batch_search(queries, fuzzy=fuzzy, wildcards=wildcards)     # the reference's `results` list (dicts built on access) ...
     res.write(out)                                  # ... and all formatted lines in one native call
     print(f"{len(queries)} queries -> {len(res)} result lines in {out}")
     for (qn, _), text in zip(queries, res.corrected_queries or ()):
         if text is not None:
             print(f"query {qn}: searched for {text!r}")
+    for (qn, _), exp in zip(queries, res.expansions or ()):
+        for pattern, info in exp.items():
+            print(f"query {qn}: {pattern} -> {', '.join(info['terms']) or 'nothing'} ({info['total']} matches)")
     rt.engine.close()
 
 

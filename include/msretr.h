@@ -42,7 +42,8 @@ extern "C" {
                                      13: msr_bind_tokens, msr_phrase_sets, msr_combine_sets; 14: msr_proximity_sets;
                                      15: msr_best_windows; also 15 (calls added, none changed: a library
                                      that lacks them fails to load by symbol): msr_bind_vocab, msr_fuzzy_scratch_bytes,
-                                     msr_fuzzy_terms; msr_debug_chunk_layout; msr_dense_pass_info */
+                                     msr_fuzzy_terms; msr_debug_chunk_layout; msr_dense_pass_info;
+                                     msr_wildcard_scratch_bytes, msr_wildcard_terms */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -56,6 +57,9 @@ extern "C" {
 #define MSR_FUZZY_MAX_LIMIT 16     /* msr_fuzzy_terms: most candidates returned per word */
 #define MSR_FUZZY_SPAN_TERMS 1024  /* msr_fuzzy_terms: consecutive vocabulary terms one workgroup of its first kernel owns */
 #define MSR_FUZZY_WORD_GROUP 16    /* msr_fuzzy_terms: words that kernel stages in LDS at a time */
+#define MSR_WILD_MAX_LEN 32        /* msr_wildcard_terms: the longest pattern, in symbols, and the longest term it matches */
+#define MSR_WILD_MAX_PATTERNS 1024 /* msr_wildcard_terms: most patterns of one call */
+#define MSR_WILD_MAX_LIMIT 16      /* msr_wildcard_terms: most matches returned per pattern */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -363,6 +367,33 @@ int64_t msr_fuzzy_scratch_bytes(int64_t n_terms, int32_t n_words, int32_t limit)
 int msr_fuzzy_terms(msr_engine* e, int32_t n_words, const int32_t* word_off, const uint16_t* word_chars, const int32_t* word_max,
                     int32_t limit, int32_t* out_term, int32_t* out_dist, int32_t* out_n, int32_t* out_total, void* scratch,
                     int64_t scratch_bytes, void* stream);
+
+/* Prefix and wildcard lookup: the vocabulary terms a pattern matches, over the vocabulary bound
+ * with msr_bind_vocab.
+ *   PATTERN: 1 .. MSR_WILD_MAX_LEN symbols, each a 16-bit code point.  `*` (0x002A) matches any run of zero or more code points,
+ *   `?` (0x003F) exactly one; every other symbol matches itself.  There is no escape: a term that itself holds 0x2A or 0x3F is
+ *   matched only through a metacharacter.  The match is anchored at both ends (the whole term must match); `**` means `*`; a
+ *   pattern without a metacharacter is an exact lookup.
+ *   MATCHES of pattern p: the terms t with weight[t] > 0, at most MSR_WILD_MAX_LEN code points and match(p, t), ORDERED by
+ *   weight descending, then term id ascending (a total order).
+ *
+ * msr_wildcard_scratch_bytes: bytes of scratch one msr_wildcard_terms call over a vocabulary of n_terms terms needs for
+ *   n_patterns patterns and `limit` matches (-1 for arguments the call would refuse; 0 for n_patterns == 0): the formula of
+ *   msr_fuzzy_scratch_bytes, n_patterns * ceil(n_terms / 1024) * (8 * limit + 4).  The caller supplies the scratch (8-byte
+ *   aligned); the engine keeps none.
+ *
+ * msr_wildcard_terms: pattern i's symbols are pat_chars[pat_off[i] .. pat_off[i + 1]) (int32 offsets).  Row i of out_term
+ *   (int32 [n_patterns][limit]) receives the first out_n[i] = min(out_total[i], limit) matches in the order above, the
+ *   remaining slots of the row -1; out_total[i] = the number of ALL matches.  The kernel itself writes the row empty (out_n =
+ *   out_total = 0, every slot -1) for a pattern of 0 or of more than MSR_WILD_MAX_LEN symbols.  All pointers are device
+ *   pointers.  The call only enqueues (two launches); repeated calls give the same bytes (no atomics); nothing is written at
+ *   or beyond row n_patterns.  Refused before any launch, outputs untouched: MSR_ERR_NOT_BOUND without a vocabulary;
+ *   MSR_ERR_INVALID for n_patterns < 0 or > MSR_WILD_MAX_PATTERNS, limit outside [1, MSR_WILD_MAX_LIMIT], and with
+ *   n_patterns > 0 a NULL pointer, a scratch that is not 8-byte aligned or scratch_bytes <
+ *   msr_wildcard_scratch_bytes(n_terms, n_patterns, limit).  n_patterns == 0 succeeds and launches nothing. */
+int64_t msr_wildcard_scratch_bytes(int64_t n_terms, int32_t n_patterns, int32_t limit);
+int msr_wildcard_terms(msr_engine* e, int32_t n_patterns, const int32_t* pat_off, const uint16_t* pat_chars, int32_t limit,
+                       int32_t* out_term, int32_t* out_n, int32_t* out_total, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* msr_combine_sets: out[r] = AND of in[s] for s in and_rows[and_off[r] .. and_off[r + 1])  AND NOT  OR of in[s] for s in
  *   not_rows[not_off[r] .. not_off[r + 1]), rows of in_bits (n_in rows in_stride words apart) in the layout above.  An empty

@@ -12,6 +12,7 @@ MSR_CFG_NO_ROW_COPY = 1
 MSR_CFG_SINGLE_EMIT = 2
 MSR_DIM = 768
 MSR_MAX_K = 1024
+MSR_MAX_QUERY_TERMS = 64
 MSR_RERANK_MAX_CHUNKS = 10
 MSR_MERGE_MAX_ENTRIES = 8192
 MSR_TERMSET_SPAN_DOCS = 8192
@@ -23,6 +24,9 @@ MSR_FUZZY_MAX_WORDS = 1024
 MSR_FUZZY_MAX_LIMIT = 16
 MSR_FUZZY_SPAN_TERMS = 1024
 MSR_FUZZY_WORD_GROUP = 16
+MSR_WILD_MAX_LEN = 32
+MSR_WILD_MAX_PATTERNS = 1024
+MSR_WILD_MAX_LIMIT = 16
 MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
 
 
@@ -90,6 +94,8 @@ _SIGNATURES = {
     "msr_bind_vocab": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, _P]),
     "msr_fuzzy_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "msr_fuzzy_terms": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "msr_wildcard_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "msr_wildcard_terms": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
     "msr_combine_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,

@@ -10,6 +10,7 @@ in the reference too: tokenising the query string and formatting the snippet.
 from typing import Callable, List, Optional, Sequence, Union
 
 from . import fuzzy as _fuzzy
+from . import wildcard as _wildcard
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .text import Near, parse_operators, parse_phrases, parse_proximity, simple_tokenize
@@ -58,6 +59,20 @@ class BM25:
         df = np.diff(_np(self.index.term_off).astype(np.int64))
         return [[(self._name_of(t), d, int(df[t])) for t, d in cands] for cands, _ in self.engine.fuzzy_terms(list(words), limit=limit)]
 
+    def wildcard_terms(self, patterns, limit=8):
+        """Which vocabulary words does each pattern match (`*` any run of code points, `?` exactly one, anchored at both
+        ends)?  -> per pattern ([(term, doc_freq), ...], total): the most frequent first (then the smaller term id), at most
+        `limit` (1 .. 16) of them, and the number of all matches.  Patterns are lower-cased like a query.  One
+        DeviceEngine.wildcard_terms call (msr_wildcard_terms, DESIGN K16); an index without term strings raises ValueError."""
+        import numpy as np
+        from .index import _np
+        if not self.engine.has_vocab:
+            raise ValueError("wildcards: the index has no vocabulary (CorpusIndex.vocab: term strings); a term-id-only index "
+                             "cannot expand a pattern")
+        df = np.diff(_np(self.index.term_off).astype(np.int64))
+        got = self.engine.wildcard_terms([str(p).lower() for p in patterns], limit=limit)
+        return [([(self._name_of(t), int(df[t])) for t in terms], total) for terms, total in got]
+
     # -- engine-level entry points (usable without spaCy: pre-tokenised terms or term ids) ----------
     def search_terms(self, terms: Sequence[Union[str, int]], top_k: int = 1000, min_score: float = 0.0, within=None):
         return self.search_terms_batch([terms], top_k, min_score, within=within)[0]
@@ -99,8 +114,13 @@ class BM25:
     # -- the reference's method ------------------------------------------------------------------------
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
                must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None,
-               proximity: bool = False, fuzzy: bool = False):
-        """fuzzy=True (DESIGN K15): a query word (or must word) the vocabulary lacks is replaced by its nearest vocabulary term
+               proximity: bool = False, fuzzy: bool = False, wildcards: bool = False, max_expansions: int = 8, patterns=None):
+        """wildcards=True (DESIGN K16): a token of the query with `*` or `?` is a pattern (wildcard.parse_wildcards, in front of
+        the phrases and the operators): it leaves the scoring text and the vocabulary terms it matches, the most frequent
+        first, at most max_expansions (1 .. 16), are appended to the query's terms (wildcard.expand); patterns=: further
+        pattern strings.  The result is then a fuzzy.Results list whose `expansions` says what each pattern became.  Patterns
+        are never required, excluded or corrected.  Needs an index with term strings (ValueError).  Off by default.
+        fuzzy=True (DESIGN K15): a query word (or must word) the vocabulary lacks is replaced by its nearest vocabulary term
         -- optimal string alignment distance within the AUTO tolerance of its length, then the largest document frequency
         (fuzzy.py) -- before scoring; the result is a fuzzy.Results list whose `corrections` maps typed to used terms (`corrected_query`: the scoring text with them, or None).  Words
         of the vocabulary are never touched; must_not words, phrases and proximity conditions are NOT corrected (excluding
@@ -117,12 +137,24 @@ class BM25:
         in must_phrases / must_not_phrases is one without the text syntax: the terms within a window, in any order or in
         order, instead of next to each other (DESIGN K13)."""
         phrases = phrases or proximity
+        pats = None
+        if wildcards or patterns is not None:
+            from ._abi import MSR_WILD_MAX_LIMIT
+            if isinstance(max_expansions, bool) or not isinstance(max_expansions, int) or not 1 <= max_expansions <= MSR_WILD_MAX_LIMIT:
+                raise ValueError(f"max_expansions must be 1 .. MSR_WILD_MAX_LIMIT = {MSR_WILD_MAX_LIMIT} (got {max_expansions!r})")
+            if not self.engine.has_vocab:
+                raise ValueError("wildcards: the index has no vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
+                                 "index cannot expand a pattern")
+            pats = []
+            if wildcards:
+                query, pats = _wildcard.parse_wildcards(query)
+            pats = list(pats) + [str(p).lower() for p in (patterns or ())]
         if phrases:
             query, m_ph, x_ph = (parse_proximity if proximity else parse_phrases)(query)
         if operators:
             query, m_words, x_words = parse_operators(query)
         query_terms = self._tokenize(query)
-        if not query_terms:
+        if not query_terms and not pats:
             return []                                              # bm25_indexer.py:396-397
         m, x = list(must or ()), list(must_not or ())
         if operators:
@@ -147,8 +179,15 @@ class BM25:
                                              within=None if within is None else [within])
         elif m or x:
             within = self.engine.term_sets([ids(m)], [ids(x)], within=None if within is None else [within])
+        expansions = None
+        if pats is not None:
+            new_ids, exp = _wildcard.expand(lambda ps: self.engine.wildcard_terms(ps, limit=max_expansions), self._name_of,
+                                            [ids(query_terms)], [pats], max_expansions)
+            query_terms, expansions = new_ids[0], exp[0]
         rows = self._finish(self.search_terms(query_terms, top_k, min_score, within=within))
-        return rows if corrections is None else _fuzzy.Results(rows, corrections, _fuzzy.corrected_text(query, corrections))
+        if corrections is None and expansions is None:
+            return rows
+        return _fuzzy.Results(rows, corrections, _fuzzy.corrected_text(query, corrections) if corrections else None, expansions)
 
     def _finish(self, ranked):
         """urlsDB join after the cut: documents without a row are dropped, snippet = title + 200 chars

@@ -37,6 +37,7 @@ UNITS = {
     "msr_proximity.hip": [],
     "msr_snippet.hip": [],
     "msr_fuzzy.hip": [],
+    "msr_wildcard.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)

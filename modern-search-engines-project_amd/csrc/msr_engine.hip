@@ -1122,6 +1122,36 @@ extern "C" int msr_fuzzy_terms(msr_engine* e, int32_t n_words, const int32_t* wo
     return MSR_OK;
 }
 
+// ---- K16: prefix and wildcard lookup (msr_wildcard.hip) -------------------------------------------------------------------------
+extern "C" int64_t msr_wildcard_scratch_bytes(int64_t n_terms, int32_t n_patterns, int32_t limit) {
+    if (n_terms < 0 || n_terms >= (1ll << 31) || n_patterns < 0 || n_patterns > MSR_WILD_MAX_PATTERNS || limit < 1 ||
+        limit > MSR_WILD_MAX_LIMIT)
+        return -1;
+    return (int64_t)n_patterns * msr_fuzzy_spans(n_terms) * ((int64_t)limit * 8 + 4);
+}
+
+extern "C" int msr_wildcard_terms(msr_engine* e, int32_t n_patterns, const int32_t* pat_off, const uint16_t* pat_chars,
+                                  int32_t limit, int32_t* out_term, int32_t* out_n, int32_t* out_total, void* scratch,
+                                  int64_t scratch_bytes, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_vocab)
+        return fail(e, MSR_ERR_NOT_BOUND, "msr_wildcard_terms: vocabulary not bound (msr_bind_vocab: the index has no term strings)");
+    if (n_patterns < 0 || n_patterns > MSR_WILD_MAX_PATTERNS || limit < 1 || limit > MSR_WILD_MAX_LIMIT)
+        return fail(e, MSR_ERR_INVALID, "msr_wildcard_terms: bad argument (n_patterns=%d, at most %d; limit=%d, 1 .. %d)",
+                    n_patterns, MSR_WILD_MAX_PATTERNS, limit, MSR_WILD_MAX_LIMIT);
+    if (n_patterns == 0) return MSR_OK;
+    if (!pat_off || !pat_chars || !out_term || !out_n || !out_total || !scratch)
+        return fail(e, MSR_ERR_INVALID, "msr_wildcard_terms: bad argument (a NULL pointer with n_patterns=%d)", n_patterns);
+    const int64_t need = msr_wildcard_scratch_bytes(e->bm25.n_terms, n_patterns, limit);
+    if (need < 0 || scratch_bytes < need || ((uintptr_t)scratch & 7))
+        return fail(e, MSR_ERR_INVALID, "msr_wildcard_terms: bad argument (scratch_bytes=%lld, needed %lld, 8-byte aligned)",
+                    (long long)scratch_bytes, (long long)need);
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_wildcard_terms_run(e->voc_char_off, e->voc_chars, e->voc_weight, e->voc_sig, e->bm25.n_terms, n_patterns,
+                                      pat_off, pat_chars, limit, out_term, out_n, out_total, scratch, (hipStream_t)stream));
+    return MSR_OK;
+}
+
 extern "C" int msr_combine_sets(msr_engine* e, int32_t n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int32_t n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, void* stream) {

@@ -1,4 +1,6 @@
-// K15: typo-tolerant lookup (msr_bind_vocab / msr_fuzzy_terms; include/msretr.h).
+// K15: typo-tolerant lookup (msr_bind_vocab / msr_fuzzy_terms; include/msretr.h).  The pieces K16
+// (msr_wildcard.hip) uses too -- signature bit, 64-bit shuffles, keys, wave_first_keys, the slot store, the merge -- are in
+// msr_vocabscan.h.
 //
 // For every word of a call: the vocabulary terms within its tolerance m <= 2 of it by optimal string alignment (insertion,
 // deletion, substitution, swap of two adjacent code points; no substring edited twice), ordered by (distance, weight
@@ -31,24 +33,20 @@
 #include "../../include/msretr.h"
 #include "msr_internal.h"
 #include "msr_sort.h"
+#include "msr_vocabscan.h"
 
 namespace {
 
-constexpr int FZ_SPAN = MSR_FUZZY_SPAN_TERMS;
-constexpr int FZ_WAVES = FZ_SPAN / 64;
-constexpr int FZ_G = MSR_FUZZY_WORD_GROUP;
-constexpr int FZ_LEN = MSR_FUZZY_MAX_LEN;
-constexpr int FZ_LIM = MSR_FUZZY_MAX_LIMIT;
+using namespace msr_vocabscan;                               // sig_bit, the 64-bit shuffles, the keys, wave_first_keys, the merge
+
+constexpr int FZ_SPAN = VS_SPAN;
+constexpr int FZ_WAVES = VS_WAVES;
+constexpr int FZ_G = VS_G;
+constexpr int FZ_LEN = VS_LEN;
+constexpr int FZ_LIM = VS_LIM;
 constexpr int FZ_PAD = 4;                                    // code points of padding on either side of a staged word
 constexpr int FZ_ROW = FZ_LEN + 2 * FZ_PAD;
-constexpr uint64_t FZ_NONE = ~0ull;                          // "no candidate": distance 3, which no key has
-constexpr int MG_THREADS = 256;
-constexpr int MG_CAP = 2048;                                 // keys of one sort of the merge
-static_assert(FZ_SPAN == 1024, "one lane per term, the largest workgroup");
-static_assert(FZ_G == FZ_WAVES, "wave v of the scan merges word v of the group");
-static_assert(FZ_LEN == 32 && FZ_G * 32 <= FZ_SPAN, "32 staging threads per word, a term in 16 registers");
-static_assert(FZ_LIM <= 64 && FZ_WAVES * FZ_LIM <= 256, "a wave holds a group's lists in four keys per lane");
-static_assert((MG_CAP - FZ_LIM) / FZ_LIM >= 1, "a round of the merge takes at least one span");
+constexpr uint64_t FZ_NONE = VS_NONE;
 
 struct FuzzyArgs {
     const int64_t* char_off; const uint16_t* chars; const uint32_t* weight; const uint64_t* sig;
@@ -57,23 +55,6 @@ struct FuzzyArgs {
     uint64_t* keys; int32_t* counts;                         // the scratch: [n_words][n_spans][limit], [n_words][n_spans]
     int32_t* out_term; int32_t* out_dist; int32_t* out_n; int32_t* out_total;
 };
-
-__device__ __forceinline__ uint64_t sig_bit(uint32_t c) { return 1ull << ((c * 0x9E3779B1u) >> 26); }
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-    for (int m = 32; m; m >>= 1) {
-        const uint64_t o = shfl_xor_u64(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 
 // min(d(term, word), 3): tc = the term's L <= 32 code points, two per register; w = the word's LDS row (code point j, 1-based,
 // at w[FZ_PAD + j - 1]; the padding never matches and is never inside a valid cell), n its length.  Row i, band slot k is the
@@ -121,25 +102,6 @@ __device__ __forceinline__ int osa_le2(const uint32_t (&tc)[FZ_LEN / 2], int L, 
     return res;
 }
 
-// The first `limit` keys of a wave in ascending order, key r in lane r (FZ_NONE where there is none).  mine[0 .. N): the
-// lane's own keys.  Every lane of the wave calls it.
-template <int N>
-__device__ __forceinline__ uint64_t wave_first_keys(uint64_t (&mine)[N], int limit, int lane) {
-    uint64_t keep = FZ_NONE;
-    for (int r = 0; r < limit; ++r) {
-        uint64_t lo = mine[0];
-#pragma unroll
-        for (int k = 1; k < N; ++k) lo = mine[k] < lo ? mine[k] : lo;
-        const uint64_t mn = wave_min_u64(lo);
-        if (mn == FZ_NONE) break;                            // (wave-uniform)
-        if (lane == r) keep = mn;
-#pragma unroll
-        for (int k = 0; k < N; ++k)
-            if (mine[k] == mn) mine[k] = FZ_NONE;            // (keys are unique: exactly one goes)
-    }
-    return keep;
-}
-
 __global__ __launch_bounds__(FZ_SPAN) void fuzzy_scan_kernel(const FuzzyArgs a) {
     __shared__ uint16_t s_wch[FZ_G][FZ_ROW];
     __shared__ int32_t s_wlen[FZ_G], s_wmax[FZ_G];           // length 0: not a valid word
@@ -165,7 +127,7 @@ __global__ __launch_bounds__(FZ_SPAN) void fuzzy_scan_kernel(const FuzzyArgs a) 
             term_ok = true;
             L = (int)len;
             st = a.sig[t];
-            key_low = ((uint64_t)(0x7FFFFFFFu - wt) << 31) | (uint64_t)t;
+            key_low = msr_vocabscan::key_low(wt, t);
 #pragma unroll
             for (int i = 0; i < FZ_LEN; ++i) {
                 const uint32_t c = i < L ? a.chars[o0 + i] : 0u;
@@ -215,18 +177,7 @@ __global__ __launch_bounds__(FZ_SPAN) void fuzzy_scan_kernel(const FuzzyArgs a) 
         if (wave < ng) {                                     // wave v merges word v of the group
             const int g = wave;
             const int64_t slot = (int64_t)(g0 + g) * a.n_spans + span;
-            uint64_t e[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int idx = lane + 64 * k;
-                e[k] = idx < FZ_WAVES * limit ? s_key[g][idx] : FZ_NONE;
-            }
-            int total = lane < FZ_WAVES ? s_cnt[g][lane] : 0;
-            for (int mk = 32; mk; mk >>= 1) total += __shfl_xor(total, mk);
-            uint64_t keep = FZ_NONE;
-            if (total > 0) keep = wave_first_keys<4>(e, limit, lane);
-            if (lane < limit) a.keys[slot * limit + lane] = keep;
-            if (lane == 0) a.counts[slot] = total;
+            span_slot_store(&s_key[g][0], &s_cnt[g][0], limit, lane, slot, a.keys, a.counts);
         }
         // (no barrier: the next group's staging writes what this merge does not read, and the barrier behind the staging
         // stands between this merge and the next group's lists)
@@ -234,44 +185,7 @@ __global__ __launch_bounds__(FZ_SPAN) void fuzzy_scan_kernel(const FuzzyArgs a) 
 }
 
 __global__ __launch_bounds__(MG_THREADS) void fuzzy_merge_kernel(const FuzzyArgs a) {
-    __shared__ uint64_t s_hi[MG_CAP];
-    __shared__ uint32_t s_lo[MG_CAP];                         // the sort's key extension: unused, all zero
-    __shared__ int32_t s_sum[MG_THREADS / 64];
-    const int tid = (int)threadIdx.x, w = (int)blockIdx.x, limit = a.limit;
-    const int64_t base = (int64_t)w * a.n_spans;
-    for (int i = tid; i < MG_CAP; i += MG_THREADS) s_lo[i] = 0;
-    if (tid < limit) s_hi[tid] = FZ_NONE;
-    int sum = 0;
-    for (int s = tid; s < a.n_spans; s += MG_THREADS) sum += a.counts[base + s];
-    for (int mk = 32; mk; mk >>= 1) sum += __shfl_xor(sum, mk);
-    if ((tid & 63) == 0) s_sum[tid >> 6] = sum;
-    __syncthreads();
-    int total = 0;
-#pragma unroll
-    for (int k = 0; k < MG_THREADS / 64; ++k) total += s_sum[k];
-    if (total > 0) {                                         // (the same in every thread)
-        const int per = (MG_CAP - limit) / limit;            // spans of one round: their keys and the best so far fit the sort
-        for (int s0 = 0; s0 < a.n_spans; s0 += per) {
-            const int ne = imin(per, a.n_spans - s0) * limit;
-            int P = 2;
-            while (P < limit + ne) P <<= 1;
-            const uint64_t* src = a.keys + (base + s0) * limit;               // the round's keys are contiguous
-            int any = 0;
-            for (int i = tid; i < P - limit; i += MG_THREADS) {
-                const uint64_t k = i < ne ? src[i] : FZ_NONE;
-                s_hi[limit + i] = k;
-                any |= k != FZ_NONE;
-            }
-            if (__syncthreads_or(any)) msr_sort::bitonic_sort<MG_THREADS, false>(s_hi, s_lo, nullptr, P, true);
-        }
-    }
-    __syncthreads();
-    if (tid < limit) {
-        const uint64_t k = s_hi[tid];
-        a.out_term[(int64_t)w * limit + tid] = k == FZ_NONE ? -1 : (int32_t)(k & 0x7FFFFFFFu);
-        a.out_dist[(int64_t)w * limit + tid] = k == FZ_NONE ? -1 : (int32_t)(k >> 62);
-    }
-    if (tid == 0) { a.out_total[w] = total; a.out_n[w] = imin(total, limit); }
+    merge_rows<true>(a.keys, a.counts, a.n_spans, a.limit, a.out_term, a.out_dist, a.out_n, a.out_total);
 }
 
 // *flag <- max(*flag, code): 1 char_off does not run from 0 to n_chars, 2 it descends, 3 a weight of 2^31 or more

@@ -212,6 +212,11 @@ hipError_t msr_fuzzy_terms_run(const int64_t* char_off, const uint16_t* chars, c
                                int64_t n_terms, int n_words, const int32_t* word_off, const uint16_t* word_chars,
                                const int32_t* word_max, int limit, int32_t* out_term, int32_t* out_dist, int32_t* out_n,
                                int32_t* out_total, void* scratch, hipStream_t stream);
+// K16 (msr_wildcard.hip): the vocabulary terms a pattern matches (see msretr.h; arguments checked by the caller); the scratch
+// is laid out as msr_fuzzy_terms_run's
+hipError_t msr_wildcard_terms_run(const int64_t* char_off, const uint16_t* chars, const uint32_t* weight, const uint64_t* sig,
+                                  int64_t n_terms, int n_patterns, const int32_t* pat_off, const uint16_t* pat_chars, int limit,
+                                  int32_t* out_term, int32_t* out_n, int32_t* out_total, void* scratch, hipStream_t stream);
 hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);

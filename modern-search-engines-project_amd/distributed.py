@@ -314,12 +314,17 @@ class ShardedEngine:
 
     # ------------------------------------------------------------------ the sharded hot path
     def search(self, term_lists, qvec, k1=1000, k2=100, min_score=0.0, max_chunks_per_doc=0, rerank=True,
-               packed=None, dense_batched=False, rerank_keep=None, fuzzy=False, **rerank_params):
+               packed=None, dense_batched=False, rerank_keep=None, fuzzy=False, wildcards=False, **rerank_params):
         """-> dict(bm25=(doc, score, n), dense=(doc, score, chunk, n), rerank=(doc, score, orig, chunk, n, rows)); documents
         and chunk rows are GLOBAL indices; every rank returns the same tensors.  rerank_keep: entries per query of the fused
         lists to return (None: all k1; the reranker facade's diversification wants them all, a top-100 service k2).
         fuzzy=True is refused: a shard knows only its own document frequencies, so the ranks would pick different nearest
-        terms and their lists would disagree (DESIGN K15); correct the words on an unsharded engine and pass the ids."""
+        terms and their lists would disagree (DESIGN K15); correct the words on an unsharded engine and pass the ids.
+        wildcards=True is refused for the same reason (DESIGN K16): a pattern's first matches depend on the frequencies."""
+        if wildcards:
+            raise ValueError("wildcards=True is not available on a sharded engine: a shard orders a pattern's matches by its own "
+                             "document frequencies, so the ranks would cut different expansions and their lists disagree; "
+                             "expand the patterns on an unsharded index (DeviceEngine.wildcard_terms) and pass the term ids")
         if fuzzy:
             raise ValueError("fuzzy=True is not available on a sharded engine: shard-local document frequencies would make the "
                              "ranks choose different corrections and their ranks disagree; look the words up on an unsharded "

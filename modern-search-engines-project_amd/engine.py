@@ -186,7 +186,7 @@ class DeviceEngine:
 
     @property
     def has_vocab(self):
-        """True if the bound index came with its term strings (CorpusIndex.vocab): fuzzy_terms works."""
+        """True if the bound index came with its term strings (CorpusIndex.vocab): fuzzy_terms and wildcard_terms work."""
         return "voc_off" in self._t
 
     def fuzzy_terms(self, words, max_edits=None, limit=1):
@@ -236,6 +236,45 @@ class DeviceEngine:
             cnt, total = host[2 * n * limit:2 * n * limit + n], host[2 * n * limit + n:]
             for j, i in enumerate(part):
                 out[i] = ([(int(term[j, c]), int(dist[j, c])) for c in range(int(cnt[j]))], int(total[j]))
+        return out
+
+    def wildcard_terms(self, patterns, limit=8):
+        """The vocabulary terms each pattern matches (msr_wildcard_terms, DESIGN K16) -> per pattern ([term id, ...], total):
+        the first `limit` (1 .. 16) matches -- terms with a document frequency above 0 that the pattern matches as a whole,
+        `*` standing for any run of code points and `?` for exactly one -- ordered by document frequency descending, then
+        term id, and the number of all matches.  A pattern the device cannot take (empty, more than 32 symbols, a code point
+        above 0xFFFE) gets ([], 0) without a lookup.  ONE upload, two launches, one copy back for up to
+        MSR_WILD_MAX_PATTERNS patterns; longer lists go in slices.  Raises MsrError without a vocabulary."""
+        from .fuzzy import encode_words
+        from .wildcard import encodable
+        if not self.has_vocab:
+            raise _abi.MsrError(-2, "wildcard_terms: the index has no vocabulary (CorpusIndex.vocab: term strings); a "
+                                    "term-id-only index cannot expand a pattern")
+        limit = int(limit)
+        if not 1 <= limit <= _abi.MSR_WILD_MAX_LIMIT:
+            raise ValueError(f"wildcard_terms: limit must be 1 .. MSR_WILD_MAX_LIMIT = {_abi.MSR_WILD_MAX_LIMIT} (got {limit})")
+        patterns = list(patterns)
+        out = [([], 0)] * len(patterns)
+        ask = [i for i in range(len(patterns)) if encodable(patterns[i])]
+        step = _abi.MSR_WILD_MAX_PATTERNS
+        for a in range(0, len(ask), step):
+            part = ask[a:a + step]
+            n = len(part)
+            off, chars = encode_words([patterns[i] for i in part])
+            chars32 = np.zeros((len(chars) + 1) // 2 + 1, np.int32)         # ONE upload: offsets, then the symbols two to a word
+            chars32.view(np.uint16)[:len(chars)] = chars
+            up = self._dev(np.concatenate([off, chars32]), torch.int32)
+            d_off, d_chars = up[:n + 1], up[n + 1:]
+            res = torch.empty((n * limit + 2 * n,), dtype=torch.int32, device=self.device)
+            need = int(self.lib.msr_wildcard_scratch_bytes(self.index.n_terms, n, limit))
+            scratch = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=self.device)
+            r_term, r_n, r_total = res[:n * limit], res[n * limit:n * limit + n], res[n * limit + n:]
+            self._check(self.lib.msr_wildcard_terms(self.handle, n, _ptr(d_off), _ptr(d_chars), limit, _ptr(r_term), _ptr(r_n),
+                                                    _ptr(r_total), _ptr(scratch), need, self._stream()))
+            host = res.cpu().numpy()
+            term, cnt, total = host[:n * limit].reshape(n, limit), host[n * limit:n * limit + n], host[n * limit + n:]
+            for j, i in enumerate(part):
+                out[i] = ([int(term[j, c]) for c in range(int(cnt[j]))], int(total[j]))
         return out
 
     def scan_arith(self):

@@ -108,11 +108,15 @@ def corrected_text(processed_query, corrections):
 
 class Results(list):
     """A result list that also says what was corrected: `corrections` {typed term: used term} (empty: nothing) and
-    `corrected_query` (the processed query with the replacements, or None).  Equal to the plain list of its rows."""
+    `corrected_query` (the processed query with the replacements, or None) -- and, with wildcards=True (DESIGN K16), what its
+    patterns were expanded to: `expansions` {pattern: {"terms": [...], "total": n, ...}} (wildcard.expand; empty: no
+    pattern).  Equal to the plain list of its rows."""
     corrections = {}
     corrected_query = None
+    expansions = {}
 
-    def __init__(self, rows=(), corrections=None, corrected_query=None):
+    def __init__(self, rows=(), corrections=None, corrected_query=None, expansions=None):
         super().__init__(rows)
         self.corrections = dict(corrections or {})
         self.corrected_query = corrected_query
+        self.expansions = dict(expansions or {})

@@ -13,6 +13,7 @@ import numpy as np
 
 from .bm25 import BM25
 from . import fuzzy as _fuzzy
+from . import wildcard as _wildcard
 from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
@@ -375,7 +376,8 @@ class Retriever:
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
-                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None):
+                          must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None,
+                          wildcards=None):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
@@ -404,7 +406,12 @@ class Retriever:
         each -1 of the chunk's term ids and must ids by the word's nearest vocabulary term (fuzzy.correct); must_not and the
         phrases are not corrected.  The generator fills fuzzy["corrections"] (per query {typed: used}) and fuzzy["ids"] (the
         term ids that were scored).  The lookup's answer comes back to the host before the chunk is enqueued: with fuzzy the
-        host does not run ahead of the device.  Needs an index with term strings (ValueError); not with prepare=."""
+        host does not run ahead of the device.  Needs an index with term strings (ValueError); not with prepare=.
+        wildcards (DESIGN K16): None, or a dict {"patterns": per query its pattern strings, "limit": 1 .. 16}: per chunk ONE
+        DeviceEngine.wildcard_terms call over all its distinct patterns, where the fuzzy lookup stands (behind it when both are
+        given: a pattern is never corrected), appends each query's expansions behind its term ids (wildcard.expand).  The
+        generator fills wildcards["expansions"] (per query {pattern: {...}}) and wildcards["ids"] (the term ids that were
+        scored).  Like fuzzy, the answer comes back before the chunk is enqueued; same needs, same refusal of prepare=."""
         import torch
         eng = self.engine
         _check_mode(mode)
@@ -413,6 +420,11 @@ class Retriever:
             if prepare is not None or len(fuzzy["terms"]) != len(term_id_lists):
                 raise ValueError("fuzzy: needs the term strings of every query (not with prepare=)")
             fuzzy["corrections"], fuzzy["ids"] = [], []
+        if wildcards is not None:
+            self._check_wildcards(wildcards.get("limit", 8))
+            if prepare is not None or len(wildcards["patterns"]) != len(term_id_lists):
+                raise ValueError("wildcards: needs the patterns of every query (not with prepare=)")
+            wildcards["expansions"], wildcards["ids"] = [], []
         if operators:
             raise ValueError("operators=True needs the query text: use search / search_batch / batch_search, or parse with "
                              "text.parse_operators and pass must= / must_not=")
@@ -452,6 +464,12 @@ class Retriever:
                                                   None if must is None else must[a:b], m_ids)
                 fuzzy["corrections"] += corr
                 fuzzy["ids"] += ids
+            if wildcards is not None:
+                lim = int(wildcards.get("limit", 8))
+                ids, exp = _wildcard.expand(lambda ps: eng.wildcard_terms(ps, limit=lim), self.bm25._name_of, ids,
+                                            wildcards["patterns"][a:b], lim)
+                wildcards["expansions"] += exp
+                wildcards["ids"] += ids
             job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=m_ids,
                                       must_not=op_ids(must_not, a, b), must_phrases=ph_ids(must_phrases, a, b),
                                       must_not_phrases=ph_ids(must_not_phrases, a, b))
@@ -467,6 +485,17 @@ class Retriever:
             raise ValueError("fuzzy=True needs an index with a vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
                              "index cannot correct a word")
 
+    def _check_wildcards(self, max_expansions):
+        """What wildcards=True needs, checked before any device work: max_expansions of 1 .. MSR_WILD_MAX_LIMIT and an index
+        with term strings (ValueError)."""
+        from ._abi import MSR_WILD_MAX_LIMIT
+        if isinstance(max_expansions, bool) or not isinstance(max_expansions, (int, np.integer)) or \
+                not 1 <= int(max_expansions) <= MSR_WILD_MAX_LIMIT:
+            raise ValueError(f"max_expansions must be 1 .. MSR_WILD_MAX_LIMIT = {MSR_WILD_MAX_LIMIT} (got {max_expansions!r})")
+        if self.bm25 is None or not self.engine.has_vocab:
+            raise ValueError("wildcards=True needs an index with a vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
+                             "index cannot expand a pattern")
+
     def _phrase_ids(self, p):
         """A phrase's term ids; a text.Near keeps its slop and mode (a Near of a string is tokenised like the query)."""
         if isinstance(p, Near):
@@ -480,19 +509,20 @@ class Retriever:
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
-                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None):
+                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
         with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
-        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity / fuzzy: final_list_chunks."""
+        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity / fuzzy / wildcards:
+        final_list_chunks."""
         _check_mode(mode)
         if with_source and mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
         parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
                                             operators=operators, must=must, must_not=must_not, phrases=phrases,
                                             must_phrases=must_phrases, must_not_phrases=must_not_phrases, proximity=proximity,
-                                            fuzzy=fuzzy))
+                                            fuzzy=fuzzy, wildcards=wildcards))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -543,19 +573,43 @@ class Retriever:
         return processed, m, x, mp, xp
 
     def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not, phrases=False, must_phrases=None,
-                     must_not_phrases=None, proximity=False, keep=None):
+                     must_not_phrases=None, proximity=False, keep=None, wild=None):
         """_prepare with operators and phrases: -> (term ids, vectors, keyword arguments of final_lists: must / must_not /
         must_phrases / must_not_phrases where there are any).  The scoring text (excluded words and phrases removed, quotes
-        gone) is what gets tokenised and embedded."""
-        processed, m, x, mp, xp = self._operators([preprocess_query(q) for q in queries], operators, must, must_not, phrases,
-                                                  must_phrases, must_not_phrases, proximity)
+        gone) is what gets tokenised and embedded.
+        wild (DESIGN K16): None, or a dict {"parse": take the patterns out of the texts (wildcard.parse_wildcards, on the text
+        that still has its quotes: in front of the phrases and the operators), "explicit": None or per query a list of pattern
+        strings}; it receives "patterns", per query the parsed patterns and then the explicit ones, lower-cased.  A parsed
+        pattern leaves the scoring text; the text that is EMBEDDED keeps it (the dense stage sees the query as typed)."""
+        processed = [preprocess_query(q) for q in queries]
+        embed_text = None
+        if wild is not None:
+            typed, pats = processed, [[] for _ in queries]
+            if wild.get("parse"):
+                pairs = [_wildcard.parse_wildcards(p) for p in processed]
+                processed, pats = [s for s, _ in pairs], [list(p) for _, p in pairs]
+            explicit = wild.get("explicit")
+            if explicit is not None:
+                if len(explicit) != len(queries):
+                    raise ValueError(f"patterns: {len(explicit)} entries for {len(queries)} queries")
+                for q, ps in enumerate(explicit):
+                    if isinstance(ps, str) or not all(isinstance(p, str) for p in (ps or ())):
+                        raise ValueError("patterns: per query a LIST of pattern strings")
+                    pats[q] += [p.lower() for p in (ps or ())]
+            wild["patterns"] = pats
+            if processed != typed:
+                embed_text = self._operators(typed, operators, must, must_not, phrases, must_phrases, must_not_phrases,
+                                             proximity)[0]
+        processed, m, x, mp, xp = self._operators(processed, operators, must, must_not, phrases, must_phrases, must_not_phrases,
+                                                  proximity)
         ops = {} if m is None else {"must": m, "must_not": x}
         if mp is not None:
             ops.update(must_phrases=mp, must_not_phrases=xp)
-        return self._prepare(queries, query_embeddings, term_lists, processed, keep) + (ops,)
+        return self._prepare(queries, query_embeddings, term_lists, processed, keep, embed_text) + (ops,)
 
-    def _prepare(self, queries, query_embeddings, term_lists, processed=None, keep=None):
-        """keep (a dict, optional) receives "processed" (the scoring texts) and "terms" (the term lists the ids came from)."""
+    def _prepare(self, queries, query_embeddings, term_lists, processed=None, keep=None, embed_text=None):
+        """keep (a dict, optional) receives "processed" (the scoring texts) and "terms" (the term lists the ids came from).
+        embed_text: None, or per query the text to embed where it differs from the scoring text."""
         if processed is None:
             processed = [preprocess_query(q) for q in queries]
         if term_lists is None:
@@ -566,7 +620,7 @@ class Retriever:
         if isinstance(query_embeddings, np.ndarray) and query_embeddings.ndim == 2:
             qv = np.ascontiguousarray(query_embeddings, np.float32)             # (a matrix of vectors: taken as it is)
         else:
-            qv = np.stack([self._embed(processed[i], None if query_embeddings is None else query_embeddings[i])
+            qv = np.stack([self._embed((embed_text or processed)[i], None if query_embeddings is None else query_embeddings[i])
                            for i in range(len(queries))]) if len(queries) else np.zeros((0, 768), np.float32)
         return ids, qv
 
@@ -625,7 +679,7 @@ class Retriever:
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
                      must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS,
-                     fuzzy=False):
+                     fuzzy=False, wildcards=False, max_expansions=8, patterns=None):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
@@ -664,18 +718,35 @@ class Retriever:
         often than right).  Correction is lexical: the dense stage and the reranker use the embedding of the query AS TYPED.
         Each query's result is then a fuzzy.Results list -- the same rows, plus `corrections` ({typed term: used term}, empty if
         none) and `corrected_query` (the processed query with the replacements, or None).  Needs an index with term strings
-        (ValueError).  Off by default: without it every row and every list is what it was."""
+        (ValueError).  Off by default: without it every row and every list is what it was.
+        wildcards=True (DESIGN K16): a query token with `*` (any run of code points) or `?` (exactly one) -- `bibliothek*`,
+        `*bibliothek`, `t?bingen` -- is a pattern (wildcard.parse_wildcards: only letters and the two metacharacters, one
+        trailing `?` is punctuation, nothing inside quotes): it leaves the scoring text, and the vocabulary terms it matches as
+        a whole, the most frequent first, at most max_expansions (1 .. 16) of them, are appended to the query's terms as
+        ordinary scoring terms (wildcard.expand: no id twice, at most MSR_MAX_QUERY_TERMS unique ids, a pattern with fewer
+        than two literal code points is skipped); ONE DeviceEngine.wildcard_terms call per chunk of queries.  patterns=: per
+        query a list of further pattern strings, with or without wildcards=True.  Patterns match the vocabulary AS INDEXED
+        (lemmas, with a lemmatising tokenizer); they are never required, excluded (`+uni*` / `-uni*`: ValueError), part of a
+        phrase, or corrected by fuzzy=True; hybrid mode scores the expanded terms in its lexical half and the dense stage keeps
+        the embedding of the query as typed.  Each query's result is then a fuzzy.Results list whose `expansions` maps each
+        pattern to {"terms": the terms used, "total": all matches, "skipped" / "truncated": True where that happened}.  Needs
+        an index with term strings; max_expansions outside 1 .. 16 raises ValueError.  Off by default."""
         _check_mode(mode)
         if snippets:
             self._check_snippets(snippet_tokens)
-        fz = None
+        fz = wc = None
         if fuzzy:
             self._check_fuzzy()
             fz = {}
+        if wildcards or patterns is not None:
+            self._check_wildcards(max_expansions)
+            wc = {"parse": bool(wildcards), "explicit": patterns, "limit": int(max_expansions)}
         ids, qv, ops = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not, phrases, must_phrases,
-                                         must_not_phrases, proximity, keep=fz)
+                                         must_not_phrases, proximity, keep=fz, wild=wc)
         if fz is not None:
             ops["fuzzy"] = fz
+        if wc is not None:
+            ops["wildcards"] = wc
         src = None
         if mode == "hybrid":
             doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
@@ -685,6 +756,8 @@ class Retriever:
         ix = self.index
         if fz is not None:
             ids = fz["ids"]                                  # (the snippets look for the words that were scored)
+        if wc is not None:
+            ids = wc["ids"]                                  # (... the expansions among them)
         passages, row_names = self._snippets(ids, doc, n, snippet_tokens) if snippets else (None, None)
         out = []
         for q in range(len(queries)):
@@ -707,28 +780,35 @@ class Retriever:
                         rows[-1]["snippet"] = hit[0]
                     rows[-1]["highlights"] = hit[1] if hit is not None else []
                     rows[-1]["missing"] = hit[2] if hit is not None else list(row_names[q] or [])
-            if fz is not None:
-                rows = _fuzzy.Results(rows, fz["corrections"][q], _fuzzy.corrected_text(fz["processed"][q], fz["corrections"][q]))
+            if fz is not None or wc is not None:
+                corr = fz["corrections"][q] if fz is not None else {}
+                rows = _fuzzy.Results(rows, corr, _fuzzy.corrected_text(fz["processed"][q], corr) if fz is not None else None,
+                                      wc["expansions"][q] if wc is not None else None)
             out.append(rows)
         return out
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-               must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False):
+               must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
+               wildcards=False, max_expansions=8, patterns=None):
         """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
         list of phrases (or text.Near conditions) each; snippets / snippet_tokens / fuzzy: search_batch (fuzzy=True: the
-        result is a fuzzy.Results list with `corrections` and `corrected_query`)."""
+        result is a fuzzy.Results list with `corrections` and `corrected_query`); wildcards / max_expansions: search_batch
+        (the result is a fuzzy.Results list with `expansions`); patterns: ONE list of pattern strings."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
                                  mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
                                  must_not=None if must_not is None else [must_not], phrases=phrases,
                                  must_phrases=None if must_phrases is None else [must_phrases],
                                  must_not_phrases=None if must_not_phrases is None else [must_not_phrases],
-                                 proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens, fuzzy=fuzzy)[0]
+                                 proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens, fuzzy=fuzzy,
+                                 wildcards=wildcards, max_expansions=max_expansions,
+                                 patterns=None if patterns is None else [patterns])[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
-                     must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False):
+                     must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
+                     wildcards=False, max_expansions=8, patterns=None):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
@@ -737,18 +817,24 @@ class Retriever:
         page has no window), "highlights" and "missing" as in search_batch; the formatted lines are what they were.
         fuzzy=True: unknown words are corrected as in search_batch; the returned BatchLines then carries `corrections` (per
         query {typed term: used term}) and `corrected_queries` (per query the corrected text or None); the entries keep
-        their keys."""
+        their keys.  wildcards / max_expansions / patterns: search_batch; the BatchLines then carries `expansions` (per query
+        {pattern: {...}})."""
         _check_mode(mode)
         if snippets:
             self._check_snippets(snippet_tokens)
-        fz = None
+        fz = wc = None
         if fuzzy:
             self._check_fuzzy()
             fz = {}
+        if wildcards or patterns is not None:
+            self._check_wildcards(max_expansions)
+            wc = {"parse": bool(wildcards), "explicit": patterns, "limit": int(max_expansions)}
         ids, qv, ops = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators, must, must_not,
-                                         phrases, must_phrases, must_not_phrases, proximity, keep=fz)
+                                         phrases, must_phrases, must_not_phrases, proximity, keep=fz, wild=wc)
         if fz is not None:
             ops["fuzzy"] = fz
+        if wc is not None:
+            ops["wildcards"] = wc
         doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
@@ -757,6 +843,9 @@ class Retriever:
             ids = fz["ids"]
             lines.corrections = fz["corrections"]
             lines.corrected_queries = [_fuzzy.corrected_text(p, c) for p, c in zip(fz["processed"], fz["corrections"])]
+        if wc is not None:
+            ids = wc["ids"]
+            lines.expansions = wc["expansions"]
         if snippets:
             lines.passages, lines.row_names = self._snippets(ids, doc, n, snippet_tokens)
         return lines
@@ -818,6 +907,7 @@ class BatchLines:
         np.cumsum(n, out=self._start[1:])
         self.passages = self.row_names = None                # Retriever.batch_search(snippets=True) fills them
         self.corrections = self.corrected_queries = None     # ... and fuzzy=True these
+        self.expansions = None                               # ... and wildcards=True / patterns= this
 
     def __len__(self):
         return int(self._start[-1])

@@ -75,6 +75,9 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         snippet_tokens: int = 30      # "missing" (Retriever.search, DESIGN K14); the passage's width in tokens, 1 .. 64
         fuzzy: bool = False           # a word the vocabulary lacks is replaced by its nearest term (Retriever.search, DESIGN K15);
         #                               the response then carries "corrected_query" and "corrections"
+        wildcards: bool = False       # `bibliothek*`, `*bibliothek`, `t?bingen`: a token with `*` / `?` is expanded over the
+        max_expansions: int = 8       # vocabulary into at most max_expansions (1 .. 16) scoring terms (Retriever.search, DESIGN
+        patterns: Optional[List[str]] = None  # K16); patterns: further patterns; the response then carries "expansions"
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -135,6 +138,7 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             if req.phrases or req.must_phrases is not None or req.must_not_phrases is not None:
                 kw.update(phrases=req.phrases, must_phrases=req.must_phrases, must_not_phrases=req.must_not_phrases)
             specs = [p for ps in (req.must_phrases, req.must_not_phrases) for p in ps or () if isinstance(p, NearSpec)]
+            wild = req.wildcards or req.patterns is not None
             near = req.proximity or bool(specs)      # a proximity condition the engine cannot hold is the caller's error: 400
             try:
                 if near:
@@ -147,19 +151,26 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                     kw.update(snippets=True, snippet_tokens=req.snippet_tokens)
                 if req.fuzzy:
                     kw.update(fuzzy=True)
+                if wild:
+                    kw.update(wildcards=req.wildcards, max_expansions=req.max_expansions, patterns=req.patterns)
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
-                if req.mode == "lexical" and not near and not req.snippets and not req.fuzzy:
+                if req.mode == "lexical" and not near and not req.snippets and not req.fuzzy and not wild:
                     raise
-                # a dense_k the engine cannot hold; fuzzy on an index without term strings
+                # a dense_k the engine cannot hold; fuzzy / wildcards on an index without term strings; max_expansions outside
+                # 1 .. 16; a required or excluded pattern
                 return JSONResponse(status_code=400, content={"error": str(e)})
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
-            if req.fuzzy:
-                return {"llm_response": llm_response, "documents": list(docs), "corrected_query": docs.corrected_query,
-                        "corrections": docs.corrections}
+            if req.fuzzy or wild:
+                out = {"llm_response": llm_response, "documents": list(docs)}
+                if req.fuzzy:
+                    out.update(corrected_query=docs.corrected_query, corrections=docs.corrections)
+                if wild:
+                    out.update(expansions=docs.expansions)
+                return out
             return {"llm_response": llm_response, "documents": docs}
         except Exception:
             return JSONResponse(status_code=500, content={"error": "Internal server error"})
