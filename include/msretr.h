@@ -43,7 +43,8 @@ extern "C" {
                                      15: msr_best_windows; also 15 (calls added, none changed: a library
                                      that lacks them fails to load by symbol): msr_bind_vocab, msr_fuzzy_scratch_bytes,
                                      msr_fuzzy_terms; msr_debug_chunk_layout; msr_dense_pass_info;
-                                     msr_wildcard_scratch_bytes, msr_wildcard_terms */
+                                     msr_wildcard_scratch_bytes, msr_wildcard_terms; msr_facet_table, msr_bind_facet,
+                                     msr_facet_scratch_bytes, msr_facet_counts */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -60,6 +61,7 @@ extern "C" {
 #define MSR_WILD_MAX_LEN 32        /* msr_wildcard_terms: the longest pattern, in symbols, and the longest term it matches */
 #define MSR_WILD_MAX_PATTERNS 1024 /* msr_wildcard_terms: most patterns of one call */
 #define MSR_WILD_MAX_LIMIT 16      /* msr_wildcard_terms: most matches returned per pattern */
+#define MSR_FACET_MAX_LIMIT 64     /* msr_facet_counts: most facet values returned per row */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -394,6 +396,58 @@ int msr_fuzzy_terms(msr_engine* e, int32_t n_words, const int32_t* word_off, con
 int64_t msr_wildcard_scratch_bytes(int64_t n_terms, int32_t n_patterns, int32_t limit);
 int msr_wildcard_terms(msr_engine* e, int32_t n_patterns, const int32_t* pat_off, const uint16_t* pat_chars, int32_t limit,
                        int32_t* out_term, int32_t* out_n, int32_t* out_total, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* Facet counts: how many documents of a query's WHOLE match set carry each facet value, and how many
+ * match at all.  A facet is one int32 value per document: value[d] in [0, n_values), or -1 for "none".  For row r
+ *     M(r) = base(r)  AND  (OR of D(t) for t in any_terms[any_off[r] .. any_off[r + 1]))
+ *     hits[r] = |M(r)|,   count[r][v] = |{d in M(r) : value[d] == v}|
+ * with D(t) and base(r) exactly msr_term_sets': a term outside [0, n_terms) or with an empty list contributes nothing, repeated
+ * terms are allowed, an EMPTY list is no term condition (M = base); row_base[r] == -1 or n_base == 0 is every document, a row
+ * index picks that row, anything else is empty; bits at or above n_docs never count.  Documents with value -1 are counted in
+ * hits only, so sum_v count[r][v] <= hits[r].  The top list of a row holds the values with count > 0 in (count desc, value asc)
+ * order, the first `limit` of them; n_values_hit[r] is the number of values with count > 0.
+ *
+ * msr_facet_table (host; no device is touched): the table the kernels need.  With S = MSR_TERMSET_SPAN_DOCS, for each span s of
+ *   S consecutive documents span_values[span_off[s] .. span_off[s + 1]) holds the distinct values of the span, strictly
+ *   ascending; local[d] is the position of value[d] in its span's list (at most S - 1; 0xFFFF for value -1); for every value v
+ *   value_pos[value_off[v] .. value_off[v + 1]) holds the positions in span_values that hold v, ascending.  Sizes: local
+ *   [n_docs], span_off [ceil(n_docs / S) + 1], span_values and value_pos [T], value_off [n_values + 1].  Returns T =
+ *   span_off[n_spans] <= n_docs; a negative number for a value outside [-1, n_values) or a NULL pointer.  Called with local ==
+ *   NULL it only counts and returns T (the other outputs are not touched): the caller sizes the arrays with that.
+ *
+ * msr_bind_facet: device pointers, caller-owned, borrowed like the forward index; local must be 16-byte aligned.  The table is
+ *   checked once on the device (the call synchronises the stream), MSR_ERR_INVALID unless: n_docs equals the bound postings'
+ *   count; span_off[0] == 0, span_off is non-decreasing and each span has at most S entries; every local[d] is below its span's
+ *   entry count or equals 0xFFFF; span_values is in [0, n_values) and strictly ascending within a span; value_off[0] == 0,
+ *   value_off is non-decreasing and value_off[n_values] == T = span_off[n_spans]; value_pos is strictly ascending within a value
+ *   and span_values[value_pos[i]] == v for every i of value v (together: value_pos is a bijection).  A refused table leaves the
+ *   previous binding in place.  MSR_ERR_NOT_BOUND without postings.  msr_unbind and msr_bind_postings drop the binding; all
+ *   five pointers NULL unbinds.
+ *
+ * msr_facet_scratch_bytes: bytes of scratch one msr_facet_counts call of n_rows rows needs: per row 2 T rounded up to 16, plus
+ *   4 per span.  Negative (MSR_ERR_INVALID / MSR_ERR_NOT_BOUND) for n_rows < 0 / without a bound table.
+ *
+ * msr_facet_counts: every array is a device pointer; the call only enqueues on `stream` (two kernels, no global atomic, no
+ *   memset); no output has to be zeroed beforehand; repeated calls give the same bytes.  out_hits / out_n_values_hit [n_rows];
+ *   out_top_value / out_top_count [n_rows][limit], the rest of a row -1 / 0; out_counts (nullable) [n_rows][count_stride]:
+ *   every element [0, n_values) of every row is written, elements past n_values are left untouched.  Refused with
+ *   MSR_ERR_INVALID before any launch, outputs untouched: n_rows < 0; limit outside [0, MSR_FACET_MAX_LIMIT]; with n_rows > 0 a
+ *   NULL any_off, out_hits or out_n_values_hit; NULL top arrays with limit > 0; count_stride < n_values with out_counts given;
+ *   scratch_bytes below msr_facet_scratch_bytes(e, n_rows), or a scratch that is NULL or not 16-byte aligned when bytes are
+ *   needed; msr_term_sets' refusals of the base arguments.  MSR_ERR_NOT_BOUND without postings or without a facet table.
+ *   n_rows == 0 succeeds and launches nothing.  Cost per row: 4 bytes per posting of the listed terms, 2 bytes per document of a
+ *   non-empty word of M(r), the base row, and 2 T bytes written and read again. */
+int64_t msr_facet_table(const int32_t* value, int64_t n_docs, int32_t n_values, uint16_t* local, int32_t* span_off,
+                        int32_t* span_values, int32_t* value_off, int32_t* value_pos);
+int msr_bind_facet(msr_engine* e, const uint16_t* local, const int32_t* span_off, const int32_t* span_values,
+                   const int32_t* value_off, const int32_t* value_pos, int64_t n_docs, int32_t n_values, void* stream);
+int64_t msr_facet_scratch_bytes(const msr_engine* e, int32_t n_rows);
+int msr_facet_counts(msr_engine* e, int32_t n_rows, const int32_t* any_off, const int32_t* any_terms,
+                     const uint32_t* base_bits, int32_t n_base, int64_t base_stride, const int32_t* row_base,
+                     int32_t limit, int32_t* out_hits, int32_t* out_n_values_hit,
+                     int32_t* out_top_value, int32_t* out_top_count,   /* [n_rows][limit]; rest of a row -1 / 0 */
+                     int32_t* out_counts, int64_t count_stride,        /* nullable: all counts, [n_rows][count_stride] */
+                     void* scratch, int64_t scratch_bytes, void* stream);
 
 /* msr_combine_sets: out[r] = AND of in[s] for s in and_rows[and_off[r] .. and_off[r + 1])  AND NOT  OR of in[s] for s in
  *   not_rows[not_off[r] .. not_off[r + 1]), rows of in_bits (n_in rows in_stride words apart) in the layout above.  An empty

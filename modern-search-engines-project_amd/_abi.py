@@ -27,6 +27,7 @@ MSR_FUZZY_WORD_GROUP = 16
 MSR_WILD_MAX_LEN = 32
 MSR_WILD_MAX_PATTERNS = 1024
 MSR_WILD_MAX_LIMIT = 16
+MSR_FACET_MAX_LIMIT = 64
 MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
 
 
@@ -96,6 +97,11 @@ _SIGNATURES = {
     "msr_fuzzy_terms": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     "msr_wildcard_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "msr_wildcard_terms": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
+    "msr_facet_table": (C.c_int64, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    "msr_bind_facet": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, _P]),
+    "msr_facet_scratch_bytes": (C.c_int64, [_P, C.c_int32]),
+    "msr_facet_counts": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64,
+                                   _P, C.c_int64, _P]),
     "msr_combine_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,

@@ -38,9 +38,11 @@ UNITS = {
     "msr_snippet.hip": [],
     "msr_fuzzy.hip": [],
     "msr_wildcard.hip": [],
+    "msr_facet.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)
+    "msr_facet_table.cpp": [],        # host-only C++ (the facet table of msr_bind_facet)
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 

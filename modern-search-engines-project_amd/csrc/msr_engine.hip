@@ -41,6 +41,8 @@ struct msr_engine {
     const uint32_t* voc_weight = nullptr;
     int64_t voc_n_chars = 0;
     bool have_vocab = false;
+    FacetTable facet{};                    // msr_bind_facet (borrowed): the facet table of the bound postings' documents (K17)
+    bool have_facet = false;
     DenseIndex dense{};
     bool have_chunks = false;
     const int32_t* url_group = nullptr;
@@ -160,8 +162,13 @@ static void drop_vocab(msr_engine* e) {
     e->voc_char_off = nullptr; e->voc_chars = nullptr; e->voc_weight = nullptr; e->voc_n_chars = 0;
     e->mem_postings.free_one(&e->voc_sig);
 }
+static void drop_facet(msr_engine* e) {
+    e->have_facet = false;
+    e->facet = FacetTable{};
+}
 static void drop_postings(msr_engine* e) {
     e->have_postings = e->have_tokens = false;
+    drop_facet(e);
     e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
     drop_vocab(e);
     e->bm25 = Bm25Index{};
@@ -962,6 +969,101 @@ extern "C" int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_term_sets_run(e->bm25, n_rows, must_off, must_terms, not_off, not_terms, base_bits, n_base, base_stride,
                                  row_base, out_bits, out_stride, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+// ---- K17: facet counts (msr_facet.hip) ----------------------------------------------------------------------------------------
+extern "C" int msr_bind_facet(msr_engine* e, const uint16_t* local, const int32_t* span_off, const int32_t* span_values,
+                              const int32_t* value_off, const int32_t* value_pos, int64_t n_docs, int32_t n_values, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_bind_facet: postings not bound");
+    if (!local && !span_off && !span_values && !value_off && !value_pos) {       // all NULL: unbind
+        drop_facet(e);
+        return MSR_OK;
+    }
+    // a refused table leaves the previous binding as it is: nothing of the engine changes before the check has passed
+    if (!span_off || !value_off || n_values < 0 || (n_docs > 0 && !local))
+        return fail(e, MSR_ERR_INVALID, "msr_bind_facet: bad argument");
+    if (n_docs != e->bm25.n_docs)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_facet: n_docs %lld differs from bound postings (%lld)", (long long)n_docs,
+                    (long long)e->bm25.n_docs);
+    if ((uintptr_t)local % 16)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_facet: local is not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    if (!e->sim_flag) ALLOC(e, e->mem_engine, e->sim_flag, 64);
+    const int64_t n_spans = (n_docs + MSR_TERMSET_SPAN_DOCS - 1) / MSR_TERMSET_SPAN_DOCS;
+    int32_t ends[2] = {0, 0};                                // T = span_off[n_spans] sizes span_values and value_pos
+    HIP_TRY(e, hipMemcpyAsync(&ends[0], span_off + n_spans, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipMemcpyAsync(&ends[1], value_off + n_values, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (ends[0] < 0 || ends[0] > n_docs)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_facet: malformed table: span_off ends at %d, outside [0, n_docs]", ends[0]);
+    if (ends[1] != ends[0])
+        return fail(e, MSR_ERR_INVALID, "msr_bind_facet: malformed table: value_off[n_values] = %d, span_off[n_spans] = %d",
+                    ends[1], ends[0]);
+    if (ends[0] > 0 && (!span_values || !value_pos)) return fail(e, MSR_ERR_INVALID, "msr_bind_facet: bad argument");
+    const FacetTable f{local, span_off, span_values, value_off, value_pos, n_values, ends[0]};
+    // two kernels: the first reads the offsets and local[] by its own index only; the second follows the offsets and returns
+    // at once unless the first found them sound, so a malformed table cannot send a read out of bounds
+    int32_t flag = 0;
+    HIP_TRY(e, hipMemsetAsync(e->sim_flag, 0, sizeof(int32_t), st));
+    HIP_TRY(e, msr_facet_validate(f, n_docs, e->sim_flag, st));
+    HIP_TRY(e, hipMemcpyAsync(&flag, e->sim_flag, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    if (flag) {
+        static const char* why[] = {"", "span_off does not start at 0, descends, or a span holds more entries than documents",
+                                    "a local id at or past its span's entry count", "value_off does not start at 0 or descends",
+                                    "span_values out of range or not strictly ascending within a span",
+                                    "value_pos out of range, not strictly ascending within a value, or naming another value"};
+        return fail(e, MSR_ERR_INVALID, "msr_bind_facet: malformed table: %s", why[std::min(std::max(flag, 0), 5)]);
+    }
+    e->facet = f;
+    e->have_facet = true;
+    return MSR_OK;
+}
+
+extern "C" int64_t msr_facet_scratch_bytes(const msr_engine* e, int32_t n_rows) {
+    if (!e || n_rows < 0) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_facet) return MSR_ERR_NOT_BOUND;
+    return (int64_t)n_rows * msr_facet_row_bytes(e->facet, e->bm25.n_docs);
+}
+
+extern "C" int msr_facet_counts(msr_engine* e, int32_t n_rows, const int32_t* any_off, const int32_t* any_terms,
+                                const uint32_t* base_bits, int32_t n_base, int64_t base_stride, const int32_t* row_base,
+                                int32_t limit, int32_t* out_hits, int32_t* out_n_values_hit, int32_t* out_top_value,
+                                int32_t* out_top_count, int32_t* out_counts, int64_t count_stride, void* scratch,
+                                int64_t scratch_bytes, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_facet_counts: postings not bound");
+    if (!e->have_facet) return fail(e, MSR_ERR_NOT_BOUND, "msr_facet_counts: facet table not bound (msr_bind_facet)");
+    const int64_t W = (e->bm25.n_docs + 31) / 32;
+    if (n_rows < 0 || n_base < 0)
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: bad argument (n_rows=%d, n_base=%d)", n_rows, n_base);
+    if (limit < 0 || limit > MSR_FACET_MAX_LIMIT)
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: limit %d outside [0, MSR_FACET_MAX_LIMIT = %d]", limit, MSR_FACET_MAX_LIMIT);
+    if (n_rows > 0 && (!any_off || !out_hits || !out_n_values_hit))
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: bad argument (any_off, out_hits or out_n_values_hit is NULL with n_rows=%d)",
+                    n_rows);
+    if (n_rows > 0 && limit > 0 && (!out_top_value || !out_top_count))
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: bad argument (out_top_value or out_top_count is NULL with limit=%d)", limit);
+    if (out_counts && count_stride < e->facet.n_values)
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: bad argument (count_stride=%lld < n_values = %d)", (long long)count_stride,
+                    e->facet.n_values);
+    if (n_base > 0 && (!base_bits || !row_base))
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: bad argument (base_bits or row_base is NULL with n_base=%d)", n_base);
+    if (n_base > 0 && base_stride < W)
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: bad argument (base_stride=%lld < ceil(n_docs / 32) = %lld)",
+                    (long long)base_stride, (long long)W);
+    const int64_t need = (int64_t)n_rows * msr_facet_row_bytes(e->facet, e->bm25.n_docs);
+    if (scratch_bytes < need || (need > 0 && (!scratch || (uintptr_t)scratch % 16)))
+        return fail(e, MSR_ERR_INVALID, "msr_facet_counts: scratch of %lld bytes, %lld needed (msr_facet_scratch_bytes; 16-byte aligned)",
+                    (long long)scratch_bytes, (long long)need);
+    if (n_rows == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_facet_counts_run(e->bm25, e->facet, n_rows, any_off, any_terms, base_bits, n_base, base_stride, row_base, limit,
+                                    out_hits, out_n_values_hit, out_top_value, out_top_count, out_counts, count_stride, scratch,
+                                    (hipStream_t)stream));
     return MSR_OK;
 }
 

@@ -217,6 +217,26 @@ hipError_t msr_fuzzy_terms_run(const int64_t* char_off, const uint16_t* chars, c
 hipError_t msr_wildcard_terms_run(const int64_t* char_off, const uint16_t* chars, const uint32_t* weight, const uint64_t* sig,
                                   int64_t n_terms, int n_patterns, const int32_t* pat_off, const uint16_t* pat_chars, int limit,
                                   int32_t* out_term, int32_t* out_n, int32_t* out_total, void* scratch, hipStream_t stream);
+// K17 (msr_facet.hip): facet counts of whole match sets (see msretr.h; arguments checked by the caller).  The table of
+// msr_facet_table as msr_bind_facet keeps it (borrowed device pointers).
+struct FacetTable {
+    const uint16_t* local;       // [n_docs] position of the document's value in its span's list, 0xFFFF = no value
+    const int32_t* span_off;     // [n_spans + 1]
+    const int32_t* span_values;  // [n_entries] the spans' distinct values, ascending within a span
+    const int32_t* value_off;    // [n_values + 1]
+    const int32_t* value_pos;    // [n_entries] per value the slots of span_values that hold it, ascending
+    int32_t n_values;
+    int64_t n_entries;           // T = span_off[n_spans]
+};
+// *flag <- max(*flag, code) of the first broken rule (1 .. 5, msr_facet.hip); f.n_entries and value_off[n_values] were checked
+// on the host
+hipError_t msr_facet_validate(const FacetTable& f, int64_t n_docs, int32_t* flag, hipStream_t stream);
+int64_t msr_facet_row_bytes(const FacetTable& f, int64_t n_docs);      // scratch of one row: its slots as uint16 (rounded up to 16 bytes), then a word per span
+hipError_t msr_facet_counts_run(const Bm25Index& ix, const FacetTable& f, int n_rows, const int32_t* any_off,
+                                const int32_t* any_terms, const uint32_t* base_bits, int n_base, int64_t base_stride,
+                                const int32_t* row_base, int limit, int32_t* out_hits, int32_t* out_n_values_hit,
+                                int32_t* out_top_value, int32_t* out_top_count, int32_t* out_counts, int64_t count_stride,
+                                void* scratch, hipStream_t stream);
 hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);

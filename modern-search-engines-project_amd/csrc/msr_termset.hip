@@ -4,7 +4,8 @@
 // layout of K8 (document d = bit d & 31 of word d >> 5): the producer of the rows that msr_*_topk_within consume.
 //
 // One workgroup owns (row, span of MSR_TERMSET_SPAN_DOCS consecutive documents): one 32-bit word per thread (the ownership
-// rule, its constants and the base word of a row stand in msr_tokscan.h, which K12 and K13 share).  The row's accumulator word
+// rule, its constants and the base word of a row stand in msr_tokscan.h, which K12 and K13 share; so do span_postings and
+// or_postings below, which K17's count kernel in msr_facet.hip uses as well).  The row's accumulator word
 // lives in a register of its thread, the bits of ONE posting list (or of all not lists together) in LDS.
 // Per term one thread finds the postings of the span -- two loads of the BM25 skip table for a long list, a binary search
 // on post_doc otherwise; up to 256 terms' searches run side by side -- then the workgroup streams post_doc (4 bytes per
@@ -21,7 +22,6 @@
 namespace {
 
 using namespace tokscan;
-static_assert(SPAN % MSR_BM25_TILE == 0, "a span is a whole number of skip-table tiles");
 
 struct TermSetArgs {
     const int64_t* term_off;
@@ -36,43 +36,6 @@ struct TermSetArgs {
     uint32_t* out_bits; int64_t out_stride;
     int32_t row0;
 };
-
-// [*lo, *hi): the postings of term t (a valid id) whose document lies in [d0, d0 + SPAN).
-__device__ __forceinline__ void span_postings(const TermSetArgs& a, int32_t t, int64_t d0, int64_t* lo, int64_t* hi) {
-    const int64_t p0 = a.term_off[t], p1 = a.term_off[t + 1];
-    const int32_t h = a.heavy_id ? a.heavy_id[t] : -1;
-    if (h >= 0) {
-        const uint32_t* row = a.tile_off + (int64_t)h * (a.n_tiles + 1);
-        const int32_t t0 = (int32_t)(d0 / MSR_BM25_TILE);
-        const int32_t t1 = min(t0 + SPAN / MSR_BM25_TILE, a.n_tiles);
-        *lo = p0 + row[t0];
-        *hi = p0 + row[t1];
-        return;
-    }
-    // first posting with document >= d0, then (from there on) the first with document >= d0 + SPAN
-    int64_t l = p0, r = p1;
-    while (l < r) {
-        const int64_t m = l + ((r - l) >> 1);
-        if (a.post_doc[m] < d0) l = m + 1; else r = m;
-    }
-    *lo = l;
-    r = min(p1, l + SPAN);                               // documents ascend strictly: a span holds at most SPAN postings
-    const int64_t d1 = d0 + SPAN;
-    while (l < r) {
-        const int64_t m = l + ((r - l) >> 1);
-        if (a.post_doc[m] < d1) l = m + 1; else r = m;
-    }
-    *hi = l;
-}
-
-// bits |= the documents of postings [lo, hi) (all inside the span; the range test keeps a malformed table out of LDS)
-__device__ __forceinline__ void or_postings(const int32_t* __restrict__ post_doc, int64_t lo, int64_t hi, int64_t d0,
-                                            uint32_t* bits) {
-    for (int64_t p = lo + threadIdx.x; p < hi; p += THREADS) {
-        const int64_t d = (int64_t)post_doc[p] - d0;
-        if (d >= 0 && d < SPAN) atomicOr(&bits[d >> 5], 1u << (d & 31));
-    }
-}
 
 __global__ __launch_bounds__(THREADS) void term_sets_kernel(const TermSetArgs a) {
     __shared__ uint32_t bits[THREADS];

@@ -1,5 +1,6 @@
 // What K11 - K14 share (msr_termset.hip, msr_phrase.hip, msr_proximity.hip, msr_snippet.hip): the ownership
-// of a row's words, the candidate list of a span, the walk of one document's token stream, and the host loop over row slices.
+// of a row's words, the candidate list of a span, the walk of one document's token stream, and the host loop over row slices --
+// and what K11 shares with K17 (msr_facet.hip): a term's postings inside a span and their OR into the span's LDS bits.
 // Every piece is a correctness rule with ONE definition here; what a kernel does with it stays in the kernel's file.
 //
 // Everything on the device side is a free __forceinline__ function over values and arrays that the CALLER declares, and the
@@ -15,6 +16,7 @@
 #include <algorithm>
 
 #include "../../include/msretr.h"
+#include "msr_internal.h"
 
 namespace tokscan {
 
@@ -46,6 +48,48 @@ __device__ __forceinline__ uint32_t set_word(const uint32_t* bits, int32_t n_row
         else if (sel != -1) acc = 0;
     }
     return acc;
+}
+
+// ---- a term's postings inside a span (K11, K17) ---------------------------------------------------------------------------------
+// [*lo, *hi): the postings of term t (a valid id) whose document lies in [d0, d0 + SPAN).  `a` is the kernel's argument struct:
+// term_off, post_doc, heavy_id (nullable), tile_off and n_tiles of the bound postings (Bm25Index).  Two loads of the BM25 skip
+// table for a long list, a binary search on post_doc otherwise.
+static_assert(SPAN % MSR_BM25_TILE == 0, "a span is a whole number of skip-table tiles");
+template <class Args>
+__device__ __forceinline__ void span_postings(const Args& a, int32_t t, int64_t d0, int64_t* lo, int64_t* hi) {
+    const int64_t p0 = a.term_off[t], p1 = a.term_off[t + 1];
+    const int32_t h = a.heavy_id ? a.heavy_id[t] : -1;
+    if (h >= 0) {
+        const uint32_t* row = a.tile_off + (int64_t)h * (a.n_tiles + 1);
+        const int32_t t0 = (int32_t)(d0 / MSR_BM25_TILE);
+        const int32_t t1 = min(t0 + SPAN / MSR_BM25_TILE, a.n_tiles);
+        *lo = p0 + row[t0];
+        *hi = p0 + row[t1];
+        return;
+    }
+    // first posting with document >= d0, then (from there on) the first with document >= d0 + SPAN
+    int64_t l = p0, r = p1;
+    while (l < r) {
+        const int64_t m = l + ((r - l) >> 1);
+        if (a.post_doc[m] < d0) l = m + 1; else r = m;
+    }
+    *lo = l;
+    r = min(p1, l + SPAN);                               // documents ascend strictly: a span holds at most SPAN postings
+    const int64_t d1 = d0 + SPAN;
+    while (l < r) {
+        const int64_t m = l + ((r - l) >> 1);
+        if (a.post_doc[m] < d1) l = m + 1; else r = m;
+    }
+    *hi = l;
+}
+
+// bits |= the documents of postings [lo, hi) (all inside the span; the range test keeps a malformed table out of LDS)
+__device__ __forceinline__ void or_postings(const int32_t* __restrict__ post_doc, int64_t lo, int64_t hi, int64_t d0,
+                                            uint32_t* bits) {
+    for (int64_t p = lo + threadIdx.x; p < hi; p += THREADS) {
+        const int64_t d = (int64_t)post_doc[p] - d0;
+        if (d >= 0 && d < SPAN) atomicOr(&bits[d >> 5], 1u << (d & 31));
+    }
 }
 
 // ---- candidate compaction (K12, K13) --------------------------------------------------------------------------------------------

@@ -454,6 +454,89 @@ class DeviceEngine:
                                                self._stream()))
         return bits, q_set, n_sets, stride, d_tail
 
+    # ------------------------------------------------------------------ facet counts (msr_facet_counts, DESIGN K17)
+    @property
+    def has_facet(self):
+        """True while a facet table is bound (bind_facet); a rebind drops it with the postings."""
+        return "facet_local" in self._t
+
+    def bind_facet(self, value, n_values):
+        """Bind one facet to the bound postings' documents: value int32 [N] in [-1, n_values) (-1: none; facets.facet_values).
+        The table is built on the host (facets.build_table, msr_facet_table), uploaded and checked once on the device
+        (msr_bind_facet: the call synchronises).  The arrays live with the postings' tensors: rebind / unbind drop them.
+        value=None unbinds."""
+        from .facets import build_table
+        names = ("facet_local", "facet_span_off", "facet_span_values", "facet_value_off", "facet_value_pos")
+        if value is None:
+            null = C.c_void_p(0)
+            self._check(self.lib.msr_bind_facet(self.handle, null, null, null, null, null, 0, 0, self._stream()))
+            for k in names:
+                self._t.pop(k, None)
+            self._facet_n_values = 0
+            return
+        value = np.ascontiguousarray(value, np.int32)
+        if value.shape != (self.index.n_docs,):
+            raise ValueError(f"bind_facet: {value.shape} values for {self.index.n_docs} documents")
+        local, span_off, span_values, value_off, value_pos = build_table(value, n_values)
+        with torch.cuda.device(self.device):
+            dev = [self._dev(local.view(np.int16), torch.int16)] + \
+                  [self._dev(a, torch.int32) for a in (span_off, span_values, value_off, value_pos)]
+            self._check(self.lib.msr_bind_facet(self.handle, *[_ptr(t) if t.numel() else C.c_void_p(0) for t in dev],
+                                                self.index.n_docs, int(n_values), self._stream()))
+        self._t.update(zip(names, dev))                      # (a refused table leaves the previous binding and its tensors)
+        self._facet_n_values = int(n_values)
+
+    def facet_counts(self, term_lists, within=None, limit=10, counts=False):
+        """Per row: how many documents hold AT LEAST ONE of the row's terms inside its set, and how many of those carry each
+        value of the bound facet (msr_facet_counts) -> host arrays (hits int32 [R], n_values_hit int32 [R], top_value int32
+        [R, limit], top_count int32 [R, limit][, counts int32 [R, n_values] with counts=True]): the values with a count above 0
+        in (count desc, value asc) order, the first `limit` (0 .. MSR_FACET_MAX_LIMIT) of them, the rest of a row -1 / 0.
+        term_lists: per row a list of term ids (repeats allowed; ids the index lacks contribute nothing); an EMPTY list is no
+        term condition -- the row counts its whole set.  within: None, a DocSet, a list of DocSet / None per row, or a
+        DeviceSets (term_sets / phrase_sets), through pack_within.  Documents without a value count in hits only.  The rows go
+        through the device in slices of at most max_queries, one scratch tensor for all of them, one copy back per slice."""
+        if not self.has_facet:
+            raise _abi.MsrError(-2, "facet_counts: no facet bound (bind_facet)")
+        limit = int(limit)
+        if not 0 <= limit <= _abi.MSR_FACET_MAX_LIMIT:
+            raise ValueError(f"facet_counts: limit must be 0 .. MSR_FACET_MAX_LIMIT = {_abi.MSR_FACET_MAX_LIMIT} (got {limit})")
+        term_lists = [[int(t) for t in tl] for tl in term_lists]
+        R, V = len(term_lists), self._facet_n_values
+        bits, q_set, n_base, stride = self.pack_within(within, R)
+        hits, n_hit = np.zeros(R, np.int32), np.zeros(R, np.int32)
+        top_value, top_count = np.full((R, limit), -1, np.int32), np.zeros((R, limit), np.int32)
+        all_counts = np.zeros((R, V), np.int32) if counts else None
+        step = max(1, self.max_queries)
+        need = int(self.lib.msr_facet_scratch_bytes(self.handle, min(step, R)))
+        if need < 0:
+            self._check(need)
+        scratch = torch.empty((max(1, (need + 15) // 16 * 2),), dtype=torch.int64, device=self.device)
+        for a in range(0, R, step):
+            b = min(R, a + step)
+            n = b - a
+            off, terms = [0], []
+            for tl in term_lists[a:b]:
+                terms += tl
+                off.append(len(terms))
+            up = torch.from_numpy(np.asarray(off + terms, np.int32)).to(self.device)     # ONE upload: offsets, then the ids
+            d_off, d_terms = up[:n + 1], up[n + 1:]
+            res = torch.empty((2 * n + 2 * n * limit + (n * V if counts else 0),), dtype=torch.int32, device=self.device)
+            r_hits, r_nh = res[:n], res[n:2 * n]
+            r_tv, r_tc = res[2 * n:2 * n + n * limit], res[2 * n + n * limit:2 * n + 2 * n * limit]
+            r_cnt = res[2 * n + 2 * n * limit:] if counts else None
+            self._check(self.lib.msr_facet_counts(
+                self.handle, n, _ptr(d_off), _ptr(d_terms) if terms else C.c_void_p(0), _ptr(bits) if n_base else C.c_void_p(0),
+                n_base, stride, _ptr(q_set[a:b]) if n_base else C.c_void_p(0), limit, _ptr(r_hits), _ptr(r_nh),
+                _ptr(r_tv) if limit else C.c_void_p(0), _ptr(r_tc) if limit else C.c_void_p(0),
+                _ptr(r_cnt) if counts and V else C.c_void_p(0), V, _ptr(scratch), need, self._stream()))
+            host = res.cpu().numpy()
+            hits[a:b], n_hit[a:b] = host[:n], host[n:2 * n]
+            top_value[a:b] = host[2 * n:2 * n + n * limit].reshape(n, limit)
+            top_count[a:b] = host[2 * n + n * limit:2 * n + 2 * n * limit].reshape(n, limit)
+            if counts:
+                all_counts[a:b] = host[2 * n + 2 * n * limit:].reshape(n, V)
+        return (hits, n_hit, top_value, top_count) + ((all_counts,) if counts else ())
+
     def phrase_sets(self, must_phrases, must_not_phrases=None, must=None, must_not=None, within=None):
         """Per-query document sets of phrase search, built on the device: query q's set is the documents of within[q] that hold
         every term of must[q], none of must_not[q] (term_sets' rules), EVERY phrase of must_phrases[q] and NO phrase of

@@ -110,13 +110,22 @@ class Results(list):
     """A result list that also says what was corrected: `corrections` {typed term: used term} (empty: nothing) and
     `corrected_query` (the processed query with the replacements, or None) -- and, with wildcards=True (DESIGN K16), what its
     patterns were expanded to: `expansions` {pattern: {"terms": [...], "total": n, ...}} (wildcard.expand; empty: no
-    pattern).  Equal to the plain list of its rows."""
+    pattern) -- and, with facets=True (DESIGN K17), what the whole match set holds: `hits` (pages that match at all, None
+    without facets), `facets` ([{"value": name, "count": n}, ...], the values with the most matching pages first) and
+    `facet_values` (the number of distinct values hit).  Equal to the plain list of its rows."""
     corrections = {}
     corrected_query = None
     expansions = {}
+    hits = None
+    facets = []
+    facet_values = 0
 
-    def __init__(self, rows=(), corrections=None, corrected_query=None, expansions=None):
+    def __init__(self, rows=(), corrections=None, corrected_query=None, expansions=None, hits=None, facets=None,
+                 facet_values=0):
         super().__init__(rows)
         self.corrections = dict(corrections or {})
         self.corrected_query = corrected_query
         self.expansions = dict(expansions or {})
+        self.hits = None if hits is None else int(hits)
+        self.facets = list(facets or [])
+        self.facet_values = int(facet_values)

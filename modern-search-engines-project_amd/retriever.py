@@ -12,6 +12,7 @@ import weakref
 import numpy as np
 
 from .bm25 import BM25
+from . import facets as _facets
 from . import fuzzy as _fuzzy
 from . import wildcard as _wildcard
 from .docset import DeviceSets
@@ -65,6 +66,7 @@ class Retriever:
         ids = self.index.doc_ids
         self._ids = ids.cpu().numpy() if hasattr(ids, "cpu") else np.asarray(ids)
         self._domains_bound = False
+        self._facet_bound = None
         self._formatter = None
         self._pinned = {}
         self._tokenizer, self._span_tokenizer = tokenizer, span_tokenizer
@@ -92,6 +94,7 @@ class Retriever:
         ids = ix.doc_ids
         self._ids = ids.cpu().numpy() if hasattr(ids, "cpu") else np.asarray(ids)
         self._domains_bound = False
+        self._facet_bound = None
         self._formatter = None
         self._term_names = None
         if ix.term_off is None:
@@ -277,11 +280,41 @@ class Retriever:
             self.engine.bind_doc_domains(self._doc_domains())
             self._domains_bound = True
 
+    def _check_facets(self, facet_by, facet_limit):
+        """What facets=True needs, checked before any device work: a key of facets.FACET_KEYS, facet_limit of 1 ..
+        MSR_FACET_MAX_LIMIT and an index with postings and URLs (ValueError)."""
+        _facets.check_options(facet_by, facet_limit)
+        if self.bm25 is None or self.index.urls is None:
+            raise ValueError("facets=True needs an index with postings and URLs (CorpusIndex.urls)")
+
+    def _ensure_facet(self, by):
+        """The facet table of key `by`, bound lazily per index (one table at a time: another key rebinds) and again after
+        update_index, like the response tables -> the key's value names."""
+        value, names = _facets.facet_values(self.index, by)
+        if self._facet_bound != by or not self.engine.has_facet:
+            self.engine.bind_facet(value, len(names))
+            self._facet_bound = by
+        return names
+
+    def _facet_chunk(self, term_ids, within, facet):
+        """One facet_counts call for a chunk's queries: the counting terms (facets.counting_terms) of the ids that are scored,
+        inside `within` -- what stage 1 is restricted to, the chunk's DeviceSets when operators, phrases or proximity built
+        one.  A query without a valid term gets a list that matches nothing (0 hits); a chunk of such queries makes no call."""
+        Q, limit = len(term_ids), int(facet["limit"])
+        lists = [_facets.counting_terms(self.index, t) or [-1] for t in term_ids]
+        if any(l != [-1] for l in lists):
+            hits, n_hit, tv, tc = self.engine.facet_counts(lists, within=within, limit=limit)
+        else:
+            hits, n_hit = np.zeros(Q, np.int32), np.zeros(Q, np.int32)
+            tv, tc = np.full((Q, limit), -1, np.int32), np.zeros((Q, limit), np.int32)
+        for key, part in (("hits", hits), ("n_values_hit", n_hit), ("top_value", tv), ("top_count", tc)):
+            facet[key] += list(part)
+
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
     def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, must=None, must_not=None,
-                       must_phrases=None, must_not_phrases=None):
+                       must_phrases=None, must_not_phrases=None, facet=None):
         """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
         within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
         mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
@@ -290,7 +323,9 @@ class Retriever:
         must / must_not (None | term-id lists per query of the chunk): ONE term_sets call in front of stage 1 turns them, inside
         `within`, into device sets that take within's place in both stages; nothing else changes.
         must_phrases / must_not_phrases (None | per query of the chunk a list of phrases, each a list of term ids): ONE
-        phrase_sets call takes the term_sets call's place (it makes that call itself, with the phrases' candidate rows)."""
+        phrase_sets call takes the term_sets call's place (it makes that call itself, with the phrases' candidate rows).
+        facet (None | the dict of final_list_chunks' facets=): ONE facet_counts call over the chunk's scored terms inside the
+        sets stage 1 is restricted to (_facet_chunk); its answer comes back to the host before stage 1 is enqueued."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
         union = None
@@ -298,6 +333,8 @@ class Retriever:
             within = eng.phrase_sets(must_phrases, must_not_phrases, must, must_not, within=within)
         elif must is not None or must_not is not None:
             within = eng.term_sets(must, must_not, within=within)
+        if facet is not None:
+            self._facet_chunk(term_ids, within, facet)
         if mode == "hybrid":
             k_lex = hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
             packed = eng.pack_queries(term_ids)
@@ -377,7 +414,7 @@ class Retriever:
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
                           must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None,
-                          wildcards=None):
+                          wildcards=None, facets=None):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
@@ -411,7 +448,13 @@ class Retriever:
         DeviceEngine.wildcard_terms call over all its distinct patterns, where the fuzzy lookup stands (behind it when both are
         given: a pattern is never corrected), appends each query's expansions behind its term ids (wildcard.expand).  The
         generator fills wildcards["expansions"] (per query {pattern: {...}}) and wildcards["ids"] (the term ids that were
-        scored).  Like fuzzy, the answer comes back before the chunk is enqueued; same needs, same refusal of prepare=."""
+        scored).  Like fuzzy, the answer comes back before the chunk is enqueued; same needs, same refusal of prepare=.
+        facets (DESIGN K17): None, or a dict {"by": "host" | "domain", "limit": 1 .. 64}: per chunk ONE
+        DeviceEngine.facet_counts call counts, per query, the pages that hold at least one counting term
+        (facets.counting_terms of the ids that are scored: after fuzzy correction and wildcard expansion) inside `within` and
+        inside what operators, phrases and proximity built, and how many of them each facet value has.  The generator fills
+        facets["hits"], ["n_values_hit"], ["top_value"], ["top_count"] (per query) and ["names"] (the key's value names).  In
+        mode="hybrid" the counts are of the LEXICAL matches only.  Needs an index with URLs (ValueError)."""
         import torch
         eng = self.engine
         _check_mode(mode)
@@ -425,6 +468,10 @@ class Retriever:
             if prepare is not None or len(wildcards["patterns"]) != len(term_id_lists):
                 raise ValueError("wildcards: needs the patterns of every query (not with prepare=)")
             wildcards["expansions"], wildcards["ids"] = [], []
+        if facets is not None:
+            self._check_facets(facets.get("by", "host"), facets.get("limit", 10))
+            facets["names"] = self._ensure_facet(facets.get("by", "host"))
+            facets.update(limit=int(facets.get("limit", 10)), hits=[], n_values_hit=[], top_value=[], top_count=[])
         if operators:
             raise ValueError("operators=True needs the query text: use search / search_batch / batch_search, or parse with "
                              "text.parse_operators and pass must= / must_not=")
@@ -472,7 +519,7 @@ class Retriever:
                 wildcards["ids"] += ids
             job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=m_ids,
                                       must_not=op_ids(must_not, a, b), must_phrases=ph_ids(must_phrases, a, b),
-                                      must_not_phrases=ph_ids(must_not_phrases, a, b))
+                                      must_not_phrases=ph_ids(must_not_phrases, a, b), facet=facets)
             if pending is not None:
                 yield (pending[0],) + self._collect(pending[1])
             pending = (a, job)
@@ -509,12 +556,12 @@ class Retriever:
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
-                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None):
+                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None, facets=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
         with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
-        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity / fuzzy / wildcards:
+        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity / fuzzy / wildcards / facets:
         final_list_chunks."""
         _check_mode(mode)
         if with_source and mode != "hybrid":
@@ -522,7 +569,7 @@ class Retriever:
         parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
                                             operators=operators, must=must, must_not=must_not, phrases=phrases,
                                             must_phrases=must_phrases, must_not_phrases=must_not_phrases, proximity=proximity,
-                                            fuzzy=fuzzy, wildcards=wildcards))
+                                            fuzzy=fuzzy, wildcards=wildcards, facets=facets))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -679,7 +726,8 @@ class Retriever:
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
                      must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS,
-                     fuzzy=False, wildcards=False, max_expansions=8, patterns=None):
+                     fuzzy=False, wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host",
+                     facet_limit=10):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
@@ -730,11 +778,27 @@ class Retriever:
         phrase, or corrected by fuzzy=True; hybrid mode scores the expanded terms in its lexical half and the dense stage keeps
         the embedding of the query as typed.  Each query's result is then a fuzzy.Results list whose `expansions` maps each
         pattern to {"terms": the terms used, "total": all matches, "skipped" / "truncated": True where that happened}.  Needs
-        an index with term strings; max_expansions outside 1 .. 16 raises ValueError.  Off by default."""
+        an index with term strings; max_expansions outside 1 .. 16 raises ValueError.  Off by default.
+        facets=True (DESIGN K17): each query's result is a fuzzy.Results list that also says what the WHOLE match set holds,
+        counted on the device (ONE DeviceEngine.facet_counts call per chunk of queries), not over the ~100 rows returned:
+        `hits` -- the pages that hold at least one counting term of the query (facets.counting_terms: the scored terms with
+        idf > 0, so not the city term preprocessing appends; all of them if none has) inside within= and inside what
+        operators, phrases and proximity built; it is NOT the length of BM25's unlimited list under an arbitrary min_score --
+        `facets` -- [{"value": name, "count": pages}, ...], the first facet_limit (1 .. 64, ValueError otherwise) values by
+        (count desc, first occurrence in the index asc) -- and `facet_values`, the number of distinct values hit.  facet_by:
+        "host" (default: docset.url_host, so a value can be handed back as a site of DocSet.from_sites / sites=[...]) or
+        "domain" (the rows' "domain" key); anything else raises ValueError.  The terms counted are the ones scored: after
+        fuzzy correction and wildcard expansion.  mode="hybrid" counts the LEXICAL matches only (a dense-only hit is in no
+        count).  A query of unknown words has 0 hits and no facets.  The table of facet_by is bound lazily per index and again
+        after update_index.  An index without URLs raises ValueError.  Off by default: without it the call uploads, launches
+        and returns exactly what it did."""
         _check_mode(mode)
         if snippets:
             self._check_snippets(snippet_tokens)
-        fz = wc = None
+        fz = wc = fc = None
+        if facets:
+            self._check_facets(facet_by, facet_limit)
+            fc = {"by": facet_by, "limit": int(facet_limit)}
         if fuzzy:
             self._check_fuzzy()
             fz = {}
@@ -747,6 +811,8 @@ class Retriever:
             ops["fuzzy"] = fz
         if wc is not None:
             ops["wildcards"] = wc
+        if fc is not None:
+            ops["facets"] = fc
         src = None
         if mode == "hybrid":
             doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
@@ -780,21 +846,25 @@ class Retriever:
                         rows[-1]["snippet"] = hit[0]
                     rows[-1]["highlights"] = hit[1] if hit is not None else []
                     rows[-1]["missing"] = hit[2] if hit is not None else list(row_names[q] or [])
-            if fz is not None or wc is not None:
+            if fz is not None or wc is not None or fc is not None:
                 corr = fz["corrections"][q] if fz is not None else {}
                 rows = _fuzzy.Results(rows, corr, _fuzzy.corrected_text(fz["processed"][q], corr) if fz is not None else None,
                                       wc["expansions"][q] if wc is not None else None)
+                if fc is not None:
+                    rows.hits, rows.facet_values = int(fc["hits"][q]), int(fc["n_values_hit"][q])
+                    rows.facets = _facets.top_list(fc["names"], fc["top_value"][q], fc["top_count"][q])
             out.append(rows)
         return out
 
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
-               wildcards=False, max_expansions=8, patterns=None):
+               wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host", facet_limit=10):
         """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
         list of phrases (or text.Near conditions) each; snippets / snippet_tokens / fuzzy: search_batch (fuzzy=True: the
         result is a fuzzy.Results list with `corrections` and `corrected_query`); wildcards / max_expansions: search_batch
-        (the result is a fuzzy.Results list with `expansions`); patterns: ONE list of pattern strings."""
+        (the result is a fuzzy.Results list with `expansions`); patterns: ONE list of pattern strings; facets / facet_by /
+        facet_limit: search_batch (the result is a fuzzy.Results list with `hits`, `facets` and `facet_values`)."""
         return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
                                  None if terms is None else [terms], None if query_id is None else [query_id], within=within,
                                  mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
@@ -803,7 +873,8 @@ class Retriever:
                                  must_not_phrases=None if must_not_phrases is None else [must_not_phrases],
                                  proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens, fuzzy=fuzzy,
                                  wildcards=wildcards, max_expansions=max_expansions,
-                                 patterns=None if patterns is None else [patterns])[0]
+                                 patterns=None if patterns is None else [patterns], facets=facets, facet_by=facet_by,
+                                 facet_limit=facet_limit)[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,

@@ -78,6 +78,9 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         wildcards: bool = False       # `bibliothek*`, `*bibliothek`, `t?bingen`: a token with `*` / `?` is expanded over the
         max_expansions: int = 8       # vocabulary into at most max_expansions (1 .. 16) scoring terms (Retriever.search, DESIGN
         patterns: Optional[List[str]] = None  # K16); patterns: further patterns; the response then carries "expansions"
+        facets: bool = False          # count the WHOLE match set on the device (Retriever.search, DESIGN K17): the response then
+        facet_by: str = "host"        # carries "hits", "facets" ([{"value", "count"}], by "host" -- usable as sites=[...] -- or by
+        facet_limit: int = 10         # "domain", the first facet_limit (1 .. 64) values) and "facet_values" (distinct values hit)
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -153,19 +156,23 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                     kw.update(fuzzy=True)
                 if wild:
                     kw.update(wildcards=req.wildcards, max_expansions=req.max_expansions, patterns=req.patterns)
+                if req.facets:
+                    kw.update(facets=True, facet_by=req.facet_by, facet_limit=req.facet_limit)
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
-                if req.mode == "lexical" and not near and not req.snippets and not req.fuzzy and not wild:
+                if req.mode == "lexical" and not near and not req.snippets and not req.fuzzy and not wild and not req.facets:
                     raise
                 # a dense_k the engine cannot hold; fuzzy / wildcards on an index without term strings; max_expansions outside
-                # 1 .. 16; a required or excluded pattern
+                # 1 .. 16; a required or excluded pattern; a facet_by the engine does not know, a facet_limit outside 1 .. 64
                 return JSONResponse(status_code=400, content={"error": str(e)})
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
-            if req.fuzzy or wild:
+            if req.fuzzy or wild or req.facets:
                 out = {"llm_response": llm_response, "documents": list(docs)}
+                if req.facets:
+                    out.update(hits=docs.hits, facets=docs.facets, facet_values=docs.facet_values)
                 if req.fuzzy:
                     out.update(corrected_query=docs.corrected_query, corrections=docs.corrections)
                 if wild:
