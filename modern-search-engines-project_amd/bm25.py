@@ -7,13 +7,15 @@ The reference opens a DuckDB file and re-reads postings per query; here the post
 (DeviceEngine) and the scoring loop + sort + cut run as msr_bm25_topk.  The host keeps what is host work
 in the reference too: tokenising the query string and formatting the snippet.
 """
+from dataclasses import replace
 from typing import Callable, List, Optional, Sequence, Union
 
 from . import fuzzy as _fuzzy
 from . import wildcard as _wildcard
 from .engine import DeviceEngine
 from .index import CorpusIndex
-from .text import Near, parse_operators, parse_phrases, parse_proximity, simple_tokenize
+from .query import Conditions, SearchOptions, parse_queries
+from .text import simple_tokenize
 
 
 class BM25:
@@ -115,70 +117,35 @@ class BM25:
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
                must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None,
                proximity: bool = False, fuzzy: bool = False, wildcards: bool = False, max_expansions: int = 8, patterns=None):
-        """wildcards=True (DESIGN K16): a token of the query with `*` or `?` is a pattern (wildcard.parse_wildcards, in front of
-        the phrases and the operators): it leaves the scoring text and the vocabulary terms it matches, the most frequent
-        first, at most max_expansions (1 .. 16), are appended to the query's terms (wildcard.expand); patterns=: further
-        pattern strings.  The result is then a fuzzy.Results list whose `expansions` says what each pattern became.  Patterns
-        are never required, excluded or corrected.  Needs an index with term strings (ValueError).  Off by default.
-        fuzzy=True (DESIGN K15): a query word (or must word) the vocabulary lacks is replaced by its nearest vocabulary term
-        -- optimal string alignment distance within the AUTO tolerance of its length, then the largest document frequency
-        (fuzzy.py) -- before scoring; the result is a fuzzy.Results list whose `corrections` maps typed to used terms (`corrected_query`: the scoring text with them, or None).  Words
-        of the vocabulary are never touched; must_not words, phrases and proximity conditions are NOT corrected (excluding
-        or quoting a guessed word is wrong more often than right).  Needs an index with term strings (ValueError).  Off by
-        default.
-        operators=True: `+word` / `-word` tokens of the query are required / excluded words (text.parse_operators; the
-        query is taken as it is -- no city is appended here); must / must_not: further term strings (or ids) every result
-        must / must not contain.  Both restrict the documents on the device (DeviceEngine.term_sets), inside `within`.
-        phrases=True: `"a b"` / `-"a b"` in the query are required / excluded phrases (text.parse_phrases, before the
-        operators); must_phrases / must_not_phrases: further phrases, each a string (tokenised like the query) or a list of
-        term strings (or ids).  A result holds the phrase's terms next to each other, in order, in its indexed token stream
-        (DeviceEngine.phrase_sets; needs a forward index, index_build.attach_tokens); scores are unchanged.
-        proximity=True: phrases=True, and `"a b"~N` / `"a b"~>N` are proximity conditions (text.parse_proximity); a text.Near
-        in must_phrases / must_not_phrases is one without the text syntax: the terms within a window, in any order or in
-        order, instead of next to each other (DESIGN K13)."""
-        phrases = phrases or proximity
-        pats = None
-        if wildcards or patterns is not None:
-            from ._abi import MSR_WILD_MAX_LIMIT
-            if isinstance(max_expansions, bool) or not isinstance(max_expansions, int) or not 1 <= max_expansions <= MSR_WILD_MAX_LIMIT:
-                raise ValueError(f"max_expansions must be 1 .. MSR_WILD_MAX_LIMIT = {MSR_WILD_MAX_LIMIT} (got {max_expansions!r})")
-            if not self.engine.has_vocab:
-                raise ValueError("wildcards: the index has no vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
-                                 "index cannot expand a pattern")
-            pats = []
-            if wildcards:
-                query, pats = _wildcard.parse_wildcards(query)
-            pats = list(pats) + [str(p).lower() for p in (patterns or ())]
-        if phrases:
-            query, m_ph, x_ph = (parse_proximity if proximity else parse_phrases)(query)
-        if operators:
-            query, m_words, x_words = parse_operators(query)
+        """The switches and lists are query.SearchOptions' and query.Conditions', for this ONE query: must / must_not are one
+        list of term strings (or ids) each, must_phrases / must_not_phrases one list of phrases (strings, lists of term
+        strings or ids, text.Near), patterns one list of pattern strings.  The query is taken as it is -- no city is appended
+        here.  The conditions restrict the documents on the device (DeviceEngine.term_sets / phrase_sets), inside `within`;
+        with fuzzy=True or patterns the result is a fuzzy.Results list (`corrections`, `corrected_query`, `expansions`)."""
+        opts = SearchOptions(operators=operators, phrases=phrases, proximity=proximity, fuzzy=fuzzy, wildcards=wildcards,
+                             max_expansions=max_expansions)
+        one = lambda v: None if v is None else [v]
+        explicit = Conditions(one(must), one(must_not), one(must_phrases), one(must_not_phrases))
+        opts.check(patterns=patterns is not None, int_types=int)
+        if (wildcards or patterns is not None) and not self.engine.has_vocab:
+            raise ValueError("wildcards: the index has no vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
+                             "index cannot expand a pattern")
+        (query,), _, cond, pats = parse_queries([query], self._tokenize, opts, explicit,       # (a pattern goes through str())
+                                                None if patterns is None else [[str(p) for p in patterns]], drop_empty=True)
+        pats = None if pats is None else pats[0]
         query_terms = self._tokenize(query)
         if not query_terms and not pats:
             return []                                              # bm25_indexer.py:396-397
-        m, x = list(must or ()), list(must_not or ())
-        if operators:
-            m += [t for w in m_words for t in self._tokenize(w)]
-            x += [t for w in x_words for t in self._tokenize(w)]
-        as_terms = lambda p: (p.with_terms(as_terms(p.terms)) if isinstance(p, Near) else self._tokenize(p) if isinstance(p, str)
-                              else list(p))
-        mp, xp = [as_terms(p) for p in must_phrases or ()], [as_terms(p) for p in must_not_phrases or ()]
-        if phrases:
-            mp += [as_terms(p) for p in m_ph]
-            xp += [as_terms(p) for p in x_ph]
-        mp, xp = [p for p in mp if p], [p for p in xp if p]
+        m = [] if cond.must is None else cond.must[0]
         ids = self.index.term_ids
         corrections = None
         if fuzzy:
             self._check_fuzzy()
             new_ids, new_must, corr = _fuzzy.correct(self._lookup, self._name_of, [query_terms], [ids(query_terms)], [m], [ids(m)])
             query_terms, m, corrections = new_ids[0], new_must[0], corr[0]
-        ph_ids = lambda p: p.with_terms(ids(list(p.terms))) if isinstance(p, Near) else ids(p)
-        if mp or xp:
-            within = self.engine.phrase_sets([[ph_ids(p) for p in mp]], [[ph_ids(p) for p in xp]], [ids(m)], [ids(x)],
-                                             within=None if within is None else [within])
-        elif m or x:
-            within = self.engine.term_sets([ids(m)], [ids(x)], within=None if within is None else [within])
+        if not cond.empty:
+            c = replace(cond, must=None if cond.must is None else [m]).ids(ids, self._tokenize)
+            within = c.sets(self.engine, None if within is None else [within])
         expansions = None
         if pats is not None:
             new_ids, exp = _wildcard.expand(lambda ps: self.engine.wildcard_terms(ps, limit=max_expansions), self._name_of,

@@ -8,6 +8,7 @@
         rerank -> top-100, formatted for the UI / as `qnum<TAB>rank<TAB>url<TAB>score` lines.
 """
 import weakref
+from dataclasses import replace
 
 import numpy as np
 
@@ -18,11 +19,10 @@ from . import wildcard as _wildcard
 from .docset import DeviceSets
 from .engine import DeviceEngine
 from .index import CorpusIndex
+from .query import Conditions, SearchOptions, parse_queries
 from .reranker import Reranker
 from .snippets import SNIPPET_TOKENS, query_row, render, term_weights
-from .text import (LineFormatter, Near, extract_domain, extract_domain_topic, format_result_line, parse_operators, parse_phrases,
-                   parse_proximity,
-                   preprocess_query, read_queries_file)
+from .text import LineFormatter, extract_domain, extract_domain_topic, format_result_line, preprocess_query, read_queries_file
 
 TOP_K_RETRIEVAL = 1000     # config.py:13
 TOP_K_RERANKING = 100      # config.py:14
@@ -41,11 +41,6 @@ def hybrid_k_lex(top_k, rerank_max_docs, dense_k):
         raise ValueError(f"dense_k {dense_k} leaves no room for lexical candidates (top_k {top_k}, rerank_max_docs "
                          f"{rerank_max_docs})")
     return k_lex
-
-
-def _check_mode(mode):
-    if mode not in ("lexical", "hybrid"):
-        raise ValueError(f"mode must be 'lexical' or 'hybrid' (got {mode!r})")
 
 
 class Retriever:
@@ -280,12 +275,28 @@ class Retriever:
             self.engine.bind_doc_domains(self._doc_domains())
             self._domains_bound = True
 
-    def _check_facets(self, facet_by, facet_limit):
-        """What facets=True needs, checked before any device work: a key of facets.FACET_KEYS, facet_limit of 1 ..
-        MSR_FACET_MAX_LIMIT and an index with postings and URLs (ValueError)."""
-        _facets.check_options(facet_by, facet_limit)
-        if self.bm25 is None or self.index.urls is None:
+    def _check_options(self, opts, patterns=False):
+        """What the options need, checked before any device work: values in range (SearchOptions.check; patterns: the call
+        has explicit patterns) and, of this index and engine, what the features that are on read.  snippets: the spans of a
+        custom tokenizer (ValueError), a forward index and texts (MsrError, as phrase search); facets: postings and URLs;
+        fuzzy, wildcards and patterns: term strings (ValueError)."""
+        from ._abi import MsrError
+        opts.check(patterns)
+        if opts.snippets:
+            if self._tokenizer is not None and self._span_tokenizer is None:
+                raise ValueError("snippets=True with a custom tokenizer needs Retriever(span_tokenizer=...): the tokenizer's "
+                                 "(term, begin, end) form (text.simple_tokenize_spans is simple_tokenize's)")
+            if not self.engine.has_tokens:
+                raise MsrError(-2, "snippets: the index has no forward index (tok_off / tok_ids): build it with keep_tokens=True "
+                                   "or attach the token streams with index_build.attach_tokens, then update_index")
+            if self.index.texts is None:
+                raise MsrError(-2, "snippets: the index has no texts to cut a passage from")
+        if opts.facets and (self.bm25 is None or self.index.urls is None):
             raise ValueError("facets=True needs an index with postings and URLs (CorpusIndex.urls)")
+        for on, name, verb in ((opts.fuzzy, "fuzzy", "correct a word"), (opts.wildcards or patterns, "wildcards", "expand a pattern")):
+            if on and (self.bm25 is None or not self.engine.has_vocab):
+                raise ValueError(f"{name}=True needs an index with a vocabulary (CorpusIndex.vocab: term strings); a "
+                                 f"term-id-only index cannot {verb}")
 
     def _ensure_facet(self, by):
         """The facet table of key `by`, bound lazily per index (one table at a time: another key rebinds) and again after
@@ -313,26 +324,23 @@ class Retriever:
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
-    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, must=None, must_not=None,
-                       must_phrases=None, must_not_phrases=None, facet=None):
+    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, cond=None, facet=None):
         """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
         within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
         mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
         with its true BM25 score (msr_bm25_score_docs, msr_union_candidates); the candidates and where each came from are
         copied to pinned buffers beside the final rows (the job's sixth entry).
-        must / must_not (None | term-id lists per query of the chunk): ONE term_sets call in front of stage 1 turns them, inside
-        `within`, into device sets that take within's place in both stages; nothing else changes.
-        must_phrases / must_not_phrases (None | per query of the chunk a list of phrases, each a list of term ids): ONE
-        phrase_sets call takes the term_sets call's place (it makes that call itself, with the phrases' candidate rows).
+        cond (None | the Conditions of the chunk's queries, over term ids): its term lists make ONE term_sets call in front of
+        stage 1, which turns them, inside `within`, into device sets that take within's place in both stages; nothing else
+        changes.  With phrase lists ONE phrase_sets call takes the term_sets call's place (it makes that call itself, with
+        the phrases' candidate rows).
         facet (None | the dict of final_list_chunks' facets=): ONE facet_counts call over the chunk's scored terms inside the
         sets stage 1 is restricted to (_facet_chunk); its answer comes back to the host before stage 1 is enqueued."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
         union = None
-        if must_phrases is not None or must_not_phrases is not None:
-            within = eng.phrase_sets(must_phrases, must_not_phrases, must, must_not, within=within)
-        elif must is not None or must_not is not None:
-            within = eng.term_sets(must, must_not, within=within)
+        if cond is not None:
+            within = cond.sets(eng, within)
         if facet is not None:
             self._facet_chunk(term_ids, within, facet)
         if mode == "hybrid":
@@ -423,81 +431,72 @@ class Retriever:
         within: None, a DocSet (every query), a list of DocSet / None per query or a DeviceSets of all Q queries (each chunk
         takes its queries' part; not together with must / must_not): BM25 stage restricted to the set, then the
         unchanged rerank / fuse / diversify on those candidates (the min-max normalisation spans the restricted candidates).
+        What the options do: query.SearchOptions; here the queries are term ids, so the options come in this form:
         mode="hybrid": the candidates are the BM25 top min(top_k, rerank_max_docs - dense_k) AND the dense top dense_k (both
         within the set, if any), see _enqueue_chunk; every chunk then carries a sixth array, int32 [Qc, S]: where each row's
         document came from (1 lexical, 2 dense, 3 both).  A query without a known term still gets its dense candidates.
-        must / must_not: None or, per query, the terms (strings or ids) every result must / must not contain -- one
-        DeviceEngine.term_sets call per chunk builds the sets on the device, inside `within`; in hybrid mode the dense
-        candidates are restricted too.  operators: here the queries are term ids, there is no text to parse -- True is refused
-        (search / search_batch / batch_search parse; or text.parse_operators and must= / must_not=).
-        must_phrases / must_not_phrases: None or, per query, a list of phrases -- each a list of terms (strings or ids) that
-        must stand next to each other, in this order, in a result's indexed token stream / in none of them: one
-        DeviceEngine.phrase_sets call per chunk (in the term_sets call's place), both stages restricted in hybrid mode.  A
-        phrase filters; the BM25 scores stay what they are.  The index needs a forward index (index_build.attach_tokens),
-        MsrError otherwise; a phrase of more than MSR_PHRASE_MAX_TERMS terms raises ValueError.  phrases=True is refused like
-        operators=True (text.parse_phrases needs the text).
-        A text.Near in must_phrases / must_not_phrases is a proximity condition (DESIGN K13): its terms within a window, in
-        order or in any order; proximity=True is refused like phrases=True (text.parse_proximity needs the text).
-        fuzzy (DESIGN K15): None, or a dict {"terms": per query the term STRINGS that term_id_lists was mapped from}: per chunk
-        ONE DeviceEngine.fuzzy_terms call over all its unknown words, in front of stage 1 (the place term_sets has), replaces
-        each -1 of the chunk's term ids and must ids by the word's nearest vocabulary term (fuzzy.correct); must_not and the
-        phrases are not corrected.  The generator fills fuzzy["corrections"] (per query {typed: used}) and fuzzy["ids"] (the
-        term ids that were scored).  The lookup's answer comes back to the host before the chunk is enqueued: with fuzzy the
-        host does not run ahead of the device.  Needs an index with term strings (ValueError); not with prepare=.
-        wildcards (DESIGN K16): None, or a dict {"patterns": per query its pattern strings, "limit": 1 .. 16}: per chunk ONE
-        DeviceEngine.wildcard_terms call over all its distinct patterns, where the fuzzy lookup stands (behind it when both are
-        given: a pattern is never corrected), appends each query's expansions behind its term ids (wildcard.expand).  The
-        generator fills wildcards["expansions"] (per query {pattern: {...}}) and wildcards["ids"] (the term ids that were
-        scored).  Like fuzzy, the answer comes back before the chunk is enqueued; same needs, same refusal of prepare=.
-        facets (DESIGN K17): None, or a dict {"by": "host" | "domain", "limit": 1 .. 64}: per chunk ONE
-        DeviceEngine.facet_counts call counts, per query, the pages that hold at least one counting term
-        (facets.counting_terms of the ids that are scored: after fuzzy correction and wildcard expansion) inside `within` and
-        inside what operators, phrases and proximity built, and how many of them each facet value has.  The generator fills
-        facets["hits"], ["n_values_hit"], ["top_value"], ["top_count"] (per query) and ["names"] (the key's value names).  In
-        mode="hybrid" the counts are of the LEXICAL matches only.  Needs an index with URLs (ValueError)."""
+        must / must_not / must_phrases / must_not_phrases (query.Conditions): the terms are strings or ids and a phrase is a
+        list of them (or a text.Near) -- one DeviceEngine.term_sets or phrase_sets call per chunk builds the sets on the
+        device, inside `within`; in hybrid mode the dense candidates are restricted too.  operators / phrases / proximity:
+        there is no text to parse -- True is refused (search / search_batch / batch_search parse; or text.parse_operators,
+        parse_phrases, parse_proximity and the lists).
+        fuzzy: None, or a dict {"terms": per query the term STRINGS that term_id_lists was mapped from}: per chunk the lookup
+        stands in front of stage 1 (the place term_sets has) and replaces each -1 of the chunk's term ids and must ids
+        (fuzzy.correct).  The generator fills fuzzy["corrections"] (per query {typed: used}) and fuzzy["ids"] (the term ids that
+        were scored).  The lookup's answer comes back to the host before the chunk is enqueued: with fuzzy the host does not
+        run ahead of the device.  Not with prepare=.
+        wildcards: None, or a dict {"patterns": per query its pattern strings, "limit": 1 .. 16}: per chunk the lookup stands
+        where the fuzzy lookup does (behind it when both are given: a pattern is never corrected) and appends each query's
+        expansions behind its term ids (wildcard.expand).  The generator fills wildcards["expansions"] (per query {pattern:
+        {...}}) and wildcards["ids"] (the term ids that were scored).  Like fuzzy, the answer comes back before the chunk is
+        enqueued; same refusal of prepare=.
+        facets: None, or a dict {"by": "host" | "domain", "limit": 1 .. 64}.  The generator fills facets["hits"],
+        ["n_values_hit"], ["top_value"], ["top_count"] (per query) and ["names"] (the key's value names)."""
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity)
+        cond = Conditions(must, must_not, must_phrases, must_not_phrases)
+        yield from self._chunks(term_id_lists, query_vectors, top_k, chunk, prepare, n_queries, within, opts, cond, fuzzy, wildcards,
+                                facets)
+
+    def _chunks(self, term_id_lists, query_vectors, top_k, chunk, prepare, n_queries, within, opts, cond, fuzzy, wildcards, facets,
+                parsed=False):
+        """final_list_chunks over the two values.  Of opts it reads mode, dense_k and the text switches -- parsed: they were
+        applied by parse_queries (else True is refused); fuzzy / wildcards / facets: final_list_chunks' dicts, which hold
+        those features' limits."""
         import torch
         eng = self.engine
-        _check_mode(mode)
+        opts = replace(opts, snippets=False, fuzzy=fuzzy is not None, wildcards=wildcards is not None,
+                       max_expansions=(wildcards or {}).get("limit", 8), facets=facets is not None,
+                       facet_by=(facets or {}).get("by", "host"), facet_limit=(facets or {}).get("limit", 10))
+        self._check_options(opts)
         if fuzzy is not None:
-            self._check_fuzzy()
             if prepare is not None or len(fuzzy["terms"]) != len(term_id_lists):
                 raise ValueError("fuzzy: needs the term strings of every query (not with prepare=)")
             fuzzy["corrections"], fuzzy["ids"] = [], []
         if wildcards is not None:
-            self._check_wildcards(wildcards.get("limit", 8))
             if prepare is not None or len(wildcards["patterns"]) != len(term_id_lists):
                 raise ValueError("wildcards: needs the patterns of every query (not with prepare=)")
             wildcards["expansions"], wildcards["ids"] = [], []
         if facets is not None:
-            self._check_facets(facets.get("by", "host"), facets.get("limit", 10))
-            facets["names"] = self._ensure_facet(facets.get("by", "host"))
-            facets.update(limit=int(facets.get("limit", 10)), hits=[], n_values_hit=[], top_value=[], top_count=[])
-        if operators:
-            raise ValueError("operators=True needs the query text: use search / search_batch / batch_search, or parse with "
-                             "text.parse_operators and pass must= / must_not=")
-        if phrases:
-            raise ValueError("phrases=True needs the query text: use search / search_batch / batch_search, or parse with "
-                             "text.parse_phrases and pass must_phrases= / must_not_phrases=")
-        if proximity:
-            raise ValueError("proximity=True needs the query text: use search / search_batch / batch_search, or parse with "
-                             "text.parse_proximity and pass must_phrases= / must_not_phrases=")
+            facets["names"] = self._ensure_facet(opts.facet_by)
+            facets.update(limit=int(opts.facet_limit), hits=[], n_values_hit=[], top_value=[], top_count=[])
+        for name, parser, lists in (("operators", "parse_operators", "must= / must_not="),
+                                    ("phrases", "parse_phrases", "must_phrases= / must_not_phrases="),
+                                    ("proximity", "parse_proximity", "must_phrases= / must_not_phrases=")):
+            if getattr(opts, name) and not parsed:
+                raise ValueError(f"{name}=True needs the query text: use search / search_batch / batch_search, or parse with "
+                                 f"text.{parser} and pass {lists}")
         if top_k > eng.rerank_max_docs or top_k > eng.max_k:
             raise ValueError(f"top_k {top_k} exceeds the engine's max_k / rerank_max_docs ({eng.max_k} / {eng.rerank_max_docs})")
-        if mode == "hybrid":
-            hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
-            if int(dense_k) > eng.max_k:
-                raise ValueError(f"dense_k {dense_k} exceeds the engine's max_k ({eng.max_k})")
+        if opts.mode == "hybrid":
+            hybrid_k_lex(top_k, eng.rerank_max_docs, opts.dense_k)
+            if int(opts.dense_k) > eng.max_k:
+                raise ValueError(f"dense_k {opts.dense_k} exceeds the engine's max_k ({eng.max_k})")
         self._ensure_response_tables()
         Q = len(term_id_lists) if prepare is None else int(n_queries)
         step = int(chunk or max(256, eng.max_queries))
         if isinstance(within, (list, tuple, DeviceSets)) and len(within) != Q:
             raise ValueError(f"within: {len(within)} entries for {Q} queries")
-        for name, lists in (("must", must), ("must_not", must_not), ("must_phrases", must_phrases),
-                            ("must_not_phrases", must_not_phrases)):
-            if lists is not None and len(lists) != Q:
-                raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
-        op_ids = lambda lists, a, b: None if lists is None else [self.index.term_ids(t) for t in lists[a:b]]
-        ph_ids = lambda lists, a, b: None if lists is None else [[self._phrase_ids(p) for p in ps] for ps in lists[a:b]]
+        cond.check(Q)
         pending = None
         for i, a in enumerate(range(0, Q, step)):
             b = min(Q, a + step)
@@ -505,49 +504,25 @@ class Retriever:
             qv = eng._dev(np.asarray(qv, np.float32) if not torch.is_tensor(qv) else qv, torch.float32).reshape(-1, 768)
             w = (list(within[a:b]) if isinstance(within, (list, tuple))
                  else within.queries(a, b) if isinstance(within, DeviceSets) else within)
-            m_ids = op_ids(must, a, b)
+            c = None if cond.empty else cond.slice(a, b).ids(self.index.term_ids, lambda t: self.bm25._tokenize(t))
             if fuzzy is not None:
                 ids, m_ids, corr = _fuzzy.correct(self.bm25._lookup, self.bm25._name_of, fuzzy["terms"][a:b], ids,
-                                                  None if must is None else must[a:b], m_ids)
+                                                  None if cond.must is None else cond.must[a:b], None if c is None else c.must)
+                c = None if c is None else replace(c, must=m_ids)
                 fuzzy["corrections"] += corr
                 fuzzy["ids"] += ids
             if wildcards is not None:
-                lim = int(wildcards.get("limit", 8))
+                lim = int(opts.max_expansions)
                 ids, exp = _wildcard.expand(lambda ps: eng.wildcard_terms(ps, limit=lim), self.bm25._name_of, ids,
                                             wildcards["patterns"][a:b], lim)
                 wildcards["expansions"] += exp
                 wildcards["ids"] += ids
-            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=mode, dense_k=dense_k, must=m_ids,
-                                      must_not=op_ids(must_not, a, b), must_phrases=ph_ids(must_phrases, a, b),
-                                      must_not_phrases=ph_ids(must_not_phrases, a, b), facet=facets)
+            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=opts.mode, dense_k=opts.dense_k, cond=c, facet=facets)
             if pending is not None:
                 yield (pending[0],) + self._collect(pending[1])
             pending = (a, job)
         if pending is not None:
             yield (pending[0],) + self._collect(pending[1])
-
-    def _check_fuzzy(self):
-        """What fuzzy=True needs, checked before any device work: an index with term strings (ValueError)."""
-        if self.bm25 is None or not self.engine.has_vocab:
-            raise ValueError("fuzzy=True needs an index with a vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
-                             "index cannot correct a word")
-
-    def _check_wildcards(self, max_expansions):
-        """What wildcards=True needs, checked before any device work: max_expansions of 1 .. MSR_WILD_MAX_LIMIT and an index
-        with term strings (ValueError)."""
-        from ._abi import MSR_WILD_MAX_LIMIT
-        if isinstance(max_expansions, bool) or not isinstance(max_expansions, (int, np.integer)) or \
-                not 1 <= int(max_expansions) <= MSR_WILD_MAX_LIMIT:
-            raise ValueError(f"max_expansions must be 1 .. MSR_WILD_MAX_LIMIT = {MSR_WILD_MAX_LIMIT} (got {max_expansions!r})")
-        if self.bm25 is None or not self.engine.has_vocab:
-            raise ValueError("wildcards=True needs an index with a vocabulary (CorpusIndex.vocab: term strings); a term-id-only "
-                             "index cannot expand a pattern")
-
-    def _phrase_ids(self, p):
-        """A phrase's term ids; a text.Near keeps its slop and mode (a Near of a string is tokenised like the query)."""
-        if isinstance(p, Near):
-            return p.with_terms(self.index.term_ids(self.bm25._tokenize(p.terms) if isinstance(p.terms, str) else list(p.terms)))
-        return self.index.term_ids(p)
 
     @classmethod
     def _collect(cls, job):
@@ -559,17 +534,19 @@ class Retriever:
                     must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None, facets=None):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
-        query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  mode / dense_k: final_list_chunks;
-        with_source (hybrid mode only): a fifth array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).
-        operators / must / must_not / phrases / must_phrases / must_not_phrases / proximity / fuzzy / wildcards / facets:
-        final_list_chunks."""
-        _check_mode(mode)
-        if with_source and mode != "hybrid":
+        query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  with_source (hybrid mode only): a fifth
+        array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).  Everything else: final_list_chunks, whose chunks this
+        joins."""
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity)
+        cond = Conditions(must, must_not, must_phrases, must_not_phrases)
+        return self._final(term_id_lists, query_vectors, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source)
+
+    def _final(self, ids, qv, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source=False, parsed=False):
+        """final_lists over the two values: _chunks' chunks joined (parsed, the dicts: _chunks)."""
+        opts.check()
+        if with_source and opts.mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
-        parts = list(self.final_list_chunks(term_id_lists, query_vectors, top_k, chunk, within=within, mode=mode, dense_k=dense_k,
-                                            operators=operators, must=must, must_not=must_not, phrases=phrases,
-                                            must_phrases=must_phrases, must_not_phrases=must_not_phrases, proximity=proximity,
-                                            fuzzy=fuzzy, wildcards=wildcards, facets=facets))
+        parts = list(self._chunks(ids, qv, top_k, chunk, None, None, within, opts, cond, fuzzy, wildcards, facets, parsed))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -580,79 +557,24 @@ class Retriever:
                np.concatenate([pad(p[3], -1) for p in parts]), np.concatenate([p[4] for p in parts]))
         return out + ((np.concatenate([pad(p[5], 0) for p in parts]),) if with_source else ())
 
-    def _operators(self, processed, operators, must, must_not, phrases=False, must_phrases=None, must_not_phrases=None,
-                   proximity=False):
-        """-> (scoring texts, must term lists, must_not term lists, must phrases, not phrases) of the preprocessed queries: the
-        parsed operator words (operators=True) and quoted phrases (phrases=True, text.parse_phrases, BEFORE the operators),
-        tokenised like the query, joined with the caller's explicit lists; a pair is (None, None) when there is nothing of
-        its kind -- the chain then runs exactly as without the feature.  An explicit phrase is a string (tokenised here) or a
-        list of term strings; a phrase that tokenises to nothing is dropped.  proximity=True: phrases=True with
-        text.parse_proximity in parse_phrases' place; a text.Near, parsed or explicit, keeps its slop and mode."""
-        phrases = phrases or proximity
-        if not operators and must is None and must_not is None and not phrases and must_phrases is None and must_not_phrases is None:
-            return processed, None, None, None, None
-        Q = len(processed)
-        for name, lists in (("must", must), ("must_not", must_not), ("must_phrases", must_phrases),
-                            ("must_not_phrases", must_not_phrases)):
-            if lists is not None and len(lists) != Q:
-                raise ValueError(f"{name}: {len(lists)} entries for {Q} queries")
-        tok = self.bm25._tokenize
-        m = [list(t) for t in must] if must is not None else [[] for _ in range(Q)]
-        x = [list(t) for t in must_not] if must_not is not None else [[] for _ in range(Q)]
-        as_terms = lambda p: (p.with_terms(as_terms(p.terms)) if isinstance(p, Near) else tok(p) if isinstance(p, str) else list(p))
-        mp = [[as_terms(p) for p in ps] for ps in must_phrases] if must_phrases is not None else [[] for _ in range(Q)]
-        xp = [[as_terms(p) for p in ps] for ps in must_not_phrases] if must_not_phrases is not None else [[] for _ in range(Q)]
-        processed = list(processed)
-        for q in range(Q):
-            if phrases:
-                processed[q], m_ph, x_ph = (parse_proximity if proximity else parse_phrases)(processed[q])
-                mp[q] += [as_terms(p) for p in m_ph]
-                xp[q] += [as_terms(p) for p in x_ph]
-            if operators:
-                processed[q], m_words, x_words = parse_operators(processed[q])
-                m[q] += [t for w in m_words for t in tok(w)]
-                x[q] += [t for w in x_words for t in tok(w)]
-            mp[q], xp[q] = [p for p in mp[q] if p], [p for p in xp[q] if p]
-        if not any(m) and not any(x):
-            m = x = None
-        if not any(mp) and not any(xp):
-            mp = xp = None
-        return processed, m, x, mp, xp
+    def _front(self, queries, query_embeddings, term_lists, opts, explicit, patterns):
+        """The front half of search_batch and batch_search: check the options, preprocess and parse the queries
+        (query.parse_queries), tokenise, map and embed them -> (term ids, vectors, Conditions, fz, wc, fc): the dicts of
+        final_list_chunks' fuzzy= / wildcards= / facets=, None where the feature is off.  fz also receives "processed" (the
+        scoring texts).  The scoring text (patterns, excluded words and phrases removed, quotes gone) is what gets
+        tokenised; the text that is embedded keeps a pattern."""
+        self._check_options(opts, patterns is not None)
+        fz = {} if opts.fuzzy else None
+        fc = {"by": opts.facet_by, "limit": int(opts.facet_limit)} if opts.facets else None
+        scoring, embed_text, cond, pats = parse_queries([preprocess_query(q) for q in queries], lambda t: self.bm25._tokenize(t),
+                                                        opts, explicit, patterns)
+        wc = None if pats is None else {"patterns": pats, "limit": int(opts.max_expansions)}
+        return self._prepare(queries, query_embeddings, term_lists, scoring, fz, embed_text) + (cond, fz, wc, fc)
 
-    def _prepare_ops(self, queries, query_embeddings, term_lists, operators, must, must_not, phrases=False, must_phrases=None,
-                     must_not_phrases=None, proximity=False, keep=None, wild=None):
-        """_prepare with operators and phrases: -> (term ids, vectors, keyword arguments of final_lists: must / must_not /
-        must_phrases / must_not_phrases where there are any).  The scoring text (excluded words and phrases removed, quotes
-        gone) is what gets tokenised and embedded.
-        wild (DESIGN K16): None, or a dict {"parse": take the patterns out of the texts (wildcard.parse_wildcards, on the text
-        that still has its quotes: in front of the phrases and the operators), "explicit": None or per query a list of pattern
-        strings}; it receives "patterns", per query the parsed patterns and then the explicit ones, lower-cased.  A parsed
-        pattern leaves the scoring text; the text that is EMBEDDED keeps it (the dense stage sees the query as typed)."""
-        processed = [preprocess_query(q) for q in queries]
-        embed_text = None
-        if wild is not None:
-            typed, pats = processed, [[] for _ in queries]
-            if wild.get("parse"):
-                pairs = [_wildcard.parse_wildcards(p) for p in processed]
-                processed, pats = [s for s, _ in pairs], [list(p) for _, p in pairs]
-            explicit = wild.get("explicit")
-            if explicit is not None:
-                if len(explicit) != len(queries):
-                    raise ValueError(f"patterns: {len(explicit)} entries for {len(queries)} queries")
-                for q, ps in enumerate(explicit):
-                    if isinstance(ps, str) or not all(isinstance(p, str) for p in (ps or ())):
-                        raise ValueError("patterns: per query a LIST of pattern strings")
-                    pats[q] += [p.lower() for p in (ps or ())]
-            wild["patterns"] = pats
-            if processed != typed:
-                embed_text = self._operators(typed, operators, must, must_not, phrases, must_phrases, must_not_phrases,
-                                             proximity)[0]
-        processed, m, x, mp, xp = self._operators(processed, operators, must, must_not, phrases, must_phrases, must_not_phrases,
-                                                  proximity)
-        ops = {} if m is None else {"must": m, "must_not": x}
-        if mp is not None:
-            ops.update(must_phrases=mp, must_not_phrases=xp)
-        return self._prepare(queries, query_embeddings, term_lists, processed, keep, embed_text) + (ops,)
+    @staticmethod
+    def _scored_ids(ids, fz, wc):
+        """The term ids that were scored (the snippets look for those words): after correction, with the expansions."""
+        return wc["ids"] if wc is not None else fz["ids"] if fz is not None else ids
 
     def _prepare(self, queries, query_embeddings, term_lists, processed=None, keep=None, embed_text=None):
         """keep (a dict, optional) receives "processed" (the scoring texts) and "terms" (the term lists the ids came from).
@@ -672,22 +594,6 @@ class Retriever:
         return ids, qv
 
     # ------------------------------------------------------------------ query-biased snippets (msr_best_windows, DESIGN K14)
-    def _check_snippets(self, snippet_tokens):
-        """What snippets=True needs, checked before any device work: a window of 1 .. MSR_PROX_MAX_SPAN tokens and the spans of a
-        custom tokenizer (ValueError); an index with a forward index and texts (MsrError, as phrase search)."""
-        from ._abi import MSR_PROX_MAX_SPAN, MsrError
-        if isinstance(snippet_tokens, bool) or not isinstance(snippet_tokens, (int, np.integer)) or \
-                not 1 <= int(snippet_tokens) <= MSR_PROX_MAX_SPAN:
-            raise ValueError(f"snippet_tokens must be 1 .. MSR_PROX_MAX_SPAN = {MSR_PROX_MAX_SPAN} (got {snippet_tokens!r})")
-        if self._tokenizer is not None and self._span_tokenizer is None:
-            raise ValueError("snippets=True with a custom tokenizer needs Retriever(span_tokenizer=...): the tokenizer's "
-                             "(term, begin, end) form (text.simple_tokenize_spans is simple_tokenize's)")
-        if not self.engine.has_tokens:
-            raise MsrError(-2, "snippets: the index has no forward index (tok_off / tok_ids): build it with keep_tokens=True "
-                               "or attach the token streams with index_build.attach_tokens, then update_index")
-        if self.index.texts is None:
-            raise MsrError(-2, "snippets: the index has no texts to cut a passage from")
-
     def _term_name(self, t):
         if self._term_names is None:
             self._term_names = {v: k for k, v in (self.index.vocab or {}).items()}
@@ -730,101 +636,23 @@ class Retriever:
                      facet_limit=10):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
-        mode="hybrid": the dense top dense_k documents join the BM25 candidates (a page that shares no term with the query can
-        be returned; a query of unknown words only still gets results); every row then carries "matched_by": "lexical" |
-        "dense" | "both".  mode="lexical" (default): the reference's path, rows without that key.
-        operators=True: `+word` / `-word` tokens of a query (text.parse_operators, after preprocess_query) name words every
-        result must / must not contain; `+word` still scores, `-word` does not.  must / must_not: per query a list of term
-        strings (for callers with their own tokenizer, like term_lists), joined with the parsed ones.  Both act inside
-        `within`, in both stages of either mode: a page that holds an excluded word is never returned.  Without operators
-        and lists the call is what it was.
-        phrases=True: `"a b c"` in a query is a required phrase (its words still score), `-"a b"` an excluded one (removed from
-        the scoring text) -- text.parse_phrases, after preprocess_query and before the operators; must_phrases /
-        must_not_phrases: per query a list of phrases, each a string (tokenised like the query) or a list of term strings.  A
-        result holds every required phrase and no excluded one IN ITS INDEXED TOKEN STREAM (words next to each other, in
-        order, after the tokenizer); the scores are unchanged.  Needs an index with a forward index (index_build.attach_tokens;
-        MsrError otherwise); a phrase of more than 16 terms raises ValueError.  Off by default.
-        proximity=True: phrases=True, and `"a b"~N` / `"a b"~>N` are proximity conditions (text.parse_proximity): the words
-        within a window with up to N other tokens among them, in any order / in this order.  A text.Near in must_phrases /
-        must_not_phrases (terms: a string or a list of term strings) is such a condition without the text syntax.  A slop
-        below 0, more than 16 terms or a window of more than 64 tokens raises ValueError.  Off by default.
-        snippets=True (DESIGN K14): every row's "snippet" is the passage of the page that holds the most of the query -- the
-        window of snippet_tokens (1 .. 64) tokens of its indexed stream with the largest summed weight of distinct query terms
-        (snippets.term_weights: the idf; then the most occurrences, then the earliest), found by ONE DeviceEngine.best_windows
-        call for all returned documents of the call and cut from the page by snippets.render -- and the row gains
-        "highlights" ([begin, end) offsets of the query's terms in the snippet) and "missing" (the query's terms the passage
-        lacks).  Documents, ranks and scores are unchanged.  A page without a query term (a dense-only hybrid hit) and a
-        query of unknown words keep the reference's snippet, with "highlights": [] and every term of the row missing.  A
-        custom tokenizer needs Retriever(span_tokenizer=...) (ValueError); the index needs a forward index and texts
-        (MsrError).  Off by default: without it the call uploads, launches and returns exactly what it did.
-        fuzzy=True (DESIGN K15): a query word the vocabulary lacks -- today silently dropped -- is replaced by its nearest
-        vocabulary term before stage 1: optimal string alignment distance (insertion, deletion, substitution, swap of two
-        adjacent code points) within the AUTO tolerance of the word's length (0 edits below 3 code points, 1 for 3 .. 5, 2
-        from 6 up), then the largest document frequency, then the smallest term id; ONE DeviceEngine.fuzzy_terms call per
-        chunk of queries.  Words of the vocabulary are never touched; must= / `+word` terms are corrected the same way;
-        must_not / `-word` terms, phrases and proximity conditions are NOT (excluding or quoting a guessed word is wrong more
-        often than right).  Correction is lexical: the dense stage and the reranker use the embedding of the query AS TYPED.
-        Each query's result is then a fuzzy.Results list -- the same rows, plus `corrections` ({typed term: used term}, empty if
-        none) and `corrected_query` (the processed query with the replacements, or None).  Needs an index with term strings
-        (ValueError).  Off by default: without it every row and every list is what it was.
-        wildcards=True (DESIGN K16): a query token with `*` (any run of code points) or `?` (exactly one) -- `bibliothek*`,
-        `*bibliothek`, `t?bingen` -- is a pattern (wildcard.parse_wildcards: only letters and the two metacharacters, one
-        trailing `?` is punctuation, nothing inside quotes): it leaves the scoring text, and the vocabulary terms it matches as
-        a whole, the most frequent first, at most max_expansions (1 .. 16) of them, are appended to the query's terms as
-        ordinary scoring terms (wildcard.expand: no id twice, at most MSR_MAX_QUERY_TERMS unique ids, a pattern with fewer
-        than two literal code points is skipped); ONE DeviceEngine.wildcard_terms call per chunk of queries.  patterns=: per
-        query a list of further pattern strings, with or without wildcards=True.  Patterns match the vocabulary AS INDEXED
-        (lemmas, with a lemmatising tokenizer); they are never required, excluded (`+uni*` / `-uni*`: ValueError), part of a
-        phrase, or corrected by fuzzy=True; hybrid mode scores the expanded terms in its lexical half and the dense stage keeps
-        the embedding of the query as typed.  Each query's result is then a fuzzy.Results list whose `expansions` maps each
-        pattern to {"terms": the terms used, "total": all matches, "skipped" / "truncated": True where that happened}.  Needs
-        an index with term strings; max_expansions outside 1 .. 16 raises ValueError.  Off by default.
-        facets=True (DESIGN K17): each query's result is a fuzzy.Results list that also says what the WHOLE match set holds,
-        counted on the device (ONE DeviceEngine.facet_counts call per chunk of queries), not over the ~100 rows returned:
-        `hits` -- the pages that hold at least one counting term of the query (facets.counting_terms: the scored terms with
-        idf > 0, so not the city term preprocessing appends; all of them if none has) inside within= and inside what
-        operators, phrases and proximity built; it is NOT the length of BM25's unlimited list under an arbitrary min_score --
-        `facets` -- [{"value": name, "count": pages}, ...], the first facet_limit (1 .. 64, ValueError otherwise) values by
-        (count desc, first occurrence in the index asc) -- and `facet_values`, the number of distinct values hit.  facet_by:
-        "host" (default: docset.url_host, so a value can be handed back as a site of DocSet.from_sites / sites=[...]) or
-        "domain" (the rows' "domain" key); anything else raises ValueError.  The terms counted are the ones scored: after
-        fuzzy correction and wildcard expansion.  mode="hybrid" counts the LEXICAL matches only (a dense-only hit is in no
-        count).  A query of unknown words has 0 hits and no facets.  The table of facet_by is bound lazily per index and again
-        after update_index.  An index without URLs raises ValueError.  Off by default: without it the call uploads, launches
-        and returns exactly what it did."""
-        _check_mode(mode)
-        if snippets:
-            self._check_snippets(snippet_tokens)
-        fz = wc = fc = None
-        if facets:
-            self._check_facets(facet_by, facet_limit)
-            fc = {"by": facet_by, "limit": int(facet_limit)}
-        if fuzzy:
-            self._check_fuzzy()
-            fz = {}
-        if wildcards or patterns is not None:
-            self._check_wildcards(max_expansions)
-            wc = {"parse": bool(wildcards), "explicit": patterns, "limit": int(max_expansions)}
-        ids, qv, ops = self._prepare_ops(queries, query_embeddings, term_lists, operators, must, must_not, phrases, must_phrases,
-                                         must_not_phrases, proximity, keep=fz, wild=wc)
-        if fz is not None:
-            ops["fuzzy"] = fz
-        if wc is not None:
-            ops["wildcards"] = wc
-        if fc is not None:
-            ops["facets"] = fc
-        src = None
-        if mode == "hybrid":
-            doc, score, _, n, src = self.final_lists(ids, qv, top_k, within=within, mode=mode, dense_k=dense_k, with_source=True,
-                                                     **ops)
-        else:
-            doc, score, _, n = self.final_lists(ids, qv, top_k, within=within, **ops)
-        ix = self.index
-        if fz is not None:
-            ids = fz["ids"]                                  # (the snippets look for the words that were scored)
-        if wc is not None:
-            ids = wc["ids"]                                  # (... the expansions among them)
-        passages, row_names = self._snippets(ids, doc, n, snippet_tokens) if snippets else (None, None)
+        The switches and limits: query.SearchOptions; must / must_not / must_phrases / must_not_phrases: query.Conditions,
+        one entry per query; patterns: per query None or a list of pattern strings.  With fuzzy, wildcards, patterns or
+        facets each query's result is a fuzzy.Results list."""
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
+                             facets, facet_by, facet_limit)
+        return self._search(queries, top_k, query_embeddings, term_lists, query_ids, within, opts,
+                            Conditions(must, must_not, must_phrases, must_not_phrases), patterns)
+
+    def _search(self, queries, top_k, query_embeddings, term_lists, query_ids, within, opts, explicit, patterns):
+        """search_batch over the two values."""
+        ids, qv, cond, fz, wc, fc = self._front(queries, query_embeddings, term_lists, opts, explicit, patterns)
+        doc, score, _, n, *src = self._final(ids, qv, top_k, None, within, opts, cond, fz, wc, fc, with_source=opts.mode == "hybrid",
+                                             parsed=True)
+        src = src[0] if src else None                        # (hybrid mode: where each row's document came from)
+        ix, snippets = self.index, opts.snippets
+        ids = self._scored_ids(ids, fz, wc)
+        passages, row_names = self._snippets(ids, doc, n, opts.snippet_tokens) if snippets else (None, None)
         out = []
         for q in range(len(queries)):
             rows = []
@@ -860,21 +688,12 @@ class Retriever:
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
                wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host", facet_limit=10):
-        """search_batch for one query; must / must_not: ONE list of term strings each; must_phrases / must_not_phrases: ONE
-        list of phrases (or text.Near conditions) each; snippets / snippet_tokens / fuzzy: search_batch (fuzzy=True: the
-        result is a fuzzy.Results list with `corrections` and `corrected_query`); wildcards / max_expansions: search_batch
-        (the result is a fuzzy.Results list with `expansions`); patterns: ONE list of pattern strings; facets / facet_by /
-        facet_limit: search_batch (the result is a fuzzy.Results list with `hits`, `facets` and `facet_values`)."""
-        return self.search_batch([query], top_k, None if query_embedding is None else [query_embedding],
-                                 None if terms is None else [terms], None if query_id is None else [query_id], within=within,
-                                 mode=mode, dense_k=dense_k, operators=operators, must=None if must is None else [must],
-                                 must_not=None if must_not is None else [must_not], phrases=phrases,
-                                 must_phrases=None if must_phrases is None else [must_phrases],
-                                 must_not_phrases=None if must_not_phrases is None else [must_not_phrases],
-                                 proximity=proximity, snippets=snippets, snippet_tokens=snippet_tokens, fuzzy=fuzzy,
-                                 wildcards=wildcards, max_expansions=max_expansions,
-                                 patterns=None if patterns is None else [patterns], facets=facets, facet_by=facet_by,
-                                 facet_limit=facet_limit)[0]
+        """search_batch for one query: must / must_not / must_phrases / must_not_phrases / patterns are ONE list each."""
+        one = lambda v: None if v is None else [v]
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
+                             facets, facet_by, facet_limit)
+        return self._search([query], top_k, one(query_embedding), one(terms), one(query_id), within, opts,
+                            Conditions(one(must), one(must_not), one(must_phrases), one(must_not_phrases)), one(patterns))[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
@@ -886,39 +705,23 @@ class Retriever:
         search_batch (the entries keep the reference's keys in either mode); operators / must / must_not / phrases /
         must_phrases / must_not_phrases / proximity: search_batch.  snippets=True: every entry gains "snippet" (None where the
         page has no window), "highlights" and "missing" as in search_batch; the formatted lines are what they were.
-        fuzzy=True: unknown words are corrected as in search_batch; the returned BatchLines then carries `corrections` (per
-        query {typed term: used term}) and `corrected_queries` (per query the corrected text or None); the entries keep
-        their keys.  wildcards / max_expansions / patterns: search_batch; the BatchLines then carries `expansions` (per query
-        {pattern: {...}})."""
-        _check_mode(mode)
-        if snippets:
-            self._check_snippets(snippet_tokens)
-        fz = wc = None
-        if fuzzy:
-            self._check_fuzzy()
-            fz = {}
-        if wildcards or patterns is not None:
-            self._check_wildcards(max_expansions)
-            wc = {"parse": bool(wildcards), "explicit": patterns, "limit": int(max_expansions)}
-        ids, qv, ops = self._prepare_ops([q for _, q in numbered_queries], query_embeddings, term_lists, operators, must, must_not,
-                                         phrases, must_phrases, must_not_phrases, proximity, keep=fz, wild=wc)
-        if fz is not None:
-            ops["fuzzy"] = fz
-        if wc is not None:
-            ops["wildcards"] = wc
-        doc, score, _, n = self.final_lists(ids, qv, TOP_K_RETRIEVAL, within=within, mode=mode, dense_k=dense_k, **ops)[:4]
+        fuzzy=True: the returned BatchLines then carries `corrections` (per query {typed term: used term}) and
+        `corrected_queries` (per query the corrected text or None); the entries keep their keys.  wildcards / max_expansions /
+        patterns: the BatchLines then carries `expansions` (per query {pattern: {...}})."""
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions)
+        ids, qv, cond, fz, wc, _ = self._front([q for _, q in numbered_queries], query_embeddings, term_lists, opts,
+                                               Conditions(must, must_not, must_phrases, must_not_phrases), patterns)
+        doc, score, _, n = self._final(ids, qv, TOP_K_RETRIEVAL, None, within, opts, cond, fz, wc, None, parsed=True)
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         lines = BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
         if fz is not None:
-            ids = fz["ids"]
             lines.corrections = fz["corrections"]
             lines.corrected_queries = [_fuzzy.corrected_text(p, c) for p, c in zip(fz["processed"], fz["corrections"])]
         if wc is not None:
-            ids = wc["ids"]
             lines.expansions = wc["expansions"]
         if snippets:
-            lines.passages, lines.row_names = self._snippets(ids, doc, n, snippet_tokens)
+            lines.passages, lines.row_names = self._snippets(self._scored_ids(ids, fz, wc), doc, n, snippet_tokens)
         return lines
 
     def batch_search_to_file(self, queries_path, out_path, query_embeddings=None, term_lists=None, chunk=None):

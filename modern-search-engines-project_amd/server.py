@@ -133,35 +133,32 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             if req.mode not in ("lexical", "hybrid"):
                 return JSONResponse(status_code=400, content={"error": "mode must be 'lexical' or 'hybrid'"})
             qid = req.query_id or uuid.uuid4().hex
-            kw = {} if req.mode == "lexical" else {"mode": req.mode, "dense_k": req.dense_k}
-            if req.sites is not None:
-                kw["within"] = within_sites(req.sites)
-            if req.operators or req.must is not None or req.must_not is not None:
-                kw.update(operators=req.operators, must=req.must, must_not=req.must_not)
-            if req.phrases or req.must_phrases is not None or req.must_not_phrases is not None:
-                kw.update(phrases=req.phrases, must_phrases=req.must_phrases, must_not_phrases=req.must_not_phrases)
+            kw = {} if req.sites is None else {"within": within_sites(req.sites)}
             specs = [p for ps in (req.must_phrases, req.must_not_phrases) for p in ps or () if isinstance(p, NearSpec)]
             wild = req.wildcards or req.patterns is not None
             near = req.proximity or bool(specs)      # a proximity condition the engine cannot hold is the caller's error: 400
+            # (feature on, its keywords, its ValueError is the caller's error): only a feature that is on passes its keywords
+            features = ((req.mode != "lexical", ("mode", "dense_k"), True),
+                        (req.operators or req.must is not None or req.must_not is not None, ("operators", "must", "must_not"), False),
+                        (req.phrases or req.must_phrases is not None or req.must_not_phrases is not None,
+                         ("phrases", "must_phrases", "must_not_phrases"), False),
+                        (near, ("phrases", "proximity", "must_phrases", "must_not_phrases"), True),
+                        (req.snippets, ("snippets", "snippet_tokens"), True), (req.fuzzy, ("fuzzy",), True),
+                        (wild, ("wildcards", "max_expansions", "patterns"), True),
+                        (req.facets, ("facets", "facet_by", "facet_limit"), True))
+            for on, names, _ in features:
+                if on:
+                    kw.update({name: getattr(req, name) for name in names})
             try:
                 if near:
                     from .text import Near
-                    cond = lambda ps: None if ps is None else [Near(p.phrase, p.slop, p.ordered) if isinstance(p, NearSpec) else p
-                                                               for p in ps]
-                    kw.update(phrases=req.phrases, proximity=req.proximity, must_phrases=cond(req.must_phrases),
-                              must_not_phrases=cond(req.must_not_phrases))
-                if req.snippets:
-                    kw.update(snippets=True, snippet_tokens=req.snippet_tokens)
-                if req.fuzzy:
-                    kw.update(fuzzy=True)
-                if wild:
-                    kw.update(wildcards=req.wildcards, max_expansions=req.max_expansions, patterns=req.patterns)
-                if req.facets:
-                    kw.update(facets=True, facet_by=req.facet_by, facet_limit=req.facet_limit)
+                    for name in ("must_phrases", "must_not_phrases"):
+                        if kw[name] is not None:
+                            kw[name] = [Near(p.phrase, p.slop, p.ordered) if isinstance(p, NearSpec) else p for p in kw[name]]
                 docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
                                         terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
-                if req.mode == "lexical" and not near and not req.snippets and not req.fuzzy and not wild and not req.facets:
+                if not any(on and bad_request for on, _, bad_request in features):
                     raise
                 # a dense_k the engine cannot hold; fuzzy / wildcards on an index without term strings; max_expansions outside
                 # 1 .. 16; a required or excluded pattern; a facet_by the engine does not know, a facet_limit outside 1 .. 64
