@@ -253,6 +253,39 @@ __global__ __launch_bounds__(256) void gemm_bucket_kernel(const int4* __restrict
     }
 }
 
+// Wave buffers -> tile maxima: tmax[q][tile] = max(tmax[q][tile], score) over the entries (row, q, score, tile) the emit
+// launches have appended so far, for passes whose kernel stores no maxima (msr_gemm_f32.hip: the 256-query pass over the f32
+// rows).  The caller sets the rows to -inf first; what is not an entry's tile stays -inf, which gemm_kth_kernel skips.  The
+// maximum is taken on the floats' bits: a score with the sign bit clear wins as a signed maximum (every negative float
+// and -inf are negative integers), one with the sign bit set (-0.0 included) as an unsigned minimum (among negative floats
+// the smaller word is the larger float, and every non-negative float is a smaller word still).  Either way the word left
+// behind is the bit pattern of the largest score -- the float the storing kernels write, up to the sign of a zero, which
+// msr_ord32 does not tell apart.  Walking entries again (an earlier segment's) changes nothing, so they are only read:
+// an entry of a tile below tile_lo, the first tile of the segment just emitted, was joined behind its own segment.  One
+// workgroup per wave buffer (a few hundred entries at the headline shape: one trip).  A wave buffer past its
+// capacity has lost entries, and with them maybe tile maxima: the thresholds taken from this matrix are then LOWER than the
+// true ones -- still lower bounds, so out_part stays valid -- and gemm_f32_cand_kernel sends every query of such a call
+// to the gated fallback anyway (wv_count > wv_cap).
+__global__ __launch_bounds__(256) void gemm_entry_tmax_kernel(const int4* __restrict__ wgbuf, int wg_cap,
+                                                               const int32_t* __restrict__ wg_count,   // (per wave)
+                                                               float* __restrict__ tmax, int stride, int tile_lo, int n_tiles,
+                                                               int nq_pad) {
+    const int wg = blockIdx.x;
+    int n = wg_count[wg];
+    if (n > wg_cap) n = wg_cap;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int4 e = wgbuf[(size_t)wg * wg_cap + i];
+        if ((unsigned)e.y >= (unsigned)nq_pad || e.w < tile_lo || e.w >= n_tiles) continue;   // (never trusted as an address)
+        float* p = tmax + (size_t)e.y * stride + e.w;
+        if (e.z >= 0) atomicMax((int*)p, e.z);
+        else atomicMin((unsigned int*)p, (unsigned int)e.z);
+    }
+}
+__global__ __launch_bounds__(256) void gemm_fill_kernel(f32x4* __restrict__ dst, size_t n4, float v) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) dst[i] = (f32x4){v, v, v, v};
+}
+
 // One workgroup per query: (row, score) pairs -> per-document maxima -> documents within `margin` of the k-th largest
 // maximum -> candidate list for the exact f32 rescoring (msr_batch.hip).  Overflow anywhere: cand_n = MSR_SEL_CAP + 1,
 // which rescore_final_kernel reports as out_n = -1 (rerun on the exact path).
@@ -411,6 +444,20 @@ hipError_t msr_gemm_bucket(const void* wvbuf, int wv_cap, const int32_t* wv_coun
                            void* pairs, int32_t* pair_n, hipStream_t stream) {
     gemm_bucket_kernel<<<dim3(2, (unsigned)n_waves), 256, 0, stream>>>((const int4*)wvbuf, wv_cap, wv_count, thr2, (int2*)pairs,
                                                                       GM_PAIR_CAP, pair_n);
+    return hipGetLastError();
+}
+hipError_t msr_gemm_tmax_clear(float* tmax, int stride, int nq_pad, hipStream_t stream) {
+    const size_t n4 = (size_t)nq_pad * stride / 4;
+    if (n4 == 0) return hipSuccess;
+    if (stride % 4 != 0) return hipErrorInvalidValue;
+    gemm_fill_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, stream>>>((f32x4*)tmax, n4, -__builtin_inff());
+    return hipGetLastError();
+}
+hipError_t msr_gemm_entry_tmax(const void* wvbuf, int wv_cap, const int32_t* wv_count, int n_waves, float* tmax, int stride,
+                               int tile_lo, int n_tiles, int nq_pad, hipStream_t stream) {
+    if (tile_lo < 0 || n_tiles > stride) return hipErrorInvalidValue;
+    gemm_entry_tmax_kernel<<<(unsigned)n_waves, 256, 0, stream>>>((const int4*)wvbuf, wv_cap, wv_count, tmax, stride, tile_lo,
+                                                                 n_tiles, nq_pad);
     return hipGetLastError();
 }
 void msr_gemm_set_dbg(int v) { g_gemm_dbg = v; }

@@ -16,9 +16,13 @@
 //
 // No score matrix, no score rows: row tiles (<= 256 rows) are cut at document boundaries, so the k-th largest TILE
 // MAXIMUM is attained by k different documents -- a lower bound of t^.  Pass 1 (every ss-th tile) computes tile maxima
-// only and gives the emission threshold; pass 2 (all tiles) stores the maxima of ALL tiles (a tighter bound afterwards)
-// and appends every (row, query, score) at or above the threshold to a buffer private to the WAVE (scalar counter +
-// lane prefix count, plain 16 B stores: no atomics).  Pass 2 runs in two segments on corpora large enough for it: the tile
+// only and gives the emission threshold; pass 2 (all tiles) appends every (row, query, score, tile) at or above the
+// threshold to a buffer private to the WAVE (scalar counter + lane prefix count, plain 16 B stores: no atomics) and yields
+// the maxima of ALL tiles that can matter (a tighter bound afterwards).  The 128-query kernel and the 16-bit images' data
+// path store every tile's maxima.  The 256-query kernel over the f32 rows stores NONE in pass 2: a tile maximum among a
+// query's k largest is at or above the emission threshold, so it is the score of an entry, and the maxima are joined out of
+// the wave buffers (gemm_entry_tmax_kernel; the argument stands in msr_gemm_f32_pass) -- a third of the epilogue's
+// instructions and 164 MB of stores per pass less.  Pass 2 runs in two segments on corpora large enough for it: the tile
 // maxima of the first raise the threshold of the second (pass_shape below).  Finish: entries above the tighter bound are bucketed per query
 // (msr_gemm_bucket), reduced to distinct documents (gemm_f32_cand_kernel), rescored and sorted.  A query whose entries do
 // not fit anywhere on the way (huge tie groups) raises a device-side gate; the engine's sweeps, always enqueued behind
@@ -462,10 +466,20 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_stream256_kernel(GemmF32Args 
     // Tile maxima, bf16 rows (1024 queries per pass: eight rows of maxima per tile would be 640 MB of writes per pass): the
     // eight waves' maxima of a (tile, query) are joined in LDS (atomic max on order-preserving keys; two sets, by tile
     // parity) and written as ONE row of 256 per tile -- after the first barrier of the NEXT tile, which every wave passes
-    // only with its epilogue behind it.  f32 rows (160 MB per 256-query pass, 1 % of its traffic): every wave stores its own
-    // row as before -- the join costs the pass 1.3 % and saves the transposing kernel the same.  The f16 image of the rows
-    // (launches of several query groups) joins like the bf16 image: the maximum of the same values either way.
+    // only with its epilogue behind it.  f32 rows: every wave stores its own row (the sample pass; joining in LDS was
+    // measured on the emit pass, when it still stored them: it cost the pass 1.3 % and saved the transposing kernel the
+    // same).  The f16 image of the rows (launches of several query groups) joins like the bf16 image: the maximum of the
+    // same values either way.
     constexpr bool JOIN = BF16;
+    // The emit pass over the f32 rows computes and stores NO tile maxima: every tile maximum that can be among a query's k
+    // largest is at or above the emission threshold, so it is the score of an entry in a wave buffer, and the host joins
+    // the maxima from the entries (msr_gemm_entry_tmax; the argument stands at msr_gemm_f32_pass).  The in-lane maximum stays:
+    // the early-out over a block of 16 queries needs it.  The sample pass (no entries) stores its maxima as before.
+#ifdef MSR_DIAG
+    const bool TMAX = !EMIT || JOIN || (a.dbg & 33554432);      // 33554432: the stored maxima and their join, for A/B timing
+#else
+    constexpr bool TMAX = !EMIT || JOIN;
+#endif
     uint32_t* tmx = (uint32_t*)(smem + G2_TMX);
     if (JOIN) tmx[tid] = 0u;                            // (512 threads, 2 x 256 keys; 0 orders below every float)
     auto flush_tmax = [&](int tile_j, int par) {        // wave w: queries 32 w .. + 31 of the tile whose maxima sit in set par
@@ -526,7 +540,8 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_stream256_kernel(GemmF32Args 
     // length = 4): younger than them are the loads of three steps (12) and one block's 8 DMAs = 20, whatever s is.  bf16
     // rows: slot p (K steps 2p, 2p + 1) is reloaded in step 2p + 1 and waited for in step 2p of the next block: younger are
     // the other slot's 4 loads and 8 DMAs = 12.  (Epilogue stores and the inverse-norm DMA only add younger operations:
-    // waiting for fewer than are in flight is always safe.)
+    // waiting for fewer than are in flight is always safe.  No count relies on a store being there: an epilogue that stores
+    // nothing -- the f32 rows' emit pass on a tile without entries -- leaves exactly the operations counted above.)
     static_assert(NMI == 2, "the wait counts below assume 4 row loads per ring slot");
     f32x4 ring[RSLOTS][NMI][2];                          // [slot][fragment][16-byte half]
     auto load_rows = [&](auto slot_c, uint64_t sb, const uint32_t* v, auto off_c) {
@@ -784,15 +799,17 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_stream256_kernel(GemmF32Args 
                     }
                 }
             }
-            float m = cmax;
-            auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-            m = max2_raw(__uint_as_float(s32[0]), __uint_as_float(s32[1]));
-            auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
-            m = max2_raw(__uint_as_float(s16[0]), __uint_as_float(s16[1]));
-            if (JOIN) {
-                if (lg_e == 0) atomicMax(tmx + (it & 1) * 256 + ni * 16 + col_e, ord_key(m));
-            } else {
-                if (lg_e == 0) a.tmax_t[((size_t)jt * 8 + w) * nq_pad + grp * 256 + ni * 16 + col_e] = m;
+            if (TMAX) {
+                float m = cmax;
+                auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+                m = max2_raw(__uint_as_float(s32[0]), __uint_as_float(s32[1]));
+                auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+                m = max2_raw(__uint_as_float(s16[0]), __uint_as_float(s16[1]));
+                if (JOIN) {
+                    if (lg_e == 0) atomicMax(tmx + (it & 1) * 256 + ni * 16 + col_e, ord_key(m));
+                } else {
+                    if (lg_e == 0) a.tmax_t[((size_t)jt * 8 + w) * nq_pad + grp * 256 + ni * 16 + col_e] = m;
+                }
             }
         }
         jt_prev = jt;
@@ -1235,9 +1252,28 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
         if ((err = msr_gemm_tmax(g.tmax_t, n_s, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride, g.tmax_stride, stream)) != hipSuccess) return err;
     }
     if ((err = msr_gemm_kth(g.tmax, n_s, g.tmax_stride, nq, W * G, k, margin, g.thr, g.flag, stream)) != hipSuccess) return err;
+    // The emit launches of the 256-query kernel over the f32 rows store no tile maxima (gemm_stream256_kernel, TMAX): the
+    // maxima the selects below need are recovered from the entries.  thr', thr2 and out_part are each "the j-th largest tile
+    // maximum, j <= k".  A tile whose maximum for query q reaches the emission threshold has its maximum row among q's
+    // entries (the kernel's f16 threshold is rounded DOWN), so with the matrix at -inf wherever no entry speaks:
+    //   raise over [0, T1): with >= k tiles at or above thr, the k largest maxima are all entry maxima -- same value; with
+    //     fewer, the k-th largest true maximum is < thr and the raise keeps thr; here the row is short or its k-th value is
+    //     < thr, and the raise keeps thr as well;
+    //   thr2, out_part over all tiles: the k-th largest maximum of all tiles is >= that of any subset, so >= thr' + margin
+    //     > thr' >= thr: every tile at or above it has entries, in whichever segment (and with one launch, SINGLE_EMIT).
+    // So the three come out bit for bit as from stored maxima (restated in numpy by tests/test_dense_entry_maxima_host.py).
+    // The sample's columns of g.tmax were consumed by the select above: the rows are set to -inf here, in stream order.
+    // A flagged query (thr = +inf) and the padding queries emit nothing: rows of -inf, thresholds that stay +inf.  The
+    // 128-query kernel and the 16-bit images' data path store their maxima and join them as before.
+    bool entry_tmax = W == 256 && !image16;
+#ifdef MSR_DIAG
+    if (g_f32_dbg & 33554432) entry_tmax = false;       // timing experiments: the kernel stores the maxima, joined per launch
+#endif
+    if (entry_tmax && (err = msr_gemm_tmax_clear(g.tmax, g.tmax_stride, W * G, stream)) != hipSuccess) return err;
     // ---- emit pass, segment by segment (pass_shape above): every group's launch over the segment's tiles -- their maxima
     //      (the launch numbers its tiles from 0: tmax_t is joined into the segment's columns of g.tmax before the next launch
-    //      overwrites it) + the entries at or above the threshold, appended to one set of wave buffers --, then the thresholds
+    //      overwrites it; with entry_tmax the segment ends with one walk over the wave buffers instead) + the entries at or
+    //      above the threshold, appended to one set of wave buffers --, then the thresholds
     //      of ALL queries are raised to what the tiles seen so far vouch for.  The refresh never writes g.flag, never lowers a
     //      threshold and leaves the padding queries at +inf (gemm_kth_kernel, raise mode). ----
     a.t_stride = 1;
@@ -1252,8 +1288,12 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
             if (ev && gi == 0 && s == 0 && (err = hipEventRecord(ev[2], stream)) != hipSuccess) return err;
             if ((err = launch_f32(W, true, a, grid, stream, tiled, image16)) != hipSuccess) return err;
             if (ev && gi == 0 && s == shape.n_seg - 1 && (err = hipEventRecord(ev[3], stream)) != hipSuccess) return err;
-            if ((err = msr_gemm_tmax(g.tmax_t, t1 - t0, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride + t0, g.tmax_stride, stream)) != hipSuccess) return err;
+            if (!entry_tmax &&
+                (err = msr_gemm_tmax(g.tmax_t, t1 - t0, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride + t0, g.tmax_stride, stream)) != hipSuccess) return err;
         }
+        // (all groups' entries in one walk; those of earlier segments, tiles below t0, are read again and skipped)
+        if (entry_tmax && (err = msr_gemm_entry_tmax(g.wvbuf, a.wv_cap, g.wv_count, grid * waves, g.tmax, g.tmax_stride, t0,
+                                                     g.n_tiles, W * G, stream)) != hipSuccess) return err;
         if (s + 1 < shape.n_seg &&
             (err = msr_gemm_kth(g.tmax, t1, g.tmax_stride, nq, W * G, k, margin, g.thr, nullptr, stream, __builtin_inff(), 1.0f, true)) != hipSuccess)
             return err;

@@ -417,6 +417,14 @@ hipError_t msr_gemm_kth(const float* tmax, int n, int stride, int nq, int nq_pad
 // fewer than k valid values and padding rows keep what they hold, flag is not written)
 hipError_t msr_gemm_bucket(const void* wvbuf, int wv_cap, const int32_t* wv_count, int n_waves, const float* thr2,
                            void* pairs, int32_t* pair_n, hipStream_t stream);
+// Tile maxima from the emitted entries, for a pass whose kernel stores none: _clear sets rows 0 .. nq_pad - 1 of tmax
+// ([.][stride], stride a multiple of 4) to -inf; _entry_tmax joins the score of every entry (row, q, score, tile) of the wave
+// buffers into tmax[q][tile] (q < nq_pad, tile_lo <= tile < n_tiles <= stride; tile_lo: entries of tiles below it were
+// joined by an earlier call) by an atomic maximum -- idempotent, so tile_lo = 0 is always right.  What gemm_kth then reads
+// there: the true maximum of every tile that has an entry, -inf elsewhere.
+hipError_t msr_gemm_tmax_clear(float* tmax, int stride, int nq_pad, hipStream_t stream);
+hipError_t msr_gemm_entry_tmax(const void* wvbuf, int wv_cap, const int32_t* wv_count, int n_waves, float* tmax, int stride,
+                               int tile_lo, int n_tiles, int nq_pad, hipStream_t stream);
 void msr_bm25_set_dbg(int v);       // honoured by -DMSR_DIAG builds only
 void msr_gemm_set_dbg(int v);       // honoured by -DMSR_DIAG builds only
 // dst[r] = bf16(src[r] * inv_norm[r]) (inv_norm null: 1), rows n_rows .. n_pad - 1 zero
