@@ -5,12 +5,14 @@ two-stage path and write `qnum<TAB>rank<TAB>url<TAB>score` lines, like POST /api
 is generated: documents are bags of words from a vocabulary that contains the query words, indexed with
 msretr.index_build (the reference's BM25.build_index semantics) and given random unit-norm chunk embeddings.
 
-    python examples/run_queries_txt.py [--fuzzy] [--wildcards] [queries.txt] [out.txt]
+    python examples/run_queries_txt.py [--fuzzy] [--wildcards] [--collapse-duplicates] [queries.txt] [out.txt]
 
 --fuzzy: words the vocabulary lacks are replaced by their nearest term (Retriever.batch_search(fuzzy=True)) and every
 correction is printed.
 --wildcards: `bibliothek*`, `*bibliothek`, `t?bingen` are expanded over the vocabulary
 (Retriever.batch_search(wildcards=True)) and every expansion is printed.
+--collapse-duplicates: every tenth page of the crawl is a mirror of the page before it under another host; near-duplicate
+pages are shown once (Retriever.batch_search(collapse_duplicates=True)) and the number of rows dropped per query is printed.
 """
 import os
 import sys
@@ -25,7 +27,7 @@ DEFAULT_QUERIES = ["tübingen attractions", "food and drinks", "university tuebi
                    "castle hohentubingen history", "botanical garden opening hours"]     # shape of queries.txt:1-5
 
 
-def synthetic_crawl(n_docs=3000, seed=7, queries=DEFAULT_QUERIES):
+def synthetic_crawl(n_docs=3000, seed=7, queries=DEFAULT_QUERIES, mirrors=False):
     rng = np.random.default_rng(seed)
     words = sorted({w for q in queries for w in simple_tokenize(preprocess_query(q))})
     filler = [f"wort{i}" for i in range(400)]
@@ -40,11 +42,13 @@ def synthetic_crawl(n_docs=3000, seed=7, queries=DEFAULT_QUERIES):
         toks = [vocab[j] for j in rng.choice(len(vocab), size=n, p=p)]
         if rng.random() < 0.85:
             toks[0] = "tübingen"
+        if mirrors and i % 10 == 9:
+            toks = list(tokens[-1])                          # the page before, once more, under another host
         tokens.append(toks)
         urls.append(f"https://www.site{int(d) % 53}.de/page/{int(d)}" + ("?ref=1" if d % 19 == 0 else ""))
         titles.append(f"Seite {int(d)}")
         texts.append(" ".join(toks))
-    ix = bm25_index_from_tokens(doc_ids, tokens)
+    ix = bm25_index_from_tokens(doc_ids, tokens, keep_tokens=mirrors)     # (the collapse reads the forward index)
     ix.urls, ix.titles, ix.texts = urls, titles, texts
     cnt = rng.integers(1, 9, size=len(doc_ids))
     ix.doc_off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32)
@@ -65,14 +69,16 @@ def fake_encoder(dim=768):
 
 def main():
     from msretr.retriever import Retriever
-    argv = [a for a in sys.argv[1:] if a not in ("--fuzzy", "--wildcards")]
+    argv = [a for a in sys.argv[1:] if a not in ("--fuzzy", "--wildcards", "--collapse-duplicates")]
     fuzzy, wildcards = "--fuzzy" in sys.argv[1:], "--wildcards" in sys.argv[1:]
+    collapse = "--collapse-duplicates" in sys.argv[1:]
     qfile = argv[0] if len(argv) > 0 else None
     out = argv[1] if len(argv) > 1 else "batch_search_results.txt"
     queries = read_queries_file(qfile) if qfile else [(str(i + 1), q) for i, q in enumerate(DEFAULT_QUERIES)]
-    ix = synthetic_crawl()
+    ix = synthetic_crawl(mirrors=collapse)
     rt = Retriever(embedder=fake_encoder(), indexer=ix, tokenizer=simple_tokenize, max_queries=8, max_k=1000)
-    res = rt.batch_search(queries, fuzzy=fuzzy, wildcards=wildcards)     # the reference's `results` list (dicts built on access) ...
+    # the reference's `results` list (dicts built on access) ...
+    res = rt.batch_search(queries, fuzzy=fuzzy, wildcards=wildcards, collapse_duplicates=collapse)
     res.write(out)                                  # ... and all formatted lines in one native call
     print(f"{len(queries)} queries -> {len(res)} result lines in {out}")
     for (qn, _), text in zip(queries, res.corrected_queries or ()):
@@ -81,6 +87,8 @@ def main():
     for (qn, _), exp in zip(queries, res.expansions or ()):
         for pattern, info in exp.items():
             print(f"query {qn}: {pattern} -> {', '.join(info['terms']) or 'nothing'} ({info['total']} matches)")
+    for (qn, _), dropped in zip(queries, res.collapsed or ()):
+        print(f"query {qn}: {dropped} near-duplicate rows collapsed")
     rt.engine.close()
 
 

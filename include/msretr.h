@@ -44,7 +44,8 @@ extern "C" {
                                      that lacks them fails to load by symbol): msr_bind_vocab, msr_fuzzy_scratch_bytes,
                                      msr_fuzzy_terms; msr_debug_chunk_layout; msr_dense_pass_info;
                                      msr_wildcard_scratch_bytes, msr_wildcard_terms; msr_facet_table, msr_bind_facet,
-                                     msr_facet_scratch_bytes, msr_facet_counts */
+                                     msr_facet_scratch_bytes, msr_facet_counts; msr_doc_signatures, msr_bind_signatures,
+                                     msr_collapse_scratch_bytes, msr_collapse_duplicates */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -62,6 +63,9 @@ extern "C" {
 #define MSR_WILD_MAX_PATTERNS 1024 /* msr_wildcard_terms: most patterns of one call */
 #define MSR_WILD_MAX_LIMIT 16      /* msr_wildcard_terms: most matches returned per pattern */
 #define MSR_FACET_MAX_LIMIT 64     /* msr_facet_counts: most facet values returned per row */
+#define MSR_SIG_WORDS 64           /* msr_doc_signatures: 32-bit words of a document's min-hash signature */
+#define MSR_SIG_MAX_SHINGLE 8      /* msr_doc_signatures: the widest shingle, in tokens */
+#define MSR_COLLAPSE_MAX_CAND 1024 /* msr_collapse_duplicates: the longest fused list (config.py:13 TOP_K_RETRIEVAL = 1000) */
 #define MSR_MERGE_MAX_ENTRIES 8192 /* msr_merge_topk(_payload): pow2ceil(n_parts) * max(64, pow2ceil(k)) may not exceed this */
 
 typedef enum msr_status {
@@ -655,6 +659,53 @@ int msr_diversify(msr_engine* e, int32_t n_queries, const int32_t* fused_doc, co
                   const double* fused_orig, const int32_t* fused_chunk, const int32_t* fused_n, int32_t max_cand,
                   int32_t top_k, double relevance_threshold, int32_t diversify, int32_t* out_doc, double* out_score,
                   double* out_orig, int32_t* out_chunk, int32_t* out_n, void* stream);
+
+/* Near-duplicate collapse: min-hash signatures of the forward index's documents, and the collapse of
+ * each query's fused list by them, between msr_rerank_fuse and msr_diversify.  All arithmetic is uint32, mod 2^32.
+ *     fmix(x):  x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16      (murmur3's finaliser)
+ *     shingles of a document with stream s[0 .. n), n >= 1, width w:  L = min(w, n), starts a = 0 .. n - L,
+ *         h(a) = fmix(x ^ L)  with  x = 0;  for j < L: x = (x ^ (s[a + j] + 1)) * 0x01000193
+ *       (a shingle never uses a token of a neighbouring document; a document shorter than w is ONE shingle of all its tokens)
+ *     sig[k] = min over a of (A[k] h(a) + B[k]),  A[k] = fmix(2 k + 1) | 1,  B[k] = fmix(2 k + 2),  k < MSR_SIG_WORDS
+ *     a document with n == 0 has the EMPTY signature: all words 0xFFFFFFFF
+ *     matches(x, y) = |{k : sig_x[k] == sig_y[k]}|  (matches / 64 estimates the Jaccard overlap of the two shingle sets)
+ *     dup(x, y)  iff  matches(x, y) >= min_matches and neither signature is EMPTY
+ * Collapse of one query's list, slots 0 .. n - 1 in fused order, greedy by leader: slot i is PASSIVE when its document index
+ * lies outside the signature table, its signature is EMPTY, or a doc-domain table is bound (msr_bind_doc_domains) and holds a
+ * negative id for it or does not reach it (msr_diversify rejects that document: it must not swallow a page that can be
+ * shown).  Passive slots are always kept, never lead, never drop.  Any other slot i is DROPPED iff some kept, non-passive
+ * slot j < i has dup(i, j); its leader is the smallest such j.  A dropped row leads nothing: A ~ B, B ~ C, A !~ C keeps A and
+ * C.  The kept rows, in order, are the output list.
+ *
+ * msr_doc_signatures: out_sig [d1 - d0][MSR_SIG_WORDS] (device) <- the signatures of documents [d0, d1) of the bound forward
+ *   index with shingle width `shingle`.  Only enqueues (one kernel); no engine scratch, no atomics; nothing outside the
+ *   rows is written; repeated calls give the same bytes.  MSR_ERR_NOT_BOUND without tokens; MSR_ERR_INVALID, nothing
+ *   launched, unless 0 <= d0 <= d1 <= n_docs and 1 <= shingle <= MSR_SIG_MAX_SHINGLE, and for a NULL out_sig with d1 > d0.
+ *   d0 == d1 succeeds without a launch.
+ * msr_bind_signatures: sig [n_docs][MSR_SIG_WORDS], a device pointer, caller-owned and borrowed like the facet table's; n_docs
+ *   must equal the bound postings' count (MSR_ERR_INVALID; MSR_ERR_NOT_BOUND without postings).  NULL unbinds.  msr_unbind
+ *   and msr_bind_postings drop the binding.  The table is not read by the bind.
+ * msr_collapse_scratch_bytes: bytes of caller scratch one msr_collapse_duplicates call needs (the dup bit matrix:
+ *   n_queries * max_cand * ceil(max_cand / 32) words, rounded up to 16 bytes); MSR_ERR_INVALID (negative) for n_queries < 0
+ *   or max_cand outside [1, MSR_COLLAPSE_MAX_CAND].  The engine keeps none.
+ * msr_collapse_duplicates: fused_* [n_queries][max_cand] / fused_n [n_queries] as msr_rerank_fuse returns them; fused_n[q] is
+ *   clamped to [0, max_cand] on the device.  out_* have the shape and padding of msr_diversify's outputs (-1 / -inf / 0.0 /
+ *   -1 past out_n[q]) and feed msr_diversify unchanged.  out_drop_doc / out_drop_leader / out_drop_matches
+ *   [n_queries][max_cand] int32: in the order they were dropped, the dropped document, its leader's DOCUMENT index and
+ *   matches(dropped, leader); -1 / -1 / 0 past out_drop_n[q].  No output may alias an input.  Two kernels over the scratch,
+ *   only enqueued, no global atomic, no memset, nothing to zero beforehand; repeated calls give the same bytes.  Refused
+ *   before any launch, outputs untouched: MSR_ERR_NOT_BOUND without bound signatures; MSR_ERR_INVALID for min_matches
+ *   outside [1, MSR_SIG_WORDS], max_cand outside [1, MSR_COLLAPSE_MAX_CAND], n_queries < 0, a NULL pointer with n_queries >
+ *   0, scratch_bytes below msr_collapse_scratch_bytes or a scratch that is not 16-byte aligned.  n_queries == 0 succeeds and
+ *   launches nothing. */
+int msr_doc_signatures(msr_engine* e, int64_t d0, int64_t d1, int32_t shingle, uint32_t* out_sig, void* stream);
+int msr_bind_signatures(msr_engine* e, const uint32_t* sig, int64_t n_docs, void* stream);
+int64_t msr_collapse_scratch_bytes(int32_t n_queries, int32_t max_cand);
+int msr_collapse_duplicates(msr_engine* e, int32_t n_queries, const int32_t* fused_doc, const double* fused_score,
+                            const double* fused_orig, const int32_t* fused_chunk, const int32_t* fused_n, int32_t max_cand,
+                            int32_t min_matches, int32_t* out_doc, double* out_score, double* out_orig, int32_t* out_chunk,
+                            int32_t* out_n, int32_t* out_drop_doc, int32_t* out_drop_leader, int32_t* out_drop_matches,
+                            int32_t* out_drop_n, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* HOST function (every pointer is host memory; no device is touched): the batch result lines of search_api.py:290,
  * "{query_num}\t{rank}\t{url}\t{score:.3f}\n", for n_queries final lists in one call.  Query q's number is the bytes

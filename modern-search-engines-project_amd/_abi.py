@@ -28,6 +28,9 @@ MSR_WILD_MAX_LEN = 32
 MSR_WILD_MAX_PATTERNS = 1024
 MSR_WILD_MAX_LIMIT = 16
 MSR_FACET_MAX_LIMIT = 64
+MSR_SIG_WORDS = 64
+MSR_SIG_MAX_SHINGLE = 8
+MSR_COLLAPSE_MAX_CAND = 1024
 MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
 
 
@@ -102,6 +105,11 @@ _SIGNATURES = {
     "msr_facet_scratch_bytes": (C.c_int64, [_P, C.c_int32]),
     "msr_facet_counts": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int64,
                                    _P, C.c_int64, _P]),
+    "msr_doc_signatures": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, _P, _P]),
+    "msr_bind_signatures": (C.c_int, [_P, _P, C.c_int64, _P]),
+    "msr_collapse_scratch_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "msr_collapse_duplicates": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, C.c_int64, _P]),
     "msr_combine_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, C.c_int64, _P]),
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,

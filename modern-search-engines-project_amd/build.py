@@ -39,6 +39,7 @@ UNITS = {
     "msr_fuzzy.hip": [],
     "msr_wildcard.hip": [],
     "msr_facet.hip": [],
+    "msr_dedup.hip": [],
     "msr_encoder.hip": ["-ffp-contract=off"],
     "msr_enc_attention_long.hip": ["-ffp-contract=off"],
     "msr_format.cpp": [],             # host-only C++ (result-line formatter)

@@ -43,6 +43,8 @@ struct msr_engine {
     bool have_vocab = false;
     FacetTable facet{};                    // msr_bind_facet (borrowed): the facet table of the bound postings' documents (K17)
     bool have_facet = false;
+    const uint32_t* sig = nullptr;         // msr_bind_signatures (borrowed): [sig_n][MSR_SIG_WORDS] min-hash signatures (K18)
+    int64_t sig_n = 0;
     DenseIndex dense{};
     bool have_chunks = false;
     const int32_t* url_group = nullptr;
@@ -169,6 +171,7 @@ static void drop_facet(msr_engine* e) {
 static void drop_postings(msr_engine* e) {
     e->have_postings = e->have_tokens = false;
     drop_facet(e);
+    e->sig = nullptr; e->sig_n = 0;
     e->tok_off = nullptr; e->tok_ids = nullptr; e->n_tokens = 0;
     drop_vocab(e);
     e->bm25 = Bm25Index{};
@@ -1064,6 +1067,76 @@ extern "C" int msr_facet_counts(msr_engine* e, int32_t n_rows, const int32_t* an
     HIP_TRY(e, msr_facet_counts_run(e->bm25, e->facet, n_rows, any_off, any_terms, base_bits, n_base, base_stride, row_base, limit,
                                     out_hits, out_n_values_hit, out_top_value, out_top_count, out_counts, count_stride, scratch,
                                     (hipStream_t)stream));
+    return MSR_OK;
+}
+
+// ---- K18: near-duplicate collapse (msr_dedup.hip) -----------------------------------------------------------------------------
+extern "C" int msr_doc_signatures(msr_engine* e, int64_t d0, int64_t d1, int32_t shingle, uint32_t* out_sig, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings || !e->have_tokens)
+        return fail(e, MSR_ERR_NOT_BOUND, "msr_doc_signatures: tokens not bound (msr_bind_tokens: the index has no forward index)");
+    if (d0 < 0 || d1 < d0 || d1 > e->bm25.n_docs)
+        return fail(e, MSR_ERR_INVALID, "msr_doc_signatures: bad range [%lld, %lld) of %lld documents", (long long)d0, (long long)d1,
+                    (long long)e->bm25.n_docs);
+    if (shingle < 1 || shingle > MSR_SIG_MAX_SHINGLE)
+        return fail(e, MSR_ERR_INVALID, "msr_doc_signatures: shingle %d outside [1, MSR_SIG_MAX_SHINGLE = %d]", shingle,
+                    MSR_SIG_MAX_SHINGLE);
+    if (d1 > d0 && !out_sig) return fail(e, MSR_ERR_INVALID, "msr_doc_signatures: bad argument (out_sig is NULL)");
+    if (d0 == d1) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_doc_signatures_run(e->tok_off, e->tok_ids, d0, d1, shingle, out_sig, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+extern "C" int msr_bind_signatures(msr_engine* e, const uint32_t* sig, int64_t n_docs, void* stream) {
+    (void)stream;
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_bind_signatures: postings not bound");
+    if (!sig) {
+        e->sig = nullptr; e->sig_n = 0;
+        return MSR_OK;
+    }
+    if (n_docs != e->bm25.n_docs)
+        return fail(e, MSR_ERR_INVALID, "msr_bind_signatures: n_docs %lld differs from bound postings (%lld)", (long long)n_docs,
+                    (long long)e->bm25.n_docs);
+    e->sig = sig;
+    e->sig_n = n_docs;
+    return MSR_OK;
+}
+
+extern "C" int64_t msr_collapse_scratch_bytes(int32_t n_queries, int32_t max_cand) {
+    if (n_queries < 0 || max_cand < 1 || max_cand > MSR_COLLAPSE_MAX_CAND) return MSR_ERR_INVALID;
+    return msr_collapse_bytes(n_queries, max_cand);
+}
+
+extern "C" int msr_collapse_duplicates(msr_engine* e, int32_t n_queries, const int32_t* fused_doc, const double* fused_score,
+                                       const double* fused_orig, const int32_t* fused_chunk, const int32_t* fused_n,
+                                       int32_t max_cand, int32_t min_matches, int32_t* out_doc, double* out_score,
+                                       double* out_orig, int32_t* out_chunk, int32_t* out_n, int32_t* out_drop_doc,
+                                       int32_t* out_drop_leader, int32_t* out_drop_matches, int32_t* out_drop_n, void* scratch,
+                                       int64_t scratch_bytes, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->sig) return fail(e, MSR_ERR_NOT_BOUND, "msr_collapse_duplicates: signatures not bound (msr_bind_signatures)");
+    if (min_matches < 1 || min_matches > MSR_SIG_WORDS)
+        return fail(e, MSR_ERR_INVALID, "msr_collapse_duplicates: min_matches %d outside [1, MSR_SIG_WORDS = %d]", min_matches,
+                    MSR_SIG_WORDS);
+    if (max_cand < 1 || max_cand > MSR_COLLAPSE_MAX_CAND)
+        return fail(e, MSR_ERR_INVALID, "msr_collapse_duplicates: max_cand %d outside [1, MSR_COLLAPSE_MAX_CAND = %d]", max_cand,
+                    MSR_COLLAPSE_MAX_CAND);
+    if (n_queries < 0) return fail(e, MSR_ERR_INVALID, "msr_collapse_duplicates: bad argument (n_queries=%d)", n_queries);
+    if (n_queries > 0 && (!fused_doc || !fused_score || !fused_orig || !fused_chunk || !fused_n || !out_doc || !out_score ||
+                          !out_orig || !out_chunk || !out_n || !out_drop_doc || !out_drop_leader || !out_drop_matches || !out_drop_n))
+        return fail(e, MSR_ERR_INVALID, "msr_collapse_duplicates: null argument");
+    const int64_t need = msr_collapse_bytes(n_queries, max_cand);
+    if (scratch_bytes < need || (need > 0 && (!scratch || (uintptr_t)scratch % 16)))
+        return fail(e, MSR_ERR_INVALID,
+                    "msr_collapse_duplicates: scratch of %lld bytes, %lld needed (msr_collapse_scratch_bytes; 16-byte aligned)",
+                    (long long)scratch_bytes, (long long)need);
+    if (n_queries == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_collapse_run(e->sig, e->sig_n, e->doc_domain, e->doc_domain_n, n_queries, fused_doc, fused_score, fused_orig,
+                                fused_chunk, fused_n, max_cand, min_matches, out_doc, out_score, out_orig, out_chunk, out_n,
+                                out_drop_doc, out_drop_leader, out_drop_matches, out_drop_n, scratch, (hipStream_t)stream));
     return MSR_OK;
 }
 

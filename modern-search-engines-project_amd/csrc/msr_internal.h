@@ -237,6 +237,16 @@ hipError_t msr_facet_counts_run(const Bm25Index& ix, const FacetTable& f, int n_
                                 const int32_t* row_base, int limit, int32_t* out_hits, int32_t* out_n_values_hit,
                                 int32_t* out_top_value, int32_t* out_top_count, int32_t* out_counts, int64_t count_stride,
                                 void* scratch, hipStream_t stream);
+// K18 (msr_dedup.hip): min-hash signatures of the forward index and the collapse of fused lists by them (see msretr.h;
+// arguments checked by the caller).  doc_domain nullable; scratch: msr_collapse_bytes(n_queries, max_cand) bytes.
+hipError_t msr_doc_signatures_run(const int64_t* tok_off, const int32_t* tok_ids, int64_t d0, int64_t d1, int shingle,
+                                  uint32_t* out, hipStream_t stream);
+int64_t msr_collapse_bytes(int n_queries, int max_cand);
+hipError_t msr_collapse_run(const uint32_t* sig, int64_t n_sig, const int32_t* doc_domain, int64_t n_domain, int n_queries,
+                            const int32_t* f_doc, const double* f_score, const double* f_orig, const int32_t* f_chunk,
+                            const int32_t* f_n, int max_cand, int min_matches, int32_t* out_doc, double* out_score,
+                            double* out_orig, int32_t* out_chunk, int32_t* out_n, int32_t* drop_doc, int32_t* drop_leader,
+                            int32_t* drop_matches, int32_t* drop_n, void* scratch, hipStream_t stream);
 hipError_t msr_combine_sets_run(int64_t n_docs, int n_rows, const int32_t* and_off, const int32_t* and_rows,
                                 const int32_t* not_off, const int32_t* not_rows, const uint32_t* in_bits, int n_in,
                                 int64_t in_stride, uint32_t* out_bits, int64_t out_stride, hipStream_t stream);

@@ -537,6 +537,64 @@ class DeviceEngine:
                 all_counts[a:b] = host[2 * n + 2 * n * limit:].reshape(n, V)
         return (hits, n_hit, top_value, top_count) + ((all_counts,) if counts else ())
 
+    # ------------------------------------------------------------------ near-duplicate collapse (msr_collapse_duplicates, DESIGN K18)
+    def doc_signatures(self, shingle=4, d0=0, d1=None, out=None):
+        """The min-hash signatures of documents [d0, d1) of the bound forward index (msr_doc_signatures) -> device tensor int32
+        [d1 - d0, MSR_SIG_WORDS] (the bits of the uint32 words).  shingle: 1 .. MSR_SIG_MAX_SHINGLE tokens.  out: write into
+        the rows of this tensor instead.  Only enqueues."""
+        d1 = self.index.n_docs if d1 is None else int(d1)
+        d0 = int(d0)
+        if out is None:
+            out = torch.empty((max(d1 - d0, 0), _abi.MSR_SIG_WORDS), dtype=torch.int32, device=self.device)
+        self._check(self.lib.msr_doc_signatures(self.handle, d0, d1, int(shingle), _ptr(out) if out.numel() else C.c_void_p(0),
+                                                self._stream()))
+        return out
+
+    @property
+    def has_signatures(self):
+        """True while a signature table is bound (bind_signatures); a rebind drops it with the postings."""
+        return "doc_sig" in self._t
+
+    def bind_signatures(self, sig):
+        """Bind the signatures of ALL bound documents (doc_signatures(); int32 device tensor [N, MSR_SIG_WORDS]) for
+        collapse_duplicates.  The tensor lives with the postings' tensors: rebind drops it.  None unbinds."""
+        if sig is None:
+            self._check(self.lib.msr_bind_signatures(self.handle, C.c_void_p(0), 0, self._stream()))
+            self._t.pop("doc_sig", None)
+            return
+        if sig.dtype != torch.int32 or sig.dim() != 2 or sig.shape[1] != _abi.MSR_SIG_WORDS or sig.device != self.device:
+            raise ValueError(f"bind_signatures: an int32 [N, {_abi.MSR_SIG_WORDS}] tensor on {self.device} is needed")
+        sig = sig.contiguous()
+        n = int(sig.shape[0])
+        self._check(self.lib.msr_bind_signatures(self.handle, _ptr(sig) if n else C.c_void_p(0), n, self._stream()))
+        if n:
+            self._t["doc_sig"] = sig
+        else:
+            self._t.pop("doc_sig", None)
+
+    def collapse_duplicates(self, fused, min_matches):
+        """fused = (doc, score, orig, chunk, n, ...) of rerank / rerank_fuse -> ((doc, score f64, orig f64, chunk, n), (drop_doc,
+        drop_leader, drop_matches, drop_n)): every query's list without the rows whose signature agrees with an earlier kept
+        row's in at least min_matches (1 .. 64) of 64 words -- the first tuple feeds diversify unchanged -- and, in drop
+        order, the dropped documents, the document that swallowed each and their match counts (int32 [Q, M] / [Q]).  The
+        bound doc-domain table is read: a document it rejects neither drops nor leads.  Only enqueues."""
+        if not self.has_signatures:
+            raise _abi.MsrError(-2, "collapse_duplicates: no signatures bound (bind_signatures)")
+        doc, score, orig, chunk, n = [x.contiguous() for x in fused[:5]]
+        Q, M = int(doc.shape[0]), int(doc.shape[1])
+        mk = lambda dt: torch.empty((Q, M), dtype=dt, device=self.device)
+        o_doc, o_score, o_orig, o_chunk = mk(torch.int32), mk(torch.float64), mk(torch.float64), mk(torch.int32)
+        d_doc, d_lead, d_m = mk(torch.int32), mk(torch.int32), mk(torch.int32)
+        o_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        d_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
+        need = int(self.lib.msr_collapse_scratch_bytes(Q, M))
+        scratch = torch.empty((max(need, 16) // 8,), dtype=torch.int64, device=self.device)
+        self._check(self.lib.msr_collapse_duplicates(
+            self.handle, Q, _ptr(doc), _ptr(score), _ptr(orig), _ptr(chunk), _ptr(n), M, int(min_matches), _ptr(o_doc),
+            _ptr(o_score), _ptr(o_orig), _ptr(o_chunk), _ptr(o_n), _ptr(d_doc), _ptr(d_lead), _ptr(d_m), _ptr(d_n), _ptr(scratch),
+            max(need, 0), self._stream()))
+        return (o_doc, o_score, o_orig, o_chunk, o_n), (d_doc, d_lead, d_m, d_n)
+
     def phrase_sets(self, must_phrases, must_not_phrases=None, must=None, must_not=None, within=None):
         """Per-query document sets of phrase search, built on the device: query q's set is the documents of within[q] that hold
         every term of must[q], none of must_not[q] (term_sets' rules), EVERY phrase of must_phrases[q] and NO phrase of

@@ -112,16 +112,19 @@ class Results(list):
     patterns were expanded to: `expansions` {pattern: {"terms": [...], "total": n, ...}} (wildcard.expand; empty: no
     pattern) -- and, with facets=True (DESIGN K17), what the whole match set holds: `hits` (pages that match at all, None
     without facets), `facets` ([{"value": name, "count": n}, ...], the values with the most matching pages first) and
-    `facet_values` (the number of distinct values hit).  Equal to the plain list of its rows."""
+    `facet_values` (the number of distinct values hit) -- and, with collapse_duplicates=True (DESIGN K18), `collapsed`: the
+    number of near-duplicate rows dropped from the list (the rows that swallowed them carry "duplicates").  Equal to the plain
+    list of its rows."""
     corrections = {}
     corrected_query = None
     expansions = {}
     hits = None
     facets = []
     facet_values = 0
+    collapsed = 0
 
     def __init__(self, rows=(), corrections=None, corrected_query=None, expansions=None, hits=None, facets=None,
-                 facet_values=0):
+                 facet_values=0, collapsed=0):
         super().__init__(rows)
         self.corrections = dict(corrections or {})
         self.corrected_query = corrected_query
@@ -129,3 +132,4 @@ class Results(list):
         self.hits = None if hits is None else int(hits)
         self.facets = list(facets or [])
         self.facet_values = int(facet_values)
+        self.collapsed = int(collapsed)

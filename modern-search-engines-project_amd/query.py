@@ -7,13 +7,14 @@
 Retriever (search / search_batch / batch_search, after preprocess_query) and BM25.search go through parse_queries; what the
 conditions and patterns then cost on the device is theirs.  Pure Python: nothing here needs a GPU.
 """
+import math
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
 from . import facets as _facets
-from ._abi import MSR_PROX_MAX_SPAN, MSR_WILD_MAX_LIMIT
+from ._abi import MSR_PROX_MAX_SPAN, MSR_SIG_WORDS, MSR_WILD_MAX_LIMIT
 from .text import Near, parse_operators, parse_phrases, parse_proximity
 from .wildcard import parse_wildcards
 
@@ -85,7 +86,20 @@ class SearchOptions:
     "domain" (the rows' "domain" key); anything else raises ValueError.  The terms counted are the ones scored: after
     fuzzy correction and wildcard expansion.  mode="hybrid" counts the LEXICAL matches only (a dense-only hit is in no
     count).  A query of unknown words has 0 hits and no facets.  The table of facet_by is bound lazily per index and again
-    after update_index.  An index without URLs raises ValueError."""
+    after update_index.  An index without URLs raises ValueError.
+    collapse_duplicates=True (DESIGN K18): pages that differ in URL and not in content -- `www.` against the bare host,
+    `http` against `https`, print views, mirrors -- are shown once.  Every document has a min-hash signature of 64 words over
+    the 4-token shingles of its indexed stream (ONE DeviceEngine.doc_signatures call per index, bound lazily and again after
+    update_index); between fuse and diversification ONE DeviceEngine.collapse_duplicates call per chunk of queries walks each
+    fused list in rank order and drops a row whose signature agrees with an earlier KEPT row's in at least
+    ceil(duplicate_threshold * 64) words (the share of equal words estimates the Jaccard overlap of the two pages' shingle
+    sets; duplicate_threshold in (0, 1], ValueError otherwise; default 0.9 -> 58 of 64).  A dropped row leads nothing: of
+    A ~ B ~ C with A unlike C, A and C stay.  A page the response models reject and a page without tokens neither drop nor
+    lead.  Each query's result is then a fuzzy.Results list whose `collapsed` is the number of rows dropped, and every row
+    that swallowed one gains "duplicates": [{"doc_id", "url", "title", "similarity": equal words / 64}, ...] in the order
+    they were dropped; rows that swallowed nothing lack the key.  The scores are unchanged, diversification then works on
+    the collapsed list, matched_by and snippets are those of the rows that stay, and facets=True still counts ALL matches,
+    copies included.  Needs an index with a forward index (MsrError)."""
     mode: str = "lexical"
     dense_k: int = 100
     operators: bool = False
@@ -99,11 +113,18 @@ class SearchOptions:
     facets: bool = False
     facet_by: str = "host"
     facet_limit: int = 10
+    collapse_duplicates: bool = False
+    duplicate_threshold: float = 0.9
+
+    @property
+    def min_matches(self):
+        """Equal signature words (of MSR_SIG_WORDS) from which two pages are duplicates: ceil(duplicate_threshold * 64)."""
+        return int(math.ceil(float(self.duplicate_threshold) * MSR_SIG_WORDS))
 
     def check(self, patterns=False, int_types=(int, np.integer)):
         """ValueError unless the values are in range: the mode; and of the features that are on, snippet_tokens of 1 ..
         MSR_PROX_MAX_SPAN, the facet key and limit (facets.check_options), max_expansions of 1 .. MSR_WILD_MAX_LIMIT
-        (patterns: the call has explicit patterns, which need it like wildcards=True).  int_types: what counts as a whole
+        (patterns: the call has explicit patterns, which need it like wildcards=True), duplicate_threshold in (0, 1].  int_types: what counts as a whole
         number (BM25.search takes no numpy integer)."""
         whole = lambda v, top: not isinstance(v, bool) and isinstance(v, int_types) and 1 <= int(v) <= top
         if self.mode not in MODES:
@@ -114,6 +135,10 @@ class SearchOptions:
             _facets.check_options(self.facet_by, self.facet_limit)
         if (self.wildcards or patterns) and not whole(self.max_expansions, MSR_WILD_MAX_LIMIT):
             raise ValueError(f"max_expansions must be 1 .. MSR_WILD_MAX_LIMIT = {MSR_WILD_MAX_LIMIT} (got {self.max_expansions!r})")
+        if self.collapse_duplicates:
+            t = self.duplicate_threshold
+            if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not 0.0 < float(t) <= 1.0:
+                raise ValueError(f"duplicate_threshold must be in (0, 1] (got {t!r})")
 
 
 @dataclass(frozen=True)

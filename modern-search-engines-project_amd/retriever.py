@@ -28,6 +28,7 @@ TOP_K_RETRIEVAL = 1000     # config.py:13
 TOP_K_RERANKING = 100      # config.py:14
 RERANK_MAX_CHUNKS = 10     # reranker_api.py:58
 DENSE_K = 100              # mode="hybrid": dense candidates that join the BM25 list (default)
+SIGNATURE_SHINGLE = 4      # collapse_duplicates=True: tokens per shingle of the documents' min-hash signatures (DESIGN K18)
 MATCHED_BY = {1: "lexical", 2: "dense", 3: "both"}       # msr_union_candidates' out_src
 
 
@@ -279,9 +280,12 @@ class Retriever:
         """What the options need, checked before any device work: values in range (SearchOptions.check; patterns: the call
         has explicit patterns) and, of this index and engine, what the features that are on read.  snippets: the spans of a
         custom tokenizer (ValueError), a forward index and texts (MsrError, as phrase search); facets: postings and URLs;
-        fuzzy, wildcards and patterns: term strings (ValueError)."""
+        fuzzy, wildcards and patterns: term strings (ValueError); collapse_duplicates: a forward index (MsrError)."""
         from ._abi import MsrError
         opts.check(patterns)
+        if opts.collapse_duplicates and not self.engine.has_tokens:
+            raise MsrError(-2, "collapse_duplicates: the index has no forward index (tok_off / tok_ids): build it with "
+                               "keep_tokens=True or attach the token streams with index_build.attach_tokens, then update_index")
         if opts.snippets:
             if self._tokenizer is not None and self._span_tokenizer is None:
                 raise ValueError("snippets=True with a custom tokenizer needs Retriever(span_tokenizer=...): the tokenizer's "
@@ -307,6 +311,12 @@ class Retriever:
             self._facet_bound = by
         return names
 
+    def _ensure_signatures(self):
+        """The documents' min-hash signatures, built on the device and bound lazily per index and again after update_index
+        (the rebind drops the tensor with the postings'), like the facet table."""
+        if not self.engine.has_signatures:
+            self.engine.bind_signatures(self.engine.doc_signatures(SIGNATURE_SHINGLE))
+
     def _facet_chunk(self, term_ids, within, facet):
         """One facet_counts call for a chunk's queries: the counting terms (facets.counting_terms) of the ids that are scored,
         inside `within` -- what stage 1 is restricted to, the chunk's DeviceSets when operators, phrases or proximity built
@@ -324,25 +334,11 @@ class Retriever:
     FINAL_COLS = 128           # columns of the final lists copied back per query (top_k = 100 + slack; a longer list -- more
     #                            than top_k "high" domains -- makes that chunk come back in full)
 
-    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, cond=None, facet=None):
-        """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
-        within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
-        mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
-        with its true BM25 score (msr_bm25_score_docs, msr_union_candidates); the candidates and where each came from are
-        copied to pinned buffers beside the final rows (the job's sixth entry).
-        cond (None | the Conditions of the chunk's queries, over term ids): its term lists make ONE term_sets call in front of
-        stage 1, which turns them, inside `within`, into device sets that take within's place in both stages; nothing else
-        changes.  With phrase lists ONE phrase_sets call takes the term_sets call's place (it makes that call itself, with
-        the phrases' candidate rows).
-        facet (None | the dict of final_list_chunks' facets=): ONE facet_counts call over the chunk's scored terms inside the
-        sets stage 1 is restricted to (_facet_chunk); its answer comes back to the host before stage 1 is enqueued."""
-        import torch
+    def _fused_chunk(self, term_ids, qv, top_k, within=None, mode="lexical", dense_k=DENSE_K):
+        """Stage 1 and the rerank chain up to the fused lists of one chunk -> (fused, union): what rerank_fuse returns and, in
+        hybrid mode, what union_candidates does (else None).  Only enqueues."""
         eng, cfg = self.engine, self.reranker.cfg
         union = None
-        if cond is not None:
-            within = cond.sets(eng, within)
-        if facet is not None:
-            self._facet_chunk(term_ids, within, facet)
         if mode == "hybrid":
             k_lex = hybrid_k_lex(top_k, eng.rerank_max_docs, dense_k)
             packed = eng.pack_queries(term_ids)
@@ -354,7 +350,34 @@ class Retriever:
         else:
             b = eng.bm25_topk(term_ids, k=top_k, within=within)
         cos, meta = eng.rerank_gather(qv, b[0], b[2], max_chunks=RERANK_MAX_CHUNKS)
-        fused = eng.rerank_fuse(b[0], b[1], b[2], cos, meta, smoothing=cfg["smoothing"], max_chunks=RERANK_MAX_CHUNKS)
+        return eng.rerank_fuse(b[0], b[1], b[2], cos, meta, smoothing=cfg["smoothing"], max_chunks=RERANK_MAX_CHUNKS), union
+
+    def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, cond=None, facet=None,
+                       min_matches=None):
+        """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
+        within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
+        mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
+        with its true BM25 score (msr_bm25_score_docs, msr_union_candidates); the candidates and where each came from are
+        copied to pinned buffers beside the final rows (the job's sixth entry).
+        cond (None | the Conditions of the chunk's queries, over term ids): its term lists make ONE term_sets call in front of
+        stage 1, which turns them, inside `within`, into device sets that take within's place in both stages; nothing else
+        changes.  With phrase lists ONE phrase_sets call takes the term_sets call's place (it makes that call itself, with
+        the phrases' candidate rows).
+        facet (None | the dict of final_list_chunks' facets=): ONE facet_counts call over the chunk's scored terms inside the
+        sets stage 1 is restricted to (_facet_chunk); its answer comes back to the host before stage 1 is enqueued.
+        min_matches (None | 1 .. 64, SearchOptions.min_matches): ONE collapse_duplicates call between fuse and diversify; what
+        it dropped is copied to pinned buffers beside the final rows (the job's seventh entry; the sixth is then None in
+        lexical mode)."""
+        import torch
+        eng, cfg = self.engine, self.reranker.cfg
+        if cond is not None:
+            within = cond.sets(eng, within)
+        if facet is not None:
+            self._facet_chunk(term_ids, within, facet)
+        fused, union = self._fused_chunk(term_ids, qv, top_k, within, mode, dense_k)
+        drops = None
+        if min_matches is not None:
+            fused, drops = eng.collapse_duplicates(fused, min_matches)
         fin = eng.diversify(fused, top_k=int(cfg["top_k"]), diversification=bool(cfg.get("diversification", False)))
         Qc, W = len(term_ids), min(self.FINAL_COLS, int(fin[0].shape[1]))
         pin = self._pinned.get(slot)
@@ -380,8 +403,21 @@ class Retriever:
             upin[0][:Qc].copy_(union[0], non_blocking=True)
             upin[1][:Qc].copy_(union[2], non_blocking=True)
             upin[2][:Qc].copy_(union[3], non_blocking=True)
+        dpin = None
+        if drops is not None:
+            M = int(drops[0].shape[1])
+            dpin = self._pinned.get(("drops", slot))
+            if dpin is None or dpin[0].shape[0] < Qc or dpin[0].shape[1] != M:
+                rows = max(Qc, 256)
+                dpin = self._pinned[("drops", slot)] = tuple(torch.empty((rows, M), dtype=torch.int32, pin_memory=True)
+                                                             for _ in range(3)) + (torch.empty((rows,), dtype=torch.int32,
+                                                                                               pin_memory=True),)
+            for k in range(4):
+                dpin[k][:Qc].copy_(drops[k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(eng.device))
+        if dpin is not None:
+            return (fin, pin, ev, Qc, W, upin, dpin)
         return (fin, pin, ev, Qc, W) if upin is None else (fin, pin, ev, Qc, W, upin)
 
     @staticmethod
@@ -418,6 +454,16 @@ class Retriever:
         hit = key[pos] == want
         src[fq[hit], fr[hit]] = val[pos[hit]]
         return src
+
+    @staticmethod
+    def _collect_drops(job, dedup):
+        """After _collect_chunk (the event has been waited for): what the chunk's collapse dropped, appended per query to
+        dedup["drops"] as int32 [n, 3] rows (dropped document, leader document, matches), in drop order."""
+        Qc = job[3]
+        d_doc, d_lead, d_m, d_n = (x[:Qc].numpy() for x in job[6])
+        for q in range(Qc):
+            n = int(d_n[q])
+            dedup["drops"].append(np.stack([d_doc[q, :n], d_lead[q, :n], d_m[q, :n]], axis=1).astype(np.int32))
 
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
@@ -458,16 +504,21 @@ class Retriever:
                                 facets)
 
     def _chunks(self, term_id_lists, query_vectors, top_k, chunk, prepare, n_queries, within, opts, cond, fuzzy, wildcards, facets,
-                parsed=False):
+                parsed=False, dedup=None):
         """final_list_chunks over the two values.  Of opts it reads mode, dense_k and the text switches -- parsed: they were
         applied by parse_queries (else True is refused); fuzzy / wildcards / facets: final_list_chunks' dicts, which hold
-        those features' limits."""
+        those features' limits.  dedup: None, or a dict: collapse_duplicates is on with opts' duplicate_threshold; the generator
+        fills dedup["drops"] (per query, _collect_drops)."""
         import torch
         eng = self.engine
         opts = replace(opts, snippets=False, fuzzy=fuzzy is not None, wildcards=wildcards is not None,
                        max_expansions=(wildcards or {}).get("limit", 8), facets=facets is not None,
-                       facet_by=(facets or {}).get("by", "host"), facet_limit=(facets or {}).get("limit", 10))
+                       facet_by=(facets or {}).get("by", "host"), facet_limit=(facets or {}).get("limit", 10),
+                       collapse_duplicates=dedup is not None)
         self._check_options(opts)
+        if dedup is not None:
+            self._ensure_signatures()
+            dedup.update(min_matches=opts.min_matches, drops=[])
         if fuzzy is not None:
             if prepare is not None or len(fuzzy["terms"]) != len(term_id_lists):
                 raise ValueError("fuzzy: needs the term strings of every query (not with prepare=)")
@@ -517,17 +568,20 @@ class Retriever:
                                             wildcards["patterns"][a:b], lim)
                 wildcards["expansions"] += exp
                 wildcards["ids"] += ids
-            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=opts.mode, dense_k=opts.dense_k, cond=c, facet=facets)
+            job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=opts.mode, dense_k=opts.dense_k, cond=c, facet=facets,
+                                      min_matches=None if dedup is None else dedup["min_matches"])
             if pending is not None:
-                yield (pending[0],) + self._collect(pending[1])
+                yield (pending[0],) + self._collect(pending[1], dedup)
             pending = (a, job)
         if pending is not None:
-            yield (pending[0],) + self._collect(pending[1])
+            yield (pending[0],) + self._collect(pending[1], dedup)
 
     @classmethod
-    def _collect(cls, job):
+    def _collect(cls, job, dedup=None):
         out = cls._collect_chunk(job)
-        return out if len(job) == 5 else out + (cls._collect_source(job, out[0], out[3]),)
+        if dedup is not None:
+            cls._collect_drops(job, dedup)
+        return out if len(job) == 5 or job[5] is None else out + (cls._collect_source(job, out[0], out[3]),)
 
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
@@ -541,12 +595,13 @@ class Retriever:
         cond = Conditions(must, must_not, must_phrases, must_not_phrases)
         return self._final(term_id_lists, query_vectors, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source)
 
-    def _final(self, ids, qv, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source=False, parsed=False):
+    def _final(self, ids, qv, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source=False, parsed=False,
+               dedup=None):
         """final_lists over the two values: _chunks' chunks joined (parsed, the dicts: _chunks)."""
         opts.check()
         if with_source and opts.mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
-        parts = list(self._chunks(ids, qv, top_k, chunk, None, None, within, opts, cond, fuzzy, wildcards, facets, parsed))
+        parts = list(self._chunks(ids, qv, top_k, chunk, None, None, within, opts, cond, fuzzy, wildcards, facets, parsed, dedup))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -633,22 +688,23 @@ class Retriever:
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
                      must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS,
                      fuzzy=False, wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host",
-                     facet_limit=10):
+                     facet_limit=10, collapse_duplicates=False, duplicate_threshold=0.9):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         The switches and limits: query.SearchOptions; must / must_not / must_phrases / must_not_phrases: query.Conditions,
-        one entry per query; patterns: per query None or a list of pattern strings.  With fuzzy, wildcards, patterns or
-        facets each query's result is a fuzzy.Results list."""
+        one entry per query; patterns: per query None or a list of pattern strings.  With fuzzy, wildcards, patterns,
+        facets or collapse_duplicates each query's result is a fuzzy.Results list."""
         opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
-                             facets, facet_by, facet_limit)
+                             facets, facet_by, facet_limit, collapse_duplicates, duplicate_threshold)
         return self._search(queries, top_k, query_embeddings, term_lists, query_ids, within, opts,
                             Conditions(must, must_not, must_phrases, must_not_phrases), patterns)
 
     def _search(self, queries, top_k, query_embeddings, term_lists, query_ids, within, opts, explicit, patterns):
         """search_batch over the two values."""
         ids, qv, cond, fz, wc, fc = self._front(queries, query_embeddings, term_lists, opts, explicit, patterns)
+        dd = {} if opts.collapse_duplicates else None
         doc, score, _, n, *src = self._final(ids, qv, top_k, None, within, opts, cond, fz, wc, fc, with_source=opts.mode == "hybrid",
-                                             parsed=True)
+                                             parsed=True, dedup=dd)
         src = src[0] if src else None                        # (hybrid mode: where each row's document came from)
         ix, snippets = self.index, opts.snippets
         ids = self._scored_ids(ids, fz, wc)
@@ -657,6 +713,7 @@ class Retriever:
         for q in range(len(queries)):
             rows = []
             qid = None if query_ids is None else query_ids[q]
+            led = self._duplicates_of(dd["drops"][q]) if dd is not None else {}
             for r in range(int(n[q])):
                 i = int(doc[q, r])
                 url = ix.urls[i] if ix.urls is not None else ""
@@ -668,37 +725,51 @@ class Retriever:
                              "domain": extract_domain_topic(url), "doc_id": str(int(self._ids[i]))})
                 if src is not None:
                     rows[-1]["matched_by"] = MATCHED_BY[int(src[q, r])]
+                if i in led:
+                    rows[-1]["duplicates"] = led[i]
                 if snippets:
                     hit = passages.get((q, r))
                     if hit is not None:
                         rows[-1]["snippet"] = hit[0]
                     rows[-1]["highlights"] = hit[1] if hit is not None else []
                     rows[-1]["missing"] = hit[2] if hit is not None else list(row_names[q] or [])
-            if fz is not None or wc is not None or fc is not None:
+            if fz is not None or wc is not None or fc is not None or dd is not None:
                 corr = fz["corrections"][q] if fz is not None else {}
                 rows = _fuzzy.Results(rows, corr, _fuzzy.corrected_text(fz["processed"][q], corr) if fz is not None else None,
-                                      wc["expansions"][q] if wc is not None else None)
+                                      wc["expansions"][q] if wc is not None else None,
+                                      collapsed=len(dd["drops"][q]) if dd is not None else 0)
                 if fc is not None:
                     rows.hits, rows.facet_values = int(fc["hits"][q]), int(fc["n_values_hit"][q])
                     rows.facets = _facets.top_list(fc["names"], fc["top_value"][q], fc["top_count"][q])
             out.append(rows)
         return out
 
+    def _duplicates_of(self, drops):
+        """One query's drops (int32 [n, 3]: dropped document, leader document, matches) -> {leader document index: the
+        "duplicates" entries of its row, in drop order}."""
+        ix, led = self.index, {}
+        for d, lead, m in drops.tolist():
+            led.setdefault(lead, []).append({"doc_id": str(int(self._ids[d])), "url": ix.urls[d] if ix.urls is not None else "",
+                                             "title": (ix.titles[d] if ix.titles is not None else "") or "No Title",
+                                             "similarity": m / 64.0})
+        return led
+
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
-               wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host", facet_limit=10):
+               wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host", facet_limit=10,
+               collapse_duplicates=False, duplicate_threshold=0.9):
         """search_batch for one query: must / must_not / must_phrases / must_not_phrases / patterns are ONE list each."""
         one = lambda v: None if v is None else [v]
         opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
-                             facets, facet_by, facet_limit)
+                             facets, facet_by, facet_limit, collapse_duplicates, duplicate_threshold)
         return self._search([query], top_k, one(query_embedding), one(terms), one(query_id), within, opts,
                             Conditions(one(must), one(must_not), one(must_phrases), one(must_not_phrases)), one(patterns))[0]
 
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                      must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
-                     wildcards=False, max_expansions=8, patterns=None):
+                     wildcards=False, max_expansions=8, patterns=None, collapse_duplicates=False, duplicate_threshold=0.9):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
@@ -707,11 +778,16 @@ class Retriever:
         page has no window), "highlights" and "missing" as in search_batch; the formatted lines are what they were.
         fuzzy=True: the returned BatchLines then carries `corrections` (per query {typed term: used term}) and
         `corrected_queries` (per query the corrected text or None); the entries keep their keys.  wildcards / max_expansions /
-        patterns: the BatchLines then carries `expansions` (per query {pattern: {...}})."""
-        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions)
+        patterns: the BatchLines then carries `expansions` (per query {pattern: {...}}).  collapse_duplicates /
+        duplicate_threshold: search_batch; the entries and lines are those of the rows that stay, and the BatchLines then
+        carries `collapsed` (per query the number of rows dropped) and `duplicates` (per query {leader's url: the
+        "duplicates" entries of search_batch})."""
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
+                             collapse_duplicates=collapse_duplicates, duplicate_threshold=duplicate_threshold)
         ids, qv, cond, fz, wc, _ = self._front([q for _, q in numbered_queries], query_embeddings, term_lists, opts,
                                                Conditions(must, must_not, must_phrases, must_not_phrases), patterns)
-        doc, score, _, n = self._final(ids, qv, TOP_K_RETRIEVAL, None, within, opts, cond, fz, wc, None, parsed=True)
+        dd = {} if opts.collapse_duplicates else None
+        doc, score, _, n = self._final(ids, qv, TOP_K_RETRIEVAL, None, within, opts, cond, fz, wc, None, parsed=True, dedup=dd)
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         lines = BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
@@ -720,6 +796,10 @@ class Retriever:
             lines.corrected_queries = [_fuzzy.corrected_text(p, c) for p, c in zip(fz["processed"], fz["corrections"])]
         if wc is not None:
             lines.expansions = wc["expansions"]
+        if dd is not None:
+            url = lambda d: (self.index.urls[d] if self.index.urls is not None else "") or ""
+            lines.collapsed = [len(d) for d in dd["drops"]]
+            lines.duplicates = [{url(lead): rows for lead, rows in self._duplicates_of(d).items()} for d in dd["drops"]]
         if snippets:
             lines.passages, lines.row_names = self._snippets(self._scored_ids(ids, fz, wc), doc, n, snippet_tokens)
         return lines
@@ -782,6 +862,7 @@ class BatchLines:
         self.passages = self.row_names = None                # Retriever.batch_search(snippets=True) fills them
         self.corrections = self.corrected_queries = None     # ... and fuzzy=True these
         self.expansions = None                               # ... and wildcards=True / patterns= this
+        self.collapsed = self.duplicates = None              # ... and collapse_duplicates=True these
 
     def __len__(self):
         return int(self._start[-1])

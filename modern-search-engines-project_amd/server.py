@@ -81,6 +81,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         facets: bool = False          # count the WHOLE match set on the device (Retriever.search, DESIGN K17): the response then
         facet_by: str = "host"        # carries "hits", "facets" ([{"value", "count"}], by "host" -- usable as sites=[...] -- or by
         facet_limit: int = 10         # "domain", the first facet_limit (1 .. 64) values) and "facet_values" (distinct values hit)
+        collapse_duplicates: bool = False   # near-duplicate pages are shown once (Retriever.search, DESIGN K18): the response then
+        duplicate_threshold: float = 0.9    # carries "collapsed"; rows that swallowed copies carry "duplicates"; threshold in (0, 1]
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -145,7 +147,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                         (near, ("phrases", "proximity", "must_phrases", "must_not_phrases"), True),
                         (req.snippets, ("snippets", "snippet_tokens"), True), (req.fuzzy, ("fuzzy",), True),
                         (wild, ("wildcards", "max_expansions", "patterns"), True),
-                        (req.facets, ("facets", "facet_by", "facet_limit"), True))
+                        (req.facets, ("facets", "facet_by", "facet_limit"), True),
+                        (req.collapse_duplicates, ("collapse_duplicates", "duplicate_threshold"), True))
             for on, names, _ in features:
                 if on:
                     kw.update({name: getattr(req, name) for name in names})
@@ -161,13 +164,16 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                 if not any(on and bad_request for on, _, bad_request in features):
                     raise
                 # a dense_k the engine cannot hold; fuzzy / wildcards on an index without term strings; max_expansions outside
-                # 1 .. 16; a required or excluded pattern; a facet_by the engine does not know, a facet_limit outside 1 .. 64
+                # 1 .. 16; a required or excluded pattern; a facet_by the engine does not know, a facet_limit outside 1 .. 64;
+                # a duplicate_threshold outside (0, 1]
                 return JSONResponse(status_code=400, content={"error": str(e)})
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
-            if req.fuzzy or wild or req.facets:
+            if req.fuzzy or wild or req.facets or req.collapse_duplicates:
                 out = {"llm_response": llm_response, "documents": list(docs)}
+                if req.collapse_duplicates:
+                    out.update(collapsed=docs.collapsed)
                 if req.facets:
                     out.update(hits=docs.hits, facets=docs.facets, facet_values=docs.facet_values)
                 if req.fuzzy:
