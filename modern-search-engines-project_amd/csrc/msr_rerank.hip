@@ -27,13 +27,39 @@ constexpr int RR_MAXM = 1024;
 
 // One wave per query and block of 8 candidate slots: lanes 0 .. 7 sort the slots into "mine" (the document lies in this
 // shard) and "not mine" (zeros: the owner's words arrive through the join of the shards' halves), then the wave takes the
-// slots that are mine one after the other.  (One wave per slot, as before, launches N times the waves a rank of an N-way
+// rows of all the slots that are mine as ONE list (<= 80 rows) and runs one row pipeline over it, RC_DEPTH rows in flight.
+// (Before, the slots were taken one after the other with, by the source, two rows in flight; the compiled loop had at most
+// one: lane 0's out[..] = s * inv_norm[c] is a load, an s_waitcnt vmcnt(0) and a store behind the next row's loads, and
+// vmcnt retires in order, so the wait for the norm drained the row just asked for; the document offsets were one more
+// round trip per slot.  Now offsets and norms are loaded once per block, nothing in the row loop depends on a load but
+// the rows themselves, and a slot's cosines are stored by one instruction behind its last row.)
+// (One wave per slot, as before, launches N times the waves a rank of an N-way
 // sharded run has work for -- 2 M waves per 2048-query step at N = 8, most of which only wrote zeros: 2.2 ms instead of 0.7;
 // workgroups of several waves sharing a block lose 12 % on the unsharded corpus, where every slot is work: a workgroup
 // keeps its place on the CU until its slowest wave is done.)
 // SLOTS = 1 (calls of a few queries, no records): one wave per candidate slot -- a single query has 1000 slots, i.e. 125 waves
 // of 8 slots each on a chip with room for thousands; its gather took 43 us of one after the other.
 constexpr int RC_SLOTS = 8;
+#ifndef MSR_RC_DEPTH
+#define MSR_RC_DEPTH 4
+#endif
+// rows in flight per wave: 2 / 3 / 4 = 56 / 68 / 79 VGPRs = 8 / 7 / 6 waves per SIMD; 4 measured fastest and steadiest
+// (profiles/rerank_stage_pipeline.md)
+constexpr int RC_DEPTH = MSR_RC_DEPTH;
+static_assert(RC_DEPTH >= 2 && RC_DEPTH <= 4, "the tail's waits are written out for 2 .. 4 rows");
+
+typedef const __attribute__((address_space(1))) char* rr_gptr;    // (global, not flat)
+// loads the compiler neither moves nor counts: the caller waits (rr_wait) and pins the destination before its first use
+template <int OFF>
+__device__ __forceinline__ void rr_load16(f32x4& r, rr_gptr p) {
+    asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(r) : "v"(p), "n"(OFF) : "memory");
+}
+__device__ __forceinline__ void rr_load4(float& r, rr_gptr p) {
+    asm volatile("global_load_dword %0, %1, off" : "=v"(r) : "v"(p) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void rr_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+
 template <bool TILED, int SLOTS = RC_SLOTS>
 __global__ __launch_bounds__(64) void rerank_cos_kernel(DenseIndex ix, const int32_t* __restrict__ url_group,
                                                          const float* __restrict__ qn,
@@ -66,92 +92,157 @@ __global__ __launch_bounds__(64) void rerank_cos_kernel(DenseIndex ix, const int
             mt[0] = 0; mt[1] = 0; mt[2] = 0;
         }
     }
-    unsigned long long todo = __ballot(d_mine >= 0);
-    if (todo == 0) return;
-    const unsigned long long mine_all = todo;
+    const unsigned long long mine_all = __ballot(d_mine >= 0);
+    if (mine_all == 0) return;
+    const f32x4* q4 = (const f32x4*)(qn + (size_t)q * MSR_DIM);
+    f32x4 qa = q4[lane], qb = q4[lane + 64], qc = q4[lane + 128];
+
+    // ---- every slot of the block at once: lane sl < SLOTS owns slot m0 + sl ------------------------------------------------
+    // One round trip for the 2 x SLOTS document offsets, meta written by the slots' lanes; rows = the slot's row count
+    // clamped to max_chunks (0: not mine, no chunk, or a record past rec.capacity, which is dropped whole as before).
     int64_t rec_first = 0;
     if (records) rec_first = (int64_t)rec.q_base[q] + rec.blk_off[(int64_t)q * gridDim.x + blockIdx.x];
-    const f32x4* q4 = (const f32x4*)(qn + (size_t)q * MSR_DIM);
-    const f32x4 qa = q4[lane], qb = q4[lane + 64], qc = q4[lane + 128];
-    for (; todo != 0; todo &= todo - 1) {
-        const int sl = __builtin_ctzll(todo);            // (wave-uniform)
-        const int d = __builtin_amdgcn_readlane(d_mine, sl), m = m0 + sl;
-        float* out = cos_out + (int64_t)m * RR_MAXC;
-        int32_t* mt = meta + (int64_t)m * 3;
+    auto record_of = [&](int sl) -> int64_t { return rec_first + __builtin_popcountll(mine_all & ((1ull << sl) - 1)); };
+    auto cos_of = [&](int sl) -> float* {
+        return records ? (float*)(rec.out + record_of(sl) * MSR_RERANK_RECORD_WORDS + 4) : cos_out + (int64_t)(m0 + sl) * RR_MAXC;
+    };
+    // Loads first, stores after.  The URL group is asked for beside the offsets, without a branch (in a branch of its own,
+    // or behind a store, it is one more round trip).  The query was asked for before the offsets, so it has landed with them:
+    // pinned between the loads and the stores, the compiler's wait for it costs nothing -- behind the stores it would be a
+    // vmcnt(0) that waits for them, and behind the loads of inv_norm one that drains those.
+    int ds = 0, rows = 0, group = 0;                         // (doc_off is 32-bit: row numbers fit an int)
+    bool live = d_mine >= 0;
+    int64_t at = 0;
+    if (records && live) {
+        at = record_of(lane);
+        live = at >= 0 && at < rec.capacity;
+    }
+    if (live) {
+        const int32_t* gp = url_group ? url_group + d_mine : ix.doc_off + d_mine;
+        const int gword = *gp;
+        ds = ix.doc_off[d_mine];
+        rows = ix.doc_off[d_mine + 1] - ds;
+        group = url_group ? gword : d_mine + doc_base;
+        if (rows > max_chunks) rows = max_chunks;
+    }
+    asm volatile("" : "+v"(qa), "+v"(qb), "+v"(qc), "+v"(ds), "+v"(rows), "+v"(group));
+    if (live) {
+        int32_t* mt = meta + (int64_t)(m0 + lane) * 3;
         if (records) {
-            const int64_t at = rec_first + __builtin_popcountll(mine_all & ((1ull << sl) - 1));
-            if (at < 0 || at >= rec.capacity) continue;      // (wave-uniform)
             int32_t* r = rec.out + at * MSR_RERANK_RECORD_WORDS;
-            out = (float*)(r + 4);
             mt = r + 1;
-            if (lane == 0) { r[0] = m; r[14] = rec.q_first + q; r[15] = 0; }
+            r[0] = m0 + lane; r[14] = rec.q_first + q; r[15] = 0;
         }
-        const int64_t ds = ix.doc_off[d];
-        int64_t de = ix.doc_off[d + 1];
-        if (ds + max_chunks < de) de = ds + max_chunks;
-        if (lane == 0) {
-            mt[0] = (int32_t)(de - ds);                      // chunk rows that take part (<= max_chunks)
-            // URL group + 2, so that after the join of the shards' halves 0 = nobody owns it, 1 = owned, not in urlsDB
-            mt[1] = (url_group ? url_group[d] : d + doc_base) + 2;
-            mt[2] = (int32_t)ds + row_base;                  // global row of the document's first chunk
+        mt[0] = rows;                                        // chunk rows that take part (<= max_chunks)
+        // URL group + 2, so that after the join of the shards' halves 0 = nobody owns it, 1 = owned, not in urlsDB
+        mt[1] = group + 2;
+        mt[2] = ds + row_base;                               // global row of the document's first chunk
+        if (rows <= 0) {                                     // no row: all ten places are zero (a slot with rows writes its ten
+            float* out = cos_of(lane);                       // places, zeros included, behind its last row)
+#pragma unroll
+            for (int i = 0; i < RR_MAXC; ++i) out[i] = 0.f;
         }
-        if (lane >= (int)(de - ds) && lane < RR_MAXC) out[lane] = 0.f;
-        // two rows in flight per wave: the loads of row c + 1 are issued before row c is reduced (a document's rows are
-        // consecutive: 6 KB per pair)
-        auto load_row = [&](int64_t c, f32x4& a, f32x4& b, f32x4& e2) {
-            if (TILED) {
-                const f32x4* base = (const f32x4*)(ix.emb + (size_t)(c >> 4) * (16 * MSR_DIM));
-                const int i = (int)(c & 15);
-                // float4 number v of the row (dims 4v..4v+3) lives at block t = v >> 2, lane 16 (v & 3) + i
-                const int v0 = lane, v1 = lane + 64, v2 = lane + 128;
-                a = base[(v0 >> 2) * 64 + (v0 & 3) * 16 + i];
-                b = base[(v1 >> 2) * 64 + (v1 & 3) * 16 + i];
-                e2 = base[(v2 >> 2) * 64 + (v2 & 3) * 16 + i];
-            } else {
-                const f32x4* p = (const f32x4*)(ix.emb + (size_t)c * MSR_DIM);
-                a = p[lane]; b = p[lane + 64]; e2 = p[lane + 128];
+    }
+    if (rows < 0) rows = 0;
+    // the block's flat row list: slot sl's rows are numbers [incl(sl) - rows(sl), incl(sl)), R <= 10 SLOTS rows in all
+    int incl = rows;
+#pragma unroll
+    for (int o = 1; o < SLOTS; o <<= 1) {
+        const int t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    const int R = __builtin_amdgcn_readlane(incl, SLOTS - 1);
+    if (R == 0) return;
+    // inv_norm of row number `lane` (and lane + 64) of the list goes into that lane.  The loads are inline asm like the rows':
+    // a load the compiler counts would be waited for with vmcnt(0) at its first use, behind the first rows of the pipeline.
+    // Lanes past the list load the list's last row's (an address that is a candidate's row, whatever the lane).
+    auto list_row = [&](int r) -> int64_t {                  // (per lane) global row of list entry min(r, R - 1)
+        r = r < R ? r : R - 1;
+        int sl = 0;
+#pragma unroll
+        for (int j = 0; j + 1 < SLOTS; ++j) sl += r >= __builtin_amdgcn_readlane(incl, j) ? 1 : 0;
+        return (int64_t)__shfl(ds, sl) + (r - (__shfl(incl, sl) - __shfl(rows, sl)));
+    };
+    float inv_a, inv_b = 0.f;
+    rr_load4(inv_a, (rr_gptr)(ix.inv_norm + list_row(lane)));
+    if (SLOTS > 6) rr_load4(inv_b, (rr_gptr)(ix.inv_norm + list_row(lane + 64)));
+
+    // ---- one row pipeline over the list, across the slots' boundaries: RC_DEPTH rows in flight per wave ---------------------
+    // Driven by hand as the row ring of msr_gemm_f32.hip: inline-asm loads the compiler neither counts nor moves, a counted
+    // s_waitcnt before every use.  Vector-memory operations retire in order, so with `ahead` rows issued behind row r,
+    // vmcnt(3 ahead) says row r has landed (and inv_norm, which is older than every row); a candidate's cosine store, issued
+    // behind some of those rows, only makes the wait ask for a little more.  Row r + RC_DEPTH is asked for as soon as row r's
+    // 12 products per lane are taken (they read the slot; the butterfly, the scaling and the store follow the new loads).
+    // Only the list's last RC_DEPTH - 1 rows wait with fewer rows behind them, the last one with vmcnt(0).
+    // The ring hazard of DESIGN K2+K3: the compiler takes an asm load's destination as written at once, so no copy of a slot
+    // may live across its reload -- the products are forced out (the empty asm on dot) before the slot is loaded again.
+    struct Walk { int sl, j, n; unsigned left; };            // (wave-uniform) a position in the list: slot, row within it, its rows
+    auto start = [&](Walk& w) {
+        w.left = (unsigned)__ballot(rows > 0);
+        w.sl = __builtin_ctz(w.left); w.left &= w.left - 1; w.j = 0; w.n = __builtin_amdgcn_readlane(rows, w.sl);
+    };
+    auto advance = [&](Walk& w) {
+        if (++w.j == w.n && w.left != 0) { w.sl = __builtin_ctz(w.left); w.left &= w.left - 1; w.j = 0; w.n = __builtin_amdgcn_readlane(rows, w.sl); }
+    };
+    Walk wi, wr;                                             // the next row to ask for; the next row to reduce
+    start(wi);
+    wr = wi;
+    const rr_gptr emb = (rr_gptr)ix.emb;
+    // float4 number v of a row of the interleaved image (dims 4v .. 4v + 3) lives at block v >> 2, place 16 (v & 3) + i of the
+    // 16-row group: lane + 64 k is 16384 k bytes behind lane's
+    const int64_t lane_off = TILED ? (int64_t)((lane >> 2) * 64 + (lane & 3) * 16) * 16 : (int64_t)lane * 16;
+    auto issue = [&](f32x4 (&s)[3]) {
+        const int64_t c = (int64_t)__builtin_amdgcn_readlane(ds, wi.sl) + wi.j;
+        if (TILED) {
+            const rr_gptr p = emb + (c >> 4) * (int64_t)(16 * MSR_DIM * 4) + (c & 15) * 16 + lane_off;
+            rr_load16<0>(s[0], p); rr_load16<0>(s[1], p + 16384); rr_load16<0>(s[2], p + 32768);
+        } else {
+            const rr_gptr p = emb + c * (int64_t)(MSR_DIM * 4) + lane_off;
+            rr_load16<0>(s[0], p); rr_load16<1024>(s[1], p); rr_load16<2048>(s[2], p);
+        }
+        advance(wi);
+    };
+    f32x4 ring[RC_DEPTH][3];
+#pragma unroll
+    for (int k = 0; k < RC_DEPTH; ++k)
+        if (k < R) issue(ring[k]);
+    float park = 0.f;                                        // lane j: the cosine of row j of the candidate being reduced
+    for (int r0 = 0; r0 < R; r0 += RC_DEPTH) {
+#pragma unroll
+        for (int k = 0; k < RC_DEPTH; ++k) {
+            const int r = r0 + k;
+            if (r >= R) break;                               // (wave-uniform)
+            const int ahead = R - 1 - r;
+            if (ahead >= RC_DEPTH - 1) rr_wait<3 * (RC_DEPTH - 1)>();
+            else if (ahead == 2) rr_wait<6>();
+            else if (ahead == 1) rr_wait<3>();
+            else rr_wait<0>();
+            f32x4(&s)[3] = ring[k];
+            asm volatile("" : "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(inv_a), "+v"(inv_b));
+            float dot = s[0].x * qa.x + s[0].y * qa.y + s[0].z * qa.z + s[0].w * qa.w;
+            dot += s[1].x * qb.x + s[1].y * qb.y + s[1].z * qb.z + s[1].w * qb.w;
+            dot += s[2].x * qc.x + s[2].y * qc.y + s[2].z * qc.z + s[2].w * qc.w;
+            asm volatile("" : "+v"(dot));
+            if (r + RC_DEPTH < R) issue(s);
+            for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+            const float inv = __int_as_float((SLOTS > 6 && r >= 64) ? __builtin_amdgcn_readlane(__float_as_int(inv_b), r - 64)
+                                                                     : __builtin_amdgcn_readlane(__float_as_int(inv_a), r));
+            if (lane == wr.j) park = dot * inv;
+            if (wr.j + 1 == wr.n) {                          // the candidate's last row: its ten places with one store
+                float* out = cos_of(wr.sl);
+                if (lane < RR_MAXC) out[lane] = park;
+                park = 0.f;
             }
-        };
-        auto dot_row = [&](const f32x4& a, const f32x4& b, const f32x4& e2) {
-            float s = a.x * qa.x + a.y * qa.y + a.z * qa.z + a.w * qa.w;
-            s += b.x * qb.x + b.y * qb.y + b.z * qb.z + b.w * qb.w;
-            s += e2.x * qc.x + e2.y * qc.y + e2.z * qc.z + e2.w * qc.w;
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-            return s;
-        };
-        f32x4 a0, b0, e0, a1, b1, e1;
-        if (ds < de) load_row(ds, a0, b0, e0);
-        for (int64_t c = ds; c < de; c += 2) {
-            const bool two = c + 1 < de;                     // (wave-uniform)
-            if (two) load_row(c + 1, a1, b1, e1);
-            const float s0 = dot_row(a0, b0, e0);
-            if (c + 2 < de) load_row(c + 2, a0, b0, e0);
-            if (lane == 0) out[c - ds] = s0 * ix.inv_norm[c];
-            if (two) {
-                const float s1 = dot_row(a1, b1, e1);
-                if (lane == 0) out[c + 1 - ds] = s1 * ix.inv_norm[c + 1];
-            }
+            advance(wr);
         }
     }
 }
 
-__device__ __forceinline__ double block_reduce(double v, bool is_min, double* red) {
-    // red: LDS scratch of RR_THREADS/64 doubles
-    for (int o = 32; o > 0; o >>= 1) {
-        const double u = __shfl_xor(v, o);
-        v = is_min ? (u < v ? u : v) : (u > v ? u : v);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int i = 1; i < RR_THREADS / 64; ++i) {
-        const double u = red[i];
-        r = is_min ? (u < r ? u : r) : (u > r ? u : r);
-    }
-    return r;
-}
-
+// (B) one workgroup per query, thread i = candidate slot i.  Everything a slot needs from memory -- document, (rows, group,
+// first row), BM25 score and its ten cosines as five 8-byte loads (a slot's cosines start at a multiple of 40 bytes) -- is
+// asked for once, before anything is used, and stays in registers for both the min-max and the chain; the chain's rows
+// v[0 .. 9] are indexed by constants only (the row loops are unrolled and predicated), so nothing lives in scratch.
+constexpr int RF_TABLE = 2048;        // URL-group table: twice the slots, linear probing
 __global__ __launch_bounds__(RR_THREADS) void rerank_fuse_kernel(
     const int32_t* __restrict__ cand_doc, const double* __restrict__ cand_bm25,
     const int32_t* __restrict__ cand_n, int max_cand, RerankParams prm, const float* __restrict__ cos_in,
@@ -164,104 +255,138 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_fuse_kernel(
     __shared__ double sc[RR_MAXM];
     __shared__ double og[RR_MAXM];
     __shared__ int32_t ch[RR_MAXM];
-    __shared__ uint8_t keep[RR_MAXM];
-    __shared__ double red[RR_THREADS / 64];
-    __shared__ int cnt[2];
+    __shared__ uint32_t tkey[RF_TABLE];                          // group word (>= 2), 0 = free
+    __shared__ unsigned long long tmin[RF_TABLE];                // the group's smallest (document, slot)
+    __shared__ double red_b[2][RR_THREADS / 64];
+    __shared__ float red_c[2][RR_THREADS / 64];
+    __shared__ int red_n[2][RR_THREADS / 64];
 
-    const int q = blockIdx.x, tid = threadIdx.x;
+    const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int n = cand_n[q];
     if (n > max_cand) n = max_cand;
     if (n > RR_MAXM) n = RR_MAXM;
     int P = 64;
     while (P < n) P <<= 1;
-    const int32_t* cd = cand_doc + (int64_t)q * max_cand;
-    const double* cb = cand_bm25 + (int64_t)q * max_cand;
-    const int32_t* mt = meta + (int64_t)q * max_cand * 3;      // (rows, url group, first row) per candidate
 
-    // 1. sort candidates by (url group, doc, slot) so the first entry of each group is MIN(id)   (:38-47) and, among repeated
-    //    slots of that document, the first slot (msretr.h): the network is not stable, so the slot is part of the key
-    for (int i = tid; i < P; i += RR_THREADS) {
-        uint64_t key = ~0ull;
-        if (i < n) {
-            const int d = cd[i];
-            const int g = mt[3 * i + 1] - 2;
-            if (d >= 0 && g >= 0) key = ((uint64_t)(uint32_t)g << 32) | (uint32_t)d;
-        }
-        khi[i] = key; klo[i] = (uint32_t)i; val[i] = (uint32_t)i;
+    // 0. the slot's words
+    int d = -1, nr = 0, gw = 0, first = 0;
+    double bm = 0.0;
+    float c[RR_MAXC];
+#pragma unroll
+    for (int j = 0; j < RR_MAXC; ++j) c[j] = 0.f;
+    if (tid < n) {
+        const int64_t m = (int64_t)q * max_cand + tid;
+        const float2* cs = (const float2*)(cos_in + m * RR_MAXC);
+        float2 c2[RR_MAXC / 2];
+#pragma unroll
+        for (int j = 0; j < RR_MAXC / 2; ++j) c2[j] = cs[j];
+        d = cand_doc[m];
+        nr = meta[3 * m]; gw = meta[3 * m + 1]; first = meta[3 * m + 2];
+        bm = cand_bm25[m];
+#pragma unroll
+        for (int j = 0; j < RR_MAXC / 2; ++j) { c[2 * j] = c2[j].x; c[2 * j + 1] = c2[j].y; }
     }
-    if (tid < 2) cnt[tid] = 0;
+    for (int i = tid; i < RF_TABLE; i += RR_THREADS) { tkey[i] = 0; tmin[i] = ~0ull; }
     __syncthreads();
-    msr_sort::bitonic_sort<RR_THREADS, true>(khi, klo, val, P, true);
 
-    // 2. keep = first of its URL group, has at least one chunk row
-    double cmin = __builtin_inf(), cmax = -__builtin_inf(), bmin = __builtin_inf(), bmax = -__builtin_inf();
-    int my_rows = 0;
-    for (int i = tid; i < P; i += RR_THREADS) {                  // at most one iteration
-        bool k = false;
-        const uint64_t key = khi[i];
-        if (key != ~0ull && (i == 0 || (khi[i - 1] >> 32) != (key >> 32))) {
-            const int m = (int)val[i];
-            const int nr = mt[3 * m];
-            if (nr > 0) {
-                k = true;
-                const float* cs = cos_in + ((int64_t)q * max_cand + m) * RR_MAXC;
-                for (int j = 0; j < (int)nr; ++j) {
-                    const double c = (double)cs[j];
-                    cmin = c < cmin ? c : cmin; cmax = c > cmax ? c : cmax;
-                }
-                const double bm = cb[m];
-                bmin = bm < bmin ? bm : bmin; bmax = bm > bmax ? bm : bmax;
-                my_rows += (int)nr;
-            }
+    // 1. keep = the smallest (document, slot) of its URL group (MIN(id) per URL, :38-47; among repeated slots of that
+    //    document the first slot, msretr.h) that has at least one chunk row.  This is the rule the sort by (group, document,
+    //    slot) implemented -- "first entry of its group" IS the group's minimum -- found with one 64-bit LDS minimum per slot
+    //    in a table keyed by the group instead of a 55-stage network.  The final order does not depend on the order the kept
+    //    slots are found in: kept documents are distinct (one per group, and a document has one group), so the keys
+    //    (score, ~document) of the sort below are unique and val carries the slot.
+    const bool valid = d >= 0 && gw >= 2;
+    const unsigned long long mine = ((unsigned long long)(uint32_t)d << 32) | (uint32_t)tid;
+    int h = 0;
+    if (valid) {
+        h = (int)(((uint32_t)gw * 2654435761u) >> 21);           // top 11 bits: RF_TABLE places
+        for (;;) {
+            const uint32_t old = atomicCAS(&tkey[h], 0u, (uint32_t)gw);
+            if (old == 0u || old == (uint32_t)gw) break;
+            h = (h + 1) & (RF_TABLE - 1);                        // (<= 1024 groups in 2048 places: a free place exists)
         }
-        keep[i] = k ? 1 : 0;
+        atomicMin(&tmin[h], mine);
     }
-    cmin = block_reduce(cmin, true, red);
-    cmax = block_reduce(cmax, false, red);
-    bmin = block_reduce(bmin, true, red);
-    bmax = block_reduce(bmax, false, red);
-    if (my_rows) atomicAdd(&cnt[0], my_rows);
     __syncthreads();
+    const bool keep = valid && nr > 0 && tmin[h] == mine;
+
+    // 2. min-max over the kept slots' rows and BM25 scores, the counts: per wave by shuffles / ballot, then 16 partials
+    //    per value in LDS -- two barriers for all of it.  (Minima and maxima of the f32 cosines are taken in f32: the
+    //    conversion to double is exact and monotone.)
+    float cmin_f = __builtin_inff(), cmax_f = -__builtin_inff();
+    double bmin = __builtin_inf(), bmax = -__builtin_inf();
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < RR_MAXC; ++j)
+            if (j < nr) { cmin_f = c[j] < cmin_f ? c[j] : cmin_f; cmax_f = c[j] > cmax_f ? c[j] : cmax_f; }
+        bmin = bm; bmax = bm;
+    }
+    int rows_w = keep ? nr : 0;
+    for (int o = 32; o > 0; o >>= 1) {
+        const float u0 = __shfl_xor(cmin_f, o), u1 = __shfl_xor(cmax_f, o);
+        const double u2 = __shfl_xor(bmin, o), u3 = __shfl_xor(bmax, o);
+        cmin_f = u0 < cmin_f ? u0 : cmin_f; cmax_f = u1 > cmax_f ? u1 : cmax_f;
+        bmin = u2 < bmin ? u2 : bmin; bmax = u3 > bmax ? u3 : bmax;
+        rows_w += __shfl_xor(rows_w, o);
+    }
+    const unsigned long long kept_w = __ballot(keep);
+    if (lane == 0) {
+        red_c[0][wave] = cmin_f; red_c[1][wave] = cmax_f; red_b[0][wave] = bmin; red_b[1][wave] = bmax;
+        red_n[0][wave] = rows_w; red_n[1][wave] = __builtin_popcountll(kept_w);
+    }
+    __syncthreads();
+    int n_rows = 0, n_keep = 0;
+    for (int i = 0; i < RR_THREADS / 64; ++i) {
+        const float u0 = red_c[0][i], u1 = red_c[1][i];
+        const double u2 = red_b[0][i], u3 = red_b[1][i];
+        cmin_f = u0 < cmin_f ? u0 : cmin_f; cmax_f = u1 > cmax_f ? u1 : cmax_f;
+        bmin = u2 < bmin ? u2 : bmin; bmax = u3 > bmax ? u3 : bmax;
+        n_rows += red_n[0][i]; n_keep += red_n[1][i];
+    }
+    const double cmin = (double)cmin_f, cmax = (double)cmax_f;
 
     // 3. per kept document: normalise, blend, positional weighting, first maximum
     const double one_m_s = 1.0 - prm.smoothing;
     if (tid < P) {                                               // P <= RR_THREADS: one entry per thread
-        const int i = tid;
         uint64_t shi = 0; uint32_t slo = 0;
-        if (keep[i]) {
-            const int d = (int)(uint32_t)khi[i];
-            const int m = (int)val[i];
-            const int nr = mt[3 * m];
-            const float* cs = cos_in + ((int64_t)q * max_cand + m) * RR_MAXC;
-            const double old = (bmax == bmin) ? 0.0 : (cb[m] - bmin) / (bmax - bmin);
+        if (keep) {
+            const double old = (bmax == bmin) ? 0.0 : (bm - bmin) / (bmax - bmin);
             double v[RR_MAXC];
             int best = 0;
-            for (int j = 0; j < nr; ++j) {
-                const double nw = (cmax == cmin) ? 0.0 : ((double)cs[j] - cmin) / (cmax - cmin);
-                v[j] = nw * one_m_s + old * prm.smoothing;
-                if (v[j] > v[best]) best = j;
+            double vb = 0.0;                                     // v[best]
+#pragma unroll
+            for (int j = 0; j < RR_MAXC; ++j) {
+                v[j] = 0.0;
+                if (j < nr) {
+                    const double nw = (cmax == cmin) ? 0.0 : ((double)c[j] - cmin) / (cmax - cmin);
+                    v[j] = nw * one_m_s + old * prm.smoothing;
+                    if (j == 0) vb = v[0];
+                    else if (v[j] > vb) { best = j; vb = v[j]; }
+                }
             }
             if (nr > 1) {
                 const double ratio = (double)best / (double)(nr - 1);
                 const double adj = prm.max_boost - (prm.max_boost + prm.max_decay) * ratio;
-                double a = v[best] + adj;
+                double a = vb + adj;
                 a = a < 1.0 ? a : 1.0;                           // min(1.0, adjusted)
                 a = a > 0.0 ? a : 0.0;                           // max(0.0, ...)
-                v[best] = a;
+                const int shifted = best;
                 best = 0;
-                for (int j = 1; j < nr; ++j)
-                    if (v[j] > v[best]) best = j;
+                vb = shifted == 0 ? a : v[0];
+#pragma unroll
+                for (int j = 1; j < RR_MAXC; ++j) {
+                    const double vj = shifted == j ? a : v[j];
+                    if (j < nr && vj > vb) { best = j; vb = vj; }
+                }
             }
-            sc[i] = v[best]; og[i] = old; ch[i] = mt[3 * m + 2] + best;
-            shi = msr_ord64(v[best]); slo = ~(uint32_t)d;
-            atomicAdd(&cnt[1], 1);
+            sc[tid] = vb; og[tid] = old; ch[tid] = first + best;
+            shi = msr_ord64(vb); slo = ~(uint32_t)d;
         }
-        khi[i] = shi; klo[i] = slo; val[i] = (uint32_t)i;
+        khi[tid] = shi; klo[tid] = slo; val[tid] = (uint32_t)tid;
     }
     __syncthreads();
     // 4. order by (score desc, doc asc)
     msr_sort::bitonic_sort<RR_THREADS, true>(khi, klo, val, P, false);
-    const int n_keep = cnt[1];
     for (int i = tid; i < max_cand; i += RR_THREADS) {
         const int64_t o = (int64_t)q * max_cand + i;
         if (i < n_keep) {
@@ -271,7 +396,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_fuse_kernel(
             out_doc[o] = -1; out_score[o] = -__builtin_inf(); out_orig[o] = 0.0; out_chunk[o] = -1;
         }
     }
-    if (tid == 0) { out_n[q] = n_keep; out_rows[q] = cnt[0]; }
+    if (tid == 0) { out_n[q] = n_keep; out_rows[q] = n_rows; }
 }
 
 

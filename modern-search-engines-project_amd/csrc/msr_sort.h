@@ -1,5 +1,5 @@
 // Bitonic sort of records (64-bit key, 32-bit key extension[, 32-bit value]) held in LDS, by one workgroup (gfx950).
-// Used by the select's final kernel (msr_topk.hip) and the two sorts of the fuse kernel (msr_rerank.hip).
+// Used by the select's final kernel (msr_topk.hip) and the final sort of the fuse kernel (msr_rerank.hip).
 //
 // The usual network (levels kk = 2, 4, .. P; stages j = kk / 2 .. 1), one compare-exchange per thread and stage.  Between two
 // stages with partner distance <= 64 no workgroup barrier is needed: thread t's pair of such a stage lies in the 128-record
