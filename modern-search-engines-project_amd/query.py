@@ -68,8 +68,10 @@ class SearchOptions:
     trailing `?` is punctuation, nothing inside quotes): it leaves the scoring text, and the vocabulary terms it matches as
     a whole, the most frequent first, at most max_expansions (1 .. 16) of them, are appended to the query's terms as
     ordinary scoring terms (wildcard.expand: no id twice, at most MSR_MAX_QUERY_TERMS unique ids, a pattern with fewer
-    than two literal code points is skipped); ONE DeviceEngine.wildcard_terms call per chunk of queries.  patterns=: per
-    query a list of further pattern strings, with or without wildcards=True.  Patterns match the vocabulary AS INDEXED
+    than two literal code points is skipped; a word the vocabulary lacks and fuzzy=True did not replace still takes ONE of
+    those MSR_MAX_QUERY_TERMS places -- the engine packs it as a term of its own and refuses a query of more); ONE
+    DeviceEngine.wildcard_terms call per chunk of queries.  patterns=: per query a list of further pattern strings, with
+    or without wildcards=True.  Patterns match the vocabulary AS INDEXED
     (lemmas, with a lemmatising tokenizer); they are never required, excluded (`+uni*` / `-uni*`: ValueError), part of a
     phrase, or corrected by fuzzy=True; hybrid mode scores the expanded terms in its lexical half and the dense stage keeps
     the embedding of the query as typed.  Each query's result is then a fuzzy.Results list whose `expansions` maps each

@@ -93,10 +93,11 @@ def expand(lookup, name_of, ids, patterns, limit):
     all when there is none.  name_of(term id) -> the term string.
     -> (ids, expansions): new id lists in which a query's expansions stand BEHIND its typed ids, in pattern order, then in
     the lookup's order -- an id the query already holds is not added twice, and appending stops when the query holds
-    MSR_MAX_QUERY_TERMS unique ids (the engine refuses more) -- and per query {pattern: {"terms": [the term strings that
-    were added or already there, in order], "total": all matches}}, with "skipped": True for a pattern that was not looked
-    up (fewer than MIN_LITERALS literal code points, or not encodable: "terms" [] and "total" 0) and "truncated": True where
-    the cut at MSR_MAX_QUERY_TERMS left matches out.  The inputs are not modified."""
+    MSR_MAX_QUERY_TERMS unique ids (the engine refuses more; the unknown id -1 is one of them, as DeviceEngine.pack_queries
+    counts it) -- and per query {pattern: {"terms": [the term strings that were added or already there, in order], "total":
+    all matches}}, with "skipped": True for a pattern that was not looked up (fewer than MIN_LITERALS literal code points,
+    or not encodable: "terms" [] and "total" 0) and "truncated": True where the cut at MSR_MAX_QUERY_TERMS left matches
+    out.  The inputs are not modified."""
     limit = int(limit)
     Q = len(ids)
     pats = [[str(p).lower() for p in (patterns[q] or ())] if patterns is not None else [] for q in range(Q)]

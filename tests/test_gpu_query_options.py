@@ -1,5 +1,6 @@
 """The query options all at once, through the public API only: a batch equals its queries one by one, and chunking the
-final lists changes nothing.  No reference implementation: each side of an equality is the engine's own answer."""
+final lists changes nothing.  No reference implementation here: each side of an equality is the engine's own answer (the
+options against a CPU oracle: test_gpu_options_oracle.py)."""
 import numpy as np
 import pytest
 import torch
@@ -10,30 +11,12 @@ from msretr.index_build import attach_tokens
 from msretr.retriever import Retriever
 from msretr.synthetic import synthetic_corpus
 from msretr.text import Near, preprocess_query, simple_tokenize
+from options_cases import _streams, _word
 
 pytestmark = pytest.mark.gpu
 
 N_DOCS = 2000
 HOSTS = ["uni-tuebingen.de", "www.tuebingen.de", "tuebingen.de", "example.org"] + [f"s{i}.example.net" for i in range(40)]
-
-
-def _word(t):
-    s, t = "", int(t)
-    while True:
-        s = chr(ord("a") + t % 26) + s
-        t //= 26
-        if t == 0:
-            return "w" + s
-
-
-def _streams(ix):
-    """A forward index that agrees with the postings: every document's terms ascending, each tf times."""
-    off, doc, tf = _np(ix.term_off).astype(np.int64), _np(ix.post_doc).astype(np.int64), _np(ix.post_tf).astype(np.int64)
-    term = np.repeat(np.arange(len(off) - 1), np.diff(off))
-    order = np.lexsort((term, doc))
-    tok = np.repeat(term[order], tf[order]).astype(np.int32)
-    lens = np.bincount(doc, weights=tf, minlength=ix.n_docs).astype(np.int64)
-    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64), tok
 
 
 @pytest.fixture(scope="module")
