@@ -15,6 +15,7 @@ from . import wildcard as _wildcard
 from .engine import DeviceEngine
 from .index import CorpusIndex
 from .query import Conditions, SearchOptions, parse_queries
+from .serial import serialised
 from .text import simple_tokenize
 
 
@@ -29,6 +30,7 @@ class BM25:
         self._tokenize = tokenizer or simple_tokenize
         self.attach(self.engine.index)
 
+    @serialised
     def attach(self, index: CorpusIndex):
         """Point the facade at the index its engine now serves (DeviceEngine.rebind)."""
         self.index = index
@@ -50,6 +52,7 @@ class BM25:
         """fuzzy.correct's lookup: per word the id of its first candidate or -1 (ONE DeviceEngine.fuzzy_terms call)."""
         return [c[0][0] if c else -1 for c, _ in self.engine.fuzzy_terms(words, limit=1)]
 
+    @serialised
     def fuzzy_terms(self, words, limit=5):
         """Which vocabulary words are near these?  -> per word a list of (term, distance, doc_freq), nearest first (distance,
         then document frequency descending), at most `limit` of them, within the AUTO tolerance of the word's length (0 edits
@@ -61,6 +64,7 @@ class BM25:
         df = np.diff(_np(self.index.term_off).astype(np.int64))
         return [[(self._name_of(t), d, int(df[t])) for t, d in cands] for cands, _ in self.engine.fuzzy_terms(list(words), limit=limit)]
 
+    @serialised
     def wildcard_terms(self, patterns, limit=8):
         """Which vocabulary words does each pattern match (`*` any run of code points, `?` exactly one, anchored at both
         ends)?  -> per pattern ([(term, doc_freq), ...], total): the most frequent first (then the smaller term id), at most
@@ -76,9 +80,11 @@ class BM25:
         return [([(self._name_of(t), int(df[t])) for t in terms], total) for terms, total in got]
 
     # -- engine-level entry points (usable without spaCy: pre-tokenised terms or term ids) ----------
+    @serialised
     def search_terms(self, terms: Sequence[Union[str, int]], top_k: int = 1000, min_score: float = 0.0, within=None):
         return self.search_terms_batch([terms], top_k, min_score, within=within)[0]
 
+    @serialised
     def search_terms_batch(self, term_lists, top_k: int = 1000, min_score: float = 0.0, within=None):
         """-> per query: list of (doc_id, score) in rank order (before the urlsDB join).  within: None, a DocSet (every query)
         or a list of DocSet / None per query -- the top_k of the documents in the set (docset.py)."""
@@ -90,6 +96,7 @@ class BM25:
         return [[(int(doc_ids[d]), float(s)) for d, s in zip(doc[q, :n[q]], score[q, :n[q]])] for q in range(len(ids))]
 
     # -- BM25 scores of named documents (msr_bm25_score_docs) -----------------------------------------
+    @serialised
     def score_terms(self, terms: Sequence[Union[str, int]], doc_ids):
         """-> [(doc_id, score, matched)] in the order of doc_ids: the BM25 score search_terms gives (query, document) -- also
         for documents outside its top_k or below its min_score -- and whether the document holds any of the terms (False:
@@ -109,11 +116,13 @@ class BM25:
         score, touched = score.cpu().numpy()[0], touched.cpu().numpy()[0]
         return [(int(d), float(s), bool(t)) for d, s, t in zip(ids, score, touched)]
 
+    @serialised
     def score_docs(self, query: str, doc_ids):
         """score_terms for a query string (tokenised like search)."""
         return self.score_terms(self._tokenize(query), doc_ids)
 
     # -- the reference's method ------------------------------------------------------------------------
+    @serialised
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
                must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None,
                proximity: bool = False, fuzzy: bool = False, wildcards: bool = False, max_expansions: int = 8, patterns=None):

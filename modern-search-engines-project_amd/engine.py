@@ -5,6 +5,7 @@ a HIP kernel in csrc/ reached through the C ABI (include/msretr.h).  There is no
 or without the built library, construction raises.
 """
 import ctypes as C
+import threading
 
 import numpy as np
 import torch
@@ -56,6 +57,9 @@ def stream_to_device(arr, device, block_bytes=128 << 20):
 
 
 class DeviceEngine:
+    """Single-threaded: its methods take no lock.  `lock` (an RLock that lives as long as the engine, rebind included) is what
+    the facades hold for a whole request (serial.py)."""
+
     def __init__(self, index: CorpusIndex, device=0, max_queries=32, max_k=1000, rerank_max_docs=1000,
                  scan_layout=0, scan_variant=0, row_copy=True, single_emit=False):
         """row_copy=False: MSR_CFG_NO_ROW_COPY -- the 256-query pass reads the row-major matrix instead of an engine-owned
@@ -65,6 +69,7 @@ class DeviceEngine:
         if not torch.cuda.is_available():
             raise _abi.MsrError(-102, "no GPU visible: the retrieval path runs on MI355X only (no CPU fallback)")
         self.lib = _abi.load()
+        self.lock = threading.RLock()
         self.index = index
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         self.max_k = int(max_k)

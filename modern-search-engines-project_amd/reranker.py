@@ -14,6 +14,7 @@ import numpy as np
 
 from .engine import RERANK_DEFAULTS, DeviceEngine
 from .index import CorpusIndex
+from .serial import serialised
 from .text import extract_domain
 
 SIMILARITY_DEFAULTS = dict(batch_size=32, smoothing=0.15, diversification=True, top_k=100)   # reranker/config.yaml:25-30
@@ -69,6 +70,7 @@ class Reranker:
         self.encoder = encoder
         self.attach(self.engine.index)
 
+    @serialised
     def attach(self, index: CorpusIndex):
         """Point the facade (and its id maps) at the index its engine now serves (DeviceEngine.rebind)."""
         self.index = index
@@ -88,6 +90,7 @@ class Reranker:
         enc = self.encoder.encode if hasattr(self.encoder, "encode") else self.encoder
         return np.asarray(enc(query), np.float32)
 
+    @serialised
     def rerank_batch(self, requests: Sequence[dict]):
         """requests: dicts with doc_ids, similarities, query / query_embedding.  One GPU call for all."""
         M = self.engine.rerank_max_docs
@@ -119,6 +122,7 @@ class Reranker:
         out = [x.cpu().numpy() for x in self.engine.rerank(qv, cand, bm, n, **p)]
         return [self._response(r, out) for r in range(Q)]
 
+    @serialised
     def rerank(self, doc_ids: List[str], similarities: Optional[List[float]] = None, query: Optional[str] = None,
                query_embedding=None) -> dict:
         return self.rerank_batch([dict(doc_ids=doc_ids, similarities=similarities, query=query,

@@ -21,6 +21,7 @@ from .engine import DeviceEngine
 from .index import CorpusIndex
 from .query import Conditions, SearchOptions, parse_queries
 from .reranker import Reranker
+from .serial import serialised
 from .snippets import SNIPPET_TOKENS, query_row, render, term_weights
 from .text import LineFormatter, extract_domain, extract_domain_topic, format_result_line, preprocess_query, read_queries_file
 
@@ -75,12 +76,14 @@ class Retriever:
             gc.collect()
             gc.freeze()
 
+    @serialised
     def update_index(self, ix: CorpusIndex):
         """Serve `ix` from now on (an index grown by index_build.bm25_add_token_ids + chunk_index.attach_chunks, shrunk by
         index_build.remove_documents, or both -- a replace): the engine
         rebinds (DeviceEngine.rebind), and everything copied from the old index is refreshed -- the id map, the domain table,
         the line formatter, the per-chunk engine of return_unique_docs=False (closed; rebuilt on first use), the BM25 and
-        Reranker facades."""
+        Reranker facades.  Under the engine's lock (serial.py): a request of another thread sees the old index or the new one,
+        whole."""
         ce = getattr(self, "_chunk_engine", None)
         if ce is not None:
             ce.close()
@@ -115,6 +118,7 @@ class Retriever:
         return np.asarray(enc(query), np.float32)
 
     # ------------------------------------------------------------------ dense full scan
+    @serialised
     def quick_search_batch(self, queries=None, top_k=10, return_unique_docs=True, query_embeddings=None,
                            max_chunks_per_doc=0, within=None):
         """within: None, a DocSet of this index (every query) or a list of DocSet / None per query: the dense top_k of the
@@ -190,6 +194,7 @@ class Retriever:
                                     DocSet.from_mask(view, np.repeat(ds.mask, np.diff(self._chunk_doc_off))))
         return got[1]
 
+    @serialised
     def quick_search(self, query=None, top_k=10, return_unique_docs=True, query_embedding=None, max_chunks_per_doc=0,
                      within=None):
         return self.quick_search_batch([query], top_k, return_unique_docs,
@@ -197,6 +202,7 @@ class Retriever:
                                        within=None if within is None else [within])[0]
 
     # ------------------------------------------------------------------ similar documents (msr_dense_topk_grouped)
+    @serialised
     def similar_batch(self, groups, top_k=10, max_source_chunks=RERANK_MAX_CHUNKS, within=None, min_score=None):
         """Documents like the given ones, one ranked list per group, in ONE engine call.  groups: per entry one doc_id or a list
         of doc_ids (the sources).  Each source contributes its first max_source_chunks chunk rows (0 = all; the default 10 is
@@ -243,6 +249,7 @@ class Retriever:
             out.append(res)
         return out
 
+    @serialised
     def similar(self, doc_ids, top_k=10, max_source_chunks=RERANK_MAX_CHUNKS, within=None, min_score=None):
         """The documents most similar to doc_ids (one id or a list): similar_batch with one group."""
         return self.similar_batch([doc_ids], top_k, max_source_chunks, within=None if within is None else [within],
@@ -465,6 +472,7 @@ class Retriever:
             n = int(d_n[q])
             dedup["drops"].append(np.stack([d_doc[q, :n], d_lead[q, :n], d_m[q, :n]], axis=1).astype(np.int32))
 
+    @serialised
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
                           must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None,
@@ -497,7 +505,11 @@ class Retriever:
         {...}}) and wildcards["ids"] (the term ids that were scored).  Like fuzzy, the answer comes back before the chunk is
         enqueued; same refusal of prepare=.
         facets: None, or a dict {"by": "host" | "domain", "limit": 1 .. 64}.  The generator fills facets["hits"],
-        ["n_values_hit"], ["top_value"], ["top_count"] (per query) and ["names"] (the key's value names)."""
+        ["n_values_hit"], ["top_value"], ["top_count"] (per query) and ["names"] (the key's value names).
+        Threads: the generator holds the engine's lock (serial.py) from its first next() to exhaustion, close() or an
+        exception -- also while the caller works between two chunks: the pinned buffers, the facet table and the index
+        belong to this call until then, so no other request can read or overwrite a chunk's rows.  Finish or close it on the
+        thread that started it (the lock is that thread's), and soon: every other request on this engine waits."""
         opts = SearchOptions(mode, dense_k, operators, phrases, proximity)
         cond = Conditions(must, must_not, must_phrases, must_not_phrases)
         yield from self._chunks(term_id_lists, query_vectors, top_k, chunk, prepare, n_queries, within, opts, cond, fuzzy, wildcards,
@@ -583,6 +595,7 @@ class Retriever:
             cls._collect_drops(job, dedup)
         return out if len(job) == 5 or job[5] is None else out + (cls._collect_source(job, out[0], out[3]),)
 
+    @serialised
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
                     must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None, facets=None):
@@ -684,6 +697,7 @@ class Retriever:
             got[q, r] = (snippet, highlights, [w for j, w in enumerate(names[q]) if not int(terms[i]) >> j & 1])
         return got, names
 
+    @serialised
     def search_batch(self, queries, top_k=TOP_K_RETRIEVAL, query_embeddings=None, term_lists=None, query_ids=None, within=None,
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
                      must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS,
@@ -754,6 +768,7 @@ class Retriever:
                                              "similarity": m / 64.0})
         return led
 
+    @serialised
     def search(self, query, top_k=TOP_K_RETRIEVAL, query_embedding=None, terms=None, query_id=None, within=None,
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
@@ -766,6 +781,7 @@ class Retriever:
         return self._search([query], top_k, one(query_embedding), one(terms), one(query_id), within, opts,
                             Conditions(one(must), one(must_not), one(must_phrases), one(must_not_phrases)), one(patterns))[0]
 
+    @serialised
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                      must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
@@ -804,12 +820,14 @@ class Retriever:
             lines.passages, lines.row_names = self._snippets(self._scored_ids(ids, fz, wc), doc, n, snippet_tokens)
         return lines
 
+    @serialised
     def batch_search_to_file(self, queries_path, out_path, query_embeddings=None, term_lists=None, chunk=None):
         """search_api.py:331-367: queries.txt -> one formatted line per result in out_path; -> number of lines.  (Quotes and
         signs in the file's queries are punctuation here: no operators, no phrases.)  Three things
         run side by side, chunk by chunk: this thread preprocesses / tokenises chunk i + 1 and enqueues it, the GPU ranks
         chunk i, a second host thread waits for chunk i - 1's final rows, formats them (native code, outside the interpreter
-        lock) and writes them."""
+        lock) and writes them.  Threads: this thread holds the engine's lock until the second one has drained; the second
+        one only waits on events and formats, and takes no lock."""
         import sys
         nq = read_queries_file(queries_path)
         if self._formatter is None:
@@ -833,11 +851,12 @@ class Retriever:
     def _batch_to_file(self, nq, texts, nums, sub, step, out_path, query_embeddings, term_lists):
         from concurrent.futures import ThreadPoolExecutor
         import torch
-        eng = self.engine
+        eng, fmt = self.engine, self._formatter
         with open(out_path, "wb") as f, ThreadPoolExecutor(max_workers=1) as pool:
             def consume(a, job):
                 doc, score, _, n = self._collect_chunk(job)
-                f.write(self._formatter.format(nums[a:a + len(n)], doc, score, n))
+                with fmt.lock:                                # (a BatchLines of an earlier request may be formatting with it)
+                    f.write(fmt.format(nums[a:a + len(n)], doc, score, n))
                 return int(n.sum())
             futs = []
             for i, a in enumerate(range(0, len(nq), step)):
@@ -899,9 +918,11 @@ class BatchLines:
         return list(self) == list(other)
 
     def text(self) -> bytes:
-        """All formatted lines, each ending in a newline (UTF-8)."""
-        return self._fmt.format(self.query_nums, self.doc, self.score, self.n)
+        """All formatted lines, each ending in a newline (UTF-8).  A copy: the formatter's buffer is the retriever's, and
+        these lines outlive their request."""
+        with self._fmt.lock:
+            return bytes(self._fmt.format(self.query_nums, self.doc, self.score, self.n))
 
     def write(self, path):
-        with open(path, "wb") as f:
-            f.write(self.text())
+        with open(path, "wb") as f, self._fmt.lock:
+            f.write(self._fmt.format(self.query_nums, self.doc, self.score, self.n))

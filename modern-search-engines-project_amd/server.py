@@ -19,6 +19,9 @@ Requests may carry `query_embedding` (768 floats) and `terms` (pre-tokenised que
 keep the encoder / spaCy in another process.  /api/search also takes `sites` (a list of domains): results only from
 documents whose URL's host is one of them or a subdomain (a `site:` search; docset.DocSet.from_sites, restricted inside
 the BM25 stage; the sets of the last `site_cache_size` distinct site lists are kept).  The response shape does not change.
+Threads: the routes are plain `def` (FastAPI runs them on a thread pool) and the engine is single-threaded; the retriever's
+public methods run under the engine's lock (serial.py), and a route that reads the retriever more than once holds the same
+lock around all of it.  /api/batch_search_file writes a temporary file and renames it over results_file.
 """
 import uuid
 from typing import List, Optional, Union
@@ -26,6 +29,7 @@ from typing import List, Optional, Union
 import numpy as np
 
 from .reranker import RerankNotFound
+from .serial import lock_of
 from .text import extract_domain_topic, preprocess_query, read_queries_file
 
 LLM_MAX_WINDOWS = 10          # config.py:22
@@ -116,6 +120,18 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
 
     app.state.site_sets = site_sets
 
+    # Routes run on a thread pool and the engine is single-threaded: the facades take the engine's lock per call (serial.py).
+    # A route that reads more than one thing of the retriever (the index for the site set, then the search) takes the same
+    # re-entrant lock around all of it, so that an update_index falls before or after the request.  Order: the engine's lock
+    # first, the site cache's inside it -- never the other way round.  (A retriever without a lock gets the app's own.)
+    app_lock = threading.RLock()
+
+    def engine_lock():
+        try:
+            return lock_of(retriever)
+        except AttributeError:
+            return app_lock
+
     @app.post("/rerank")
     def rerank(req: RerankRequest):
         try:
@@ -135,7 +151,7 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             if req.mode not in ("lexical", "hybrid"):
                 return JSONResponse(status_code=400, content={"error": "mode must be 'lexical' or 'hybrid'"})
             qid = req.query_id or uuid.uuid4().hex
-            kw = {} if req.sites is None else {"within": within_sites(req.sites)}
+            kw = {}
             specs = [p for ps in (req.must_phrases, req.must_not_phrases) for p in ps or () if isinstance(p, NearSpec)]
             wild = req.wildcards or req.patterns is not None
             near = req.proximity or bool(specs)      # a proximity condition the engine cannot hold is the caller's error: 400
@@ -158,8 +174,11 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                     for name in ("must_phrases", "must_not_phrases"):
                         if kw[name] is not None:
                             kw[name] = [Near(p.phrase, p.slop, p.ordered) if isinstance(p, NearSpec) else p for p in kw[name]]
-                docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
-                                        terms=req.terms, query_id=qid, **kw)
+                with engine_lock():                           # the site set and the search: of ONE index
+                    if req.sites is not None:
+                        kw["within"] = within_sites(req.sites)
+                    docs = retriever.search(req.query, top_k=req.top_k, query_embedding=req.query_embedding,
+                                            terms=req.terms, query_id=qid, **kw)
             except ValueError as e:
                 if not any(on and bad_request for on, _, bad_request in features):
                     raise
@@ -197,16 +216,17 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                 ids = [int(d) for d in ids]
             except (TypeError, ValueError):
                 return JSONResponse(status_code=400, content={"error": "doc_ids must be integers"})
-            within = None if req.sites is None else within_sites(req.sites)
-            try:
-                rows = retriever.similar(ids, top_k=req.top_k, within=within, min_score=req.min_score)
-            except LookupError as e:
-                return JSONResponse(status_code=404, content={"error": str(e)})
-            ix = retriever.index
+            with engine_lock():                               # the site set, the search and the texts: of ONE index
+                within = None if req.sites is None else within_sites(req.sites)
+                try:
+                    rows = retriever.similar(ids, top_k=req.top_k, within=within, min_score=req.min_score)
+                except LookupError as e:
+                    return JSONResponse(status_code=404, content={"error": str(e)})
+                ix = retriever.index
+                texts = [_doc_text(ix, r["doc_id"]) for r in rows]
             docs = []
-            for r in rows:
+            for r, text in zip(rows, texts):
                 url = r["url"] or ""
-                text = _doc_text(ix, r["doc_id"])
                 docs.append({"query_id": None, "rank": r["rank"], "url": url, "score": r["score"],
                              "title": r["title"] or "No Title",
                              "snippet": (text[:200] + "..." if len(text) > 200 else text) or "No content available",
@@ -252,12 +272,22 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
             if status != 200:
                 return JSONResponse(status_code=status, content=body)
             lines = body.get("_lines")
-            if hasattr(lines, "write"):                       # Retriever.batch_search: all lines formatted natively in one call
-                lines.write(results_file)
-            else:
-                with open(results_file, "w", encoding="utf-8") as f:
-                    for r in body["results"]:
-                        f.write(r["formatted_line"] + "\n")
+            # into a temporary file beside the target, then renamed over it: two requests at once leave one request's lines,
+            # and a reader sees a complete file or none
+            path = os.fspath(results_file)
+            tmp = f"{path}.{uuid.uuid4().hex}.tmp"
+            try:
+                if hasattr(lines, "write"):                   # Retriever.batch_search: all lines formatted natively in one call
+                    lines.write(tmp)
+                else:
+                    with open(tmp, "w", encoding="utf-8") as f:
+                        for r in body["results"]:
+                            f.write(r["formatted_line"] + "\n")
+                os.replace(tmp, path)
+            except BaseException:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+                raise
             return {"message": f"Results saved to {results_file}", "total_queries": body["total_queries"],
                     "total_results": body["total_results"], "output_file": str(results_file),
                     "format": "query_num<tab>rank<tab>url<tab>score per line"}

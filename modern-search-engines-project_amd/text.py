@@ -5,6 +5,7 @@ Mirrors, by behaviour, /root/reference/search_api.py:155-166 (preprocess_query),
 (create_sliding_windows) and the batch line format of search_api.py:290.
 """
 import re
+import threading
 from urllib.parse import urlparse
 
 from ._abi import MSR_PHRASE_MAX_TERMS, MSR_PROX_MAX_SPAN
@@ -251,10 +252,13 @@ class LineFormatter:
         self.n_docs = n
         self.max_url = int(np.diff(self.off).max()) if n else 0
         self._buf = self._cbuf = None
+        self.lock = threading.Lock()
 
     def format(self, query_nums, doc, score, n):
         """query_nums: list of str; doc int32 [Q, S], score float64 [Q, S], n int32 [Q] (host arrays) -> the lines as a
-        bytes-like view of the formatter's own buffer (valid until the next call; bytes(...) for a copy)."""
+        bytes-like view of the formatter's own buffer (valid until the next call; bytes(...) for a copy).  A formatter that
+        several threads share (a Retriever's, which its BatchLines keep after their request) is called, and its view used,
+        under `lock`."""
         import ctypes as C
 
         import numpy as np
