@@ -2,8 +2,9 @@
 //
 // Replaces the per-query SQL fetch + Python grouping + scoring loop of the reference
 // (indexer/bm25_indexer.py:434-481).  The dense doc index is cut into tiles of TILE documents; a WAVE scores one query
-// over a span of up to 8 consecutive tiles, with its own float64 accumulators (one per document of the current tile) and
-// the list of the documents it has touched in LDS.  Waves are independent: no workgroup barrier anywhere.
+// over a span of up to 8 consecutive tiles in ONE pass: it marks the span's touched documents in an LDS bitmap, ranks them,
+// and accumulates in float64 slots indexed by a document's RANK among the touched documents of the span -- a few hundred
+// slots cover 8192 documents.  Waves are independent: no workgroup barrier anywhere.
 //
 // What is streamed and what is looked up.  A posting is read as {doc, tf_component} (12 bytes): the tf_component
 // (tf (k1 + 1)) / (tf + k1 (1 - b + b dl / avgdl)) (:473-475) depends on (tf, document) only and is evaluated ONCE at bind
@@ -17,19 +18,26 @@
 // term without a table, every list is streamed; the result is the same either way, bit for bit.
 //
 // Summation order.  The reference adds the contributions of a document's terms in the query's first-occurrence order
-// (:466-478) in float64.  A wave walks its query's terms in that order:
-//   streamed term j: for each posting of the tile, acc[doc] += (idf * tfc) * qtf as an LDS read-modify-write (a wave's LDS
-//     operations execute in order; a document occurs at most once per list, PRIMARY KEY (doc_id, term) :100-104, so no
-//     atomics).  A document touched for the FIRST time starts from 0.0 plus the looked-up contributions of the negative
-//     terms BEFORE j, in order, and is appended to the wave's list;
-//   looked-up term i: for each document on the list so far, acc[doc] += (idf * table_i[doc]) * qtf if the table has it.
+// (:466-478) in float64.  Every slot starts at 0.0 (:466) and the wave walks its query's terms in that order:
+//   streamed term j: for each posting of the span, acc[rank] += (idf * tfc) * qtf as an LDS read-modify-write (a wave's
+//     LDS operations execute in order; a document occurs at most once per list, PRIMARY KEY (doc_id, term) :100-104, so
+//     the lanes of a step hold distinct slots: no atomics);
+//   looked-up term i: for every slot, acc[rank] += (idf * table_i[document of the slot]) * qtf if the table has it.
 // So every candidate's sum is the reference's sum operation by operation; this file is compiled with -ffp-contract=off.
-// At the end of a tile the list is what is emitted (score >= min_score, :480) and what is reset -- there is no pass over
-// all TILE accumulators.
 //
-// The plan (where each term's slices are: skip-table row segment for long lists, the whole list for <= 64 postings, ONE
-// round of 64 probes for the lists in between) is built once per span, lane-parallel (lane j = term j); the loads of
-// tile t + 1 are issued before tile t is accumulated (two register sets).
+// Phases of a (query, span) wave, each over the WHOLE span with all its loads in flight:
+//   plan    where each term's slice of the span is: the two ends of a skip-table row segment for long lists, the whole list
+//           for <= 64 postings, ONE round of 64 probes for the lists in between; lane-parallel (lane j = term j);
+//   load    the slices in chunks of 64 postings; the first BM25_RES chunks stay in registers, a span with more re-reads the
+//           rest in each later phase;
+//   mark    one bit per document (LDS atomic OR);   rank  pre[w] = touched documents below bitmap word w (one wave scan),
+//           rank(d) = pre[d / 32] + popcount(bits of the word below d), slot[rank] = d: the slots are in document order;
+//   gather  the table values of the looked-up terms need only slot[]: issued here, ahead of the accumulation;
+//   accumulate in query order, as above;   emit  the slots with score >= min_score (:480), ballot-compacted.
+// Rounds: there are MSR_BM25_ROUND_CAP slots.  A span that touches more (min_score < 0, untabled negative lists, dense
+// positive lists) runs rank .. emit in rounds over consecutive whole bitmap words; a word joins the round while the touched
+// count up to its end fits, so every rank is below the cap by construction.  One round is the common case and pays only
+// wave-uniform branches for the general one.
 //
 // Output: the candidates of a (query, span) go to a segment of the query's candidate row that belongs to that wave alone
 // -- no atomics, no counters to clear; the top-k select (msr_topk.hip) walks the segments.
@@ -37,8 +45,6 @@
 // HBM traffic per query: 12 B per posting of its streamed terms + 8 B per (touched document, looked-up term) from tables
 // that stay in the L2 / Infinity Cache + 12 B per candidate (the (score, doc) list consumed by the top-k select).
 #include <stdio.h>
-
-#include <type_traits>
 
 #include "msr_common.h"
 #include "msr_internal.h"
@@ -49,11 +55,29 @@ constexpr int BM25_TILE = MSR_BM25_TILE;
 #ifndef BM25_WPW
 #define BM25_WPW 1                                             // one-wave workgroups: work items differ by an order of magnitude (a long
 #endif                                                         // positive list or not) and a workgroup holds its LDS until its slowest
-constexpr int BM25_WAVES = BM25_WPW;                          // wave is done (measured: 1 wave 0.18 ms, 2 waves 0.21, 4 waves 0.23)
+constexpr int BM25_WAVES = BM25_WPW;                          // wave is done (measured per 256 queries: 1 wave 0.23 ms, 2 waves 0.32)
 constexpr int BM25_THREADS = 64 * BM25_WAVES;
 constexpr int BM25_TPW = 8;                                   // at most this many consecutive tiles per work item
 constexpr int BM25_MAX_TERMS = 64;                            // MSR_MAX_QUERY_TERMS: one lane per term
-constexpr uint64_t UNTOUCHED = 0x7FF8DEADBEEF0001ull;   // a quiet-NaN payload no computation produces
+constexpr int BM25_CAP = MSR_BM25_ROUND_CAP;                  // rank-indexed accumulators: the touched documents of one round
+constexpr int BM25_RES = 4;                                   // R: 64-posting chunks of a span held in registers (measured, per 256
+                                                              // queries: R = 4 0.19 ms, 6 0.20, 8 0.20, 12 0.29 with scratch)
+#ifndef BM25_U
+#define BM25_U 4                                               // chunks per step of the postings beyond the resident ones (8: 0.20-0.23)
+#endif
+#ifndef BM25_UM
+#define BM25_UM 8                                              // the same in the mark phase, which reads the documents only (4, 8
+#endif                                                         // and 16 measure the same)
+constexpr int BM25_WORDS = BM25_TPW * BM25_TILE / 32;         // the span's bitmap: one bit per document
+static_assert(BM25_WORDS == 4 * 64, "four bitmap words per lane");
+static_assert(BM25_CAP % 128 == 0 && BM25_CAP >= 128 && BM25_CAP <= BM25_TILE, "whole batches of slots; a word (32) always fits");
+
+// Between two phases of a wave that hand values from lane to lane through LDS: a wave's LDS operations execute in order, so
+// this emits no instruction; it only keeps the compiler from moving LDS accesses across the phase boundary.
+__device__ __forceinline__ void lds_phase() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 __device__ __forceinline__ int64_t lane_i64(int64_t v, int j) {          // v of lane j (j wave-uniform)
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, j);
@@ -77,10 +101,10 @@ __device__ __forceinline__ gtable table_of(int64_t bits) { return (gtable)(uint6
 enum : int { K_DEAD = 0, K_LOOKUP = 1, K_HEAVY = 2, K_RANGE = 3 };
 
 #ifndef BM25_WPE
-#define BM25_WPE 4                                             // waves per SIMD the register budget is cut for
-#endif
+#define BM25_WPE 4                                             // waves per SIMD the register budget is cut for (5 and 6, with a cap
+#endif                                                         // of 640 / 512 and no scratch, measure within 3 % of 4)
 // Set: empty (the unrestricted kernel) or one MsrSetView (msr_bm25_topk_within): a touched document outside the query's set is
-// not emitted.  Only the emission at the end of a tile differs; the scores are the same operations either way.
+// not emitted.  Only the emission at the end of a round differs; the scores are the same operations either way.
 template <typename... Set>
 __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM25_WPE, BM25_WPE))) void bm25_taat_kernel(Bm25Index ix,
                                                                   const int32_t* __restrict__ q_term_off,
@@ -91,13 +115,16 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
                                                                   int32_t* __restrict__ cand_doc,
                                                                   int32_t* __restrict__ seg_n, int dbg_arg, Set... set) {
 #ifdef MSR_DIAG
-    const int dbg = dbg_arg;   // timing experiments (wrong results): 1 no table lookups, 2 no accumulator update, 4 no streaming
-                               // beyond the prefetch, 8 no prefetch, 16 no emission, 64 stream every list (no pruning)
+    const int dbg = dbg_arg;   // timing experiments (wrong results): 1 no table gathers, 2 no accumulation of streamed postings,
+                               // 4 nothing read beyond the resident chunks, 16 no emission, 64 stream every list (no pruning);
+                               // 8 (the parent's "no prefetch") is retired: the resident chunks are the only first read there is
 #else
     constexpr int dbg = 0;
 #endif
-    __shared__ double acc_all[BM25_WAVES][BM25_TILE];
-    __shared__ uint16_t list_all[BM25_WAVES][BM25_TILE];
+    __shared__ __attribute__((aligned(16))) double acc_all[BM25_WAVES][BM25_CAP];      // by rank inside the round
+    __shared__ __attribute__((aligned(16))) uint32_t bits_all[BM25_WAVES][BM25_WORDS];   // one bit per document of the span
+    __shared__ uint16_t pre_all[BM25_WAVES][BM25_WORDS];                               // touched documents below each word
+    __shared__ uint16_t slot_all[BM25_WAVES][BM25_CAP];                                // rank -> document (span-relative)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // work item = (query, span of tiles), the query running fastest: the waves of a workgroup and of its neighbours score the
@@ -122,23 +149,22 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
     const int tile0 = span * tpw;                              // this wave's tiles: tile0 .. tile0 + n_my - 1
     const int n_my = tile0 + tpw <= ix.n_tiles ? tpw : ix.n_tiles - tile0;
     double* acc = acc_all[wave];
-    uint16_t* list = list_all[wave];
-    {   // every accumulator starts untouched; a tile resets exactly the ones it touched
-        const double un = __longlong_as_double((long long)UNTOUCHED);
-#pragma unroll
-        for (int u = 0; u < BM25_TILE / 128; ++u) ((double2*)acc)[lane + 64 * u] = make_double2(un, un);
-    }
+    uint32_t* bits = bits_all[wave];
+    uint16_t* pre = pre_all[wave];
+    uint16_t* slot = slot_all[wave];
+    // the span's documents: [lo_span, lo_span + n_span), n_span <= 8192
+    const int64_t lo_span = (int64_t)tile0 * BM25_TILE;
+    const int64_t hi_span = lo_span + (int64_t)n_my * BM25_TILE < ix.n_docs ? lo_span + (int64_t)n_my * BM25_TILE : ix.n_docs;
+    const uint32_t n_span = (uint32_t)(hi_span - lo_span);
     // a negative term's list need not be streamed when nothing below 0 can be a candidate (:480)
     const bool prune = min_score >= 0.0 && ix.dense_id != nullptr && !(dbg & 64);
-    // ---- 1. the query's plan, ONCE for all tiles of the span; lane j = term j ----
+    // ---- 1. the query's plan, ONCE for the span; lane j = term j ----
     int nt = 0, klass = K_DEAD;
     int64_t s_v = 0;                                 // long list: its first posting; looked-up term: its table row
-    uint32_t off_v[BM25_TPW + 1];                    // long list: where each of the span's tiles starts inside it
-    int64_t r0_v = 0, r1_v = 0;                      // other lists: the postings to look at, for EVERY tile of the span
+    int h_v = -1;                                    // long list: its row of the skip table
+    int64_t ps_v = 0, pe_v = 0;                      // streamed list: the postings to look at for the whole span
     double idf_v = 0.0, qtf_v = 0.0;
     bool medium = false;
-#pragma unroll
-    for (int i = 0; i <= BM25_TPW; ++i) off_v[i] = 0;
     {
         const int t0 = q_term_off[q_first + q];
         nt = q_term_off[q_first + q + 1] - t0;
@@ -155,16 +181,17 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
                     if (dh >= 0 && idf_v < 0.0 && qtf_v > 0.0) {   // every contribution < 0: looked up, never streamed
                         klass = K_LOOKUP;
                         s_v = (int64_t)(ix.dense_comp + (int64_t)dh * ix.dense_stride);
-                    } else if (h >= 0) {                     // long list: the slices come from the skip table, one row
-                        klass = K_HEAVY;                     // segment for all the span's tiles
+                    } else if (h >= 0) {                     // long list: the span's slice comes from the skip table, the
+                        klass = K_HEAVY;                     // two ends of one row segment
                         s_v = s;
+                        h_v = h;
                         const uint32_t* row = ix.tile_off + (int64_t)h * (ix.n_tiles + 1) + tile0;
-#pragma unroll
-                        for (int i = 0; i <= BM25_TPW; ++i) off_v[i] = row[i < n_my ? i : n_my];
+                        ps_v = s + row[0];
+                        pe_v = s + row[n_my];
                     } else {
                         klass = K_RANGE;
-                        r0_v = s;                            // short list: all of it (postings of other tiles are masked)
-                        r1_v = e;
+                        ps_v = s;                            // short list: all of it (postings of other spans are masked)
+                        pe_v = e;
                         medium = e - s > 64;
                     }
                 }
@@ -177,12 +204,11 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
         if (lane == 0) *seg_len = 0;
         return;
     }
-    const int64_t seg_base = (int64_t)q * ix.n_docs + (int64_t)tile0 * BM25_TILE;
-    // ---- 2. lists of 65 .. HEAVY_DF-1 postings: one round of 64 probes narrows [r0, r1) to the chunks that can hold
-    //         documents of the span's tiles; MED lists side by side (the probes are independent loads) ----
+    const int64_t seg_base = (int64_t)q * ix.n_docs + lo_span;
+    // ---- 2. lists of 65 .. HEAVY_DF-1 postings: one round of 64 probes narrows [ps, pe) to the chunks that can hold
+    //         documents of the span; MED lists side by side (the probes are independent loads) ----
     {
-        const int64_t lo8 = (int64_t)tile0 * BM25_TILE;
-        const int64_t hi8 = lo8 + (int64_t)n_my * BM25_TILE < ix.n_docs ? lo8 + (int64_t)n_my * BM25_TILE : ix.n_docs;
+        const int64_t lo8 = lo_span, hi8 = hi_span;
         constexpr int MED = 4;
         unsigned long long todo = __ballot(medium);
         while (todo) {
@@ -195,8 +221,8 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
                 if (todo) todo &= todo - 1;
                 probe[m] = 0; s_[m] = e_[m] = ch_[m] = 0;
                 if (jj[m] >= 0) {                            // wave-uniform
-                    s_[m] = lane_i64(r0_v, jj[m]);
-                    e_[m] = lane_i64(r1_v, jj[m]);
+                    s_[m] = lane_i64(ps_v, jj[m]);
+                    e_[m] = lane_i64(pe_v, jj[m]);
                     ch_[m] = (e_[m] - s_[m] + 63) >> 6;
                     int64_t idx = s_[m] + (int64_t)(lane + 1) * ch_[m] - 1;     // last posting of chunk `lane`
                     if (idx > e_[m] - 1) idx = e_[m] - 1;
@@ -217,203 +243,287 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
                         if (pe > e_[m]) pe = e_[m];
                     }
                 }
-                if (lane == jj[m]) { r0_v = ps; r1_v = pe; }
+                if (lane == jj[m]) { ps_v = ps; pe_v = pe; }
             }
         }
     }
-    // the first TPRE streamed terms get their first PFC x 64 postings of a tile prefetched (for nearly all terms: the whole slice)
-    constexpr int TPRE = 4, PFC = 2;
-    int sj[TPRE];
+    // ---- 3. the span's postings.  The slices of the streamed terms, in query order, are cut into chunks of 64 postings (a
+    //         chunk belongs to one term: its lanes hold distinct documents).  The first R chunks stay in registers for the
+    //         whole item (indexed by constants only); a span with more re-reads the rest in every later phase (the L2 has
+    //         them).  All R loads are issued unconditionally, back to back: a lane without a posting, and a chunk that does
+    //         not exist, load the sentinel {doc -1, 0.0} the bind step put behind the last posting. ----
+    const int64_t null_post = ix.n_postings;
+    int cj[BM25_RES];                                          // (wave-uniform) the chunk's term, -1: no such chunk
+    int64_t cps[BM25_RES], cpe[BM25_RES];                      // its first posting, the end of its term's slice
     {
         unsigned long long m = stream_mask;
+        int j = -1;
+        int64_t pos = 0, pe = 0;
 #pragma unroll
-        for (int k = 0; k < TPRE; ++k) {
-            sj[k] = m ? __ffsll((long long)m) - 1 : -1;
-            if (m) m &= m - 1;
+        for (int k = 0; k < BM25_RES; ++k) {
+            while (pos >= pe && m) {
+                j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                pos = lane_i64(ps_v, j);
+                pe = lane_i64(pe_v, j);
+            }
+            if (pos < pe) { cj[k] = j; cps[k] = pos; cpe[k] = pe; pos += 64; }
+            else { cj[k] = -1; cps[k] = null_post; cpe[k] = null_post; }
         }
     }
-    const int j_rest = sj[TPRE - 1] >= 0 ? sj[TPRE - 1] + 1 : nt;       // terms from here on are not prefetched
-    // Two tiles are in flight per wave: the loads of tile t + 1 are issued BEFORE tile t is accumulated and emitted, into a
-    // second register set -- the pass is latency-bound, every wave hides its own memory latency behind its own arithmetic.
-    // Inside a chunk a lane without a posting loads the sentinel {doc -1, 0.0} the bind step put behind the last posting: no
-    // load sits in a divergent branch, and the loaded words are not touched before they are used.
-    const int64_t null_post = ix.n_postings;
-    struct TileRegs {
-        Bm25Post p[TPRE][PFC];                               // the first PFC x 64 postings of the first TPRE streamed slices
-        int64_t ps, pe;                                      // lane j: this tile's slice of term j
-    };
-    auto issue = [&](int tt, TileRegs& r) {
-        // the tile's slice of every list (no memory access: the plan holds everything)
-        r.ps = r0_v; r.pe = r1_v;
-        if (klass == K_HEAVY) {
-            uint32_t o0 = 0, o1 = 0;
+    if (cj[0] < 0) {                                 // no streamed term has a posting near this span
+        if (lane == 0) *seg_len = 0;
+        return;
+    }
+    Bm25Post res[BM25_RES];
 #pragma unroll
-            for (int i = 0; i < BM25_TPW; ++i)
-                if (i == tt) { o0 = off_v[i]; o1 = off_v[i + 1]; }
-            r.ps = s_v + o0;
-            r.pe = s_v + o1;
+    for (int k = 0; k < BM25_RES; ++k) {
+        const int64_t i = cps[k] + lane;
+        res[k] = ix.post[i < cpe[k] ? i : null_post];
+    }
+    int64_t rs_v = ps_v;                             // lane j: where term j's postings beyond the resident chunks start
+#pragma unroll
+    for (int k = 0; k < BM25_RES; ++k)
+        if (cj[k] >= 0 && lane == cj[k]) rs_v = cps[k] + 64 < cpe[k] ? cps[k] + 64 : cpe[k];
+    const bool has_rest = __ballot(klass >= K_HEAVY && rs_v < pe_v) != 0 && !(dbg & 4);      // (wave-uniform)
+    constexpr int U = BM25_U;
+    // ---- 4. mark: one bit per document of the span that a streamed posting names.  From here on a resident posting carries
+    //         its document relative to the span, or -1 (no posting, or a document of another span). ----
+    ((uint4*)bits)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    lds_phase();
+#pragma unroll
+    for (int k = 0; k < BM25_RES; ++k) {
+        const uint32_t d = (uint32_t)(res[k].doc - (int32_t)lo_span);
+        const bool ok = d < n_span;
+        if (ok) atomicOr(&bits[d >> 5], 1u << (d & 31));
+        res[k].doc = ok ? (int32_t)d : -1;
+    }
+    if (has_rest) {
+        // the postings [rs, pe) of every streamed term beyond the resident chunks: only their documents are read here, UM x 64
+        // per step, all loads of a step issued before the first is used
+        constexpr int UM = BM25_UM;
+        unsigned long long m = __ballot(klass >= K_HEAVY && rs_v < pe_v);
+        while (m) {
+            const int j = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int64_t a = lane_i64(rs_v, j), b = lane_i64(pe_v, j);
+            for (int64_t at = a; at < b; at += (int64_t)UM * 64) {
+                int32_t pd[UM];
+#pragma unroll
+                for (int u = 0; u < UM; ++u) {
+                    const int64_t i = at + lane + (int64_t)u * 64;
+                    pd[u] = ix.post[i < b ? i : null_post].doc;
+                }
+#pragma unroll
+                for (int u = 0; u < UM; ++u) {
+                    const uint32_t d = (uint32_t)(pd[u] - (int32_t)lo_span);
+                    if (d < n_span) atomicOr(&bits[d >> 5], 1u << (d & 31));
+                }
+            }
         }
+    }
+    lds_phase();
+    // ---- 5. pre[w] = touched documents below word w (one wave scan over four words per lane) ----
+    int total;
+    {
+        const uint4 w4 = ((const uint4*)bits)[lane];
+        const int p0 = __popc(w4.x), p1 = __popc(w4.y), p2 = __popc(w4.z), p3 = __popc(w4.w);
+        int incl = p0 + p1 + p2 + p3;
 #pragma unroll
-        for (int k = 0; k < TPRE; ++k) {
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        const int ex = incl - (p0 + p1 + p2 + p3);
+        pre[4 * lane + 0] = (uint16_t)ex;
+        pre[4 * lane + 1] = (uint16_t)(ex + p0);
+        pre[4 * lane + 2] = (uint16_t)(ex + p0 + p1);
+        pre[4 * lane + 3] = (uint16_t)(ex + p0 + p1 + p2);
+        total = __builtin_amdgcn_readlane(incl, 63);
+    }
+    lds_phase();
+    // The rank of span document d inside the round that covers the bitmap words [w0, w1) and starts at rank `base` of the
+    // span, or -1 for "no posting" and for a document of another round.  It is below the round's touched count, which the
+    // round cut keeps at or below BM25_CAP: that bound, not a clamp, is what keeps the LDS indices inside the arrays.
+    auto rank_of = [&](int32_t doc, int w0, int w1, int base) -> int {
+        const bool ok = doc >= 0;
+        const uint32_t d = ok ? (uint32_t)doc : 0u;
+        const uint32_t wd = d >> 5;
+        const int r = (int)pre[wd] - base + __popc(bits[wd] & ((1u << (d & 31)) - 1u));
+        return ok && (int)wd >= w0 && (int)wd < w1 ? r : -1;
+    };
+    // ---- 6. rounds.  A span's touched documents nearly always fit one round (w0 = 0, w1 = all words, base = 0).  Otherwise
+    //         a round takes consecutive whole words while their touched count stays within BM25_CAP: a word has at most 32,
+    //         so a round always advances.  Every branch on `multi` is wave-uniform. ----
+    const bool multi = total > BM25_CAP;
+    int w0 = 0, base = 0;
+    while (w0 < BM25_WORDS) {
+        int w1 = BM25_WORDS, cnt = total;
+        int64_t rs_r = rs_v, pe_r = pe_v;
+        if (multi) {
+            const uint4 w4 = ((const uint4*)bits)[lane];
+            const int lim = base + BM25_CAP;                 // a word belongs to the round if the count up to its END fits
+            w1 = __popcll(__ballot((int)pre[4 * lane + 0] + __popc(w4.x) <= lim)) +
+                 __popcll(__ballot((int)pre[4 * lane + 1] + __popc(w4.y) <= lim)) +
+                 __popcll(__ballot((int)pre[4 * lane + 2] + __popc(w4.z) <= lim)) +
+                 __popcll(__ballot((int)pre[4 * lane + 3] + __popc(w4.w) <= lim));
+            cnt = __builtin_amdgcn_readfirstlane((int)pre[w1 - 1] + __popc(bits[w1 - 1])) - base;
+            if (klass == K_HEAVY) {                          // a long list: only its postings of the round's tiles
+                const int t_lo = w0 >> 5, t_hi = ((w1 + 31) >> 5) < n_my ? ((w1 + 31) >> 5) : n_my;
+                const uint32_t* row = ix.tile_off + (int64_t)h_v * (ix.n_tiles + 1) + tile0;
+                const int64_t a = s_v + row[t_lo], b = s_v + row[t_hi];
+                rs_r = rs_v > a ? rs_v : a;
+                pe_r = pe_v < b ? pe_v : b;
+                if (rs_r > pe_r) rs_r = pe_r;
+            }
+        }
+        if (cnt > 0) {
+            // ---- 6a. rank: a resident posting of the round keeps its rank in a register; slot[rank] = document, so the
+            //          slots are in document order ----
+            int rk[BM25_RES];
 #pragma unroll
-            for (int c = 0; c < PFC; ++c) r.p[k][c].doc = -1;
-            if (sj[k] >= 0 && !(dbg & 8)) {                  // wave-uniform
-                const int64_t ps = lane_i64(r.ps, sj[k]), pe = lane_i64(r.pe, sj[k]);
-#pragma unroll
-                for (int c = 0; c < PFC; ++c) {
-                    if (ps + 64 * c < pe) {                  // wave-uniform: no instruction for chunks past the slice
-                        const int64_t i = ps + 64 * c + lane;
-                        r.p[k][c] = ix.post[i < pe ? i : null_post];
+            for (int k = 0; k < BM25_RES; ++k) {
+                rk[k] = rank_of(res[k].doc, w0, w1, base);
+                if (rk[k] >= 0) slot[rk[k]] = (uint16_t)res[k].doc;
+            }
+            if (has_rest) {
+                // postings beyond the resident chunks: their slots come from the bitmap, not from another pass over the
+                // postings -- lane l takes the words w0 + l, w0 + l + 64, ...; a word's documents get the ranks from
+                // pre[w] - base on, all below cnt
+                for (int w = w0 + lane; w < w1; w += 64) {
+                    uint32_t x = bits[w];
+                    int r = (int)pre[w] - base;
+                    while (x) {
+                        slot[r++] = (uint16_t)(32 * w + __ffs((int)x) - 1);
+                        x &= x - 1;
                     }
                 }
             }
-        }
-    };
-    auto process = [&](int tt, TileRegs& r) {
-        const int tile = tile0 + tt;
-        const int64_t lo = (int64_t)tile * BM25_TILE;
-        const int64_t hi = lo + BM25_TILE < ix.n_docs ? lo + BM25_TILE : ix.n_docs;
-        const int n = (int)(hi - lo);
-        const int64_t ps_v = r.ps, pe_v = r.pe;
-        int list_n = 0;                                      // documents touched so far in this tile (wave-uniform)
-        // U postings of streamed term j per lane.  Nothing is branched around per lane: a posting of another tile (covering
-        // ranges) or a missing one computes on document 0 and only its stores are masked.  A document occurs once per
-        // posting list, so the lanes of one step never touch the same slot.
-        auto apply = [&](auto u_c, const int32_t* pdoc, const double* pcomp, double idf, double qtf, int j) {
-            constexpr int U = decltype(u_c)::value;
-            bool ok[U];
-            uint32_t d[U];
-            double c[U];
+            lds_phase();
+            // ---- 6b. the table values of the first LK looked-up terms for the first LG x 64 slots: the gathers need only
+            //          slot[], so they are all issued here, ahead of the accumulation, whatever the term's position ----
+            constexpr int LK = 2, LG = 6;
+            double tv[LK][LG];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t dd = (uint32_t)(pdoc[u] - (int32_t)lo);
-                ok[u] = dd < (uint32_t)n;
-                d[u] = ok[u] ? dd : 0u;
-                // term_score = idf * tf_component * query_term_freq[term]  (:478)
-                c[u] = (idf * pcomp[u]) * qtf;
+            for (int l = 0; l < LK; ++l)
+#pragma unroll
+                for (int g = 0; g < LG; ++g) tv[l][g] = 0.0;
+            if (look_mask && !(dbg & 1)) {
+                uint32_t sd[LG];
+#pragma unroll
+                for (int g = 0; g < LG; ++g) sd[g] = slot[g * 64 + lane < cnt ? g * 64 + lane : 0];
+                unsigned long long lm = look_mask;
+#pragma unroll
+                for (int l = 0; l < LK; ++l) {
+                    if (!lm) break;
+                    const int i = __ffsll((long long)lm) - 1;
+                    lm &= lm - 1;
+                    const gtable tbl = table_of(lane_i64(s_v, i)) + lo_span;
+#pragma unroll
+                    for (int g = 0; g < LG; ++g)
+                        if (g * 64 < cnt) tv[l][g] = tbl[sd[g]];     // (wave-uniform; a lane past cnt reads slot 0's entry)
+                }
             }
-            if (dbg & 2) return;
+            // ---- 6c. accumulate in query order: bm25_score = 0.0 (:466), then the terms' contributions (:478) ----
+            for (int s = 2 * lane; s < cnt; s += 128) *(double2*)(acc + s) = make_double2(0.0, 0.0);
+            lds_phase();
+            // looked-up term i: its contribution to every slot of the round whose document has the term
+            auto lookup = [&](int i) {
+                if (dbg & 1) return;
+                const double idf = lane_f64(idf_v, i), qtf = lane_f64(qtf_v, i);
+                const int li = __popcll(look_mask & ((1ull << i) - 1ull));
+                int from = 0;
+                if (li < LK) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                double a = acc[d[u]];
-                const bool first = ok[u] && (uint64_t)__double_as_longlong(a) == UNTOUCHED;
-                const unsigned long long fm = __ballot(first);
-                if (fm) {                                    // (wave-uniform) first touch: bm25_score = 0.0 (:466), then the
-                    double a0 = 0.0;                         // negative terms that precede term j in the query, in order
-                    unsigned long long lm = (dbg & 1) ? 0ull : look_mask & ((1ull << j) - 1ull);
-                    while (lm) {
-                        const int i = __ffsll((long long)lm) - 1;
-                        lm &= lm - 1;
-                        const gtable tbl = table_of(lane_i64(s_v, i)) + lo;
-                        const double tc = first ? tbl[d[u]] : 0.0;
-                        const double ci = (lane_f64(idf_v, i) * tc) * lane_f64(qtf_v, i);
-                        if (tc != 0.0) a0 = a0 + ci;         // (0.0: the document lacks term i)
+                    for (int l = 0; l < LK; ++l) {
+                        if (li != l) continue;               // wave-uniform
+#pragma unroll
+                        for (int g = 0; g < LG; ++g) {
+                            if (g * 64 >= cnt) break;        // wave-uniform
+                            const int s = g * 64 + lane;
+                            double t = tv[l][g];
+                            // the gathered value is first looked at HERE: without this the compiler hoists the select and
+                            // the compare below out of the term loop, and with them the wait for every gather
+                            asm volatile("" : "+v"(t));
+                            const double tc = s < cnt ? t : 0.0;
+                            if (tc != 0.0) acc[s] = acc[s] + (idf * tc) * qtf;       // (0.0: the document lacks term i)
+                        }
                     }
-                    if (first) { list[list_n + lane_rank(fm)] = (uint16_t)d[u]; a = a0; }
-                    list_n += __popcll(fm);
+                    from = LG * 64;
                 }
-                const double x = a + c[u];                   // bm25_score += term_score
-                if (ok[u]) acc[d[u]] = x;
-            }
-        };
-        // The rest of a slice, U x 64 postings per round: all loads of a round are issued before the first is used.
-        auto stream = [&](int64_t from, int64_t pe, double idf, double qtf, int j) {
-            constexpr int U = 4;
-            if (dbg & 4) return;
-            for (int64_t base = from; base < pe; base += (int64_t)U * 64) {
-                int32_t pd[U];
-                double pc[U];
+                if (from >= cnt) return;
+                const gtable tbl = table_of(lane_i64(s_v, i)) + lo_span;
+                for (int b = from; b < cnt; b += LG * 64) {  // LG batches of gathers in flight
+                    double tc[LG];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int64_t i = base + lane + (int64_t)u * 64;
-                    const Bm25Post x = ix.post[i < pe ? i : null_post];
-                    pd[u] = x.doc; pc[u] = post_comp(x);
+                    for (int g = 0; g < LG; ++g) {
+                        const int s = b + g * 64 + lane;
+                        tc[g] = tbl[slot[s < cnt ? s : 0]];
+                    }
+#pragma unroll
+                    for (int g = 0; g < LG; ++g) {
+                        const int s = b + g * 64 + lane;
+                        if (s < cnt && tc[g] != 0.0) acc[s] = acc[s] + (idf * tc[g]) * qtf;
+                    }
                 }
-                apply(std::integral_constant<int, U>{}, pd, pc, idf, qtf, j);
-            }
-        };
-        // looked-up term i: its contribution to every document touched so far
-        auto walk = [&](int i) {
-            if (list_n == 0 || (dbg & 1)) return;
-            const gtable tbl = table_of(lane_i64(s_v, i)) + lo;
-            const double idf = lane_f64(idf_v, i), qtf = lane_f64(qtf_v, i);
-            for (int b = 0; b < list_n; b += 128) {          // two batches of gathers in flight
-                const int e0 = b + lane, e1 = b + 64 + lane;
-                const uint32_t d0 = list[e0 < list_n ? e0 : 0], d1 = list[e1 < list_n ? e1 : 0];
-                const double t0 = e0 < list_n ? tbl[d0] : 0.0, t1 = e1 < list_n ? tbl[d1] : 0.0;
-                if (t0 != 0.0) acc[d0] = acc[d0] + (idf * t0) * qtf;
-                if (t1 != 0.0) acc[d1] = acc[d1] + (idf * t1) * qtf;
-            }
-        };
-        auto walks = [&](int from, int to) {                 // the looked-up terms at positions [from, to)
-            unsigned long long lm = look_mask & ~((1ull << from) - 1ull);
-            if (to < 64) lm &= (1ull << to) - 1ull;
-            while (lm) {
-                const int i = __ffsll((long long)lm) - 1;
-                lm &= lm - 1;
-                walk(i);
-            }
-        };
-        // ---- the terms in query order: the first TPRE streamed ones from the prefetched registers ----
-        int jprev = 0;
+            };
+            for (int j = 0; j < nt; ++j) {
+                const int kj = __builtin_amdgcn_readlane(klass, j);
+                if (kj == K_DEAD) continue;
+                if (kj == K_LOOKUP) { lookup(j); continue; }
+                // streamed term j: acc[rank] += (idf * tf_component) * qtf, a plain LDS read-modify-write (the lanes of a
+                // step hold distinct documents; a wave's LDS operations execute in order)
+                const double idf = lane_f64(idf_v, j), qtf = lane_f64(qtf_v, j);
 #pragma unroll
-        for (int k = 0; k < TPRE; ++k) {
-            const int j = sj[k];
-            if (j < 0) break;                                // wave-uniform
-            walks(jprev, j);
-            jprev = j + 1;
-            const int64_t ps = lane_i64(ps_v, j), pe = lane_i64(pe_v, j);
-            if (pe <= ps) continue;
-            const double idf = lane_f64(idf_v, j), qtf = lane_f64(qtf_v, j);
-            int32_t pd[PFC];
-            double pc[PFC];
+                for (int k = 0; k < BM25_RES; ++k) {
+                    if (cj[k] != j) continue;                // wave-uniform
+                    const double c = (idf * post_comp(res[k])) * qtf;
+                    if (rk[k] >= 0 && !(dbg & 2)) acc[rk[k]] = acc[rk[k]] + c;
+                }
+                const int64_t a = lane_i64(rs_r, j), b = lane_i64(pe_r, j);
+                if (a >= b || (dbg & 4)) continue;
+                for (int64_t at = a; at < b; at += (int64_t)U * 64) {
+                    int32_t pd[U];
+                    double pc[U];
 #pragma unroll
-            for (int c = 0; c < PFC; ++c) { pd[c] = r.p[k][c].doc; pc[c] = post_comp(r.p[k][c]); }   // (no posting: doc -1)
-            if (pe - ps <= 64) apply(std::integral_constant<int, 1>{}, pd, pc, idf, qtf, j);
-            else apply(std::integral_constant<int, PFC>{}, pd, pc, idf, qtf, j);
-            if (pe - ps > 64 * PFC) stream(ps + 64 * PFC, pe, idf, qtf, j);
-        }
-        for (int j = j_rest; j < nt; ++j) {
-            const int kj = __builtin_amdgcn_readlane(klass, j);
-            if (kj == K_LOOKUP) { walk(j); continue; }
-            if (kj == K_DEAD) continue;
-            const int64_t ps = lane_i64(ps_v, j), pe = lane_i64(pe_v, j);
-            if (pe <= ps) continue;
-            stream(ps, pe, lane_f64(idf_v, j), lane_f64(qtf_v, j), j);
-        }
-        if (jprev < j_rest) walks(jprev, j_rest);            // (fewer than TPRE streamed terms: the looked-up ones behind the last)
-        if (list_n == 0) return;
-        // ---- the tile's candidates: the touched documents with score >= min_score (:461,480) as (score, doc) pairs appended
-        //      to the item's segment; every touched accumulator goes back to "untouched" ----
-        const double un = __longlong_as_double((long long)UNTOUCHED);
-        for (int b = 0; b < list_n; b += 64) {
-            const int e = b + lane;
-            const bool in = e < list_n;
-            const uint32_t d = list[in ? e : 0];
-            const double sc = acc[d];
-            bool keep = in && sc >= min_score && !(dbg & 16);
-            if constexpr (WITHIN) {                          // one 32-bit load per candidate from a row that stays in the L2
-                if (keep) keep = msr_in_set(srow, lo + d);
+                    for (int u = 0; u < U; ++u) {
+                        const int64_t i = at + lane + (int64_t)u * 64;
+                        const Bm25Post x = ix.post[i < b ? i : null_post];
+                        pd[u] = x.doc; pc[u] = post_comp(x);
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const uint32_t d = (uint32_t)(pd[u] - (int32_t)lo_span);
+                        const int r = rank_of(d < n_span ? (int32_t)d : -1, w0, w1, base);
+                        const double c = (idf * pc[u]) * qtf;
+                        if (r >= 0 && !(dbg & 2)) acc[r] = acc[r] + c;
+                    }
+                }
             }
-            const unsigned long long km = __ballot(keep);
-            if (keep) {
-                const int64_t w = seg_base + seg_cnt + lane_rank(km);
-                cand_score[w] = sc;
-                cand_doc[w] = (int32_t)(lo + d);
+            lds_phase();
+            // ---- 6d. the round's candidates: the slots with score >= min_score (:461,480) as (score, doc) pairs appended
+            //          to the item's segment, in document order ----
+            for (int b = 0; b < cnt; b += 64) {
+                const int s = b + lane;
+                const bool in = s < cnt;
+                const uint32_t d = slot[in ? s : 0];
+                const double sc = acc[in ? s : 0];
+                bool keep = in && sc >= min_score && !(dbg & 16);
+                if constexpr (WITHIN) {                      // one 32-bit load per candidate from a row that stays in the L2
+                    if (keep) keep = msr_in_set(srow, lo_span + d);
+                }
+                const unsigned long long km = __ballot(keep);
+                if (keep) {
+                    const int64_t w = seg_base + seg_cnt + lane_rank(km);
+                    cand_score[w] = sc;
+                    cand_doc[w] = (int32_t)(lo_span + d);
+                }
+                seg_cnt += __popcll(km);
             }
-            seg_cnt += __popcll(km);
-            if (in) acc[d] = un;
+            lds_phase();
         }
-    };
-    TileRegs ra, rb;
-    issue(0, ra);
-    for (int tt = 0; tt < n_my; tt += 2) {
-        if (tt + 1 < n_my) issue(tt + 1, rb);
-        process(tt, ra);
-        if (tt + 1 < n_my) {
-            if (tt + 2 < n_my) issue(tt + 2, ra);
-            process(tt + 1, rb);
-        }
+        w0 = w1;
+        base += cnt;
     }
     if (lane == 0) *seg_len = seg_cnt;
 }

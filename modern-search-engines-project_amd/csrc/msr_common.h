@@ -5,6 +5,11 @@
 
 #define MSR_WAVE 64
 
+// K1 (msr_bm25.hip): accumulator slots of one round of a (query, span) wave -- the touched documents of a span of up to 8
+// tiles of MSR_BM25_TILE (msr_internal.h) documents are scored in rounds of at most this many.  A multiple of 128, at most
+// one tile (tests/test_bm25_round_cases.py reads it from this line).
+#define MSR_BM25_ROUND_CAP 768
+
 // Order-preserving maps float -> unsigned (larger float <=> larger unsigned), and back.
 __host__ __device__ __forceinline__ uint32_t msr_ord32(float f) {
     uint32_t u;

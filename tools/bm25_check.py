@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """BM25 stage (msr_bm25_topk) timings on a synthetic corpus, with the diagnostic build's knock-out switches.
-    MSR_DIAG_LIB=1 python tools/bm25_check.py --docs 1000000 --queries 128 --k 1000 --dbg 0,1,2,4,16"""
+    MSR_DIAG_LIB=1 python tools/bm25_check.py --docs 1000000 --queries 256 --k 1000 --dbg 0,1,2,4,16
+Knock-out masks of bm25_taat_kernel (sums of; the results are then wrong): 1 no table gathers (looked-up terms add nothing),
+2 no accumulation of streamed postings, 4 nothing is read beyond a span's register-resident chunks, 16 no emission, 64 every
+list is streamed (no pruning of negative lists).  8 is retired (it switched the old kernel's prefetch off) and does nothing."""
 import argparse
 import json
 import os
@@ -26,7 +29,8 @@ ap.add_argument("--terms", type=int, default=1_000_000)
 ap.add_argument("--queries", type=int, default=128)
 ap.add_argument("--k", type=int, default=1000)
 ap.add_argument("--iters", type=int, default=7)
-ap.add_argument("--dbg", default="0", help="comma-separated knock-out masks (msr_tune(102, mask)); non-zero: diagnostic build only")
+ap.add_argument("--dbg", default="0", help="comma-separated knock-out masks (msr_tune(102, mask)): 1 no table gathers, 2 no accumulation, 4 resident chunks "
+                     "only, 16 no emission, 64 stream every list; non-zero: diagnostic build only")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 ix = synthetic_corpus(a.docs, n_chunks=0, n_terms=a.terms, device=dev)
