@@ -100,6 +100,36 @@ __device__ __forceinline__ gtable table_of(int64_t bits) { return (gtable)(uint6
 
 enum : int { K_DEAD = 0, K_LOOKUP = 1, K_HEAVY = 2, K_RANGE = 3 };
 
+// What the scoring kernel does with one term of a query -- shared by the kernel's plan phase and by bm25_plan_kernel, which
+// weighs a query by the postings the scoring kernel will stream for it: the two must agree on which lists those are.
+// K_DEAD: unknown term or empty list; K_LOOKUP: every contribution < 0 and a dense table exists (looked up, never streamed);
+// K_HEAVY: streamed, its slice of a span comes from skip-table row h; K_RANGE: streamed, short or probed.
+struct Bm25Term {
+    int klass, dh, h;                                // dh: row of the dense tables, h: row of the skip table (or -1)
+    int64_t s, e;                                    // the posting list
+    double idf, qtf;
+};
+__device__ __forceinline__ Bm25Term bm25_classify(const Bm25Index& ix, int32_t t, int32_t qtf, bool prune) {
+    Bm25Term r{K_DEAD, -1, -1, 0, 0, 0.0, 0.0};
+    if (t < 0 || t >= ix.n_terms) return r;
+    r.s = ix.term_off[t];                            // (the five loads of a known term are independent: one round trip)
+    r.e = ix.term_off[t + 1];
+    const double idf = (double)ix.idf[t];
+    const int dh = prune ? ix.dense_id[t] : -1;
+    const int h = ix.heavy_id ? ix.heavy_id[t] : -1;
+    if (r.e <= r.s) return r;
+    r.idf = idf;
+    r.qtf = (double)qtf;
+    r.dh = dh;
+    r.h = h;
+    r.klass = dh >= 0 && idf < 0.0 && r.qtf > 0.0 ? K_LOOKUP : (h >= 0 ? K_HEAVY : K_RANGE);
+    return r;
+}
+// prune: a negative term's list need not be streamed when nothing below 0 can be a candidate (:480)
+__device__ __forceinline__ bool bm25_prune(const Bm25Index& ix, double min_score) {
+    return min_score >= 0.0 && ix.dense_id != nullptr;
+}
+
 #ifndef BM25_WPE
 #define BM25_WPE 4                                             // waves per SIMD the register budget is cut for (5 and 6, with a cap
 #endif                                                         // of 640 / 512 and no scratch, measure within 3 % of 4)
@@ -113,7 +143,8 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
                                                                   int q_first, int nq, double min_score, int tpw, int n_spans,
                                                                   double* __restrict__ cand_score,
                                                                   int32_t* __restrict__ cand_doc,
-                                                                  int32_t* __restrict__ seg_n, int dbg_arg, Set... set) {
+                                                                  int32_t* __restrict__ seg_n,
+                                                                  const int32_t* __restrict__ order, int dbg_arg, Set... set) {
 #ifdef MSR_DIAG
     const int dbg = dbg_arg;   // timing experiments (wrong results): 1 no table gathers, 2 no accumulation of streamed postings,
                                // 4 nothing read beyond the resident chunks, 16 no emission, 64 stream every list (no pruning);
@@ -128,10 +159,25 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // work item = (query, span of tiles), the query running fastest: the waves of a workgroup and of its neighbours score the
-    // SAME tiles for different queries, so the table lines and the slices of terms the queries share come from the L2
+    // SAME tiles for different queries, so the table lines and the slices of terms the queries share come from the L2.
+    // LONG ITEMS FIRST: the items of a slice differ by an order of magnitude (a query with a long positive list streams dozens
+    // of chunks per span, a typical one fits the resident chunks) and the kernel ends with its last long item, so the items of
+    // the n_heavy = order[nq] queries that stream more than the resident chunks per span (bm25_plan_kernel: order[] = the
+    // queries by descending weight) come first, span-major among themselves, then those of the other queries, span-major:
+    // the long items start while the grid is full and the short ones fill in behind them.  Two scalar loads per wave.
     const int item = (int)blockIdx.x * BM25_WAVES + wave;
-    const int span = item / nq, q = item - span * nq;          // q: row of the candidate lists
-    if (span >= n_spans) return;                               // (wave-uniform; there is no barrier in this kernel)
+    if (item >= nq * n_spans) return;                          // (wave-uniform; there is no barrier in this kernel)
+    const int n_heavy = order[nq], heavy_items = n_heavy * n_spans;
+    int span, qj;
+    if (item < heavy_items) {
+        span = item / n_heavy;
+        qj = item - span * n_heavy;
+    } else {
+        const int n_light = nq - n_heavy, r = item - heavy_items;
+        span = r / n_light;
+        qj = n_heavy + (r - span * n_light);
+    }
+    const int q = order[qj];                                   // q: row of the candidate lists
     // The candidates of this item go to segment `span` of row q of the candidate arrays: positions [span tpw TILE, ...) of
     // the row belong to this wave alone (a span cannot yield more candidates than it has documents), so nothing is reserved
     // with an atomic; the segment's length is written once, at the end.
@@ -157,7 +203,7 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
     const int64_t hi_span = lo_span + (int64_t)n_my * BM25_TILE < ix.n_docs ? lo_span + (int64_t)n_my * BM25_TILE : ix.n_docs;
     const uint32_t n_span = (uint32_t)(hi_span - lo_span);
     // a negative term's list need not be streamed when nothing below 0 can be a candidate (:480)
-    const bool prune = min_score >= 0.0 && ix.dense_id != nullptr && !(dbg & 64);
+    const bool prune = bm25_prune(ix, min_score) && !(dbg & 64);
     // ---- 1. the query's plan, ONCE for the span; lane j = term j ----
     int nt = 0, klass = K_DEAD;
     int64_t s_v = 0;                                 // long list: its first posting; looked-up term: its table row
@@ -170,31 +216,22 @@ __global__ __launch_bounds__(BM25_THREADS) __attribute__((amdgpu_waves_per_eu(BM
         nt = q_term_off[q_first + q + 1] - t0;
         if (nt > BM25_MAX_TERMS) nt = BM25_MAX_TERMS;        // the host never sends more
         if (lane < nt) {
-            const int32_t t = q_terms[t0 + lane];
-            if (t >= 0 && t < ix.n_terms) {
-                const int64_t s = ix.term_off[t], e = ix.term_off[t + 1];
-                if (e > s) {
-                    idf_v = (double)ix.idf[t];
-                    qtf_v = (double)q_qtf[t0 + lane];
-                    const int dh = prune ? ix.dense_id[t] : -1;
-                    const int h = ix.heavy_id ? ix.heavy_id[t] : -1;
-                    if (dh >= 0 && idf_v < 0.0 && qtf_v > 0.0) {   // every contribution < 0: looked up, never streamed
-                        klass = K_LOOKUP;
-                        s_v = (int64_t)(ix.dense_comp + (int64_t)dh * ix.dense_stride);
-                    } else if (h >= 0) {                     // long list: the span's slice comes from the skip table, the
-                        klass = K_HEAVY;                     // two ends of one row segment
-                        s_v = s;
-                        h_v = h;
-                        const uint32_t* row = ix.tile_off + (int64_t)h * (ix.n_tiles + 1) + tile0;
-                        ps_v = s + row[0];
-                        pe_v = s + row[n_my];
-                    } else {
-                        klass = K_RANGE;
-                        ps_v = s;                            // short list: all of it (postings of other spans are masked)
-                        pe_v = e;
-                        medium = e - s > 64;
-                    }
-                }
+            const Bm25Term tm = bm25_classify(ix, q_terms[t0 + lane], q_qtf[t0 + lane], prune);
+            klass = tm.klass;
+            idf_v = tm.idf;
+            qtf_v = tm.qtf;
+            if (klass == K_LOOKUP) {                         // every contribution < 0: looked up, never streamed
+                s_v = (int64_t)(ix.dense_comp + (int64_t)tm.dh * ix.dense_stride);
+            } else if (klass == K_HEAVY) {                   // long list: the span's slice comes from the skip table, the
+                s_v = tm.s;                                  // two ends of one row segment
+                h_v = tm.h;
+                const uint32_t* row = ix.tile_off + (int64_t)tm.h * (ix.n_tiles + 1) + tile0;
+                ps_v = tm.s + row[0];
+                pe_v = tm.s + row[n_my];
+            } else if (klass == K_RANGE) {
+                ps_v = tm.s;                                 // short list: all of it (postings of other spans are masked)
+                pe_v = tm.e;
+                medium = tm.e - tm.s > 64;
             }
         }
     }
@@ -671,32 +708,91 @@ int msr_bm25_max_segments(int64_t n_docs) { return (int)((n_docs + BM25_TILE - 1
 // key) the select's window pass anchors its 4096 bins to: U = (k1 + 1) * sum over the query's terms with positive idf of
 // idf * qtf (a tf_component is below k1 + 1), a little raised; out[q] = prefix(U) - 4094, i.e. U falls into bin 4094 and bin
 // 4095 stays empty unless the bound is wrong -- which the select notices (it then takes its general path).
-__global__ __launch_bounds__(256) void bm25_window_kernel(Bm25Index ix, const int32_t* __restrict__ q_term_off,
-                                                           const int32_t* __restrict__ q_terms,
-                                                           const int32_t* __restrict__ q_qtf, int q_first, int nq,
-                                                           uint64_t* __restrict__ out) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= nq) return;
-    const int t0 = q_term_off[q_first + q];
-    int nt = q_term_off[q_first + q + 1] - t0;
-    if (nt > BM25_MAX_TERMS) nt = BM25_MAX_TERMS;
-    double u = 0.0;
-    for (int j = 0; j < nt; ++j) {
-        const int32_t t = q_terms[t0 + j];
-        if (t < 0 || t >= ix.n_terms) continue;
-        const double w = (double)ix.idf[t] * (double)q_qtf[t0 + j];
-        if (w > 0.0) u += w;
+//
+// The same walk over a query's terms gives the scoring kernel its ITEM ORDER: weight[q] = the postings of the lists the scoring
+// kernel will stream for q (bm25_classify, the kernel's own rule); order[0 .. nq) = the slice's queries by descending weight,
+// ties by query number (rank by counting in LDS); order[nq] = n_heavy, the queries whose items are expected to stream more
+// than the BM25_RES resident chunks: weight * (documents of a span) / n_docs > BM25_RES * 64.  They are a prefix of order[].
+// Equal weights (and nq = 1) leave order[] the identity and n_heavy 0 or nq: the item order (span, query) without a plan.
+// Workgroup b ranks the queries [64 b, 64 b + 64): every workgroup weighs ALL queries of the slice into its own LDS (the
+// same loads in every workgroup, side by side on different CUs: one chain of round trips, whatever nq), then 16 threads
+// per query count over a sixteenth of the weights each.  One workgroup for all of it took 25 us at 256 queries
+// (profiles/stage1_query_skew.md), and its counting is nq^2 LDS reads on one CU.
+constexpr int PLAN_THREADS = 1024;
+constexpr int PLAN_QUERIES = 64;                   // queries a workgroup ranks
+constexpr int PLAN_SLICES = PLAN_THREADS / PLAN_QUERIES;
+constexpr int PLAN_MAX = 4096;                     // queries of a slice, at most (msr_create: max_queries <= 4096)
+__global__ __launch_bounds__(PLAN_THREADS) void bm25_plan_kernel(Bm25Index ix, const int32_t* __restrict__ q_term_off,
+                                                                  const int32_t* __restrict__ q_terms,
+                                                                  const int32_t* __restrict__ q_qtf, int q_first, int nq,
+                                                                  double min_score, int tpw, uint64_t* __restrict__ win_out,
+                                                                  int32_t* __restrict__ order) {
+    __shared__ unsigned long long weight[PLAN_MAX];
+    __shared__ int rank_sh[PLAN_QUERIES];
+    __shared__ int n_heavy;
+    const int t = threadIdx.x;
+    const int q_lo = (int)blockIdx.x * PLAN_QUERIES;             // this workgroup ranks [q_lo, q_lo + PLAN_QUERIES)
+    const bool prune = bm25_prune(ix, min_score);
+    if (t == 0) n_heavy = 0;
+    if (t < PLAN_QUERIES) rank_sh[t] = 0;
+    for (int q = t; q < nq; q += PLAN_THREADS) {
+        const int t0 = q_term_off[q_first + q];
+        int nt = q_term_off[q_first + q + 1] - t0;
+        if (nt > BM25_MAX_TERMS) nt = BM25_MAX_TERMS;
+        double u = 0.0;
+        unsigned long long wt = 0;
+        constexpr int TB = 8;                                    // terms side by side: their loads are independent
+        for (int j0 = 0; j0 < nt; j0 += TB) {
+            int32_t tq[TB], tf[TB];
+#pragma unroll
+            for (int j = 0; j < TB; ++j) {
+                tq[j] = j0 + j < nt ? q_terms[t0 + j0 + j] : -1;
+                tf[j] = j0 + j < nt ? q_qtf[t0 + j0 + j] : 0;
+            }
+            Bm25Term tm[TB];
+#pragma unroll
+            for (int j = 0; j < TB; ++j) tm[j] = bm25_classify(ix, tq[j], tf[j], prune);
+#pragma unroll
+            for (int j = 0; j < TB; ++j) {
+                if (tq[j] < 0 || tq[j] >= ix.n_terms) continue;
+                const double w = (double)ix.idf[tq[j]] * (double)tf[j];
+                if (w > 0.0) u += w;
+                if (tm[j].klass >= K_HEAVY) wt += (unsigned long long)(tm[j].e - tm[j].s);
+            }
+        }
+        if (q >= q_lo && q < q_lo + PLAN_QUERIES) {
+            u = u * (ix.k1 + 1.0) * 1.0000001 + 1e-300;
+            const uint64_t pre = msr_ord64(u) >> 44;
+            win_out[q] = pre > 4094 ? pre - 4094 : 0;
+        }
+        weight[q] = wt;
     }
-    u = u * (ix.k1 + 1.0) * 1.0000001 + 1e-300;
-    const uint64_t pre = msr_ord64(u) >> 44;
-    out[q] = pre > 4094 ? pre - 4094 : 0;
-}
-
-hipError_t msr_bm25_window(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
-                           int q_first, int nq, uint64_t* out, hipStream_t stream) {
-    if (nq <= 0) return hipSuccess;
-    bm25_window_kernel<<<(unsigned)((nq + 255) / 256), 256, 0, stream>>>(ix, q_term_off, q_terms, q_qtf, q_first, nq, out);
-    return hipGetLastError();
+    __syncthreads();
+    {
+        const int q = q_lo + (t & (PLAN_QUERIES - 1)), slice = t / PLAN_QUERIES;       // (the lanes of a wave share `slice`)
+        const int per = (nq + PLAN_SLICES - 1) / PLAN_SLICES;
+        const int o_hi = (slice + 1) * per < nq ? (slice + 1) * per : nq;
+        if (q < nq) {
+            const unsigned long long w = weight[q];
+            int above = 0;
+            for (int o = slice * per; o < o_hi; ++o) {
+                const unsigned long long x = weight[o];
+                above += x > w || (x == w && o < q);
+            }
+            if (above) atomicAdd(&rank_sh[q - q_lo], above);     // (LDS)
+        }
+    }
+    __syncthreads();
+    if (t < PLAN_QUERIES && q_lo + t < nq) order[rank_sh[t]] = q_lo + t;
+    if (blockIdx.x != 0) return;
+    // expected postings of an item = weight * span documents / n_docs; heavy: more than the resident chunks hold
+    const unsigned long long span_docs = (unsigned long long)tpw * BM25_TILE;
+    const unsigned long long heavy_above = (unsigned long long)(BM25_RES * 64) * (unsigned long long)ix.n_docs;
+    int mine_heavy = 0;
+    for (int q = t; q < nq; q += PLAN_THREADS) mine_heavy += weight[q] * span_docs > heavy_above;
+    if (mine_heavy) atomicAdd(&n_heavy, mine_heavy);             // (LDS)
+    __syncthreads();
+    if (t == 0) order[nq] = n_heavy;
 }
 
 // A wave looks its query's terms up once and then walks `tpw` consecutive tiles with that plan in registers.  More tiles
@@ -711,22 +807,24 @@ void msr_bm25_split(int n_tiles, int nq, int* tpw_out, int* n_spans_out) {
 
 hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms,
                            const int32_t* q_qtf, int q_first, int nq, double min_score, double* cand_score,
-                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream,
-                           const MsrSetView* set) {
+                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, uint64_t* win, int32_t* order,
+                           hipStream_t stream, const MsrSetView* set) {
     *n_seg = 0; *seg_stride = 0;
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
+    if (nq > PLAN_MAX || !win || !order) return hipErrorInvalidValue;
     int tpw = 1, n_spans = 0;
     msr_bm25_split(ix.n_tiles, nq, &tpw, &n_spans);
     const int64_t items = (int64_t)nq * n_spans;
     if (items >= (1ll << 31)) return hipErrorInvalidValue;
     *n_seg = n_spans;
     *seg_stride = (int64_t)tpw * BM25_TILE;
+    bm25_plan_kernel<<<(unsigned)((nq + PLAN_QUERIES - 1) / PLAN_QUERIES), PLAN_THREADS, 0, stream>>>(ix, q_term_off, q_terms, q_qtf, q_first, nq, min_score, tpw, win, order);
     const unsigned blocks = (unsigned)((items + BM25_WAVES - 1) / BM25_WAVES);
     if (set)
         bm25_taat_kernel<<<blocks, BM25_THREADS, 0, stream>>>(ix, q_term_off, q_terms, q_qtf, q_first, nq, min_score, tpw, n_spans,
-                                                              cand_score, cand_doc, seg_n, g_bm25_dbg, *set);
+                                                              cand_score, cand_doc, seg_n, order, g_bm25_dbg, *set);
     else
         bm25_taat_kernel<<<blocks, BM25_THREADS, 0, stream>>>(ix, q_term_off, q_terms, q_qtf, q_first, nq, min_score, tpw, n_spans,
-                                                              cand_score, cand_doc, seg_n, g_bm25_dbg);
+                                                              cand_score, cand_doc, seg_n, order, g_bm25_dbg);
     return hipGetLastError();
 }

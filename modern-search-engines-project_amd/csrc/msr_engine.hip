@@ -78,7 +78,8 @@ struct msr_engine {
     double* bm_dense = nullptr;
     uint32_t* bm_tile_off = nullptr;
     int32_t* bm_cand_n = nullptr;      // [max_queries][tiles] candidates per (query, segment) of the candidate rows
-    uint64_t* bm_win = nullptr;        // [max_queries] anchor of the select's window pass (msr_bm25_window)
+    uint64_t* bm_win = nullptr;        // [max_queries] anchor of the select's window pass (msr_bm25_scores' plan kernel)
+    int32_t* bm_order = nullptr;       // [max_queries + 1] item order of the scoring kernel (the same plan kernel)
     uint64_t* voc_sig = nullptr;       // [n_terms] character-set signatures of the bound vocabulary (msr_bind_vocab, K15)
     // mem_engine: candidate scratch of the batched bf16 path (allocated by the first msr_enable_bf16, kept across re-binds)
     int32_t* bt_top_doc = nullptr; float* bt_top_score = nullptr; int32_t* bt_top_n = nullptr;
@@ -323,6 +324,7 @@ static int build_postings(msr_engine* e, Bm25Index cand, hipStream_t st) {
               "BM25 candidate lists");
     if (rc) return rc;
     ALLOC(e, e->mem_postings, e->bm_win, (size_t)e->cfg.max_queries * sizeof(uint64_t));
+    ALLOC(e, e->mem_postings, e->bm_order, ((size_t)e->cfg.max_queries + 1) * sizeof(int32_t));
     ALLOC(e, e->mem_postings, e->bm_cand_n, (size_t)e->cfg.max_queries * msr_bm25_max_segments(n_docs) * sizeof(int32_t));
     // the scoring kernel indexes LDS with (post_doc - tile start): validate the CSR once, on the device
     int32_t h_flag = 0;
@@ -898,19 +900,16 @@ static int bm25_topk_impl(msr_engine* e, const char* fn, const int32_t* q_term_o
         int n_seg = 0;
         int64_t seg_stride = 0;
         if (timed) HIP_TRY(e, hipEventRecord(e->ev_start[1][e->ev_count[1]], st));
+        // (the plan kernel in front of the scoring kernel -- item order and window anchors -- runs inside the timing pair)
         HIP_TRY(e, msr_bm25_scores(e->bm25, q_term_off, q_terms, q_qtf, q0, nq, min_score, (double*)e->score_rows, e->bm_cand_doc,
-                                   e->bm_cand_n, &n_seg, &seg_stride, st, set));
+                                   e->bm_cand_n, &n_seg, &seg_stride, e->bm_win, e->bm_order, st, set));
         if (timed) {
             HIP_TRY(e, hipEventRecord(e->ev_stop[1][e->ev_count[1]], st));
             e->ev_count[1]++;
         }
         // scores >= min_score >= 0 lie in a window of 16 octaves below a bound known from the query alone: one histogram
         // pass instead of two (a negative min_score keeps the general two)
-        const uint64_t* win = nullptr;
-        if (min_score >= 0.0) {
-            HIP_TRY(e, msr_bm25_window(e->bm25, q_term_off, q_terms, q_qtf, q0, nq, e->bm_win, st));
-            win = e->bm_win;
-        }
+        const uint64_t* win = min_score >= 0.0 ? e->bm_win : nullptr;
         HIP_TRY(e, msr_select_topk_list((const double*)e->score_rows, e->bm_cand_doc, e->bm_cand_n, n_seg, seg_stride, N, nq, k,
                                         e->sel, o_doc, o_score, out_n + q0, st, win));
     }

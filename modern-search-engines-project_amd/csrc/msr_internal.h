@@ -68,7 +68,7 @@ hipError_t msr_select_topk_within(const float* scores, int64_t n, int64_t stride
 // holds counts[q * n_seg + s] pairs (scores, idx) in any order, from its first position on.
 // win_base (nullable, [nq]): the first histogram pass takes a WINDOW of the 20-bit key prefixes (sign, exponent, 8 mantissa
 // bits) instead of the first 12-bit digit -- bin = clamp(prefix - win_base[q], 0, 4095) -- and resolves 20 bits at once: one
-// streaming pass instead of two when an upper bound of the scores is known (msr_bm25_window); a k-th key in bin 0 or 4095
+// streaming pass instead of two when an upper bound of the scores is known (msr_bm25_scores' win); a k-th key in bin 0 or 4095
 // (the bound was wrong, or the k-th score is 2^-15 of it) sends the query down the general in-kernel path: exact either way.
 hipError_t msr_select_topk_list(const double* scores, const int32_t* idx, const int32_t* counts, int n_seg, int64_t seg_stride,
                                 int64_t stride, int nq, int k, const SelScratch& sc, int32_t* out_doc,
@@ -149,15 +149,16 @@ hipError_t msr_bm25_build_skip(const Bm25Index& ix, const int32_t* heavy_terms, 
 // a span of tiles); segment s holds seg_n[q * n_seg + s] pairs from position s * seg_stride on, in no particular order.
 // Every count is written by the kernel (no initialisation, no atomics).  seg_n: msr_bm25_max_segments(n_docs) words per query.
 int msr_bm25_max_segments(int64_t n_docs);
-hipError_t msr_bm25_window(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms, const int32_t* q_qtf,
-                           int q_first, int nq, uint64_t* out /*[nq]: see msr_select_topk_list*/, hipStream_t stream);
 // The work split of msr_bm25_scores for one slice of nq queries over n_tiles document tiles: *tpw consecutive tiles per wave
 // (1, 2, 4 or 8) and *n_spans = ceil(n_tiles / *tpw) spans -- the n_seg / seg_stride (= *tpw * MSR_BM25_TILE) of the lists.
 void msr_bm25_split(int n_tiles, int nq, int* tpw, int* n_spans);
 hipError_t msr_bm25_scores(const Bm25Index& ix, const int32_t* q_term_off, const int32_t* q_terms,
                            const int32_t* q_qtf, int q_first, int nq, double min_score, double* cand_score,
-                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, hipStream_t stream,
-                           const MsrSetView* set = nullptr);
+                           int32_t* cand_doc, int32_t* seg_n, int* n_seg, int64_t* seg_stride, uint64_t* win, int32_t* order,
+                           hipStream_t stream, const MsrSetView* set = nullptr);
+// A small plan kernel runs in front of the scoring kernel (nq <= 4096): win [nq] <- the anchors of the select's window
+// pass (win_base of msr_select_topk_list; meaningful for min_score >= 0), order [nq + 1] <- scratch: the slice's queries by
+// descending streamed postings and the number of heavy ones, which is the order the scoring kernel starts its items in.
 // set (nullable): the restricted instantiation of the scoring kernel, set->q_set indexed by the CALL's query number
 // (q_first + q): a touched document outside query q's set is not emitted -- the candidate lists only get shorter.
 

@@ -29,7 +29,7 @@ def short(name):
 
 def stats(stats_csv, trace_csv, out):
     rows = list(csv.DictReader(open(stats_csv)))
-    ours = [r for r in rows if any(k in r["Name"] for k in ("dense_scan", "dense_ksplit", "build_qimage", "thr_compact", "rescore", "bm25_taat", "sel_", "rerank_", "best_chunk",
+    ours = [r for r in rows if any(k in r["Name"] for k in ("dense_scan", "dense_ksplit", "build_qimage", "thr_compact", "rescore", "bm25_taat", "bm25_plan", "bm25_window", "sel_", "rerank_", "best_chunk",
                                                              "prep_queries", "merge_kernel", "interleave", "row_inv_norm",
                                                              "fill_chunk_doc", "gemm_", "build_qimg", "qmat_kernel", "batch_margin",
                                                              "unit_bf16", "pad_inv", "rescore", "f16_", "build_qimg1", "enc_",
