@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MSR_ABI_VERSION 15        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
+#define MSR_ABI_VERSION 16        /* 4: msr_unbind, msr_merge_postings; 5: msr_compact_postings; 6: msr_*_topk_within;
                                      7: msr_gather_rows, msr_dense_topk_grouped; 8: msr_bm25_score_docs, msr_union_candidates;
                                      9: msr_debug_bm25_split; 10: msr_debug_select, msr_merge_topk_payload refuses what its merge
                                      tree cannot hold (MSR_MERGE_MAX_ENTRIES); 11: msr_debug_exclusive_scan; 12: msr_term_sets;
@@ -45,7 +45,8 @@ extern "C" {
                                      msr_fuzzy_terms; msr_debug_chunk_layout; msr_dense_pass_info;
                                      msr_wildcard_scratch_bytes, msr_wildcard_terms; msr_facet_table, msr_bind_facet,
                                      msr_facet_scratch_bytes, msr_facet_counts; msr_doc_signatures, msr_bind_signatures,
-                                     msr_collapse_scratch_bytes, msr_collapse_duplicates */
+                                     msr_collapse_scratch_bytes, msr_collapse_duplicates;
+                                     16: msr_debug_count_nonzero, msr_debug_scratch_dirty */
 #define MSR_DIM 768               /* config.py:2 EMBEDDING_DIMENSION */
 #define MSR_MAX_K 1024            /* config.py:13 TOP_K_RETRIEVAL = 1000 */
 #define MSR_MAX_QUERY_TERMS 64
@@ -512,6 +513,37 @@ int msr_debug_select(msr_engine* e, int32_t mode, const void* scores, int64_t n,
                      const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set, const int32_t* gate,
                      int32_t gate_per64, int32_t* out_doc, void* out_score, int32_t* out_n, msr_select_state* out_state,
                      void* stream);
+
+/* Test-only: *out (device pointer to ONE int64) <- the number of non-zero 32-bit words among dev[0 .. n_words) (device pointer,
+ * 4-byte aligned).  A word counts by its BITS: -0.0f (0x80000000) and a NaN are non-zero.  Handle-less like
+ * msr_debug_exclusive_scan, so that the counter itself can be tested on a caller's buffers; unlike it, it allocates nothing and
+ * only enqueues (a clear of *out, then one kernel: plain loads of the counted words, a reduction per workgroup, one integer
+ * add per workgroup into *out -- the counted buffer is never written and no atomic touches it).  n_words = 0: *out <- 0, dev
+ * may be NULL.  MSR_ERR_INVALID for n_words < 0, a NULL out, or n_words > 0 with a NULL or misaligned dev (text in
+ * msr_last_error(NULL)). */
+int msr_debug_count_nonzero(const void* dev, int64_t n_words, int64_t* out, void* stream);
+
+/* Test-only: a direct view of the state an engine call must leave behind for the next one.  Some engine buffers are documented
+ * "zero between calls": every kernel that counts into them puts the zero back on every exit, so that no call has to clear them
+ * first.  out (HOST pointer, n_out >= MSR_DIRTY_SLOTS entries, entries past MSR_DIRTY_SLOTS are not written): out[slot] <- the
+ * number of non-zero 32-bit words (msr_debug_count_nonzero) over the buffer's WHOLE allocated extent -- not the rows of the
+ * last call -- or -1 for a buffer that is not allocated (no chunks bound, the streaming pass or the bf16 path not built):
+ *   MSR_DIRTY_SEL_HIST        the select's histograms, max(max_queries, 128) x 4096 words
+ *   MSR_DIRTY_SEL_CAND_N      the select's candidate counts, max(max_queries, 128) words (the bind checks borrow words 0 and 1)
+ *   MSR_DIRTY_GEMM_PAIR_N     pair counts of the bf16 GEMM path (msr_enable_bf16 on a corpus with row tiles)
+ *   MSR_DIRTY_F32_PAIR_N      pair counts of the f32 streaming pass (65 queries and up; 128 x its query groups)
+ *   MSR_DIRTY_F32_CAND_N      candidate counts of the same pass
+ *   MSR_DIRTY_BT_CAND_N       candidate counts of the batched bf16 path (allocated by the first msr_enable_bf16, kept by rebinds)
+ *   MSR_DIRTY_SPLIT_PENDING   not a count: the queries of an msr_dense_topk_begin whose msr_dense_topk_end has not come (0: none)
+ * Every count is 0 after every call that returned, whatever it returned; a test asserts that after each call it makes.
+ * Buffers that each user clears on entry instead (the gate words of the streaming pass, the flag word of the bind checks) and
+ * buffers that every call rewrites before reading (score rows, candidate rows, the BM25 plan) carry no invariant and have no slot.
+ * SYNCHRONISES the stream (the counts come back to the host) -- no other msr_debug_* call with a handle does; it reads device
+ * memory only, so calling it between an msr_dense_topk_begin and its end is allowed.  MSR_ERR_INVALID for a NULL out or
+ * n_out < MSR_DIRTY_SLOTS. */
+enum { MSR_DIRTY_SEL_HIST = 0, MSR_DIRTY_SEL_CAND_N = 1, MSR_DIRTY_GEMM_PAIR_N = 2, MSR_DIRTY_F32_PAIR_N = 3,
+       MSR_DIRTY_F32_CAND_N = 4, MSR_DIRTY_BT_CAND_N = 5, MSR_DIRTY_SPLIT_PENDING = 6, MSR_DIRTY_SLOTS = 7 };
+int msr_debug_scratch_dirty(msr_engine* e, int64_t* out, int32_t n_out, void* stream);
 
 /* Hybrid candidates (dense hits join the BM25 list).
  *   msr_bm25_score_docs: the BM25 scores of NAMED documents -- a point lookup, no posting list is streamed.  Queries packed as

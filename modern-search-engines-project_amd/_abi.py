@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libmsretr.so")
 
-MSR_ABI_VERSION = 15
+MSR_ABI_VERSION = 16
 MSR_CFG_NO_ROW_COPY = 1
 MSR_CFG_SINGLE_EMIT = 2
 MSR_DIM = 768
@@ -32,6 +32,8 @@ MSR_SIG_WORDS = 64
 MSR_SIG_MAX_SHINGLE = 8
 MSR_COLLAPSE_MAX_CAND = 1024
 MSR_SELECT_F32, MSR_SELECT_F64, MSR_SELECT_F32_WITHIN, MSR_SELECT_F64_LIST = 0, 1, 2, 3
+# slots of msr_debug_scratch_dirty, in the order of the enum in include/msretr.h
+MSR_DIRTY_NAMES = ("sel_hist", "sel_cand_n", "gemm_pair_n", "f32_pair_n", "f32_cand_n", "bt_cand_n", "split_pending")
 
 
 class MsrError(RuntimeError):
@@ -114,6 +116,8 @@ _SIGNATURES = {
     "msr_debug_bm25_split": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "msr_debug_select": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, _P,
                                    _P, C.c_int32, C.c_int64, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "msr_debug_count_nonzero": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "msr_debug_scratch_dirty": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int32, _P]),
     "msr_bm25_score_docs": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "msr_union_candidates": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P]),
     "msr_gather_rows": (C.c_int, [_P, _P, C.c_int32, _P, _P]),

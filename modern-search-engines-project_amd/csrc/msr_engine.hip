@@ -121,6 +121,7 @@ struct msr_engine {
     int32_t* sim_flag = nullptr;
     void* sim_lists = nullptr; size_t sim_lists_bytes = 0;
     void* sim_over = nullptr; size_t sim_over_bytes = 0;
+    int64_t* dirty_counts = nullptr;   // mem_engine: the device counts of msr_debug_scratch_dirty (allocated by its first call)
     // timing
     bool timing = false;
     static constexpr int EV_RING = 256;
@@ -1844,6 +1845,72 @@ extern "C" int msr_tune(msr_engine* e, int32_t key, int32_t value) {
 }
 
 extern "C" int msr_batch_gemm_ok(const msr_engine* e) { return e && e->have_chunks && e->emb_bf16 && e->gemm_ok ? 1 : 0; }
+
+// Test-only: the counter of msr_debug_scratch_dirty.  Grid-stride dword loads of the counted words, a wave reduction, an LDS
+// reduction over the workgroup's waves and ONE 64-bit integer add per workgroup into *out (cleared by the launcher): integer
+// sums, so the result does not depend on the order of the adds.  The counted buffer is only read.
+static constexpr int CNZ_THREADS = 256;
+static constexpr int CNZ_MAX_BLOCKS = 1024;
+__global__ __launch_bounds__(CNZ_THREADS) void count_nonzero_kernel(const uint32_t* __restrict__ w, int64_t n,
+                                                                     unsigned long long* __restrict__ out) {
+    __shared__ unsigned int s_part[CNZ_THREADS / 64];
+    unsigned int c = 0;                                      // (a thread sees at most n / (grid x 256) + 1 < 2^32 words)
+    const int64_t step = (int64_t)gridDim.x * CNZ_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * CNZ_THREADS + threadIdx.x; i < n; i += step) c += w[i] != 0u;
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long sum = 0;
+        for (int i = 0; i < CNZ_THREADS / 64; ++i) sum += s_part[i];
+        if (sum) atomicAdd(out, sum);
+    }
+}
+
+static hipError_t count_nonzero(const void* dev, int64_t n_words, int64_t* out, hipStream_t st) {
+    hipError_t err = hipMemsetAsync(out, 0, sizeof(int64_t), st);
+    if (err != hipSuccess || n_words == 0) return err;
+    const int64_t blocks = std::min<int64_t>(CNZ_MAX_BLOCKS, (n_words + CNZ_THREADS - 1) / CNZ_THREADS);
+    count_nonzero_kernel<<<(unsigned)blocks, CNZ_THREADS, 0, st>>>((const uint32_t*)dev, n_words, (unsigned long long*)out);
+    return hipGetLastError();
+}
+
+extern "C" int msr_debug_count_nonzero(const void* dev, int64_t n_words, int64_t* out, void* stream) {
+    if (n_words < 0 || !out || (n_words > 0 && (!dev || ((uintptr_t)dev & 3))))
+        return msr_fail_global(MSR_ERR_INVALID, "msr_debug_count_nonzero: bad argument (n_words=%lld, NULL out, or dev NULL / not "
+                               "4-byte aligned)", (long long)n_words);
+    hipError_t err = count_nonzero(dev, n_words, out, (hipStream_t)stream);
+    if (err != hipSuccess) return msr_fail_global(MSR_ERR_HIP, "msr_debug_count_nonzero: %s", hipGetErrorString(err));
+    return MSR_OK;
+}
+
+// Test-only: non-zero words of every buffer documented "zero between calls", over its whole allocation (msretr.h).  The extents
+// are the ones of the ALLOC lines: create_scratch (sel), bind_stream_pass (gf), build_bf16 (gemm, bt_cand_n).
+extern "C" int msr_debug_scratch_dirty(msr_engine* e, int64_t* out, int32_t n_out, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!out || n_out < MSR_DIRTY_SLOTS)
+        return fail(e, MSR_ERR_INVALID, "msr_debug_scratch_dirty: bad argument (NULL out or n_out=%d < %d)", n_out, MSR_DIRTY_SLOTS);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    if (!e->dirty_counts) ALLOC(e, e->mem_engine, e->dirty_counts, MSR_DIRTY_SLOTS * sizeof(int64_t));
+    const int64_t nq = std::max(e->cfg.max_queries, 128);
+    const int64_t gf_q = (int64_t)e->gf.max_groups * 128;
+    struct { const void* p; int64_t words; } buf[MSR_DIRTY_SLOTS] = {};
+    buf[MSR_DIRTY_SEL_HIST] = {e->sel.hist, nq * MSR_SEL_BINS};
+    buf[MSR_DIRTY_SEL_CAND_N] = {e->sel.cand_n, nq};
+    buf[MSR_DIRTY_GEMM_PAIR_N] = {e->gemm.pair_n, GM_SLICE};
+    buf[MSR_DIRTY_F32_PAIR_N] = {e->gf.pair_n, gf_q};
+    buf[MSR_DIRTY_F32_CAND_N] = {e->gf.cand_n, gf_q};
+    buf[MSR_DIRTY_BT_CAND_N] = {e->bt_cand_n, GM_SLICE};
+    for (int s = 0; s < MSR_DIRTY_SLOTS; ++s)
+        if (buf[s].p) HIP_TRY(e, count_nonzero(buf[s].p, buf[s].words, e->dirty_counts + s, st));
+    int64_t host[MSR_DIRTY_SLOTS];
+    HIP_TRY(e, hipMemcpyAsync(host, e->dirty_counts, sizeof(host), hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipStreamSynchronize(st));
+    for (int s = 0; s < MSR_DIRTY_SLOTS; ++s) out[s] = buf[s].p ? host[s] : -1;
+    out[MSR_DIRTY_SPLIT_PENDING] = e->split_pending;
+    return MSR_OK;
+}
 
 extern "C" int msr_dense_topk_bf16(msr_engine* e, const float* q, int32_t n_queries, int32_t k,
                                    int32_t max_chunks_per_doc, int32_t* out_doc, float* out_score, int32_t* out_chunk,

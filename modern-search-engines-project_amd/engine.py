@@ -21,6 +21,19 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def count_nonzero_words(t, n_words=None):
+    """Test-only (msr_debug_count_nonzero, no engine): the number of non-zero 32-bit words among the first n_words (default:
+    all) of the contiguous device tensor t, counted by their bits (-0.0 counts).  Synchronises."""
+    assert t.is_cuda and t.is_contiguous() and (t.numel() * t.element_size()) % 4 == 0
+    n = t.numel() * t.element_size() // 4 if n_words is None else int(n_words)
+    out = torch.empty((1,), dtype=torch.int64, device=t.device)
+    with torch.cuda.device(t.device):
+        rc = _abi.load().msr_debug_count_nonzero(_ptr(t) if t.numel() else C.c_void_p(0), n, _ptr(out),
+                                                 C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
+    _abi.check(None, rc)
+    return int(out.item())
+
+
 STREAM_MIN_BYTES = 64 << 20
 _NP_OF = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int64: np.int64,
           torch.int16: np.int16}
@@ -845,6 +858,14 @@ class DeviceEngine:
             1 if gate_per64 else 0, _ptr(out_doc), _ptr(out_score), _ptr(out_n), _ptr(state), self._stream()))
         st = state.cpu().numpy().view(self.SELECT_STATE)[:Q].copy()
         return out_doc, out_score, out_n, st
+
+    def scratch_dirty(self):
+        """Test-only (msr_debug_scratch_dirty): {name: non-zero 32-bit words} of every engine buffer documented "zero between
+        calls", counted over its whole allocation (-1: not allocated), plus "split_pending": the queries of a dense_begin that
+        has not been ended.  Names: _abi.MSR_DIRTY_NAMES.  Every count is 0 after every call.  Synchronises."""
+        out = (C.c_int64 * len(_abi.MSR_DIRTY_NAMES))()
+        self._check(self.lib.msr_debug_scratch_dirty(self.handle, out, len(_abi.MSR_DIRTY_NAMES), self._stream()))
+        return {name: int(out[i]) for i, name in enumerate(_abi.MSR_DIRTY_NAMES)}
 
     # ------------------------------------------------------------------ hybrid candidates (msr_bm25_point.hip)
     def bm25_score_docs(self, term_lists, doc, doc_n=None, packed=None):

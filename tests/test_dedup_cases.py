@@ -143,7 +143,7 @@ def test_header_and_abi_agree():
     hdr = open(os.path.join(ROOT, "include", "msretr.h"), encoding="utf-8").read()
     for name, value in (("MSR_SIG_WORDS", 64), ("MSR_SIG_MAX_SHINGLE", 8), ("MSR_COLLAPSE_MAX_CAND", 1024)):
         assert int(re.search(r"#define " + name + r" (\d+)", hdr).group(1)) == getattr(_abi, name) == value
-    assert _abi.MSR_ABI_VERSION == 15 and int(re.search(r"#define MSR_ABI_VERSION (\d+)", hdr).group(1)) == 15
+    assert _abi.MSR_ABI_VERSION == 16 and int(re.search(r"#define MSR_ABI_VERSION (\d+)", hdr).group(1)) == 16
     bare = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name, n_args in (("msr_doc_signatures", 6), ("msr_bind_signatures", 4), ("msr_collapse_scratch_bytes", 2),
                          ("msr_collapse_duplicates", 21)):

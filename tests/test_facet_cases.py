@@ -172,7 +172,7 @@ def test_http_request_parsing_and_400s():
 def test_header_and_abi_agree():
     hdr = open(os.path.join(ROOT, "include", "msretr.h"), encoding="utf-8").read()
     assert int(re.search(r"#define MSR_FACET_MAX_LIMIT (\d+)", hdr).group(1)) == _abi.MSR_FACET_MAX_LIMIT == 64
-    assert _abi.MSR_ABI_VERSION == 15
+    assert _abi.MSR_ABI_VERSION == 16
     for name, n_args in (("msr_facet_table", 8), ("msr_bind_facet", 9), ("msr_facet_scratch_bytes", 2), ("msr_facet_counts", 18)):
         m = re.search(r"^(?:int|int64_t)\s+" + name + r"\s*\(([^;]*?)\);", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S),
                       flags=re.M | re.S)

@@ -255,7 +255,7 @@ def test_render_with_a_custom_span_tokenizer_and_on_random_windows():
 # ------------------------------------------------------------------------------------------------ ABI
 def test_abi_and_header_agree():
     hdr = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "msretr.h"), encoding="utf-8").read()
-    assert int(re.search(r"#define MSR_ABI_VERSION (\d+)", hdr).group(1)) == _abi.MSR_ABI_VERSION == 15
+    assert int(re.search(r"#define MSR_ABI_VERSION (\d+)", hdr).group(1)) == _abi.MSR_ABI_VERSION == 16
     m = re.search(r"#define MSR_SNIPPET_MAX_WEIGHT \(1 << (\d+)\)", hdr)
     assert m and 1 << int(m.group(1)) == _abi.MSR_SNIPPET_MAX_WEIGHT == 1 << 20
     assert _abi.MSR_PHRASE_MAX_TERMS * _abi.MSR_SNIPPET_MAX_WEIGHT == 1 << 24     # the largest cover, exact in an int32
