@@ -15,7 +15,8 @@
 // Spans are cut at document boundaries with equal chunk counts, so documents never cross spans and no
 // inter-workgroup communication exists.  The default for calls without a row limit is the K-split kernel of
 // msr_dense_ks.hip; this kernel serves what that one does not take (row limit, interleaved layout, corpora that
-// fail its ring precondition).
+// fail its ring precondition, exact products for <= 32 queries).  Which of the two runs, and which instance, is
+// decided in msr_dense_plan.h alone; msr_dense_scan / msr_dense_scan_bf16 below switch on that plan.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -486,12 +487,9 @@ hipError_t launch_scan_v2(const DenseIndex& ix, const float* qn, int nq, int max
     if (err != hipSuccess) return err;
     const int n_img = QB * L::KS * 64;
     build_qimage_kernel<MODE><<<(n_img + 255) / 256, 256, 0, stream>>>(qn, QB, (f32x4*)ix.qimg);
-    // per-wave span tables exist for 8 and for 12 waves per CU
-    const int32_t* spans = WAVES == 12 ? ix.wspan12_doc : ix.wspan_doc;
-    const int n_sp = WAVES == 12 ? ix.n_wspans12 : ix.n_wspans;
-    const int grid = (n_sp + WAVES - 1) / WAVES;
+    const int grid = (ix.n_wspans + WAVES - 1) / WAVES;
     dense_scan_v2_kernel<QB, TILED, LB, MODE, WAVES, OBD, G><<<grid, L::THREADS, lds, stream>>>(
-        ix, ix.emb, spans, n_sp, (const f32x4*)ix.qimg, nq, max_chunks, docscore, scan_debug_flags());
+        ix, ix.emb, ix.wspan_doc, ix.n_wspans, (const f32x4*)ix.qimg, nq, max_chunks, docscore, scan_debug_flags());
     return hipGetLastError();
 }
 
@@ -528,12 +526,12 @@ hipError_t launch_scan_bf16(const DenseIndex& ix, const float* qn, int nq, int m
     return launch_scan_bf16_cfg<QB, 4, 32>(ix, qn, nq, max_chunks, docscore, stream);
 }
 
-template <int QB, bool TILED>
-hipError_t dispatch_variant(const DenseIndex& ix, const float* qn, int nq, int max_chunks, float* docscore,
-                            hipStream_t stream) {
-    // the engine resolves scan_variant 0 at bind time to 7 / 14 (f16 split) or 2 (exact f32), see msr_bind_chunks
-    if (ix.variant == 2) return launch_scan_v2<QB, TILED, 12>(ix, qn, nq, max_chunks, docscore, stream);   // exact f32 MFMA
-    return launch_scan_v2<QB, TILED, 12, 8, 32, MODE_F16X2>(ix, qn, nq, max_chunks, docscore, stream);     // f16 split
+// the narrow kernel over the f32 rows in either layout
+template <int QB, int MODE>
+hipError_t launch_scan_f32(const DenseIndex& ix, const float* qn, int nq, int max_chunks, float* docscore,
+                           hipStream_t stream) {
+    return ix.layout == 1 ? launch_scan_v2<QB, true, 12, 8, 32, MODE>(ix, qn, nq, max_chunks, docscore, stream)
+                          : launch_scan_v2<QB, false, 12, 8, 32, MODE>(ix, qn, nq, max_chunks, docscore, stream);
 }
 
 // min / max of inv_norm over all rows (positive floats order like their bit patterns)
@@ -556,20 +554,14 @@ __global__ __launch_bounds__(256) void norm_range_kernel(const float* __restrict
 hipError_t msr_dense_scan(const DenseIndex& ix, const float* qn, int nq, int max_chunks, float* docscore,
                           hipStream_t stream) {
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    // variants 14 / 15: K-split kernel (msr_dense_ks.hip), f16-split products
-    if ((ix.variant == 14 || ix.variant == 15) && ix.wide_ok && ix.layout == 0 && max_chunks == 0)
-        return msr_dense_scan_wide(ix, qn, nq, docscore, stream);
-    // exact f32 products: the K-split kernel pays off above 32 queries (matrix-core bound: 4.5 ms per 64 queries against
-    // 2 x 2.8 ms on the narrow kernel; at <= 32 queries the narrow kernel is faster)
-    if (ix.variant == 2 && nq > 32 && ix.wide_ok && ix.layout == 0 && max_chunks == 0)
-        return msr_dense_scan_wide_exact(ix, qn, nq, docscore, stream);
-    if (nq > 32) return hipErrorInvalidValue;
-    const bool tiled = ix.layout == 1;
-    if (nq <= 16)
-        return tiled ? dispatch_variant<1, true>(ix, qn, nq, max_chunks, docscore, stream)
-                     : dispatch_variant<1, false>(ix, qn, nq, max_chunks, docscore, stream);
-    return tiled ? dispatch_variant<2, true>(ix, qn, nq, max_chunks, docscore, stream)
-                 : dispatch_variant<2, false>(ix, qn, nq, max_chunks, docscore, stream);
+    const DensePlan p = dense_plan(dense_binding(ix), nq, max_chunks);
+    switch (dense_case(p)) {       // (the label's qb is the instance's QB)
+    case dense_case(DENSE_NARROW_EXACT, 1): return launch_scan_f32<1, MODE_F32>(ix, qn, nq, max_chunks, docscore, stream);
+    case dense_case(DENSE_NARROW_EXACT, 2): return launch_scan_f32<2, MODE_F32>(ix, qn, nq, max_chunks, docscore, stream);
+    case dense_case(DENSE_NARROW_F16X2, 1): return launch_scan_f32<1, MODE_F16X2>(ix, qn, nq, max_chunks, docscore, stream);
+    case dense_case(DENSE_NARROW_F16X2, 2): return launch_scan_f32<2, MODE_F16X2>(ix, qn, nq, max_chunks, docscore, stream);
+    default: return msr_dense_scan_ksplit(ix, p, qn, nq, docscore, stream);
+    }
 }
 
 hipError_t msr_build_qimage(int mode, const float* qn, int n_blocks, void* qimg, hipStream_t stream) {
@@ -593,11 +585,15 @@ hipError_t msr_inv_norm_range(const float* inv_norm, int64_t n, uint32_t* out2, 
 hipError_t msr_dense_scan_bf16(const DenseIndex& ix, const float* qn, int nq, int max_chunks, float* docscore,
                                hipStream_t stream) {
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    if (nq > 64 || !ix.emb_bf16) return hipErrorInvalidValue;
-    if (nq <= 16) return launch_scan_bf16<1>(ix, qn, nq, max_chunks, docscore, stream);
-    if (nq <= 32) return launch_scan_bf16<2>(ix, qn, nq, max_chunks, docscore, stream);
-    if (nq <= 48) return launch_scan_bf16<3>(ix, qn, nq, max_chunks, docscore, stream);
-    return launch_scan_bf16<4>(ix, qn, nq, max_chunks, docscore, stream);
+    if (!ix.emb_bf16) return hipErrorInvalidValue;                 // no image: msr_enable_bf16 has not run
+    const DensePlan p = dense_bf16_plan(dense_binding(ix), nq, max_chunks);
+    switch (dense_case(p)) {       // (the label's qb is the instance's QB)
+    case dense_case(DENSE_BF16_NARROW, 1): return launch_scan_bf16<1>(ix, qn, nq, max_chunks, docscore, stream);
+    case dense_case(DENSE_BF16_NARROW, 2): return launch_scan_bf16<2>(ix, qn, nq, max_chunks, docscore, stream);
+    case dense_case(DENSE_BF16_NARROW, 3): return launch_scan_bf16<3>(ix, qn, nq, max_chunks, docscore, stream);
+    case dense_case(DENSE_BF16_NARROW, 4): return launch_scan_bf16<4>(ix, qn, nq, max_chunks, docscore, stream);
+    default: return msr_dense_scan_ksplit(ix, p, qn, nq, docscore, stream);
+    }
 }
 
 hipError_t msr_fill_f32(float* dst, int64_t n, float value, hipStream_t stream) {

@@ -380,25 +380,40 @@ hipError_t msr_presplit_rows(const float* src, int64_t n_rows, void* dst, hipStr
     return hipGetLastError();
 }
 
-// f32 rows, f16-split products, up to 64 queries per sweep (row-major layout, ix.wide_ok).
-hipError_t msr_dense_scan_wide(const DenseIndex& ix, const float* qn, int nq, float* docscore, hipStream_t stream) {
+// Every K-split instance a plan can name (msr_dense_plan.h; the label's qb is the instance's QB).
+//   f32 rows, 64 queries: 12-way K split (2 k-steps per wave, 167 VGPRs: three waves per SIMD), 2-3 % faster than the 8-way
+//   split (profile r01_m); 32 queries: 8-way (12 gain nothing there).  Exact f32 products (v_mfma_f32_16x16x4_f32) are
+//   matrix-core bound above 32 queries.  PRESPLIT: the pre-split copy of the rows (+4 bytes per value of HBM).
+//   bf16 rows (candidate generator of the batched path): 64 queries, or 128 with a ring of 64 documents (ix.wide_ok64; 128
+//   queries' partial tiles leave 32 KB of LDS for the ring; PIPE would need 32 more registers than a wave has there).
+//   Diagnostic build only: MSR_KS_PIPE=8 -> 8 waves; 2 -> 8 waves with the reduction pipelined in waves 4..7 only (see PIPE
+//   in the kernel; no gain measured); 0 -> the 64-query bf16 instance without PIPE.
+hipError_t msr_dense_scan_ksplit(const DenseIndex& ix, DensePlan plan, const float* qn, int nq, float* docscore,
+                                 hipStream_t stream) {
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    if (nq > 64 || ix.layout != 0 || !ix.wide_ok || !ix.row_meta) return hipErrorInvalidValue;
-    // 64 queries: 12-way K split (2 k-steps per wave, 167 VGPRs: three waves per SIMD), 2-3 % faster than the 8-way split
-    // (profile r01_m); 32 queries: 8-way.  Diagnostic build only: MSR_KS_PIPE=8 -> 8 waves; 2 -> 8 waves with the
-    // reduction pipelined in waves 4..7 only (see PIPE in the kernel; no gain measured).
-    const int pipe = ks_pipe_knob(0);
-    if (ix.variant == 15 && ix.emb_presplit) {              // A/B variant: pre-split copy of the rows (+4 bytes per value of HBM)
-        if (nq <= 32) return launch_ksplit<2, MODE_PRE, 3, 0>(ix, ix.emb_presplit, qn, nq, docscore, stream);
-        return launch_ksplit<4, MODE_PRE, 2, 0, MSR_WIDE_RING, 12>(ix, ix.emb_presplit, qn, nq, docscore, stream);
-    }
-    if (nq <= 32) return launch_ksplit<2, MODE_F16X2, 3, 0>(ix, ix.emb, qn, nq, docscore, stream);   // (8 waves: 12 gain nothing here)
+    const void* rows = plan.kernel == DENSE_BF16_KSPLIT ? ix.emb_bf16 : plan.kernel == DENSE_KSPLIT_PRESPLIT ? ix.emb_presplit : ix.emb;
+    if (rows && ix.row_meta) switch (dense_case(plan)) {
+        case dense_case(DENSE_KSPLIT_F16X2, 2): return launch_ksplit<2, MODE_F16X2, 3, 0>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_KSPLIT_F16X2, 4):
 #ifdef MSR_DIAG
-    if (pipe == 2) return launch_ksplit<4, MODE_F16X2, 3, 2>(ix, ix.emb, qn, nq, docscore, stream);
-    if (pipe == 8) return launch_ksplit<4, MODE_F16X2, 3, 0>(ix, ix.emb, qn, nq, docscore, stream);
+            if (ks_pipe_knob(0) == 2) return launch_ksplit<4, MODE_F16X2, 3, 2>(ix, rows, qn, nq, docscore, stream);
+            if (ks_pipe_knob(0) == 8) return launch_ksplit<4, MODE_F16X2, 3, 0>(ix, rows, qn, nq, docscore, stream);
 #endif
-    (void)pipe;
-    return launch_ksplit<4, MODE_F16X2, 2, 0, MSR_WIDE_RING, 12>(ix, ix.emb, qn, nq, docscore, stream);
+            return launch_ksplit<4, MODE_F16X2, 2, 0, MSR_WIDE_RING, 12>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_KSPLIT_PRESPLIT, 2): return launch_ksplit<2, MODE_PRE, 3, 0>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_KSPLIT_PRESPLIT, 4): return launch_ksplit<4, MODE_PRE, 2, 0, MSR_WIDE_RING, 12>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_KSPLIT_EXACT, 2): return launch_ksplit<2, MODE_F32, 3, 0>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_KSPLIT_EXACT, 4): return launch_ksplit<4, MODE_F32, 2, 0, MSR_WIDE_RING, 12>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_BF16_KSPLIT, 4):
+#ifdef MSR_DIAG
+            if (!ks_pipe_knob(1)) return launch_ksplit<4, MODE_BF16, 4, 0>(ix, rows, qn, nq, docscore, stream);
+#endif
+            return launch_ksplit<4, MODE_BF16, 4, 1>(ix, rows, qn, nq, docscore, stream);
+        case dense_case(DENSE_BF16_KSPLIT, 8): return launch_ksplit<8, MODE_BF16, 3, 0, 64>(ix, rows, qn, nq, docscore, stream);
+        default: break;
+    }
+    // the plan names no K-split instance (nq beyond the slice), or the binding lacks the rows or the row meta it reads
+    return hipErrorInvalidValue;
 }
 
 // The gated fallback behind the streaming pass: ceil(nq / 64) slices of 64 queries in ONE launch (grid.y = slice), slice s
@@ -408,32 +423,8 @@ size_t msr_ksplit_slice_image_bytes() { return (size_t)4 * KsCfg<4, MODE_F16X2, 
 hipError_t msr_dense_scan_slices(const DenseIndex& ix, const float* qn, int nq, float* docscore, void* qimg_slices,
                                  hipStream_t stream) {
     if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    if (ix.layout != 0 || !ix.wide_ok || !ix.row_meta || !ix.gate || !qimg_slices || ix.variant != 14) return hipErrorInvalidValue;
-    return launch_ksplit<4, MODE_F16X2, 2, 0, MSR_WIDE_RING, 12>(ix, ix.emb, qn, nq, docscore, stream, (nq + 63) / 64, qimg_slices);
-}
-
-// f32 rows, exact f32 products (v_mfma_f32_16x16x4_f32), up to 64 queries per sweep: matrix-core bound above 32 queries.
-hipError_t msr_dense_scan_wide_exact(const DenseIndex& ix, const float* qn, int nq, float* docscore, hipStream_t stream) {
-    if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    if (nq > 64 || ix.layout != 0 || !ix.wide_ok || !ix.row_meta) return hipErrorInvalidValue;
-    if (nq <= 32) return launch_ksplit<2, MODE_F32, 3, 0>(ix, ix.emb, qn, nq, docscore, stream);
-    return launch_ksplit<4, MODE_F32, 2, 0, MSR_WIDE_RING, 12>(ix, ix.emb, qn, nq, docscore, stream);
-}
-
-// bf16 rows (candidate generator of the batched path): up to 64 queries per sweep, or up to 128 with a ring of 64
-// documents when the corpus allows it (ix.wide_ok64; 128 queries' partial tiles leave 32 KB of LDS for the ring).
-hipError_t msr_dense_scan_bf16_wide(const DenseIndex& ix, const float* qn, int nq, float* docscore,
-                                    hipStream_t stream) {
-    if (nq <= 0 || ix.n_docs <= 0) return hipSuccess;
-    if (nq > 128 || !ix.emb_bf16 || !ix.wide_ok || !ix.row_meta || (nq > 64 && !ix.wide_ok64)) return hipErrorInvalidValue;
-    const int pipe = ks_pipe_knob(1);
-    if (nq > 64) {
-        // (PIPE would need 32 more registers than a wave has here)
-        return launch_ksplit<8, MODE_BF16, 3, 0, 64>(ix, ix.emb_bf16, qn, nq, docscore, stream);
-    }
-#ifdef MSR_DIAG
-    if (!pipe) return launch_ksplit<4, MODE_BF16, 4, 0>(ix, ix.emb_bf16, qn, nq, docscore, stream);
-#endif
-    (void)pipe;
-    return launch_ksplit<4, MODE_BF16, 4, 1>(ix, ix.emb_bf16, qn, nq, docscore, stream);
+    if (!dense_stream_bound(dense_binding(ix), true) || !ix.row_meta || !ix.gate || !qimg_slices) return hipErrorInvalidValue;
+    static_assert(MSR_DENSE_FALLBACK_SLICE == 16 * 4, "a slice is what the QB = 4 instance below takes");
+    return launch_ksplit<4, MODE_F16X2, 2, 0, MSR_WIDE_RING, 12>(ix, ix.emb, qn, nq, docscore, stream, dense_fallback_slices(nq),
+                                                                 qimg_slices);
 }

@@ -53,12 +53,11 @@ struct msr_engine {
     int64_t doc_domain_n = 0;
     // engine-owned device memory.  mem_chunks:
     int32_t* chunk_doc = nullptr;
-    void* emb_presplit = nullptr;     // scan_variant 15: f16 hi/lo image of the rows
+    void* emb_presplit = nullptr;     // MSR_SCAN_PRESPLIT: f16 hi/lo image of the rows
     void* row_meta = nullptr;         // packed {document, inverse norm} per row for the K-split kernels
     float* inv_norm_own = nullptr;
     int32_t* span_doc = nullptr;
     int32_t* wspan_doc = nullptr;
-    int32_t* wspan12_doc = nullptr;
     // mem_engine:
     float* qn = nullptr;              // [128][768] normalised queries of the current slice
     float* rr_qn = nullptr;           // [max(max_queries, 128)][768] normalised queries of a rerank gather (one launch per call)
@@ -268,8 +267,7 @@ extern "C" int msr_create(const msr_config* cfg, msr_engine** out) {
         return fail(nullptr, MSR_ERR_INVALID, "msr_create: rerank_max_docs out of range [0, 1024]");
     if (cfg->scan_layout != 0 && cfg->scan_layout != 1)
         return fail(nullptr, MSR_ERR_INVALID, "msr_create: scan_layout must be 0 or 1");
-    if (cfg->scan_variant != 0 && cfg->scan_variant != 2 && cfg->scan_variant != 7 && cfg->scan_variant != 14 &&
-        cfg->scan_variant != 15)
+    if (cfg->scan_variant != MSR_SCAN_AUTO && !dense_variant_known(cfg->scan_variant))
         return fail(nullptr, MSR_ERR_INVALID, "msr_create: scan_variant must be 0, 2, 7, 14 or 15");
     if (cfg->flags & ~(int32_t)(MSR_CFG_NO_ROW_COPY | MSR_CFG_SINGLE_EMIT))
         return fail(nullptr, MSR_ERR_INVALID, "msr_create: unknown flag bits 0x%x", cfg->flags);
@@ -435,7 +433,7 @@ extern "C" int msr_bind_postings(msr_engine* e, const int64_t* term_off, int64_t
 
 // ---- msr_bind_chunks in three steps: what doc_off says (host only), the device tables, the streaming pass ------------------
 struct ChunkLayout {
-    std::vector<int32_t> spans, wspans, wspans12;   // equal-chunk-count spans cut at document boundaries
+    std::vector<int32_t> spans, wspans;             // equal-chunk-count spans cut at document boundaries
     int wide_ok = 1, wide_ok64 = 1;                 // see DenseIndex
     bool tiles_ok = true;                           // every document fits a row tile of <= 256 rows (else: no GEMM paths)
     std::vector<int32_t> tiles;                     // [n_tiles + 1] first row of each tile
@@ -452,7 +450,7 @@ static int chunk_layout(msr_engine* e, int n_cus, const std::vector<int32_t>& h_
                     h_off[0], h_off[n_docs], (long long)n_chunks);
     for (int64_t d = 0; d < n_docs; ++d)
         if (h_off[d + 1] < h_off[d]) return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: doc_off not monotone at %lld", (long long)d);
-    // one span per workgroup (variant 1) / per wave (variant 2)
+    // one span per workgroup of the K-split kernels / per wave of the wave-streaming kernel
     auto make_spans = [&](int target, int64_t min_rows) {
         if ((int64_t)target * min_rows > n_chunks) target = (int)std::max<int64_t>(1, n_chunks / min_rows);
         std::vector<int32_t> sp;
@@ -468,7 +466,6 @@ static int chunk_layout(msr_engine* e, int n_cus, const std::vector<int32_t>& h_
     };
     L.spans = make_spans(n_cus, 256);
     L.wspans = make_spans(n_cus * 8, 64);
-    L.wspans12 = make_spans(n_cus * 12, 64);
     // K-split kernels: documents spanned by any two consecutive 16-row groups must fit the LDS ring with a block to spare
     {
         const int64_t n_groups = (n_chunks + 15) / 16;
@@ -541,8 +538,6 @@ static int bind_chunk_tables(msr_engine* e, const float* emb, int64_t n_chunks, 
     ALLOC(e, e->mem_chunks, e->wspan_doc, L.wspans.size() * sizeof(int32_t));
     HIP_TRY(e, hipMemcpyAsync(e->span_doc, L.spans.data(), L.spans.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(e, hipMemcpyAsync(e->wspan_doc, L.wspans.data(), L.wspans.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    ALLOC(e, e->mem_chunks, e->wspan12_doc, L.wspans12.size() * sizeof(int32_t));
-    HIP_TRY(e, hipMemcpyAsync(e->wspan12_doc, L.wspans12.data(), L.wspans12.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(e, msr_fill_chunk_doc(doc_off, n_docs, e->chunk_doc, st));
     if (!inv_norm) {
         ALLOC(e, e->mem_chunks, e->inv_norm_own, (size_t)n_chunks * sizeof(float));
@@ -556,7 +551,7 @@ static int bind_chunk_tables(msr_engine* e, const float* emb, int64_t n_chunks, 
     // The default scan multiplies f16-split pieces (error bound in msr_dense.hip); the bound needs row norms near 1
     // (the reference stores unit-norm rows, indexer/indexer.py:165).  Otherwise fall back to the exact f32 MFMA kernel.
     int variant = e->cfg.scan_variant;
-    if (variant == 0) {
+    if (variant == MSR_SCAN_AUTO) {
         uint32_t h_rng[2] = {0, 0};
         HIP_TRY(e, msr_inv_norm_range(inv_norm, n_chunks, (uint32_t*)e->sel.cand_n, st));   // 2 scratch words
         HIP_TRY(e, hipMemcpyAsync(h_rng, e->sel.cand_n, sizeof(h_rng), hipMemcpyDeviceToHost, st));
@@ -564,21 +559,26 @@ static int bind_chunk_tables(msr_engine* e, const float* emb, int64_t n_chunks, 
         HIP_TRY(e, hipStreamSynchronize(st));
         float lo, hi;
         memcpy(&lo, &h_rng[0], 4); memcpy(&hi, &h_rng[1], 4);
-        variant = (lo >= 0.5f && hi <= 2.0f) ? 7 : 2;
-        if (variant == 7 && e->cfg.scan_layout == 0 && L.wide_ok) variant = 14;   // K-split kernel: up to 64 queries per sweep
+        variant = (lo >= 0.5f && hi <= 2.0f) ? MSR_SCAN_F16X2 : MSR_SCAN_EXACT;
+        if (variant == MSR_SCAN_F16X2 && e->cfg.scan_layout == 0 && L.wide_ok) variant = MSR_SCAN_KSPLIT;   // up to 64 queries per sweep
     }
-    if (variant == 15) {                                  // A/B variant: K-split scan over a pre-split copy of the rows
+    if (variant == MSR_SCAN_PRESPLIT) {                   // A/B variant: K-split scan over a pre-split copy of the rows
         if (e->cfg.scan_layout != 0 || !L.wide_ok) {
-            variant = 7;                                  // preconditions of the K-split kernel not met
+            variant = MSR_SCAN_F16X2;                     // preconditions of the K-split kernel not met
         } else {
             ALLOC(e, e->mem_chunks, e->emb_presplit, (size_t)n_chunks * MSR_DIM * sizeof(float));
             HIP_TRY(e, msr_presplit_rows(emb, n_chunks, e->emb_presplit, st));
         }
     }
-    e->dense = DenseIndex{emb, doc_off, e->chunk_doc, inv_norm, e->span_doc, n_chunks, n_docs, (n_docs + 31) / 32 * 32,
-                          (int)L.spans.size() - 1, e->cfg.scan_layout, e->wspan_doc, (int)L.wspans.size() - 1, e->wspan12_doc,
-                          (int)L.wspans12.size() - 1, e->qimg, nullptr, e->emb_presplit, e->row_meta, L.wide_ok,
-                          L.wide_ok && L.wide_ok64, nullptr, variant};
+    DenseIndex d{};                                       // (emb_bf16: msr_enable_bf16; gate, gate_per64: per launch)
+    d.emb = emb; d.doc_off = doc_off; d.chunk_doc = e->chunk_doc; d.inv_norm = inv_norm;
+    d.n_chunks = n_chunks; d.n_docs = n_docs; d.score_stride = (n_docs + 31) / 32 * 32;
+    d.span_doc = e->span_doc; d.n_spans = (int)L.spans.size() - 1;
+    d.wspan_doc = e->wspan_doc; d.n_wspans = (int)L.wspans.size() - 1;
+    d.layout = e->cfg.scan_layout; d.variant = variant;
+    d.qimg = e->qimg; d.emb_presplit = e->emb_presplit; d.row_meta = e->row_meta;
+    d.wide_ok = L.wide_ok; d.wide_ok64 = L.wide_ok && L.wide_ok64;
+    e->dense = d;
     if (L.tiles_ok) {
         ALLOC(e, e->mem_chunks, e->tile_row, L.tiles.size() * 4);
         HIP_TRY(e, hipMemcpyAsync(e->tile_row, L.tiles.data(), L.tiles.size() * 4, hipMemcpyHostToDevice, st));
@@ -596,7 +596,7 @@ static int bind_chunk_tables(msr_engine* e, const float* emb, int64_t n_chunks, 
 // Batches of 65..128 queries take ONE streaming pass over the f32 rows (f16 filter + exact f32 finish, msr_gemm_f32.hip) when the
 // corpus allows it: the pass' scratch, the two optional copies of the rows, e->gf.
 static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st) {
-    if (!(e->tiles_ok && e->dense.variant == 14 && e->n_tiles >= 64)) return MSR_OK;
+    if (!dense_stream_bindable(dense_binding(e->dense), e->tiles_ok, e->n_tiles)) return MSR_OK;
     const float* emb = e->dense.emb;
     const float* inv_norm = e->dense.inv_norm;
     const int64_t n_chunks = e->dense.n_chunks;
@@ -613,7 +613,7 @@ static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st)
     ALLOC(e, e->mem_chunks, e->gf_inv_pad, (size_t)(n_chunks + 512) * 4);
     ALLOC(e, e->mem_chunks, g.qimg, (size_t)groups * 24 * 8192);
     ALLOC(e, e->mem_chunks, e->gf_qn, (QM + 64) * MSR_DIM * 4);
-    ALLOC(e, e->mem_chunks, e->gf_fb_qimg, (QM + 63) / 64 * msr_ksplit_slice_image_bytes());
+    ALLOC(e, e->mem_chunks, e->gf_fb_qimg, dense_fallback_slices((int)QM) * msr_ksplit_slice_image_bytes());
     ALLOC(e, e->mem_chunks, g.tmax_t, (size_t)n_tiles * 8 * (groups >= 2 ? 256 * max_nt : 128) * 4);   // [tile][wave][queries of a launch]
     ALLOC(e, e->mem_chunks, g.tmax, QM * stride * 4);
     ALLOC(e, e->mem_chunks, g.thr, QM * 4);
@@ -791,18 +791,16 @@ extern "C" int msr_interleave_rows(msr_engine* e, const float* src, int64_t n_ro
 
 extern "C" int msr_scan_arith(const msr_engine* e) {
     if (!e || !e->have_chunks) return -1;
-    const int v = e->dense.variant;
-    return (v == 7 || v == 14 || v == 15) ? 1 : 0;
+    return dense_variant_f16x2(e->dense.variant) ? 1 : 0;
 }
 
 extern "C" int msr_scan_width(const msr_engine* e) {
     if (!e || !e->have_chunks) return -1;
-    const int v = e->dense.variant;
-    const bool wide = (v == 2 || v == 14 || v == 15) && e->dense.layout == 0 && e->dense.wide_ok;
+    const DenseBinding b = dense_binding(e->dense);
     // streaming pass over the f32 rows for batches of more than 64 queries: 128 queries per pass, 256 for batches of more
     // than 128 (when the engine was created for that many queries per call)
-    if (e->gf_ok && wide && v == 14) return e->gf.max_groups >= 2 ? 256 : 128;
-    return wide ? 64 : 32;
+    if (dense_stream_bound(b, e->gf_ok)) return e->gf.max_groups >= 2 ? 256 : 128;
+    return dense_slice(b, 0);
 }
 
 extern "C" int msr_dense_path(const msr_engine* e) { return e ? e->last_dense_width : -1; }
@@ -835,7 +833,7 @@ extern "C" int msr_row_image_state(const msr_engine* e) { return e ? e->row_imag
 
 extern "C" int msr_batch_width(const msr_engine* e) {
     if (!e || !e->have_chunks || !e->emb_bf16) return -1;
-    return e->dense.wide_ok && e->dense.wide_ok64 ? 128 : 64;
+    return dense_bf16_slice(dense_binding(e->dense), 0);
 }
 
 extern "C" int msr_set_timing(msr_engine* e, int32_t enabled) {
@@ -870,6 +868,22 @@ static int within_args_ok(msr_engine* e, const char* fn, int64_t n_docs, const u
     if (set_stride < (n_docs + 31) / 32)
         return fail(e, MSR_ERR_INVALID, "%s: bad argument (set_stride=%lld < ceil(n_docs / 32) = %lld)", fn, (long long)set_stride,
                     (long long)((n_docs + 31) / 32));
+    return MSR_OK;
+}
+
+// What every dense top-k entry point refuses first, in this order: nothing bound (need_bf16: no bf16 image either), an open
+// msr_dense_topk_begin (they share the score rows and the select scratch), and -- args_ok false -- its arguments, which the
+// three calls over plain query rows test alike (dense_topk_args).
+static bool dense_topk_args(const msr_engine* e, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc, const float* q,
+                            const int32_t* out_doc, const float* out_score, const int32_t* out_n) {
+    return n_queries >= 0 && k >= 1 && k <= e->cfg.max_k && max_chunks_per_doc >= 0 && q && out_doc && out_score && out_n;
+}
+static int dense_entry_ok(msr_engine* e, const char* fn, bool need_bf16, bool args_ok, int32_t k) {
+    if (need_bf16 && (!e->have_chunks || !e->emb_bf16)) return fail(e, MSR_ERR_NOT_BOUND, "%s: call msr_enable_bf16 first", fn);
+    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "%s: chunks not bound", fn);
+    if (e->split_pending)
+        return fail(e, MSR_ERR_INVALID, "%s: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first", fn);
+    if (!args_ok) return fail(e, MSR_ERR_INVALID, "%s: bad argument (k=%d, max_k=%d)", fn, k, e->cfg.max_k);
     return MSR_OK;
 }
 
@@ -1458,21 +1472,8 @@ static int dense_gated_fallback(msr_engine* e, int nq, int k, int32_t* out_doc, 
     return MSR_OK;
 }
 
-// Which sweep msr_dense_topk's <= 64-query slices run: true = the K-split kernel (64 queries per pass), false = the narrow
-// kernel (32).  msr_dense_topk_within takes the same decision, so a restricted call sweeps with the kernel an unrestricted
-// call of <= 64 queries would run (its bit-for-bit contract).
-static bool dense_sweep_wide(const msr_engine* e, int max_chunks_per_doc) {
-    return (e->dense.variant == 2 || e->dense.variant == 14 || e->dense.variant == 15) && e->dense.layout == 0 &&
-           e->dense.wide_ok && max_chunks_per_doc == 0;
-}
-
-// The streaming pass (msr_gemm_f32.hip) serves calls of more than 64 queries asking for k documents
-static bool dense_stream_ok(const msr_engine* e, int k) {
-    return dense_sweep_wide(e, 0) && e->gf_ok && e->dense.variant == 14 && e->gf.n_tiles >= 2 * k;
-}
-
-// ... this many queries per call: more than 128 queries run in groups of 256, so with an odd number of 128-query groups only
-// the even part is usable
+// Queries per call of the streaming pass (msr_gemm_f32.hip; which calls it serves: dense_stream_ok, msr_dense_plan.h): more
+// than 128 queries run in groups of 256, so with an odd number of 128-query groups only the even part is usable
 static int dense_stream_cap(const msr_engine* e) { return e->gf.max_groups >= 2 ? (e->gf.max_groups & ~1) * 128 : 128; }
 
 // Event pairs of a timed two-pass launch: {start, stop} of the sample pass (kind 3), then of the pass of `kind`.  nullptr: not
@@ -1489,7 +1490,9 @@ static void pass_events_used(msr_engine* e, int kind, const hipEvent_t* ev) {
 }
 
 extern "C" int msr_dense_split_max(const msr_engine* e, int32_t k) {
-    if (!e || !e->have_chunks || k < 1 || k > e->cfg.max_k || !dense_stream_ok(e, k)) return 0;
+    if (!e || !e->have_chunks || k < 1 || k > e->cfg.max_k ||
+        !dense_stream_ok(dense_binding(e->dense), 0, e->gf_ok, e->gf.n_tiles, k))
+        return 0;
     return dense_stream_cap(e);
 }
 
@@ -1504,7 +1507,7 @@ extern "C" int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_que
                     cap, n_queries, k_part, k);
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
-    HIP_TRY(e, msr_prep_queries(q, n_queries, e->gf_qn, (n_queries + 63) / 64 * 64, st));
+    HIP_TRY(e, msr_prep_queries(q, n_queries, e->gf_qn, dense_fallback_pad(n_queries), st));
     HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
     hipEvent_t ev_buf[4];
     hipEvent_t* ev = pass_events(e, 0, ev_buf);
@@ -1532,24 +1535,26 @@ extern "C" int msr_dense_topk_end(msr_engine* e, int32_t n_queries, int32_t k, c
     return dense_gated_fallback(e, n_queries, k, out_doc, out_score, out_chunk, out_n, st);
 }
 
-// The sweeps of msr_dense_topk for queries [q0, q0 + cnt): one pass over the matrix per `wide ? 64 : 32` queries (msr_dense_scan:
+// The sweeps of msr_dense_topk for queries [q0, q0 + cnt): one pass over the matrix per dense_slice() queries (msr_dense_scan:
 // K-split or narrow kernel), the select of each slice, its best-chunk rows.  `gate` non-null = fallback launches that only do
 // work when *gate != 0.  `set` non-null (msr_dense_topk_within; set->q_set indexed by the call's query number): the restricted
-// select -- the sweep kernels and the best-chunk pass are the same.
-static int dense_sweeps(msr_engine* e, const float* q, int q0, int cnt, int k, int max_chunks_per_doc, bool wide, const int32_t* gate,
+// select -- the sweep kernels and the best-chunk pass are the same, so a restricted call sweeps with the kernel an unrestricted
+// call of <= 64 queries would run (its bit-for-bit contract).
+static int dense_sweeps(msr_engine* e, const float* q, int q0, int cnt, int k, int max_chunks_per_doc, const int32_t* gate,
                         int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, hipStream_t st,
                         const MsrSetView* set) {
     const int64_t N = e->dense.n_docs;
-    const int slice = wide ? 64 : 32;
+    const DenseBinding b = dense_binding(e->dense);
+    const int slice = dense_slice(b, max_chunks_per_doc);
     DenseIndex ix = e->dense;
     SelScratch sel = e->sel;
     for (int s0 = q0; s0 < q0 + cnt; s0 += slice) {
         const int nq = std::min(slice, q0 + cnt - s0);
         // gated fallback: one gate word per slice of 64 queries (the streaming path raises the gates of the slices that
         // hold an overflowed query)
-        ix.gate = sel.gate = gate ? gate + (s0 - q0) / 64 : nullptr;
-        // zero rows up to the query-block count of the kernel that runs (1, 2 or 4 blocks of 16)
-        const int nq_pad = nq > 32 ? 64 : (nq > 16 || (wide && e->dense.variant >= 14)) ? 32 : 16;
+        ix.gate = sel.gate = gate ? gate + (s0 - q0) / MSR_DENSE_FALLBACK_SLICE : nullptr;
+        // zero rows up to the query blocks of the instance that runs
+        const int nq_pad = 16 * dense_plan(b, nq, max_chunks_per_doc).qb;
         const bool timed = !gate && e->timing && e->ev_count[0] < msr_engine::EV_RING;
         HIP_TRY(e, msr_prep_queries(q + (int64_t)s0 * MSR_DIM, nq, e->qn, nq_pad, st));
         if (timed) HIP_TRY(e, hipEventRecord(e->ev_start[0][e->ev_count[0]], st));
@@ -1577,27 +1582,25 @@ static int dense_sweeps(msr_engine* e, const float* q, int q0, int cnt, int k, i
 extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t max_chunks_per_doc,
                               int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk: chunks not bound");
-    if (e->split_pending)
-        return fail(e, MSR_ERR_INVALID, "msr_dense_topk: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first");
-    if (n_queries < 0 || k < 1 || k > e->cfg.max_k || max_chunks_per_doc < 0 || !q || !out_doc || !out_score || !out_n)
-        return fail(e, MSR_ERR_INVALID, "msr_dense_topk: bad argument (k=%d, max_k=%d)", k, e->cfg.max_k);
+    const bool args_ok = dense_topk_args(e, n_queries, k, max_chunks_per_doc, q, out_doc, out_score, out_n);
+    if (const int rc = dense_entry_ok(e, "msr_dense_topk", false, args_ok, k)) return rc;
     if (n_queries == 0) return MSR_OK;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     // one sweep of E serves up to 32 queries (wave-streaming kernel) or 64 (K-split kernel); batches of more than 64
     // queries run as a GEMM over the f32 rows, 128 queries per pass (msr_gemm_f32.hip), when the corpus allows it
-    const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
-    const bool gemm = wide && dense_stream_ok(e, k);
-    e->last_dense_width = gemm && n_queries > 64 ? 0 : (wide ? 64 : 32);       // (the streaming path reports its own width below)
+    const DenseBinding b = dense_binding(e->dense);
+    const int slice = dense_slice(b, max_chunks_per_doc);
+    const bool gemm = dense_stream_ok(b, max_chunks_per_doc, e->gf_ok, e->gf.n_tiles, k);      // (implies the 64-query slice)
+    e->last_dense_width = gemm && n_queries > slice ? 0 : slice;               // (the streaming path reports its own width below)
     e->last_dense_segments = 0;
     int q0 = 0;
     while (q0 < n_queries) {
         const int left = n_queries - q0;
-        if (gemm && left > 64) {
+        if (gemm && left > slice) {
             const int nq = std::min(dense_stream_cap(e), left);
             // (normalised once for the pass AND for the gated sweeps behind it: zero rows up to the last slice's 64)
-            HIP_TRY(e, msr_prep_queries(q + (int64_t)q0 * MSR_DIM, nq, e->gf_qn, (nq + 63) / 64 * 64, st));
+            HIP_TRY(e, msr_prep_queries(q + (int64_t)q0 * MSR_DIM, nq, e->gf_qn, dense_fallback_pad(nq), st));
             HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
             hipEvent_t ev_buf[4];
             hipEvent_t* ev = pass_events(e, 0, ev_buf);
@@ -1615,9 +1618,8 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
             }
             q0 += nq;
         } else {
-            const int nq = std::min(wide ? 64 : 32, left);
-            int rc = dense_sweeps(e, q, q0, nq, k, max_chunks_per_doc, wide, nullptr, out_doc, out_score, out_chunk, out_n, st,
-                                  nullptr);
+            const int nq = std::min(slice, left);
+            int rc = dense_sweeps(e, q, q0, nq, k, max_chunks_per_doc, nullptr, out_doc, out_score, out_chunk, out_n, st, nullptr);
             if (rc) return rc;
             q0 += nq;
         }
@@ -1629,13 +1631,10 @@ extern "C" int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_qu
                                      const uint32_t* set_bits, int32_t n_sets, int64_t set_stride, const int32_t* q_set,
                                      int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk_within: chunks not bound");
-    if (e->split_pending)
-        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_within: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first");
-    if (n_queries < 0 || k < 1 || k > e->cfg.max_k || max_chunks_per_doc < 0 || !q || !out_doc || !out_score || !out_n)
-        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_within: bad argument (k=%d, max_k=%d)", k, e->cfg.max_k);
     {
-        const int rc = within_args_ok(e, "msr_dense_topk_within", e->dense.n_docs, set_bits, n_sets, set_stride, q_set);
+        const bool args_ok = dense_topk_args(e, n_queries, k, max_chunks_per_doc, q, out_doc, out_score, out_n);
+        int rc = dense_entry_ok(e, "msr_dense_topk_within", false, args_ok, k);
+        if (!rc) rc = within_args_ok(e, "msr_dense_topk_within", e->dense.n_docs, set_bits, n_sets, set_stride, q_set);
         if (rc) return rc;
     }
     if (n_sets == 0)                                             // the unrestricted call
@@ -1644,11 +1643,10 @@ extern "C" int msr_dense_topk_within(msr_engine* e, const float* q, int32_t n_qu
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     // every query on the sweeps (the kernels an unrestricted call of <= 64 queries runs), the restriction in the select
-    const bool wide = dense_sweep_wide(e, max_chunks_per_doc);
-    e->last_dense_width = wide ? 64 : 32;
+    e->last_dense_width = dense_slice(dense_binding(e->dense), max_chunks_per_doc);
     e->last_dense_segments = 0;
     const MsrSetView set{set_bits, set_stride, q_set, n_sets};
-    return dense_sweeps(e, q, 0, n_queries, k, max_chunks_per_doc, wide, nullptr, out_doc, out_score, out_chunk, out_n, st, &set);
+    return dense_sweeps(e, q, 0, n_queries, k, max_chunks_per_doc, nullptr, out_doc, out_score, out_chunk, out_n, st, &set);
 }
 
 // ---- K9: similar documents (msr_similar.hip) ---------------------------------------------------------------------------------
@@ -1684,9 +1682,7 @@ extern "C" int msr_dense_topk_grouped(msr_engine* e, const float* q, int32_t n_r
                                       int32_t* out_n, void* stream) {
     static const char* fn = "msr_dense_topk_grouped";
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_chunks) return fail(e, MSR_ERR_NOT_BOUND, "%s: chunks not bound", fn);
-    if (e->split_pending)
-        return fail(e, MSR_ERR_INVALID, "%s: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first", fn);
+    if (const int rc = dense_entry_ok(e, fn, false, true, k)) return rc;     // (the arguments: worded for this call below)
     if (n_rows < 0 || n_groups < 0 || k < 1 || k > e->cfg.max_k || min_score != min_score || !group_off || !excl_off ||
         (n_rows > 0 && !q) || (n_groups > 0 && (!out_doc || !out_score || !out_chunk || !out_src_row || !out_n)))
         return fail(e, MSR_ERR_INVALID, "%s: bad argument (n_rows=%d, n_groups=%d, k=%d, max_k=%d)", fn, n_rows, n_groups, k,
@@ -1916,11 +1912,8 @@ extern "C" int msr_dense_topk_bf16(msr_engine* e, const float* q, int32_t n_quer
                                    int32_t max_chunks_per_doc, int32_t* out_doc, float* out_score, int32_t* out_chunk,
                                    int32_t* out_n, void* stream) {
     if (!e) return MSR_ERR_INVALID;
-    if (!e->have_chunks || !e->emb_bf16) return fail(e, MSR_ERR_NOT_BOUND, "msr_dense_topk_bf16: call msr_enable_bf16 first");
-    if (e->split_pending)                                    // (the two share the score rows and the select scratch)
-        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_bf16: an msr_dense_topk_begin is pending (its scratch is in use): call msr_dense_topk_end first");
-    if (n_queries < 0 || k < 1 || k > e->cfg.max_k || max_chunks_per_doc < 0 || !q || !out_doc || !out_score || !out_n)
-        return fail(e, MSR_ERR_INVALID, "msr_dense_topk_bf16: bad argument (k=%d, max_k=%d)", k, e->cfg.max_k);
+    const bool args_ok = dense_topk_args(e, n_queries, k, max_chunks_per_doc, q, out_doc, out_score, out_n);
+    if (const int rc = dense_entry_ok(e, "msr_dense_topk_bf16", true, args_ok, k)) return rc;
     if (n_queries == 0) return MSR_OK;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(e, hipSetDevice(e->cfg.device));
@@ -1946,27 +1939,25 @@ extern "C" int msr_dense_topk_bf16(msr_engine* e, const float* q, int32_t n_quer
         }
         return MSR_OK;
     }
-    // 33..128 queries: K-split kernel (msr_dense_ks.hip).  Diagnostic build only (-DMSR_DIAG): MSR_BF16_WIDE=0 keeps
-    // the wave-streaming kernel everywhere.
+    // 33..128 queries: K-split kernel (msr_dense_ks.hip), by the plan of msr_dense_plan.h.  (The image holds unit rows:
+    // dense_bf16 carries inverse norms of 1.)
+    DenseIndex ix = e->dense_bf16;
 #ifdef MSR_DIAG
+    // Diagnostic build only: MSR_BF16_WIDE=0 keeps the wave-streaming kernel everywhere -- the plan sees no ring precondition
     static const bool wide_knob = [] { const char* v = getenv("MSR_BF16_WIDE"); return !v || atoi(v) != 0; }();
-#else
-    const bool wide_knob = true;
+    if (!wide_knob) ix.wide_ok = ix.wide_ok64 = 0;
 #endif
-    const bool wide_able = wide_knob && e->dense.wide_ok && max_chunks_per_doc == 0;
-    const int slice = wide_able && e->dense.wide_ok64 ? 128 : 64;
+    const DenseBinding b = dense_binding(ix);
+    const int slice = dense_bf16_slice(b, max_chunks_per_doc);
     for (int q0 = 0; q0 < n_queries; q0 += slice) {
         const int nq = std::min(slice, n_queries - q0);
-        const bool wide = wide_able && nq > 32;
-        // zero rows up to the query-block count of the kernel that runs
-        const int nq_pad = wide ? (nq > 64 ? 128 : 64) : (nq + 15) / 16 * 16;
+        // zero rows up to the query blocks of the instance that runs
+        const int nq_pad = 16 * dense_bf16_plan(b, nq, max_chunks_per_doc).qb;
         HIP_TRY(e, msr_prep_queries(q + (int64_t)q0 * MSR_DIM, nq, e->qn, nq_pad, st));
         HIP_TRY(e, msr_batch_margin(e->qn, nq, e->bf_err, e->bf_margin, st));
         const bool timed = e->timing && e->ev_count[0] < msr_engine::EV_RING;
         if (timed) HIP_TRY(e, hipEventRecord(e->ev_start[0][e->ev_count[0]], st));
-        // (the image holds unit rows: dense_bf16 carries inverse norms of 1)
-        if (wide) HIP_TRY(e, msr_dense_scan_bf16_wide(e->dense_bf16, e->qn, nq, (float*)e->score_rows, st));
-        else HIP_TRY(e, msr_dense_scan_bf16(e->dense_bf16, e->qn, nq, max_chunks_per_doc, (float*)e->score_rows, st));
+        HIP_TRY(e, msr_dense_scan_bf16(ix, e->qn, nq, max_chunks_per_doc, (float*)e->score_rows, st));
         if (timed) {
             HIP_TRY(e, hipEventRecord(e->ev_stop[0][e->ev_count[0]], st));
             e->ev_count[0]++;

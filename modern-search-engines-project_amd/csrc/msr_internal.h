@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "msr_dense_plan.h"
+
 #define MSR_DIM 768
 #define MSR_SEL_BINS 4096      // 12-bit radix digits
 #define MSR_SEL_CAP 4096       // candidate capacity per query of the exact final sort
@@ -262,19 +264,17 @@ struct DenseIndex {
     const int32_t* doc_off;    // [n_docs+1]
     const int32_t* chunk_doc;  // [n_chunks]
     const float* inv_norm;     // [n_chunks]
-    const int32_t* span_doc;   // [n_spans+1] document boundaries of the workgroup spans (scan variant 1)
+    const int32_t* span_doc;   // [n_spans+1] document boundaries of the spans of the K-split kernels: one per workgroup
     int64_t n_chunks, n_docs;
     int64_t score_stride;      // elements between the score rows of consecutive queries (n_docs rounded up to 32:
                                // every row starts on a 128 B line)
     int32_t n_spans;
     int32_t layout;            // 0 row-major, 1 interleaved
-    const int32_t* wspan_doc;  // [n_wspans+1] document boundaries of the per-wave spans (scan variants 2, 3)
+    const int32_t* wspan_doc;  // [n_wspans+1] document boundaries of the spans of the wave-streaming kernel: one per wave
     int32_t n_wspans;
-    const int32_t* wspan12_doc; // the same for 12 waves per CU (scan variants 5, 6)
-    int32_t n_wspans12;
     void* qimg;                // engine scratch: query image in MFMA-fragment order (<= 256 KB)
     const void* emb_bf16;      // bf16 [n_chunks][768] copy of emb for the batched path, or null
-    const void* emb_presplit;  // scan_variant 15 only: the rows as f16 hi/lo pieces (msr_presplit_rows), same size as emb
+    const void* emb_presplit;  // MSR_SCAN_PRESPLIT only: the rows as f16 hi/lo pieces (msr_presplit_rows), same size as emb
     const void* row_meta;      // [n_chunks + 16] x {int32 document, float inverse norm} (last row repeated as padding: a row group may stick out by 15 rows),
                                // one load per unit for the K-split kernels; null when !wide_ok
     int32_t wide_ok;           // any 32 consecutive rows (on 16-row group boundaries) span <= MSR_WIDE_RING - 32 documents
@@ -287,30 +287,25 @@ struct DenseIndex {
                                // the refused layouts are degenerate and the sweep's measured inner loop stays as it is
     int32_t wide_ok64;         // the same with a ring of 64 documents (128-query bf16 sweeps)
     const int32_t* gate;       // optional device word: when non-null and *gate == 0 the scan / best-chunk kernels return at once
-    int32_t variant;           // scan kernel: 14 = K-split kernel, f16-split products, <= 64 queries per sweep (default when
-                               // the row norms and wide_ok allow it; 13 = the same for 17..64 queries only), 7 = wave
-                               // streaming with f16-split products, 2 = wave streaming, exact f32 MFMA (default otherwise),
-                               // 1 = super-tile kernel of the first profile, others: A/B variants (msr_dense.hip)
+    int32_t variant;           // the resolved scan kind: MSR_SCAN_EXACT, _F16X2, _KSPLIT or _PRESPLIT (msr_dense_plan.h)
     int32_t gate_per64;        // best-chunk kernel only: 1 = gate[q / 64] decides for query q (0: gate[0] for all)
 };
-// qn: [ceil16(nq)][768] normalised queries (zero rows as padding).
+inline DenseBinding dense_binding(const DenseIndex& ix) { return DenseBinding{ix.variant, ix.layout, ix.wide_ok, ix.wide_ok64}; }
+// One sweep over the f32 rows for nq <= dense_slice() queries, by the kernel instance dense_plan(dense_binding(ix), nq,
+// max_chunks) names.  qn: the normalised queries as 16 * qb rows of the plan (zero rows as padding).
 // docscore[q][ix.score_stride] <- max cosine over the document's chunks (-inf for chunk-less documents).
 hipError_t msr_dense_scan(const DenseIndex& ix, const float* qn, int nq, int max_chunks, float* docscore,
                           hipStream_t stream);
-// bf16 candidate scan (<= 64 queries per sweep); qn as above with ceil16(nq) rows.
+// The same over the bf16 image (candidate scan): dense_bf16_slice() / dense_bf16_plan(), qn again 16 * qb rows of the plan.
 hipError_t msr_dense_scan_bf16(const DenseIndex& ix, const float* qn, int nq, int max_chunks, float* docscore,
                                hipStream_t stream);
-// Wide sweeps (msr_dense_ks.hip): f16-split products over f32 rows for <= 64 queries per pass; bf16 rows for <= 64,
-// or <= 128 with ix.wide_ok64.
-// Both need ix.wide_ok and have no per-document row limit (max_chunks = 0).
-hipError_t msr_dense_scan_wide(const DenseIndex& ix, const float* qn, int nq, float* docscore, hipStream_t stream);
+// The K-split instances of both (msr_dense_ks.hip), where the two dispatches above send every plan that is not a narrow one.
+hipError_t msr_dense_scan_ksplit(const DenseIndex& ix, DensePlan plan, const float* qn, int nq, float* docscore,
+                                 hipStream_t stream);
 // gated fallback of the streaming pass: all 64-query slices of a call in one launch (msr_dense_ks.hip)
 size_t msr_ksplit_slice_image_bytes();
 hipError_t msr_dense_scan_slices(const DenseIndex& ix, const float* qn, int nq, float* docscore, void* qimg_slices,
                                  hipStream_t stream);
-hipError_t msr_dense_scan_wide_exact(const DenseIndex& ix, const float* qn, int nq, float* docscore, hipStream_t stream);
-hipError_t msr_dense_scan_bf16_wide(const DenseIndex& ix, const float* qn, int nq, float* docscore,
-                                    hipStream_t stream);
 // Query image in MFMA-fragment order for n_blocks x 16 queries (mode: 0 f32, 1 bf16, 2 f16 hi/lo pieces).
 hipError_t msr_build_qimage(int mode, const float* qn, int n_blocks, void* qimg, hipStream_t stream);
 // dst (n_rows x 768 x 4 bytes) <- the rows as f16 hi/lo pieces in the slots the f16-split scan loads them from
