@@ -601,25 +601,21 @@ static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st)
     const float* inv_norm = e->dense.inv_norm;
     const int64_t n_chunks = e->dense.n_chunks;
     const int n_tiles = e->n_tiles, nw = e->n_cus * 8, stride = (n_tiles + 31) / 32 * 32;
-    // one call holds up to 8 groups of 128 queries (bounded by the select scratch, which covers max(max_queries, 128) rows)
-    const int groups = std::min(8, std::max(e->cfg.max_queries, 128) / 128);
-    // emitted entries per wave and call: ~600 per 128 queries at 5 M rows (150 x sample stride per query over 2048 waves)
-    const int GF_WV_CAP = 4096 * std::max(1, groups / 2);
-    const size_t QM = (size_t)groups * 128;
-    const int max_nt = std::max(1, std::min(4, groups / 2));      // 256-query groups that share the rows of one launch
+    const StreamCaps caps = stream_caps(e->cfg.max_queries);         // (msr_stream_plan.h)
+    const size_t QM = (size_t)caps.groups * 128;
     GemmF32Index& g = e->gf;
-    g.n_tiles = n_tiles; g.n_cus = e->n_cus; g.max_groups = groups; g.tmax_stride = stride; g.wv_cap = GF_WV_CAP; g.max_nt = max_nt;
+    g.n_tiles = n_tiles; g.n_cus = e->n_cus; g.caps = caps; g.tmax_stride = stride;
     g.single_emit = (e->cfg.flags & MSR_CFG_SINGLE_EMIT) ? 1 : 0;
     ALLOC(e, e->mem_chunks, e->gf_inv_pad, (size_t)(n_chunks + 512) * 4);
-    ALLOC(e, e->mem_chunks, g.qimg, (size_t)groups * 24 * 8192);
+    ALLOC(e, e->mem_chunks, g.qimg, (size_t)caps.groups * 24 * 8192);
     ALLOC(e, e->mem_chunks, e->gf_qn, (QM + 64) * MSR_DIM * 4);
     ALLOC(e, e->mem_chunks, e->gf_fb_qimg, dense_fallback_slices((int)QM) * msr_ksplit_slice_image_bytes());
-    ALLOC(e, e->mem_chunks, g.tmax_t, (size_t)n_tiles * 8 * (groups >= 2 ? 256 * max_nt : 128) * 4);   // [tile][wave][queries of a launch]
+    ALLOC(e, e->mem_chunks, g.tmax_t, (size_t)n_tiles * 8 * caps.tmax_row * 4);    // [tile][wave][queries of a launch]
     ALLOC(e, e->mem_chunks, g.tmax, QM * stride * 4);
     ALLOC(e, e->mem_chunks, g.thr, QM * 4);
     ALLOC(e, e->mem_chunks, g.thr2, QM * 4);
     ALLOC(e, e->mem_chunks, g.flag, QM * 4);
-    ALLOC(e, e->mem_chunks, g.wvbuf, (size_t)nw * GF_WV_CAP * 16);
+    ALLOC(e, e->mem_chunks, g.wvbuf, (size_t)nw * caps.wv_cap * 16);
     ALLOC(e, e->mem_chunks, g.wv_count, (size_t)nw * 4);
     ALLOC(e, e->mem_chunks, g.pairs, QM * 4096 * 8);
     ALLOC(e, e->mem_chunks, g.pair_n, QM * 4);
@@ -647,7 +643,7 @@ static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st)
     // tile are exactly enough, for every prefetch depth (checked against the tile table here, not assumed).
     // The row-major matrix stays what every other kernel reads.  Declined by MSR_CFG_NO_ROW_COPY, or when the allocation
     // fails (the copy doubles the matrix): the TILED = false instantiation of the same kernel reads the caller's matrix.
-    if (groups >= 2 && e->tile_trow) {
+    if (caps.want_copy && e->tile_trow) {
         const size_t copy_rows = (size_t)L.n_trows + MSR_STREAM256_TILE_ROWS;
         if ((int64_t)L.trow.back() + MSR_STREAM256_TILE_ROWS > (int64_t)copy_rows)
             return fail(e, MSR_ERR_INVALID, "msr_bind_chunks: internal: tile table exceeds the fragment-order copy");
@@ -668,9 +664,9 @@ static int bind_stream_pass(msr_engine* e, const ChunkLayout& L, hipStream_t st)
     // again.  They read an f16 image of the rows instead -- the very values the pass converts in registers (round to
     // nearest, not normalised): same products, same candidates, same results; 1536 B per row.  Declined with the other
     // copy (MSR_CFG_NO_ROW_COPY) or when the allocation fails: those launches then convert as before.
-    if (max_nt >= 2 && (e->cfg.flags & MSR_CFG_NO_ROW_COPY)) {
+    if (caps.want_image && (e->cfg.flags & MSR_CFG_NO_ROW_COPY)) {
         e->row_image_state = 2;
-    } else if (max_nt >= 2) {
+    } else if (caps.want_image) {
         const size_t img_rows = (size_t)n_chunks + 512;
         if (e->mem_chunks.alloc(&e->gf_emb_f16, img_rows * MSR_DIM * 2) != hipSuccess) {
             (void)hipGetLastError();
@@ -799,7 +795,7 @@ extern "C" int msr_scan_width(const msr_engine* e) {
     const DenseBinding b = dense_binding(e->dense);
     // streaming pass over the f32 rows for batches of more than 64 queries: 128 queries per pass, 256 for batches of more
     // than 128 (when the engine was created for that many queries per call)
-    if (dense_stream_bound(b, e->gf_ok)) return e->gf.max_groups >= 2 ? 256 : 128;
+    if (dense_stream_bound(b, e->gf_ok)) return e->gf.caps.width;
     return dense_slice(b, 0);
 }
 
@@ -1472,10 +1468,6 @@ static int dense_gated_fallback(msr_engine* e, int nq, int k, int32_t* out_doc, 
     return MSR_OK;
 }
 
-// Queries per call of the streaming pass (msr_gemm_f32.hip; which calls it serves: dense_stream_ok, msr_dense_plan.h): more
-// than 128 queries run in groups of 256, so with an odd number of 128-query groups only the even part is usable
-static int dense_stream_cap(const msr_engine* e) { return e->gf.max_groups >= 2 ? (e->gf.max_groups & ~1) * 128 : 128; }
-
 // Event pairs of a timed two-pass launch: {start, stop} of the sample pass (kind 3), then of the pass of `kind`.  nullptr: not
 // timed (every launch gets its own pair out of a ring of EV_RING; later launches are not recorded).  pass_events_used() after
 // the launch.
@@ -1493,7 +1485,7 @@ extern "C" int msr_dense_split_max(const msr_engine* e, int32_t k) {
     if (!e || !e->have_chunks || k < 1 || k > e->cfg.max_k ||
         !dense_stream_ok(dense_binding(e->dense), 0, e->gf_ok, e->gf.n_tiles, k))
         return 0;
-    return dense_stream_cap(e);
+    return e->gf.caps.call_cap;                              // (msr_stream_plan.h)
 }
 
 extern "C" int msr_dense_topk_begin(msr_engine* e, const float* q, int32_t n_queries, int32_t k, int32_t k_part, float* out_part,
@@ -1598,7 +1590,7 @@ extern "C" int msr_dense_topk(msr_engine* e, const float* q, int32_t n_queries, 
     while (q0 < n_queries) {
         const int left = n_queries - q0;
         if (gemm && left > slice) {
-            const int nq = std::min(dense_stream_cap(e), left);
+            const int nq = std::min(e->gf.caps.call_cap, left);
             // (normalised once for the pass AND for the gated sweeps behind it: zero rows up to the last slice's 64)
             HIP_TRY(e, msr_prep_queries(q + (int64_t)q0 * MSR_DIM, nq, e->gf_qn, dense_fallback_pad(nq), st));
             HIP_TRY(e, hipMemsetAsync(e->gf_gate, 0, GF_GATE_BYTES, st));
@@ -1890,7 +1882,7 @@ extern "C" int msr_debug_scratch_dirty(msr_engine* e, int64_t* out, int32_t n_ou
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     if (!e->dirty_counts) ALLOC(e, e->mem_engine, e->dirty_counts, MSR_DIRTY_SLOTS * sizeof(int64_t));
     const int64_t nq = std::max(e->cfg.max_queries, 128);
-    const int64_t gf_q = (int64_t)e->gf.max_groups * 128;
+    const int64_t gf_q = (int64_t)e->gf.caps.groups * 128;
     struct { const void* p; int64_t words; } buf[MSR_DIRTY_SLOTS] = {};
     buf[MSR_DIRTY_SEL_HIST] = {e->sel.hist, nq * MSR_SEL_BINS};
     buf[MSR_DIRTY_SEL_CAND_N] = {e->sel.cand_n, nq};

@@ -473,12 +473,11 @@ hipError_t msr_gemm_candidates(const GemmIndex& g, const DenseIndex& ix, const f
     if (grid < 8 || grid / 8 < nt) return hipErrorInvalidValue;
     hipError_t err;
     // ---- pass 1: every ss-th tile, tile maxima only ----
-    int ss = g.n_tiles / (8 * k);
-    ss = ss < 1 ? 1 : (ss > 16 ? 16 : ss);
+    StreamSample sm = stream_sample(g.n_tiles, k, 8, 16);                 // tiles ss/2, ss/2 + ss, ... (msr_stream_plan.h)
 #ifdef MSR_DIAG
-    if (g_gemm_dbg & 256) ss = 1;                      // timing experiments: the sample pass covers every tile
+    if (g_gemm_dbg & 256) sm = stream_sample(g.n_tiles, k, 8, 1);         // timing experiments: the sample pass covers every tile
 #endif
-    const int n_s = (g.n_tiles - ss / 2 + ss - 1) / ss;                   // tiles ss/2, ss/2 + ss, ...
+    const int ss = sm.ss, n_s = sm.n_s;
     {
         // The pass: the 256-query streaming kernel of msr_gemm_f32.hip over the bf16 unit-row image, nt groups of 256
         // queries in ONE launch (rows through a register ring -- no LDS, no barrier for them --, the group's query image

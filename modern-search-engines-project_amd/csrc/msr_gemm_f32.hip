@@ -23,10 +23,11 @@
 // query's k largest is at or above the emission threshold, so it is the score of an entry, and the maxima are joined out of
 // the wave buffers (gemm_entry_tmax_kernel; the argument stands in msr_gemm_f32_pass) -- a third of the epilogue's
 // instructions and 164 MB of stores per pass less.  Pass 2 runs in two segments on corpora large enough for it: the tile
-// maxima of the first raise the threshold of the second (pass_shape below).  Finish: entries above the tighter bound are bucketed per query
+// maxima of the first raise the threshold of the second (pass_shape, msr_stream_plan.h).  Finish: entries above the tighter bound are bucketed per query
 // (msr_gemm_bucket), reduced to distinct documents (gemm_f32_cand_kernel), rescored and sorted.  A query whose entries do
 // not fit anywhere on the way (huge tie groups) raises a device-side gate; the engine's sweeps, always enqueued behind
-// this path, run only when that gate is up (no host round trip).
+// this path, run only when that gate is up (no host round trip).  How wide a call's passes are, how many query groups share a
+// launch, which copy of the rows and which kernel instance a launch takes: msr_stream_plan.h decides, nothing here.
 //
 // Kernel shape (gemm_stream_kernel; one persistent workgroup per CU, 8 waves, tile 256 rows x 128 queries, K step 32):
 // wave w owns rows 32 w .. +32 of the tile and ALL 128 queries, so it is the ONLY reader of its rows -- they never pass
@@ -1055,26 +1056,21 @@ __global__ __launch_bounds__(256) void tile_rows_kernel(const char* __restrict__
         dst[i] = v;
     }
 }
-// width: queries per pass (128 or 256; both kernels: 8 waves x 32 rows)
-hipError_t launch_f32(int width, bool emit, const GemmF32Args& a, int grid, hipStream_t stream, bool tiled = false,
-                      bool image16 = false) {
-    if (image16)
-        return emit ? launch_stream256_t<true, true, false, false, true>(a, grid, stream)
-                    : launch_stream256_t<false, true, false, false, true>(a, grid, stream);
-    // One query group per launch: every row is read exactly once, by one wave -- loaded with the non-temporal policy, so that the
-    // 15 GB stream does not displace the 384 KB query image (re-read by every workgroup for every tile) from the L2s: 3.07 ->
-    // 2.94 ms per pass on one box (profiles/r04_stream256_experiments.md).  Several groups per launch share the rows through the
-    // L2 and keep the default policy.
-    bool ntl = width == 256 && tiled && a.nt == 1;
-#ifdef MSR_DIAG
-    if (g_f32_dbg & 16384) ntl = false;                     // timing experiment: default cache policy for the rows
-#endif
-    if (ntl)
-        return emit ? launch_stream256_t<true, false, true, true>(a, grid, stream) : launch_stream256_t<false, false, true, true>(a, grid, stream);
-    if (width == 256 && tiled)
-        return emit ? launch_stream256_t<true, false, true>(a, grid, stream) : launch_stream256_t<false, false, true>(a, grid, stream);
-    if (width == 256) return emit ? launch_stream256_t<true, false>(a, grid, stream) : launch_stream256_t<false, false>(a, grid, stream);
-    return emit ? launch_stream_t<true>(a, grid, stream) : launch_stream_t<false>(a, grid, stream);
+// Every instance a plan can name (stream_kernel, msr_stream_plan.h).
+hipError_t launch_f32(StreamKernel kernel, bool emit, const GemmF32Args& a, int grid, hipStream_t stream) {
+    switch (stream_case(kernel, emit)) {
+    case stream_case(STREAM_IMAGE16, true): return launch_stream256_t<true, true, false, false, true>(a, grid, stream);
+    case stream_case(STREAM_IMAGE16, false): return launch_stream256_t<false, true, false, false, true>(a, grid, stream);
+    case stream_case(STREAM_COPY_NT, true): return launch_stream256_t<true, false, true, true>(a, grid, stream);
+    case stream_case(STREAM_COPY_NT, false): return launch_stream256_t<false, false, true, true>(a, grid, stream);
+    case stream_case(STREAM_COPY, true): return launch_stream256_t<true, false, true>(a, grid, stream);
+    case stream_case(STREAM_COPY, false): return launch_stream256_t<false, false, true>(a, grid, stream);
+    case stream_case(STREAM_ROWS, true): return launch_stream256_t<true, false>(a, grid, stream);
+    case stream_case(STREAM_ROWS, false): return launch_stream256_t<false, false>(a, grid, stream);
+    case stream_case(STREAM_128, true): return launch_stream_t<true>(a, grid, stream);
+    case stream_case(STREAM_128, false): return launch_stream_t<false>(a, grid, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -1083,10 +1079,9 @@ void msr_gemm_f32_set_dbg(int v) { g_f32_dbg = v; }
 
 hipError_t msr_stream256_bf16_launch(bool emit, const StreamArgs& a, int grid, hipStream_t stream) {
     if (a.nt < 1 || (grid & 7) || (grid >> 3) < a.nt) return hipErrorInvalidValue;
-#ifdef MSR_DIAG
-    if (g_f32_dbg & (32768 | 65536 | 131072 | 262144 | 524288)) { StreamArgs b = a; b.dbg |= g_f32_dbg & (32768 | 65536 | 131072 | 262144 | 524288); return emit ? launch_stream256_t<true, true>(b, grid, stream) : launch_stream256_t<false, true>(b, grid, stream); }
-#endif
-    return emit ? launch_stream256_t<true, true>(a, grid, stream) : launch_stream256_t<false, true>(a, grid, stream);
+    StreamArgs b = a;     // + the kernel-side switches that bear on this instance (g_f32_dbg is 0 outside the diagnostic build)
+    b.dbg |= g_f32_dbg & (32768 | 65536 | 131072 | 262144 | 524288);
+    return emit ? launch_stream256_t<true, true>(b, grid, stream) : launch_stream256_t<false, true>(b, grid, stream);
 }
 hipError_t msr_stream256_bf16_qimage(const float* qn, int nq, int n_groups, void* qimg, hipStream_t stream) {
     build_qimg2_kernel<true><<<dim3((GF_KT * 256 * 4 + 255) / 256, n_groups), 256, 0, stream>>>(qn, nq, (f16x8*)qimg);
@@ -1120,72 +1115,7 @@ hipError_t msr_f16_row_error(const float* emb, const float* inv_norm, int64_t n_
     return hipGetLastError();
 }
 
-namespace {
-// The shape of a streaming call: which tiles the sample pass visits and where the emit pass is cut into segments.  Host
-// arithmetic only (restated in numpy by tests/test_dense_segments_host.py).
-//
-// Sample: every ss-th tile bounds the k-th score from below; >= 3 k sampled tiles, ss <= 64 (the weaker the bound, the more
-// entries the emit pass writes: ~150 ss per query).
-//
-// Segments: tile maxima are by-products of the emit pass itself, and ANY set of >= k distinct tiles bounds the k-th
-// document score from below (documents never straddle tiles).  So the pass emits over the first T1 tiles with the sample's
-// threshold, takes the k-th largest of THOSE T1 maxima (gemm_kth_kernel, raise mode: thr = max(thr, k-th - margin)) and
-// emits over the rest with the raised threshold.  With entries ~ c (T1 / n_s + (T - T1) / T1) the optimum is
-// T1 = sqrt(T n_s); T1 is the multiple of the grid nearest to that, so that both segments run whole rounds of the persistent
-// grid, and the cut is made only where T1 >= max(grid, 2 k) and T - T1 >= grid: smaller corpora keep the one-launch pass.
-// thr(sample) <= thr(first T1) <= thr2(all tiles) -- subsets of the same maxima, the same margin --, so what the bucket
-// keeps (score >= thr2) is the same set of entries either way: results do not move, the wave buffers only get fewer entries.
-// (Three segments, bounds at n_s r and n_s r^2 with r = (T / n_s)^(1/3), were measured too: profiles/dense_emit_segments.md.)
-struct PassShape {
-    int ss, n_s;               // sample: tiles ss / 2, ss / 2 + ss, ...: n_s of them
-    int n_seg;                 // emit launches per group
-    int bound[4];              // segment s covers tiles [bound[s], bound[s + 1])
-};
-PassShape pass_shape(int T, int k, int grid, bool single, int dbg) {
-    PassShape p{};
-    int ss = T / (3 * k);
-    ss = ss < 1 ? 1 : (ss > 64 ? 64 : ss);
-    p.ss = ss;
-    p.n_s = (T - ss / 2 + ss - 1) / ss;
-    p.n_seg = 1; p.bound[0] = 0; p.bound[1] = T;
-    if (single) return p;
-    (void)dbg;
-#ifdef MSR_DIAG
-    // timing experiments of the diagnostic build: 2097152 three segments, 4194304 / 8388608 T1 at half / double the rule's
-    // value, 16777216 the sample in whole rounds of the grid
-    if ((dbg & 16777216) && grid >= 2 * k && p.n_s > grid) {
-        p.n_s = p.n_s / grid * grid;
-        p.ss = T / p.n_s;
-    }
-#endif
-    const double root = std::sqrt((double)T * (double)p.n_s);
-    int want3 = 0;
-#ifdef MSR_DIAG
-    want3 = dbg & 2097152;
-#endif
-    if (want3) {
-        const double r = std::cbrt((double)T / (double)p.n_s);
-        const int m1 = (int)std::floor(p.n_s * r / grid + 0.5), m2 = (int)std::floor(p.n_s * r * r / grid + 0.5);
-        const int64_t t1 = (int64_t)m1 * grid, t2 = (int64_t)m2 * grid;
-        if (m1 >= 1 && m2 > m1 && t1 >= 2 * k && T - t2 >= grid) {
-            p.n_seg = 3; p.bound[1] = (int)t1; p.bound[2] = (int)t2; p.bound[3] = T;
-            return p;
-        }
-    }
-    int64_t t1 = (int64_t)std::floor(root / grid + 0.5) * grid;
-#ifdef MSR_DIAG
-    if (dbg & 4194304) t1 = std::max<int64_t>(grid, t1 / 2 / grid * grid);
-    if (dbg & 8388608) t1 = 2 * t1;
-#endif
-    if (t1 >= std::max(grid, 2 * k) && T - t1 >= grid) {
-        p.n_seg = 2; p.bound[1] = (int)t1; p.bound[2] = T;
-    }
-    return p;
-}
-
-}  // namespace
-
-// Exact f32 top-k of up to 128 x g.max_groups queries; see the header of this file.  nq <= 128: one pass of the 128-query
+// Exact f32 top-k of up to g.caps.call_cap queries; see the header of this file.  nq <= 128: one pass of the 128-query
 // kernel; more: groups of 256 queries, one pass of the 256-query kernel each (a last group that is not full is padded with
 // zero queries: the bytes are the same).  The passes of all groups are queued back to back; everything between and after
 // them (the selects over tile maxima, bucketing, candidate lists, rescoring, final sort) runs ONCE for all queries of
@@ -1197,49 +1127,40 @@ PassShape pass_shape(int T, int k, int grid, bool single, int dbg) {
 // launches per group.
 hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k, int k_part,
                              float* out_part, hipEvent_t* ev, int* width_out, int* seg_out, hipStream_t stream) {
-    const int W = nq > 128 ? 256 : 128;                 // queries per pass
-    const int waves = 8;                                // waves per workgroup = emission buffers per workgroup (both kernels)
-    const int G = (nq + W - 1) / W;
-    if (nq <= 0 || G * W > 128 * g.max_groups || k < 1 || g.n_tiles < 2 * k) return hipErrorInvalidValue;
-    if (width_out) *width_out = W;
-    hipError_t err;
-    // Launches of several query groups are bound by the matrix pipes and the vector issue beside them, not by HBM: they read
-    // the f16 image of the rows when the engine holds one (the values the pass converts in registers otherwise -- same
-    // products, same results; the conversion is not repeated by every group).  One group per launch: the f32 rows.
-    int NT0 = 1;
-    if (W == 256 && (g.n_cus & 7) == 0) NT0 = std::min(std::min(G, g.max_nt), g.n_cus >> 3);
-    bool image16 = W == 256 && NT0 > 1 && g.emb_f16 != nullptr;
+    // width, groups per launch, the rows the launches read and the emit pass' cut: msr_stream_plan.h
+    StreamPlan p = stream_plan(g.caps, g.n_cus, nq, g.emb_tiled != nullptr, g.emb_f16 != nullptr);
 #ifdef MSR_DIAG
-    if (g_f32_dbg & (2048 | 1048576)) image16 = false;      // timing experiments: one group per launch / the f32 rows
+    {   // timing experiments: the switches change the plan's inputs or flags, nothing below reads them
+        StreamCaps c = g.caps;
+        if (g_f32_dbg & 2048) c.max_nt = 1;                                   // one group per launch
+        if (g_f32_dbg & 4096) c.max_nt = std::min(c.max_nt, 2);               // at most two
+        p = stream_plan(c, g.n_cus, nq, g.emb_tiled != nullptr && !(g_f32_dbg & 8192),       // 8192: the row-major matrix
+                        g.emb_f16 != nullptr && !(g_f32_dbg & 1048576));                    // 1048576: the f32 rows
+        if (g_f32_dbg & 16384) p.nt_loads = false;                            // default cache policy for the rows
+        if (g_f32_dbg & 33554432) p.entry_tmax = false;                       // the kernel stores the maxima, joined per launch
+    }
 #endif
-    if (image16) build_qimg2_kernel<true, false><<<dim3((GF_KT * 256 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg);
-    else if (W == 256) build_qimg2_kernel<false><<<dim3((GF_KT * 256 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg);
-    else build_qimg1_kernel<<<dim3((GF_KT * 128 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg);
+    if (!p.valid || k < 1 || g.n_tiles < 2 * k) return hipErrorInvalidValue;
+    const int W = p.W, G = p.G, NT = p.NT, grid = g.n_cus;
+    const PassShape shape = pass_shape(g.n_tiles, k, grid, g.single_emit != 0);
+    const int ss = shape.ss, n_s = shape.n_s;
+    if (width_out) *width_out = W;
+    if (seg_out) *seg_out = shape.n_seg;
+    hipError_t err;
+    // (the f16 image holds the values the pass converts in registers otherwise: same products, same results)
+    switch (p.qimg) {
+    case STREAM_QIMG_256_IMAGE16: build_qimg2_kernel<true, false><<<dim3((GF_KT * 256 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg); break;
+    case STREAM_QIMG_256: build_qimg2_kernel<false><<<dim3((GF_KT * 256 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg); break;
+    case STREAM_QIMG_128: build_qimg1_kernel<<<dim3((GF_KT * 128 * 4 + 255) / 256, G), 256, 0, stream>>>(qn, nq, (f16x8*)g.qimg); break;
+    }
     f16_margin_kernel<<<(nq + 3) / 4, 256, 0, stream>>>(qn, nq, g.err_max, g.margin);
     const float* margin = g.margin;
-    const int grid = g.n_cus;
-    const PassShape shape = pass_shape(g.n_tiles, k, grid, g.single_emit != 0, g_f32_dbg);
-    const int ss = shape.ss, n_s = shape.n_s;
-    if (seg_out) *seg_out = shape.n_seg;
     const size_t qimg_bytes = (size_t)GF_KT * W * 64;   // one group's image
-    // 256-query kernel: up to 4 groups per launch walk the same tile sequence on CUs of one XCD -- the rows come from HBM
-    // once per launch and from that XCD's L2 for the other groups (the bytes per query are what the pass costs)
-    int NT = 1;
-    if (W == 256 && (grid & 7) == 0) NT = std::min(std::min(G, g.max_nt), grid >> 3);
-#ifdef MSR_DIAG
-    if (g_f32_dbg & 2048) NT = 1;                       // timing experiments: one group per launch
-    if (g_f32_dbg & 4096) NT = std::min(NT, 2);
-#endif
     GemmF32Args a{};
     a.dbg = g_f32_dbg; a.nt = 1;
     a.E = (const char*)ix.emb; a.inv_pad = g.inv_pad; a.tile_row = g.tile_row;
-    bool tiled = W == 256 && g.emb_tiled != nullptr && !image16;
-#ifdef MSR_DIAG
-    if (g_f32_dbg & 8192) tiled = false;               // timing experiments: the row-major matrix
-#endif
-    if (tiled) { a.E = (const char*)g.emb_tiled; a.tile_trow = g.tile_trow; }
-    if (image16) a.E = (const char*)g.emb_f16;
-    const int tmax_parts = image16 ? 1 : waves;         // (the 16-bit image's data path joins the waves' tile maxima in LDS: one row per tile)
+    if (p.tiled) { a.E = (const char*)g.emb_tiled; a.tile_trow = g.tile_trow; }
+    if (p.image16) a.E = (const char*)g.emb_f16;
     a.n_rows = ix.n_chunks; a.tmax_t = g.tmax_t;
     // ---- sample pass of every group: maxima of every ss-th tile -> emission thresholds ----
     a.t_first = ss / 2; a.t_stride = ss; a.t_count = n_s;
@@ -1247,9 +1168,9 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
         a.nt = std::min(NT, G - gi);
         a.qimg = (const char*)g.qimg + gi * qimg_bytes;
         if (ev && gi == 0 && (err = hipEventRecord(ev[0], stream)) != hipSuccess) return err;
-        if ((err = launch_f32(W, false, a, grid, stream, tiled, image16)) != hipSuccess) return err;
+        if ((err = launch_f32(stream_kernel(p, a.nt), false, a, grid, stream)) != hipSuccess) return err;
         if (ev && gi == 0 && (err = hipEventRecord(ev[1], stream)) != hipSuccess) return err;
-        if ((err = msr_gemm_tmax(g.tmax_t, n_s, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride, g.tmax_stride, stream)) != hipSuccess) return err;
+        if ((err = msr_gemm_tmax(g.tmax_t, n_s, p.tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride, g.tmax_stride, stream)) != hipSuccess) return err;
     }
     if ((err = msr_gemm_kth(g.tmax, n_s, g.tmax_stride, nq, W * G, k, margin, g.thr, g.flag, stream)) != hipSuccess) return err;
     // The emit launches of the 256-query kernel over the f32 rows store no tile maxima (gemm_stream256_kernel, TMAX): the
@@ -1265,19 +1186,15 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
     // The sample's columns of g.tmax were consumed by the select above: the rows are set to -inf here, in stream order.
     // A flagged query (thr = +inf) and the padding queries emit nothing: rows of -inf, thresholds that stay +inf.  The
     // 128-query kernel and the 16-bit images' data path store their maxima and join them as before.
-    bool entry_tmax = W == 256 && !image16;
-#ifdef MSR_DIAG
-    if (g_f32_dbg & 33554432) entry_tmax = false;       // timing experiments: the kernel stores the maxima, joined per launch
-#endif
-    if (entry_tmax && (err = msr_gemm_tmax_clear(g.tmax, g.tmax_stride, W * G, stream)) != hipSuccess) return err;
-    // ---- emit pass, segment by segment (pass_shape above): every group's launch over the segment's tiles -- their maxima
+    if (p.entry_tmax && (err = msr_gemm_tmax_clear(g.tmax, g.tmax_stride, W * G, stream)) != hipSuccess) return err;
+    // ---- emit pass, segment by segment (pass_shape): every group's launch over the segment's tiles -- their maxima
     //      (the launch numbers its tiles from 0: tmax_t is joined into the segment's columns of g.tmax before the next launch
     //      overwrites it; with entry_tmax the segment ends with one walk over the wave buffers instead) + the entries at or
     //      above the threshold, appended to one set of wave buffers --, then the thresholds
     //      of ALL queries are raised to what the tiles seen so far vouch for.  The refresh never writes g.flag, never lowers a
     //      threshold and leaves the padding queries at +inf (gemm_kth_kernel, raise mode). ----
     a.t_stride = 1;
-    a.wvbuf = g.wvbuf; a.wv_cap = g.wv_cap * (8 / waves); a.wv_count = g.wv_count;
+    a.wvbuf = g.wvbuf; a.wv_cap = g.caps.wv_cap; a.wv_count = g.wv_count;
     for (int s = 0; s < shape.n_seg; ++s) {
         const int t0 = shape.bound[s], t1 = shape.bound[s + 1];
         a.t_first = t0; a.t_count = t1 - t0;
@@ -1286,13 +1203,13 @@ hipError_t msr_gemm_f32_pass(const GemmF32Index& g, const DenseIndex& ix, const 
             a.qimg = (const char*)g.qimg + gi * qimg_bytes;
             a.thr = g.thr + gi * W; a.q_base = gi * W; a.append = (s > 0 || gi > 0);
             if (ev && gi == 0 && s == 0 && (err = hipEventRecord(ev[2], stream)) != hipSuccess) return err;
-            if ((err = launch_f32(W, true, a, grid, stream, tiled, image16)) != hipSuccess) return err;
+            if ((err = launch_f32(stream_kernel(p, a.nt), true, a, grid, stream)) != hipSuccess) return err;
             if (ev && gi == 0 && s == shape.n_seg - 1 && (err = hipEventRecord(ev[3], stream)) != hipSuccess) return err;
-            if (!entry_tmax &&
-                (err = msr_gemm_tmax(g.tmax_t, t1 - t0, tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride + t0, g.tmax_stride, stream)) != hipSuccess) return err;
+            if (!p.entry_tmax &&
+                (err = msr_gemm_tmax(g.tmax_t, t1 - t0, p.tmax_parts, W * a.nt, g.tmax + (size_t)gi * W * g.tmax_stride + t0, g.tmax_stride, stream)) != hipSuccess) return err;
         }
         // (all groups' entries in one walk; those of earlier segments, tiles below t0, are read again and skipped)
-        if (entry_tmax && (err = msr_gemm_entry_tmax(g.wvbuf, a.wv_cap, g.wv_count, grid * waves, g.tmax, g.tmax_stride, t0,
+        if (p.entry_tmax && (err = msr_gemm_entry_tmax(g.wvbuf, a.wv_cap, g.wv_count, grid * STREAM_WAVES, g.tmax, g.tmax_stride, t0,
                                                      g.n_tiles, W * G, stream)) != hipSuccess) return err;
         if (s + 1 < shape.n_seg &&
             (err = msr_gemm_kth(g.tmax, t1, g.tmax_stride, nq, W * G, k, margin, g.thr, nullptr, stream, __builtin_inff(), 1.0f, true)) != hipSuccess)
@@ -1320,17 +1237,16 @@ __global__ __launch_bounds__(256) void raise_thr_kernel(float* __restrict__ thr2
 hipError_t msr_gemm_f32_finish(const GemmF32Index& g, const DenseIndex& ix, const float* qn, int nq, int k, const float* bound,
                                int32_t* out_doc, float* out_score, int32_t* out_chunk, int32_t* out_n, int32_t* gate,
                                hipStream_t stream) {
-    const int waves = 8, grid = g.n_cus;
-    const int wv_cap = g.wv_cap * (8 / waves);
+    const int grid = g.n_cus, wv_cap = g.caps.wv_cap;
     if (nq <= 0 || k < 1) return hipErrorInvalidValue;
     hipError_t err;
     if (bound) {
         raise_thr_kernel<<<(nq + 255) / 256, 256, 0, stream>>>(g.thr2, bound, g.margin, nq);
         if ((err = hipGetLastError()) != hipSuccess) return err;
     }
-    if ((err = msr_gemm_bucket(g.wvbuf, wv_cap, g.wv_count, grid * waves, g.thr2, g.pairs, g.pair_n, stream)) != hipSuccess) return err;
+    if ((err = msr_gemm_bucket(g.wvbuf, wv_cap, g.wv_count, grid * STREAM_WAVES, g.thr2, g.pairs, g.pair_n, stream)) != hipSuccess) return err;
     // candidates with the runs of their emitted rows (cand_chunk carries first | len << 13 in, the arg-max row out)
-    gemm_f32_cand_kernel<<<nq, 1024, 0, stream>>>((int2*)g.pairs, g.pair_n, ix.chunk_doc, ix.n_chunks, g.wv_count, grid * waves,
+    gemm_f32_cand_kernel<<<nq, 1024, 0, stream>>>((int2*)g.pairs, g.pair_n, ix.chunk_doc, ix.n_chunks, g.wv_count, grid * STREAM_WAVES,
                                                   wv_cap, g.flag, g.cand_doc, g.cand_chunk, g.cand_n, gate);
     if ((err = hipGetLastError()) != hipSuccess) return err;
     return msr_batch_rescore_rows(ix, qn, nq, k, (const int32_t*)g.pairs, 2, GF_PAIR_CAP, g.cand_doc, g.cand_score, g.cand_chunk,

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "msr_dense_plan.h"
+#include "msr_stream_plan.h"
 
 #define MSR_DIM 768
 #define MSR_SEL_BINS 4096      // 12-bit radix digits
@@ -480,22 +481,21 @@ struct GemmF32Index {
     const int32_t* tile_row;   // [n_tiles + 1] (the tile table of the bf16 GEMM: whole documents, <= 256 rows)
     int32_t n_tiles;
     int32_t n_cus;
-    int32_t max_groups;        // groups of 128 queries one call may hold (the per-query arrays below are sized 128 x this)
+    StreamCaps caps;           // what the binding holds (msr_stream_plan.h); the per-query arrays below: 128 caps.groups rows
     const float* inv_pad;      // [n_chunks + 512] inverse row norms, padded with 1
-    void* qimg;                // [max_groups] x 24 x 8 KB query images (f16)
-    float* tmax_t;             // [n_tiles][8 waves][128], or [256 max_nt] when max_groups >= 2 (the 256-query kernel)
-    float* tmax;               // [128 max_groups][tmax_stride]
+    void* qimg;                // [caps.groups] x 24 x 8 KB query images (f16)
+    float* tmax_t;             // [n_tiles][8 waves][caps.tmax_row]
+    float* tmax;               // [128 caps.groups][tmax_stride]
     int32_t tmax_stride;
     float* thr; float* thr2; int32_t* flag;                 // [128]
-    void* wvbuf; int32_t wv_cap; int32_t* wv_count;          // [n_cus * 8][wv_cap] x 16 B / [n_cus * 8]
+    void* wvbuf; int32_t* wv_count;                          // [n_cus * 8][caps.wv_cap] x 16 B / [n_cus * 8]
     void* pairs; int32_t* pair_n;                            // [128][4096] x 8 B / [128], zero between calls
     uint32_t* err_max; float* margin;                        // measured f16 rounding error of the rows (1 word) / margin [128]
     int32_t* cand_doc; float* cand_score; int32_t* cand_chunk; int32_t* cand_n;   // [128][MSR_SEL_CAP] x 3 / [128] (zero between calls)
-    int32_t max_nt;            // groups of 256 queries one launch of the 256-query kernel may serve (tmax_t holds 256 x this per row)
     const void* emb_tiled;     // fragment-order copy of the f32 rows for the 256-query kernel (nullptr: none), see msr_tile_rows
     const int32_t* tile_trow;  // [n_tiles] first row of each tile in that copy
-    const void* emb_f16;       // row-major f16 image of the rows (as the pass converts them; [n_chunks + 512][768], zero padded)
-                               // for launches of several query groups (nullptr: none), see msr_f16_rows
+    const void* emb_f16;       // row-major f16 image of the rows (as the pass converts them; [n_chunks + 512][768], zero padded;
+                               // nullptr: none), see msr_f16_rows.  Which launches read which copy: stream_plan
     int32_t single_emit;       // MSR_CFG_SINGLE_EMIT: the emit pass as ONE launch per group, thresholds from the sample alone
 };
 // emb_tiled <- fragment-order copy of emb: tile t's rows at tile_trow[t] (multiples of 16), 16-row groups x 24 K steps x 2 KB

@@ -12,8 +12,11 @@ adversarial placements of the winners, for random T1:
 The 256-query kernel compares against the threshold rounded DOWN to f16; the restatement does the same (rounding down is
 monotone, so the order of the thresholds survives it)."""
 import math
+import subprocess
 
 import numpy as np
+
+from test_stream_plan import build_stream_plan_check
 
 ROWS = 32                                                       # rows per tile of the model corpus
 
@@ -31,7 +34,7 @@ def _kth(v, k):
 
 
 def pass_shape(T, k, grid):
-    """The rule of msr_gemm_f32.hip's pass_shape: (ss, n_s, T1) with T1 = 0 for a one-launch pass."""
+    """The rule of msr_stream_plan.h's pass_shape: (ss, n_s, T1) with T1 = 0 for a one-launch pass."""
     ss = min(64, max(1, T // (3 * k)))
     n_s = (T - ss // 2 + ss - 1) // ss
     t1 = int(math.floor(math.sqrt(T * n_s) / grid + 0.5)) * grid
@@ -77,6 +80,25 @@ def test_segment_rule_at_the_documented_shapes():
                 continue
             t1 = pass_shape(T, k, 256)[2]
             assert t1 == 0 or (t1 % 256 == 0 and t1 >= max(256, 2 * k) and T - t1 >= 256)
+
+
+def test_the_restatement_is_the_rule_the_pass_runs(tmp_path):
+    """pass_shape of csrc/msr_stream_plan.h, printed by tests/stream_plan_check.cpp case by case, equals the restatement above
+    on every case: both take the correctly rounded double square root of the same integer product (< 2^53), so no tolerance."""
+    r = subprocess.run([build_stream_plan_check(tmp_path), "shapes"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr
+    seen = set()
+    for line in r.stdout.splitlines():
+        (T, k, grid, single), (ss, n_s, n_seg, t1) = [[int(x) for x in part.split()] for part in line.split(":")]
+        want = pass_shape(T, k, grid)
+        if single:
+            want = want[:2] + (0,)
+        assert (ss, n_s, t1) == want and n_seg == (2 if t1 else 1), line
+        seen.add((T, k, grid, single))
+    Ts = list(range(1, 1201)) + [5000, 20100, 40000, 200000]
+    assert seen == {(T, k, grid, single) for T in Ts for k in (1, 3, 10, 25, 100, 250, 1000) if T >= 2 * k
+                    for grid in (8, 64, 250, 256, 304) for single in (0, 1)}
+    assert any(t for t in seen if pass_shape(*t[:3])[2])            # (the enumeration cuts some passes)
 
 
 def test_segmented_emission_keeps_what_the_bucket_keeps():
