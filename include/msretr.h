@@ -19,8 +19,17 @@
  *   - All array arguments are DEVICE pointers into HBM of the engine's device unless marked [host].
  *     The caller owns them (typically torch tensors: tensor.data_ptr()) and must keep the bound index
  *     arrays alive until msr_destroy / the next msr_bind_*.
- *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream).  Work is only
- *     enqueued; nothing synchronises.  Results are valid once the stream has drained.
+ *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream).  Every kernel, copy and
+ *     clear of a call is issued on that stream and on no other (it may be a non-blocking stream with work pending:
+ *     inputs are read and scratch is cleared in stream order).  The QUERY calls only enqueue: they return while the
+ *     work is pending, and results are valid once the stream has drained.  The calls that wait for the stream say so
+ *     in their own comment -- the binds that check an index on the device (msr_bind_postings, msr_bind_chunks,
+ *     msr_bind_tokens, msr_bind_vocab, msr_bind_facet), msr_gather_rows, msr_dense_topk_grouped, the diagnostics
+ *     msr_debug_scratch_dirty, msr_dense_pass_info (the whole device) and msr_kernel_time_ms, and the offline index
+ *     builds -- and no other call does.  msr_create returns with the engine's scratch cleared (it waits for the null
+ *     stream once).  Calls that take `stream` and launch nothing (msr_bind_doc_meta, msr_bind_doc_domains,
+ *     msr_bind_signatures) ignore it.  tests/stream_cases.py holds the table and tests/test_gpu_streams.py checks it
+ *     on a stream with pending work.
  *   - A document is addressed by its dense index: the rank of its doc_id in ascending order, so
  *     "ascending index" == "ascending doc_id" (the reference's tie order, bm25_indexer.py:445,484).
  *     A shard adds `doc_base` to its local indices before the merge.
@@ -114,6 +123,9 @@ typedef struct msr_rerank_params {
 } msr_rerank_params;
 
 int msr_abi_version(void);
+/* msr_create: allocates the engine's per-query scratch on cfg->device and clears the buffers documented "zero between
+ * calls"; the clears are issued on the null stream and the call waits for them, so the first call on ANY stream -- a
+ * non-blocking one included -- finds them done.  Not a hot path. */
 int msr_create(const msr_config* cfg, msr_engine** out);
 int msr_destroy(msr_engine* e);
 /* e may be NULL: returns the text of the last failed msr_create on this thread. */
@@ -124,6 +136,8 @@ const char* msr_last_error(const msr_engine* e);
  *   doc_len[n_docs] i32                                                          bm25_doc_stats  (:88-94)
  *   idf[n_terms] f32 (as stored: REAL, may be negative)                          bm25_term_stats (:106-113)
  *   avgdl f32 (REAL)                                                             bm25_corpus_stats (:116-122)
+ * The index is validated on the device and the term offsets are read on the host (the skip and dense tables of the long
+ * lists are built from them): the call synchronises the stream, several times.  One-time, at bind.
  */
 int msr_bind_postings(msr_engine* e, const int64_t* term_off, int64_t n_terms, const int32_t* post_doc,
                       const int32_t* post_tf, int64_t n_postings, const int32_t* doc_len, int64_t n_docs,
@@ -141,7 +155,9 @@ int msr_bind_postings(msr_engine* e, const int64_t* term_off, int64_t n_terms, c
  * When cfg.max_queries >= 512 (calls that put several 256-query groups into one launch: those launches are bound by the
  * matrix pipes, not by HBM) also an f16 image of the rows, (n_chunks + 512) x 1536 bytes: the values the 256-query pass
  * otherwise converts in registers, group after group -- the same products, the same results bit for bit.  Launches of ONE
- * group (<= 256 queries per call: the HBM-bound case) never read it; same switch, same fallback (msr_row_image_state). */
+ * group (<= 256 queries per call: the HBM-bound case) never read it; same switch, same fallback (msr_row_image_state).
+ * The document offsets are read on the host (the spans and row tiles are cut there) and the range of the row norms picks the
+ * scan's arithmetic: the call synchronises the stream.  One-time, at bind. */
 int msr_bind_chunks(msr_engine* e, const float* emb, int64_t n_chunks, const int32_t* doc_off,
                     int64_t n_docs, const float* inv_norm, void* stream);
 /* What became of that copy: 0 = not applicable (max_queries < 256 or the corpus does not qualify), 1 = built and used,
@@ -187,8 +203,9 @@ int msr_dense_path(const msr_engine* e);
  * call is served in several): *segments = emit launches per query group -- 1: one launch over all row tiles (a small corpus,
  * or MSR_CFG_SINGLE_EMIT), 2: the pass was cut after the first T1 tiles and the emission thresholds raised to what their tile
  * maxima vouch for; 0: the call ran on the sweeps (then *entries = 0) --, *entries = (row, query, score) entries the pass
- * appended to its per-wave buffers, summed over the waves (counted past a buffer's capacity when one overflowed).  DIAGNOSTIC:
- * waits for the device and copies the counters to the host; it belongs in tests and measurements, never on a serving path. */
+ * appended to its per-wave buffers, summed over the waves (counted past a buffer's capacity when one overflowed).  DIAGNOSTIC
+ * and a DEVICE-WIDE WAIT: it takes no stream, waits for the whole device (hipDeviceSynchronize: every stream of every engine)
+ * and copies the counters to the host with a blocking copy; it belongs in tests and measurements, never on a serving path. */
 int msr_dense_pass_info(msr_engine* e, int32_t* segments, int64_t* entries);
 /* The same for the <= 128-query sweeps of msr_dense_topk_bf16 (after msr_enable_bf16): 128, 64, or -1. */
 int msr_batch_width(const msr_engine* e);
@@ -908,11 +925,11 @@ int msr_debug_chunk_layout(const int32_t* doc_off, int64_t n_docs, int32_t out[4
  * since msr_set_timing(e, 1).  which: 0 = dense scan kernel, 1 = BM25 TAAT kernel, 2 = GEMM emit pass (all row tiles),
  * 3 = GEMM sample pass (every 16th tile). */
 int msr_set_timing(msr_engine* e, int32_t enabled);
+int msr_kernel_time_ms(msr_engine* e, int32_t which, float* out_ms, int32_t* out_launches);
 /* Measurement hook of the DIAGNOSTIC build (libmsretr_diag.so, -DMSR_DIAG: knock-out switches of the GEMM kernels,
  * tools/gemm_check.py --dbg).  The product library knows no key and returns MSR_ERR_INVALID: it has no switches, no
  * environment variables and one implementation per kernel. */
 int msr_tune(msr_engine* e, int32_t key, int32_t value);
-int msr_kernel_time_ms(msr_engine* e, int32_t which, float* out_ms, int32_t* out_launches);
 
 #ifdef __cplusplus
 }

@@ -239,8 +239,11 @@ static int create_scratch(msr_engine* e) {
     ALLOC(e, e->mem_engine, e->sel.cand_hi, nq * MSR_SEL_CAP * sizeof(uint64_t));
     ALLOC(e, e->mem_engine, e->sel.cand_lo, nq * MSR_SEL_CAP * sizeof(uint32_t));
     ALLOC(e, e->mem_engine, e->sel.cand_n, nq * sizeof(int32_t));
-    HIP_TRY(e, hipMemset(e->sel.hist, 0, nq * MSR_SEL_BINS * sizeof(uint32_t)));
-    HIP_TRY(e, hipMemset(e->sel.cand_n, 0, nq * sizeof(int32_t)));
+    // "zero between calls" from the start: cleared on the null stream and waited for here, so that the engine's first call finds
+    // them done on whatever stream it comes -- a non-blocking stream does not wait for the null stream (creation is no hot path)
+    HIP_TRY(e, hipMemsetAsync(e->sel.hist, 0, nq * MSR_SEL_BINS * sizeof(uint32_t), nullptr));
+    HIP_TRY(e, hipMemsetAsync(e->sel.cand_n, 0, nq * sizeof(int32_t), nullptr));
+    HIP_TRY(e, hipStreamSynchronize(nullptr));
     if (cfg.rerank_max_docs > 0) {
         ALLOC(e, e->mem_engine, e->rerank_cos, nq * (size_t)cfg.rerank_max_docs * MSR_RERANK_MAX_CHUNKS * sizeof(float));
         ALLOC(e, e->mem_engine, e->rerank_meta, nq * (size_t)cfg.rerank_max_docs * 3 * sizeof(int32_t));

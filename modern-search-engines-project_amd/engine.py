@@ -384,8 +384,9 @@ class DeviceEngine:
         -> DeviceSets (bits, q_set, n_sets, stride), to be passed as within= to bm25_topk / dense_topk / dense_topk_grouped.
         Queries with the same (set of must ids, set of must_not ids, base) share one row -- compared as sets of ids on the
         host (repeats and order do not matter), never on bits; must_not ids the index lacks or whose list is empty are dropped
-        here.  A query without operators gets its base's row, or -1, and costs no kernel row.  Only enqueues -- except the
-        FIRST call after a bind, which reads the document frequencies (term_off, for the order of the must terms) once: a
+        here.  A query without operators gets its base's row, or -1, and costs no kernel row.  Reads nothing back; the upload of
+        the lists is a blocking copy on the caller's stream (it waits for what the stream holds).  The
+        FIRST call after a bind also reads the document frequencies (term_off, for the order of the must terms) once: a
         synchronous copy of 8 bytes per term if the index lives on the device; they are kept until the next bind."""
         from .docset import DeviceSets
         bits, q_set, n_sets, stride, _ = self._term_rows(must, must_not, within)
@@ -621,7 +622,8 @@ class DeviceEngine:
         (msretr.h msr_phrase_sets).  A must phrase with an unknown id, or an empty one, empties the set; such a not phrase is
         ignored; a longer phrase raises ValueError.  -> DeviceSets, for every consumer of term_sets' result.
 
-        Three launches, nothing synchronises: ONE term_sets call builds every phrase's candidate row (a must phrase: its
+        Three launches, nothing is read back (the uploads of the host lists are blocking copies on the caller's stream: they
+        wait for what the stream holds): ONE term_sets call builds every phrase's candidate row (a must phrase: its
         terms AND the query's base and must / must_not terms; a not phrase: its terms AND the base), ONE msr_phrase_sets call
         verifies the distinct (phrase, candidate row) pairs -- compared as tuples on the host, identical pairs share a row --
         and ONE msr_combine_sets call gives each query the AND of its must rows without its not rows (a query with only not
@@ -752,7 +754,8 @@ class DeviceEngine:
         entries: start int32 (-1: no window), cover int32, hits int32, mask int64 (the uint64 position mask's bits), terms
         int32 (the uint32 term bits).  rows: lists of term ids, weights: lists of ints (one per id), spans: an int or one per
         row.  pair_doc / pair_row: host arrays or device tensors of document indices and row numbers.  Every list travels in
-        ONE upload (host pairs with them), ONE launch follows and nothing synchronises: the caller copies back.  What the
+        ONE upload (host pairs with them; a blocking copy on the caller's stream, so it waits for what the stream holds), ONE
+        launch follows and nothing is read back: the caller copies back.  What the
         ABI turns into "no window" (an id, weight, span, document or row out of range) is not checked here.  Raises MsrError
         when the index has no forward index."""
         if not self.has_tokens:

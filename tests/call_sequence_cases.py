@@ -286,7 +286,7 @@ def _named(names, arrays):
 class Bundle:
     """One engine on one index, alive for a whole test module, and the device copies of the entries' inputs."""
 
-    def __init__(self, name):
+    def __init__(self, name, stage=None):
         import torch
         from msretr.engine import DeviceEngine
         from msretr.index import CorpusIndex
@@ -294,6 +294,7 @@ class Bundle:
         self.name, self.torch = name, torch
         self.retriever = None
         self._dev, self._sets = {}, {}
+        self.stage = stage                                    # None: inputs are uploaded once and stay as they are
         self.clean = {}                                       # probe name -> its outputs as the first call after a fresh bind
         self.bf16 = name == "bf16"
         if name == "lex":
@@ -338,11 +339,7 @@ class Bundle:
         if key not in self._dev:
             a = make()
             if isinstance(a, np.ndarray):
-                if a.dtype == np.uint64:
-                    a = a.view(np.int64)
-                if a.dtype == np.uint32:
-                    a = a.view(np.int32)
-                a = self.torch.from_numpy(np.ascontiguousarray(a)).to(self.eng.device)
+                a = self._up(a, key)
             self._dev[key] = a
         return self._dev[key]
 
@@ -357,23 +354,27 @@ class Bundle:
 
     # -- shared call helpers
     def select(self, case, key, **kw):
-        d = self.dev(("select", key), lambda: dict(
-            scores=self._up(case.scores), idx=self._up(case.idx), counts=self._up(case.counts), win_base=self._up(case.win_base),
-            set_bits=self._up(case.set_bits), q_set=self._up(case.q_set)))
+        d = self.dev(("select", key), lambda: {f: self._up(getattr(case, f), ("select", key, f))
+                                               for f in ("scores", "idx", "counts", "win_base", "set_bits", "q_set")})
         doc, score, n, state = self.eng.debug_select(d["scores"], case.k, n=case.n, idx=d["idx"], counts=d["counts"],
                                                      seg_stride=case.seg_stride, win_base=d["win_base"], set_bits=d["set_bits"],
                                                      q_set=d["q_set"], **kw)
         doc, score, n = _host(doc, score, n)
         return dict(doc=doc, score=score, n=n, state=state.view(np.uint8).copy()), state
 
-    def _up(self, a):
+    def _up(self, a, key=None):
+        """Host array -> device tensor.  With a stage (stream_cases.Stage: the tests on a caller's stream) the tensor is the
+        stage's LIVE copy of input `key`, which the stage fills with a decoy or with `a` by device-to-device copies."""
         if a is None:
             return None
         if a.dtype == np.uint64:
             a = a.view(np.int64)
         if a.dtype == np.uint32:
             a = a.view(np.int32)
-        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.eng.device)
+        a = np.ascontiguousarray(a)
+        if self.stage is not None:
+            return self.stage.adopt(key, a)
+        return self.torch.from_numpy(a).to(self.eng.device)
 
     def qdev(self, key, mat):
         return self.dev(("q", key), lambda: np.ascontiguousarray(mat, np.float32))
