@@ -5,7 +5,7 @@ two-stage path and write `qnum<TAB>rank<TAB>url<TAB>score` lines, like POST /api
 is generated: documents are bags of words from a vocabulary that contains the query words, indexed with
 msretr.index_build (the reference's BM25.build_index semantics) and given random unit-norm chunk embeddings.
 
-    python examples/run_queries_txt.py [--fuzzy] [--wildcards] [--collapse-duplicates] [queries.txt] [out.txt]
+    python examples/run_queries_txt.py [--fuzzy] [--wildcards] [--collapse-duplicates] [--match VALUE] [queries.txt] [out.txt]
 
 --fuzzy: words the vocabulary lacks are replaced by their nearest term (Retriever.batch_search(fuzzy=True)) and every
 correction is printed.
@@ -13,6 +13,8 @@ correction is printed.
 (Retriever.batch_search(wildcards=True)) and every expansion is printed.
 --collapse-duplicates: every tenth page of the crawl is a mirror of the page before it under another host; near-duplicate
 pages are shown once (Retriever.batch_search(collapse_duplicates=True)) and the number of rows dropped per query is printed.
+--match all | 2 | 75%: only pages that hold all / at least two / three quarters of a query's words
+(Retriever.batch_search(match=...)); every query's slots and how many of them a page must fill are printed.
 """
 import os
 import sys
@@ -69,7 +71,15 @@ def fake_encoder(dim=768):
 
 def main():
     from msretr.retriever import Retriever
-    argv = [a for a in sys.argv[1:] if a not in ("--fuzzy", "--wildcards", "--collapse-duplicates")]
+    args, match = sys.argv[1:], "any"
+    if "--match" in args:                                    # --match all | --match 2 | --match 75%
+        at = args.index("--match")
+        if at + 1 >= len(args):
+            sys.exit("--match needs a value: all, a whole number, or a percentage like 75%")
+        match = args[at + 1]
+        match = int(match) if match.lstrip("-").isdigit() else match
+        del args[at:at + 2]
+    argv = [a for a in args if a not in ("--fuzzy", "--wildcards", "--collapse-duplicates")]
     fuzzy, wildcards = "--fuzzy" in sys.argv[1:], "--wildcards" in sys.argv[1:]
     collapse = "--collapse-duplicates" in sys.argv[1:]
     qfile = argv[0] if len(argv) > 0 else None
@@ -78,7 +88,7 @@ def main():
     ix = synthetic_crawl(mirrors=collapse)
     rt = Retriever(embedder=fake_encoder(), indexer=ix, tokenizer=simple_tokenize, max_queries=8, max_k=1000)
     # the reference's `results` list (dicts built on access) ...
-    res = rt.batch_search(queries, fuzzy=fuzzy, wildcards=wildcards, collapse_duplicates=collapse)
+    res = rt.batch_search(queries, fuzzy=fuzzy, wildcards=wildcards, collapse_duplicates=collapse, match=match)
     res.write(out)                                  # ... and all formatted lines in one native call
     print(f"{len(queries)} queries -> {len(res)} result lines in {out}")
     for (qn, _), text in zip(queries, res.corrected_queries or ()):
@@ -87,6 +97,8 @@ def main():
     for (qn, _), exp in zip(queries, res.expansions or ()):
         for pattern, info in exp.items():
             print(f"query {qn}: {pattern} -> {', '.join(info['terms']) or 'nothing'} ({info['total']} matches)")
+    for (qn, _), m in zip(queries, res.match or ()):
+        print(f"query {qn}: pages that hold at least {m['need']} of {' | '.join('/'.join(map(str, s)) for s in m['slots'])}")
     for (qn, _), dropped in zip(queries, res.collapsed or ()):
         print(f"query {qn}: {dropped} near-duplicate rows collapsed")
     rt.engine.close()

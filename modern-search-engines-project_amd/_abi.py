@@ -28,6 +28,7 @@ MSR_WILD_MAX_LEN = 32
 MSR_WILD_MAX_PATTERNS = 1024
 MSR_WILD_MAX_LIMIT = 16
 MSR_FACET_MAX_LIMIT = 64
+MSR_MATCH_MAX_GROUPS = 64
 MSR_SIG_WORDS = 64
 MSR_SIG_MAX_SHINGLE = 8
 MSR_COLLAPSE_MAX_CAND = 1024
@@ -93,6 +94,8 @@ _SIGNATURES = {
     "msr_dense_topk_within": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P,
                                         _P]),
     "msr_term_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
+    # include/msretr_match.h
+    "msr_match_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "msr_bind_tokens": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P]),
     "msr_phrase_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
     "msr_proximity_sets": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, C.c_int64, _P]),
@@ -157,7 +160,8 @@ _SIGNATURES = {
     "msr_tune": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "msr_kernel_time_ms": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
 }
-EXPORTS = tuple(_SIGNATURES)
+MATCH_EXPORTS = ("msr_match_sets",)                      # the calls of include/msretr_match.h
+EXPORTS = tuple(n for n in _SIGNATURES if n not in MATCH_EXPORTS)           # ... of msretr.h and msretr_encoder.h
 
 _lib = None
 

@@ -125,14 +125,18 @@ class BM25:
     @serialised
     def search(self, query: str, top_k: int = 1000, min_score: float = 0.0, within=None, operators: bool = False,
                must=None, must_not=None, phrases: bool = False, must_phrases=None, must_not_phrases=None,
-               proximity: bool = False, fuzzy: bool = False, wildcards: bool = False, max_expansions: int = 8, patterns=None):
+               proximity: bool = False, fuzzy: bool = False, wildcards: bool = False, max_expansions: int = 8, patterns=None,
+               match="any"):
         """The switches and lists are query.SearchOptions' and query.Conditions', for this ONE query: must / must_not are one
         list of term strings (or ids) each, must_phrases / must_not_phrases one list of phrases (strings, lists of term
         strings or ids, text.Near), patterns one list of pattern strings.  The query is taken as it is -- no city is appended
         here.  The conditions restrict the documents on the device (DeviceEngine.term_sets / phrase_sets), inside `within`;
-        with fuzzy=True or patterns the result is a fuzzy.Results list (`corrections`, `corrected_query`, `expansions`)."""
+        with fuzzy=True or patterns the result is a fuzzy.Results list (`corrections`, `corrected_query`, `expansions`).
+        match ("all", m, "75%": SearchOptions): only pages that fill enough of the query's slots (match.slots -- no city
+        term is appended here, so every word with idf > 0 is one), counted on the device by ONE match.match_sets call; the
+        result is then a fuzzy.Results list with `match`."""
         opts = SearchOptions(operators=operators, phrases=phrases, proximity=proximity, fuzzy=fuzzy, wildcards=wildcards,
-                             max_expansions=max_expansions)
+                             max_expansions=max_expansions, match=match)
         one = lambda v: None if v is None else [v]
         explicit = Conditions(one(must), one(must_not), one(must_phrases), one(must_not_phrases))
         opts.check(patterns=patterns is not None, int_types=int)
@@ -148,6 +152,7 @@ class BM25:
         m = [] if cond.must is None else cond.must[0]
         ids = self.index.term_ids
         corrections = None
+        words = list(query_terms)
         if fuzzy:
             self._check_fuzzy()
             new_ids, new_must, corr = _fuzzy.correct(self._lookup, self._name_of, [query_terms], [ids(query_terms)], [m], [ids(m)])
@@ -156,14 +161,27 @@ class BM25:
             c = replace(cond, must=None if cond.must is None else [m]).ids(ids, self._tokenize)
             within = c.sets(self.engine, None if within is None else [within])
         expansions = None
+        typed = query_terms
         if pats is not None:
             new_ids, exp = _wildcard.expand(lambda ps: self.engine.wildcard_terms(ps, limit=max_expansions), self._name_of,
                                             [ids(query_terms)], [pats], max_expansions)
             query_terms, expansions = new_ids[0], exp[0]
+        info = None
+        if opts.match_on:                                          # on top of the conditions' sets, in front of the scoring
+            from . import match as _match
+            typed_ids = ids(typed)
+            groups = _match.slots(self.index, typed_ids,
+                                  None if expansions is None else [ids(e["terms"]) for e in expansions.values()])
+            n = _match.need(match, len(groups))
+            unknown = [w for w, t in zip(words, typed_ids) if not 0 <= int(t) < self.index.n_terms]
+            info = {"slots": _match.slot_names(groups, self._name_of, unknown), "need": n}
+            if n is not None:
+                within = _match.match_sets(self.engine, [groups], [n], within)
         rows = self._finish(self.search_terms(query_terms, top_k, min_score, within=within))
-        if corrections is None and expansions is None:
+        if corrections is None and expansions is None and info is None:
             return rows
-        return _fuzzy.Results(rows, corrections, _fuzzy.corrected_text(query, corrections) if corrections else None, expansions)
+        return _fuzzy.Results(rows, corrections, _fuzzy.corrected_text(query, corrections) if corrections else None, expansions,
+                              match=info)
 
     def _finish(self, ranked):
         """urlsDB join after the cut: documents without a row are dropped, snippet = title + 200 chars

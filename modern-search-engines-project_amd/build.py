@@ -33,6 +33,7 @@ UNITS = {
     "msr_compact.hip": [],
     "msr_similar.hip": [],
     "msr_termset.hip": [],
+    "msr_match.hip": [],
     "msr_phrase.hip": [],
     "msr_proximity.hip": [],
     "msr_snippet.hip": [],
@@ -69,6 +70,7 @@ def build_library(force=False, verbose=False, save_temps=False, diag=False):
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     headers.append(os.path.join(HERE, "..", "include", "msretr.h"))
     headers.append(os.path.join(HERE, "..", "include", "msretr_encoder.h"))
+    headers.append(os.path.join(HERE, "..", "include", "msretr_match.h"))
     objs, jobs = [], []
     for src, extra in UNITS.items():
         s = os.path.join(CSRC, src)

@@ -12,6 +12,7 @@
 #include "../../include/msretr.h"
 #include "msr_devmem.h"
 #include "msr_internal.h"
+#include "msr_match_args.h"
 
 struct HipMem {
     static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
@@ -985,6 +986,23 @@ extern "C" int msr_term_sets(msr_engine* e, int32_t n_rows, const int32_t* must_
     HIP_TRY(e, hipSetDevice(e->cfg.device));
     HIP_TRY(e, msr_term_sets_run(e->bm25, n_rows, must_off, must_terms, not_off, not_terms, base_bits, n_base, base_stride,
                                  row_base, out_bits, out_stride, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+// ---- K19: match modes (msr_match.hip; include/msretr_match.h) ------------------------------------------------------------------
+extern "C" int msr_match_sets(msr_engine* e, int32_t n_rows, const int32_t* row_group_off, const int32_t* group_term_off,
+                              const int32_t* group_terms, const int32_t* row_need, const uint32_t* base_bits, int32_t n_base,
+                              int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride, void* stream) {
+    if (!e) return MSR_ERR_INVALID;
+    if (!e->have_postings) return fail(e, MSR_ERR_NOT_BOUND, "msr_match_sets: postings not bound");
+    char why[192];
+    const int rc = msr_match_args_check(e->bm25.n_docs, n_rows, out_bits && row_group_off && group_term_off && row_need, out_stride,
+                                        n_base, base_bits && row_base, base_stride, why, sizeof why);
+    if (rc) return fail(e, rc, "%s", why);
+    if (n_rows == 0) return MSR_OK;
+    HIP_TRY(e, hipSetDevice(e->cfg.device));
+    HIP_TRY(e, msr_match_sets_run(e->bm25, n_rows, row_group_off, group_term_off, group_terms, row_need, base_bits, n_base,
+                                  base_stride, row_base, out_bits, out_stride, (hipStream_t)stream));
     return MSR_OK;
 }
 

@@ -184,6 +184,13 @@ hipError_t msr_term_sets_run(const Bm25Index& ix, int n_rows, const int32_t* mus
                              int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride,
                              hipStream_t stream);
 
+// K19 (msr_match.hip): rows of document sets that count filled groups (see msretr_match.h msr_match_sets; arguments checked by
+// the caller).
+hipError_t msr_match_sets_run(const Bm25Index& ix, int n_rows, const int32_t* row_group_off, const int32_t* group_term_off,
+                              const int32_t* group_terms, const int32_t* row_need, const uint32_t* base_bits, int n_base,
+                              int64_t base_stride, const int32_t* row_base, uint32_t* out_bits, int64_t out_stride,
+                              hipStream_t stream);
+
 // K12 (msr_phrase.hip): phrase search on the forward index (see msretr.h; arguments checked by the caller).
 // *flag <- max(*flag, code): 1 tok_off does not run from 0 to n_tokens, 2 it descends, 3 an id outside [0, n_terms)
 hipError_t msr_tokens_validate(const int64_t* tok_off, const int32_t* tok_ids, int64_t n_docs, int64_t n_tokens, int64_t n_terms,

@@ -315,7 +315,7 @@ class ShardedEngine:
     # ------------------------------------------------------------------ the sharded hot path
     def search(self, term_lists, qvec, k1=1000, k2=100, min_score=0.0, max_chunks_per_doc=0, rerank=True,
                packed=None, dense_batched=False, rerank_keep=None, fuzzy=False, wildcards=False, collapse_duplicates=False,
-               **rerank_params):
+               match="any", **rerank_params):
         """-> dict(bm25=(doc, score, n), dense=(doc, score, chunk, n), rerank=(doc, score, orig, chunk, n, rows)); documents
         and chunk rows are GLOBAL indices; every rank returns the same tensors.  rerank_keep: entries per query of the fused
         lists to return (None: all k1; the reranker facade's diversification wants them all, a top-100 service k2).
@@ -323,7 +323,11 @@ class ShardedEngine:
         terms and their lists would disagree (DESIGN K15); correct the words on an unsharded engine and pass the ids.
         wildcards=True is refused for the same reason (DESIGN K16): a pattern's first matches depend on the frequencies.
         collapse_duplicates=True is refused (DESIGN K18): the fused lists hold GLOBAL documents and a shard has the signatures
-        of its own only."""
+        of its own only.
+        match other than "any" is refused (DESIGN K19): the sharded path has no restricted stage to hand the sets to."""
+        if not (match is None or (isinstance(match, str) and match == "any")):
+            raise ValueError("match= is not available on a sharded engine: its stages take no document sets (no within=); "
+                             "build the sets on an unsharded engine (match.match_sets) and search there")
         if collapse_duplicates:
             raise ValueError("collapse_duplicates=True is not available on a sharded engine: a rank holds the signatures of its "
                              "own documents only, the fused lists name documents of every shard; collapse on an unsharded "

@@ -392,6 +392,16 @@ class DeviceEngine:
         bits, q_set, n_sets, stride, _ = self._term_rows(must, must_not, within)
         return DeviceSets(self.index, bits, torch.tensor(q_set, dtype=torch.int32, device=self.device), n_sets, stride)
 
+    def _doc_freq(self):
+        """int64 [n_terms]: the document frequencies of the bound index (term_sets and match.match_sets order their lists by
+        them), read once per bind and kept until the next."""
+        from .index import _np
+        ix = self.index
+        df = getattr(self, "_df", None)
+        if df is None or df[0] is not ix:
+            df = self._df = (ix, np.diff(_np(ix.term_off).astype(np.int64)))
+        return df[1]
+
     def _term_rows(self, must, must_not, within, extra_rows=0, tail=None):
         """The work of term_sets -> (bits int32 [n_sets + extra_rows, stride] device, q_set as a HOST list, n_sets, stride,
         tail on the device or None); the extra rows (behind the n_sets rows, not written here) are for a caller that derives
@@ -421,10 +431,7 @@ class DeviceEngine:
             base_of = base_q.tolist()
             if n_base:
                 base_bits = torch.from_numpy(words.view(np.int32)).to(self.device)
-        df = getattr(self, "_df", None)
-        if df is None or df[0] is not ix:
-            df = self._df = (ix, np.diff(_np(ix.term_off).astype(np.int64)))
-        df, n_terms = df[1], int(ix.n_terms)
+        df, n_terms = self._doc_freq(), int(ix.n_terms)
         EMPTY = ((-1,), ())
         rows, row_of, q_row, keep_base = [], {}, [], False
         for q in range(Q):

@@ -113,8 +113,9 @@ class Results(list):
     pattern) -- and, with facets=True (DESIGN K17), what the whole match set holds: `hits` (pages that match at all, None
     without facets), `facets` ([{"value": name, "count": n}, ...], the values with the most matching pages first) and
     `facet_values` (the number of distinct values hit) -- and, with collapse_duplicates=True (DESIGN K18), `collapsed`: the
-    number of near-duplicate rows dropped from the list (the rows that swallowed them carry "duplicates").  Equal to the plain
-    list of its rows."""
+    number of near-duplicate rows dropped from the list (the rows that swallowed them carry "duplicates") -- and, with match=
+    (DESIGN K19), `match`: {"slots": [[term, ...], ...], "need": m}, the query's slots and how many of them every row's page
+    fills (None without match=).  Equal to the plain list of its rows."""
     corrections = {}
     corrected_query = None
     expansions = {}
@@ -122,9 +123,10 @@ class Results(list):
     facets = []
     facet_values = 0
     collapsed = 0
+    match = None
 
     def __init__(self, rows=(), corrections=None, corrected_query=None, expansions=None, hits=None, facets=None,
-                 facet_values=0, collapsed=0):
+                 facet_values=0, collapsed=0, match=None):
         super().__init__(rows)
         self.corrections = dict(corrections or {})
         self.corrected_query = corrected_query
@@ -133,3 +135,4 @@ class Results(list):
         self.facets = list(facets or [])
         self.facet_values = int(facet_values)
         self.collapsed = int(collapsed)
+        self.match = match

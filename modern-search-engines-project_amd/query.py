@@ -101,7 +101,20 @@ class SearchOptions:
     that swallowed one gains "duplicates": [{"doc_id", "url", "title", "similarity": equal words / 64}, ...] in the order
     they were dropped; rows that swallowed nothing lack the key.  The scores are unchanged, diversification then works on
     the collapsed list, matched_by and snippets are those of the rows that stay, and facets=True still counts ALL matches,
-    copies included.  Needs an index with a forward index (MsrError)."""
+    copies included.  Needs an index with a forward index (MsrError).
+    match="all" | m | "75%" (DESIGN K19; default "any": every search is an OR and ranking alone decides): a result must hold
+    ALL of the query's words, or at least m of them.  The words are the query's slots (match.slots): every distinct scored
+    word with idf > 0 is a slot (so the city term that preprocessing appends is none, and neither is a typed `tübingen`), a
+    word the vocabulary lacks is a slot that no page fills (match="all" then returns nothing, as `+word` does; fuzzy=True runs
+    first and may have replaced it), and the expansions of one wildcard pattern are ONE slot that any of them fills.  How
+    many slots a page must fill is match.need: "all" -- all G; an int m -- m, a negative one all but |m|; "75%" -- floor(0.75
+    G), "-25%" -- G less floor(0.25 G); always at least 1 and at most G (Lucene's minimum_should_match rule).  A bool, 0,
+    "0%", a float or another string raises ValueError.  ONE match.match_sets call per chunk of queries counts the slots on
+    the device, inside within= and inside what operators, phrases and proximity built, and its rows restrict BOTH stages of
+    either mode: a result of match="all" holds all the words whichever stage found it.  Scores and the order among the pages
+    that stay are unchanged.  Each query's result is then a fuzzy.Results list whose `match` is {"slots": [[term, ...],
+    ...], "need": m} (need None: the query has no slot, nothing was restricted).  With facets=True `hits` and `facets` count
+    inside the matched set -- "how many pages hold all my words" -- because they count inside the restriction."""
     mode: str = "lexical"
     dense_k: int = 100
     operators: bool = False
@@ -117,14 +130,20 @@ class SearchOptions:
     facet_limit: int = 10
     collapse_duplicates: bool = False
     duplicate_threshold: float = 0.9
+    match: object = "any"
 
     @property
     def min_matches(self):
         """Equal signature words (of MSR_SIG_WORDS) from which two pages are duplicates: ceil(duplicate_threshold * 64)."""
         return int(math.ceil(float(self.duplicate_threshold) * MSR_SIG_WORDS))
 
+    @property
+    def match_on(self):
+        """True unless match is "any" or None: only then is match.py imported and anything of it uploaded or launched."""
+        return not (self.match is None or (isinstance(self.match, str) and self.match == "any"))
+
     def check(self, patterns=False, int_types=(int, np.integer)):
-        """ValueError unless the values are in range: the mode; and of the features that are on, snippet_tokens of 1 ..
+        """ValueError unless the values are in range: the mode; the match value (match.check_value); and of the features that are on, snippet_tokens of 1 ..
         MSR_PROX_MAX_SPAN, the facet key and limit (facets.check_options), max_expansions of 1 .. MSR_WILD_MAX_LIMIT
         (patterns: the call has explicit patterns, which need it like wildcards=True), duplicate_threshold in (0, 1].  int_types: what counts as a whole
         number (BM25.search takes no numpy integer)."""
@@ -141,6 +160,9 @@ class SearchOptions:
             t = self.duplicate_threshold
             if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not 0.0 < float(t) <= 1.0:
                 raise ValueError(f"duplicate_threshold must be in (0, 1] (got {t!r})")
+        if self.match_on:
+            from .match import check_value
+            check_value(self.match)
 
 
 @dataclass(frozen=True)

@@ -360,7 +360,7 @@ class Retriever:
         return eng.rerank_fuse(b[0], b[1], b[2], cos, meta, smoothing=cfg["smoothing"], max_chunks=RERANK_MAX_CHUNKS), union
 
     def _enqueue_chunk(self, term_ids, qv, top_k, slot, within=None, mode="lexical", dense_k=DENSE_K, cond=None, facet=None,
-                       min_matches=None):
+                       min_matches=None, match=None):
         """Device work of one chunk + the asynchronous copy of its final rows into pinned host buffers.  Only enqueues.
         within (None | DocSet | list per query of the chunk): stage 1 restricted to the sets; the rerank chain is unchanged.
         mode="hybrid": stage 1 = the BM25 top k_lex (hybrid_k_lex) followed by the dense top dense_k documents it lacks, each
@@ -374,11 +374,16 @@ class Retriever:
         sets stage 1 is restricted to (_facet_chunk); its answer comes back to the host before stage 1 is enqueued.
         min_matches (None | 1 .. 64, SearchOptions.min_matches): ONE collapse_duplicates call between fuse and diversify; what
         it dropped is copied to pinned buffers beside the final rows (the job's seventh entry; the sixth is then None in
-        lexical mode)."""
+        lexical mode).
+        match (None | (slots, needs) of the chunk's queries, match.slots / match.need): ONE match.match_sets call behind the
+        conditions' call, inside what that built; its sets take within's place in both stages and in the facet counts."""
         import torch
         eng, cfg = self.engine, self.reranker.cfg
         if cond is not None:
             within = cond.sets(eng, within)
+        if match is not None:
+            from .match import match_sets
+            within = match_sets(eng, match[0], match[1], within)
         if facet is not None:
             self._facet_chunk(term_ids, within, facet)
         fused, union = self._fused_chunk(term_ids, qv, top_k, within, mode, dense_k)
@@ -476,7 +481,7 @@ class Retriever:
     def final_list_chunks(self, term_id_lists=None, query_vectors=None, top_k=TOP_K_RETRIEVAL, chunk=None, prepare=None,
                           n_queries=None, within=None, mode="lexical", dense_k=DENSE_K, operators=False, must=None,
                           must_not=None, phrases=False, must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None,
-                          wildcards=None, facets=None):
+                          wildcards=None, facets=None, match="any"):
         """The whole live path, chunk by chunk, on the device; yields (first query, doc index int32 [Qc, S], new_similarity
         float64 [Qc, S], winning chunk row int32 [Qc, S], n int32 [Qc]) per chunk of queries, rows in final rank order.
         Software-pipelined: while the GPU works on chunk i the host packs chunk i + 1 and the caller consumes chunk i - 1.
@@ -506,24 +511,39 @@ class Retriever:
         enqueued; same refusal of prepare=.
         facets: None, or a dict {"by": "host" | "domain", "limit": 1 .. 64}.  The generator fills facets["hits"],
         ["n_values_hit"], ["top_value"], ["top_count"] (per query) and ["names"] (the key's value names).
+        match: "any" (default), a match value ("all", m, "75%": SearchOptions) or a dict {"value": that value}: each query's
+        term ids are its slots (match.slots, with the expansions of each pattern as one slot) and ONE match.match_sets call per
+        chunk restricts both stages to the pages that fill enough of them.  The generator fills the dict's ["slots"] (per
+        query its groups of term ids), ["need"] (per query an int, None: no slot) and ["info"] (per query the `match` value
+        of search_batch's results).
         Threads: the generator holds the engine's lock (serial.py) from its first next() to exhaustion, close() or an
         exception -- also while the caller works between two chunks: the pinned buffers, the facet table and the index
         belong to this call until then, so no other request can read or overwrite a chunk's rows.  Finish or close it on the
         thread that started it (the lock is that thread's), and soon: every other request on this engine waits."""
-        opts = SearchOptions(mode, dense_k, operators, phrases, proximity)
+        match = self._match_dict(match)
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, match="any" if match is None else match["value"])
         cond = Conditions(must, must_not, must_phrases, must_not_phrases)
         yield from self._chunks(term_id_lists, query_vectors, top_k, chunk, prepare, n_queries, within, opts, cond, fuzzy, wildcards,
-                                facets)
+                                facets, match=match)
+
+    @staticmethod
+    def _match_dict(match):
+        """final_list_chunks' match= -> None (off) or the dict the generator fills."""
+        if isinstance(match, dict):
+            return match
+        return {"value": match} if SearchOptions(match=match).match_on else None
 
     def _chunks(self, term_id_lists, query_vectors, top_k, chunk, prepare, n_queries, within, opts, cond, fuzzy, wildcards, facets,
-                parsed=False, dedup=None):
+                parsed=False, dedup=None, match=None):
         """final_list_chunks over the two values.  Of opts it reads mode, dense_k and the text switches -- parsed: they were
         applied by parse_queries (else True is refused); fuzzy / wildcards / facets: final_list_chunks' dicts, which hold
         those features' limits.  dedup: None, or a dict: collapse_duplicates is on with opts' duplicate_threshold; the generator
-        fills dedup["drops"] (per query, _collect_drops)."""
+        fills dedup["drops"] (per query, _collect_drops).  match: None, or final_list_chunks' dict (its "terms", if given:
+        per query the term strings the ids were mapped from, for the words of the slots that no term fills)."""
         import torch
         eng = self.engine
         opts = replace(opts, snippets=False, fuzzy=fuzzy is not None, wildcards=wildcards is not None,
+                       match="any" if match is None else match["value"],
                        max_expansions=(wildcards or {}).get("limit", 8), facets=facets is not None,
                        facet_by=(facets or {}).get("by", "host"), facet_limit=(facets or {}).get("limit", 10),
                        collapse_duplicates=dedup is not None)
@@ -539,6 +559,13 @@ class Retriever:
             if prepare is not None or len(wildcards["patterns"]) != len(term_id_lists):
                 raise ValueError("wildcards: needs the patterns of every query (not with prepare=)")
             wildcards["expansions"], wildcards["ids"] = [], []
+        if match is not None:
+            from . import match as _match
+            if self.bm25 is None:
+                raise ValueError("match= needs an index with postings")
+            if prepare is not None:
+                raise ValueError("match: needs the term ids of every query (not with prepare=)")
+            match.update(slots=[], need=[], info=[])
         if facets is not None:
             facets["names"] = self._ensure_facet(opts.facet_by)
             facets.update(limit=int(opts.facet_limit), hits=[], n_values_hit=[], top_value=[], top_count=[])
@@ -574,19 +601,43 @@ class Retriever:
                 c = None if c is None else replace(c, must=m_ids)
                 fuzzy["corrections"] += corr
                 fuzzy["ids"] += ids
+            typed = ids                                          # (what the user's words became; the expansions come behind)
+            exp = None
             if wildcards is not None:
                 lim = int(opts.max_expansions)
                 ids, exp = _wildcard.expand(lambda ps: eng.wildcard_terms(ps, limit=lim), self.bm25._name_of, ids,
                                             wildcards["patterns"][a:b], lim)
                 wildcards["expansions"] += exp
                 wildcards["ids"] += ids
+            m = None
+            if match is not None:
+                m = self._match_chunk(_match, match, typed, exp, a)
             job = self._enqueue_chunk(ids, qv, top_k, i & 1, within=w, mode=opts.mode, dense_k=opts.dense_k, cond=c, facet=facets,
-                                      min_matches=None if dedup is None else dedup["min_matches"])
+                                      min_matches=None if dedup is None else dedup["min_matches"], match=m)
             if pending is not None:
                 yield (pending[0],) + self._collect(pending[1], dedup)
             pending = (a, job)
         if pending is not None:
             yield (pending[0],) + self._collect(pending[1], dedup)
+
+    def _match_chunk(self, _match, match, typed, exp, a):
+        """The slots and needs of one chunk (queries a ..): typed -- per query its term ids after correction, exp -- None or per
+        query wildcard.expand's {pattern: {"terms": [...]}}.  Appends to match["slots"] / ["need"] / ["info"] -> (slots,
+        needs) for _enqueue_chunk, or None when no query of the chunk has a slot."""
+        ix, name_of, terms = self.index, self.bm25._name_of, match.get("terms")
+        groups, needs = [], []
+        for q, ids in enumerate(typed):
+            expansions = None if exp is None else [ix.term_ids(info["terms"]) for info in exp[q].values()]
+            g = _match.slots(ix, ids, expansions)
+            n = _match.need(match["value"], len(g))
+            words = terms[a + q] if terms is not None and len(terms[a + q]) == len(ids) else ()
+            unknown = [w for w, t in zip(words, ids) if not 0 <= int(t) < ix.n_terms]
+            groups.append(g)
+            needs.append(n)
+            match["info"].append({"slots": _match.slot_names(g, name_of, unknown), "need": n})
+        match["slots"] += groups
+        match["need"] += needs
+        return (groups, needs) if any(n is not None for n in needs) else None
 
     @classmethod
     def _collect(cls, job, dedup=None):
@@ -598,23 +649,27 @@ class Retriever:
     @serialised
     def final_lists(self, term_id_lists, query_vectors, top_k=TOP_K_RETRIEVAL, chunk=None, within=None, mode="lexical",
                     dense_k=DENSE_K, with_source=False, operators=False, must=None, must_not=None, phrases=False,
-                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None, facets=None):
+                    must_phrases=None, must_not_phrases=None, proximity=False, fuzzy=None, wildcards=None, facets=None,
+                    match="any"):
         """-> host arrays (doc index int32 [Q, S], new_similarity float64 [Q, S], winning chunk row int32 [Q, S], n int32 [Q]);
         row q holds n[q] entries in final rank order (S = max n, normally the reranker's top_k = 100).  term_id_lists: per
         query its term ids (repeats allowed, unknown < 0); query_vectors [Q, 768].  with_source (hybrid mode only): a fifth
         array, int32 [Q, S]: 1 lexical, 2 dense, 3 both (0 past n).  Everything else: final_list_chunks, whose chunks this
         joins."""
-        opts = SearchOptions(mode, dense_k, operators, phrases, proximity)
+        match = self._match_dict(match)
+        opts = SearchOptions(mode, dense_k, operators, phrases, proximity, match="any" if match is None else match["value"])
         cond = Conditions(must, must_not, must_phrases, must_not_phrases)
-        return self._final(term_id_lists, query_vectors, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source)
+        return self._final(term_id_lists, query_vectors, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source,
+                           match=match)
 
     def _final(self, ids, qv, top_k, chunk, within, opts, cond, fuzzy, wildcards, facets, with_source=False, parsed=False,
-               dedup=None):
+               dedup=None, match=None):
         """final_lists over the two values: _chunks' chunks joined (parsed, the dicts: _chunks)."""
         opts.check()
         if with_source and opts.mode != "hybrid":
             raise ValueError("with_source needs mode='hybrid'")
-        parts = list(self._chunks(ids, qv, top_k, chunk, None, None, within, opts, cond, fuzzy, wildcards, facets, parsed, dedup))
+        parts = list(self._chunks(ids, qv, top_k, chunk, None, None, within, opts, cond, fuzzy, wildcards, facets, parsed, dedup,
+                                  match))
         if not parts:
             z = np.zeros((0, 0), np.int32)
             return (z, np.zeros((0, 0), np.float64), z, np.zeros(0, np.int32)) + ((z,) if with_source else ())
@@ -627,9 +682,9 @@ class Retriever:
 
     def _front(self, queries, query_embeddings, term_lists, opts, explicit, patterns):
         """The front half of search_batch and batch_search: check the options, preprocess and parse the queries
-        (query.parse_queries), tokenise, map and embed them -> (term ids, vectors, Conditions, fz, wc, fc): the dicts of
-        final_list_chunks' fuzzy= / wildcards= / facets=, None where the feature is off.  fz also receives "processed" (the
-        scoring texts).  The scoring text (patterns, excluded words and phrases removed, quotes gone) is what gets
+        (query.parse_queries), tokenise, map and embed them -> (term ids, vectors, Conditions, fz, wc, fc, mt): the dicts of
+        final_list_chunks' fuzzy= / wildcards= / facets= / match=, None where the feature is off.  fz also receives "processed"
+        (the scoring texts), mt "terms" (the term strings).  The scoring text (patterns, excluded words and phrases removed, quotes gone) is what gets
         tokenised; the text that is embedded keeps a pattern."""
         self._check_options(opts, patterns is not None)
         fz = {} if opts.fuzzy else None
@@ -637,7 +692,11 @@ class Retriever:
         scoring, embed_text, cond, pats = parse_queries([preprocess_query(q) for q in queries], lambda t: self.bm25._tokenize(t),
                                                         opts, explicit, patterns)
         wc = None if pats is None else {"patterns": pats, "limit": int(opts.max_expansions)}
-        return self._prepare(queries, query_embeddings, term_lists, scoring, fz, embed_text) + (cond, fz, wc, fc)
+        mt = {"value": opts.match} if opts.match_on else None
+        front = self._prepare(queries, query_embeddings, term_lists, scoring, fz if fz is not None else mt, embed_text)
+        if mt is not None and fz is not None:
+            mt["terms"] = fz["terms"]
+        return front + (cond, fz, wc, fc, mt)
 
     @staticmethod
     def _scored_ids(ids, fz, wc):
@@ -702,23 +761,23 @@ class Retriever:
                      mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False,
                      must_phrases=None, must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS,
                      fuzzy=False, wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host",
-                     facet_limit=10, collapse_duplicates=False, duplicate_threshold=0.9):
+                     facet_limit=10, collapse_duplicates=False, duplicate_threshold=0.9, match="any"):
         """-> per query the list of UI documents (search_api.py:110-130); [] when stage 1 finds nothing.  within: None, a DocSet
         (every query) or a list of DocSet / None per query -- results from the documents of the set only (final_list_chunks).
         The switches and limits: query.SearchOptions; must / must_not / must_phrases / must_not_phrases: query.Conditions,
         one entry per query; patterns: per query None or a list of pattern strings.  With fuzzy, wildcards, patterns,
-        facets or collapse_duplicates each query's result is a fuzzy.Results list."""
+        facets, collapse_duplicates or match each query's result is a fuzzy.Results list."""
         opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
-                             facets, facet_by, facet_limit, collapse_duplicates, duplicate_threshold)
+                             facets, facet_by, facet_limit, collapse_duplicates, duplicate_threshold, match)
         return self._search(queries, top_k, query_embeddings, term_lists, query_ids, within, opts,
                             Conditions(must, must_not, must_phrases, must_not_phrases), patterns)
 
     def _search(self, queries, top_k, query_embeddings, term_lists, query_ids, within, opts, explicit, patterns):
         """search_batch over the two values."""
-        ids, qv, cond, fz, wc, fc = self._front(queries, query_embeddings, term_lists, opts, explicit, patterns)
+        ids, qv, cond, fz, wc, fc, mt = self._front(queries, query_embeddings, term_lists, opts, explicit, patterns)
         dd = {} if opts.collapse_duplicates else None
         doc, score, _, n, *src = self._final(ids, qv, top_k, None, within, opts, cond, fz, wc, fc, with_source=opts.mode == "hybrid",
-                                             parsed=True, dedup=dd)
+                                             parsed=True, dedup=dd, match=mt)
         src = src[0] if src else None                        # (hybrid mode: where each row's document came from)
         ix, snippets = self.index, opts.snippets
         ids = self._scored_ids(ids, fz, wc)
@@ -747,11 +806,12 @@ class Retriever:
                         rows[-1]["snippet"] = hit[0]
                     rows[-1]["highlights"] = hit[1] if hit is not None else []
                     rows[-1]["missing"] = hit[2] if hit is not None else list(row_names[q] or [])
-            if fz is not None or wc is not None or fc is not None or dd is not None:
+            if fz is not None or wc is not None or fc is not None or dd is not None or mt is not None:
                 corr = fz["corrections"][q] if fz is not None else {}
                 rows = _fuzzy.Results(rows, corr, _fuzzy.corrected_text(fz["processed"][q], corr) if fz is not None else None,
                                       wc["expansions"][q] if wc is not None else None,
-                                      collapsed=len(dd["drops"][q]) if dd is not None else 0)
+                                      collapsed=len(dd["drops"][q]) if dd is not None else 0,
+                                      match=mt["info"][q] if mt is not None else None)
                 if fc is not None:
                     rows.hits, rows.facet_values = int(fc["hits"][q]), int(fc["n_values_hit"][q])
                     rows.facets = _facets.top_list(fc["names"], fc["top_value"][q], fc["top_count"][q])
@@ -773,11 +833,11 @@ class Retriever:
                mode="lexical", dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
                wildcards=False, max_expansions=8, patterns=None, facets=False, facet_by="host", facet_limit=10,
-               collapse_duplicates=False, duplicate_threshold=0.9):
+               collapse_duplicates=False, duplicate_threshold=0.9, match="any"):
         """search_batch for one query: must / must_not / must_phrases / must_not_phrases / patterns are ONE list each."""
         one = lambda v: None if v is None else [v]
         opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
-                             facets, facet_by, facet_limit, collapse_duplicates, duplicate_threshold)
+                             facets, facet_by, facet_limit, collapse_duplicates, duplicate_threshold, match)
         return self._search([query], top_k, one(query_embedding), one(terms), one(query_id), within, opts,
                             Conditions(one(must), one(must_not), one(must_phrases), one(must_not_phrases)), one(patterns))[0]
 
@@ -785,7 +845,8 @@ class Retriever:
     def batch_search(self, numbered_queries, query_embeddings=None, term_lists=None, within=None, mode="lexical",
                      dense_k=DENSE_K, operators=False, must=None, must_not=None, phrases=False, must_phrases=None,
                      must_not_phrases=None, proximity=False, snippets=False, snippet_tokens=SNIPPET_TOKENS, fuzzy=False,
-                     wildcards=False, max_expansions=8, patterns=None, collapse_duplicates=False, duplicate_threshold=0.9):
+                     wildcards=False, max_expansions=8, patterns=None, collapse_duplicates=False, duplicate_threshold=0.9,
+                     match="any"):
         """numbered_queries: [(query_num, text)] -> the result entries of search_api.py:276-292 ({query_num, rank, url, score,
         formatted_line}) as a BatchLines sequence: len / indexing / iteration give the reference's dicts, built on access;
         .text() / .write() produce all formatted lines natively (msr_format_lines) without building any.  mode / dense_k:
@@ -797,13 +858,15 @@ class Retriever:
         patterns: the BatchLines then carries `expansions` (per query {pattern: {...}}).  collapse_duplicates /
         duplicate_threshold: search_batch; the entries and lines are those of the rows that stay, and the BatchLines then
         carries `collapsed` (per query the number of rows dropped) and `duplicates` (per query {leader's url: the
-        "duplicates" entries of search_batch})."""
+        "duplicates" entries of search_batch}).  match: search_batch; the BatchLines then carries `match` (per query
+        {"slots": ..., "need": ...})."""
         opts = SearchOptions(mode, dense_k, operators, phrases, proximity, snippets, snippet_tokens, fuzzy, wildcards, max_expansions,
-                             collapse_duplicates=collapse_duplicates, duplicate_threshold=duplicate_threshold)
-        ids, qv, cond, fz, wc, _ = self._front([q for _, q in numbered_queries], query_embeddings, term_lists, opts,
+                             collapse_duplicates=collapse_duplicates, duplicate_threshold=duplicate_threshold, match=match)
+        ids, qv, cond, fz, wc, _, mt = self._front([q for _, q in numbered_queries], query_embeddings, term_lists, opts,
                                                Conditions(must, must_not, must_phrases, must_not_phrases), patterns)
         dd = {} if opts.collapse_duplicates else None
-        doc, score, _, n = self._final(ids, qv, TOP_K_RETRIEVAL, None, within, opts, cond, fz, wc, None, parsed=True, dedup=dd)
+        doc, score, _, n = self._final(ids, qv, TOP_K_RETRIEVAL, None, within, opts, cond, fz, wc, None, parsed=True, dedup=dd,
+                                       match=mt)
         if self._formatter is None:
             self._formatter = LineFormatter(self.index.urls, self.index.n_docs)
         lines = BatchLines([qn for qn, _ in numbered_queries], doc, score, n, self.index.urls, self._formatter)
@@ -812,6 +875,8 @@ class Retriever:
             lines.corrected_queries = [_fuzzy.corrected_text(p, c) for p, c in zip(fz["processed"], fz["corrections"])]
         if wc is not None:
             lines.expansions = wc["expansions"]
+        if mt is not None:
+            lines.match = mt["info"]
         if dd is not None:
             url = lambda d: (self.index.urls[d] if self.index.urls is not None else "") or ""
             lines.collapsed = [len(d) for d in dd["drops"]]
@@ -882,6 +947,7 @@ class BatchLines:
         self.corrections = self.corrected_queries = None     # ... and fuzzy=True these
         self.expansions = None                               # ... and wildcards=True / patterns= this
         self.collapsed = self.duplicates = None              # ... and collapse_duplicates=True these
+        self.match = None                                    # ... and match= this
 
     def __len__(self):
         return int(self._start[-1])

@@ -44,7 +44,7 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
 
     from fastapi import FastAPI
     from fastapi.responses import HTMLResponse, JSONResponse
-    from pydantic import BaseModel
+    from pydantic import BaseModel, StrictInt
 
     class RerankRequest(BaseModel):
         doc_ids: List[str]
@@ -87,6 +87,9 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
         facet_limit: int = 10         # "domain", the first facet_limit (1 .. 64) values) and "facet_values" (distinct values hit)
         collapse_duplicates: bool = False   # near-duplicate pages are shown once (Retriever.search, DESIGN K18): the response then
         duplicate_threshold: float = 0.9    # carries "collapsed"; rows that swallowed copies carry "duplicates"; threshold in (0, 1]
+        # "all", a whole number m or a percentage like "75%": only pages that hold all / at least m / that share of the
+        # query's words (Retriever.search, DESIGN K19); the response then carries "match": {"slots", "need"}
+        match: Union[StrictInt, str] = "any"
 
     class SimilarRequest(BaseModel):
         doc_ids: Optional[List[Union[int, str]]] = None
@@ -164,7 +167,8 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                         (req.snippets, ("snippets", "snippet_tokens"), True), (req.fuzzy, ("fuzzy",), True),
                         (wild, ("wildcards", "max_expansions", "patterns"), True),
                         (req.facets, ("facets", "facet_by", "facet_limit"), True),
-                        (req.collapse_duplicates, ("collapse_duplicates", "duplicate_threshold"), True))
+                        (req.collapse_duplicates, ("collapse_duplicates", "duplicate_threshold"), True),
+                        (req.match != "any", ("match",), True))
             for on, names, _ in features:
                 if on:
                     kw.update({name: getattr(req, name) for name in names})
@@ -184,13 +188,15 @@ def create_app(retriever, llm=None, queries_file="queries.txt", results_file="ba
                     raise
                 # a dense_k the engine cannot hold; fuzzy / wildcards on an index without term strings; max_expansions outside
                 # 1 .. 16; a required or excluded pattern; a facet_by the engine does not know, a facet_limit outside 1 .. 64;
-                # a duplicate_threshold outside (0, 1]
+                # a duplicate_threshold outside (0, 1]; a match value that is none
                 return JSONResponse(status_code=400, content={"error": str(e)})
             llm_response = ""
             if llm is not None and docs:
                 llm_response = llm(query, [d["snippet"] for d in docs[:LLM_MAX_WINDOWS]])
-            if req.fuzzy or wild or req.facets or req.collapse_duplicates:
+            if req.fuzzy or wild or req.facets or req.collapse_duplicates or req.match != "any":
                 out = {"llm_response": llm_response, "documents": list(docs)}
+                if req.match != "any":
+                    out.update(match=docs.match)
                 if req.collapse_duplicates:
                     out.update(collapsed=docs.collapsed)
                 if req.facets:
