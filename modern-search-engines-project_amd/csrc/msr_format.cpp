@@ -19,9 +19,26 @@ namespace {
 // "%.3f" of a double, digit for digit what Python's format(x, ".3f") and glibc's printf give: both round the EXACT binary
 // value half-to-even at the third decimal.  x = m / 2^k with a 53-bit integer m (read off the bits), so 1000 x = (1000 m) / 2^k
 // is an exact 63-bit integer over a power of two: quotient, remainder and the half-way comparison are integer operations.
+// A score of 1e12 and above, an infinity or a NaN takes the slow path: up to 309 digits, ".000" and a sign.  HUGE_EXTRA is what
+// such a score may need beyond the 24 characters every score is given (pass 1 of msr_format_lines adds it per such score).
+constexpr int HUGE_MAX = 320;                                           // >= 1 + 309 + 4 (-DBL_MAX), with room for snprintf's NUL
+constexpr int HUGE_EXTRA = HUGE_MAX - 24;
+static inline bool fmt3_slow(double x) { return !(fabs(x) < 1.0e12); }
+
+static int fmt3_huge(double x, char* out) {
+    if (x != x) { memcpy(out, "nan", 3); return 3; }                    // Python prints "nan" whatever the sign bit (glibc: "-nan")
+    if (x == INFINITY) { memcpy(out, "inf", 3); return 3; }
+    if (x == -INFINITY) { memcpy(out, "-inf", 4); return 4; }
+    char tmp[HUGE_MAX];
+    int n = snprintf(tmp, sizeof tmp, "%.3f", x);                       // exact decimal expansion, as Python's
+    if (n > HUGE_MAX - 1) n = HUGE_MAX - 1;                             // (cannot happen for a double; never past tmp)
+    memcpy(out, tmp, (size_t)n);
+    return n;                                                           // the bytes WRITTEN
+}
+
 static inline int fmt3(double x, char* out) {
     const double ax = fabs(x);
-    if (!(ax < 1.0e12)) return snprintf(out, 40, "%.3f", x);          // huge, inf, nan
+    if (fmt3_slow(x)) return fmt3_huge(x, out);                         // huge, inf, nan
     uint64_t v = 0;
     if (ax != 0.0) {
         uint64_t bits;
@@ -99,9 +116,10 @@ extern "C" int64_t msr_format_lines(const char* qnum_blob, const int64_t* qnum_o
     if (!qnum_blob || !qnum_off || !doc || !score || !n || !url_off || n_queries < 0 || stride < 0 || capacity < 0 || (capacity && !out))
         return INT64_MIN;
     // pass 1: an upper bound of the bytes per query, without touching the URL table (its entries are scattered: that would be
-    // a cache miss per line): rank and score take at most 10 + 24 characters (ranks < 2^32, |score| < 1e12; snprintf's output
-    // for anything larger is bounded by 40), a URL at most `max_url` bytes (the caller's max_url_len; a URL longer than
-    // that is cut to it rather than written past its line's share of the buffer)
+    // a cache miss per line): rank and score take at most 10 + 24 characters (ranks < 2^32, |score| < 1e12), a score of 1e12
+    // and above, an infinity or a NaN up to HUGE_EXTRA more (one pass over the query's contiguous scores counts them), a URL
+    // at most `max_url` bytes (the caller's max_url_len; a URL longer than that is cut to it rather than written past its
+    // line's share of the buffer)
     int64_t max_url = max_url_len;
     if (max_url <= 0) {                                                 // (not given: one sequential pass over the offsets)
         max_url = 0;
@@ -111,7 +129,10 @@ extern "C" int64_t msr_format_lines(const char* qnum_blob, const int64_t* qnum_o
     for (int32_t q = 0; q < n_queries; ++q) {
         const int64_t ql = qnum_off[q + 1] - qnum_off[q];
         const int32_t cnt = n[q] < 0 ? 0 : (n[q] > stride ? stride : n[q]);
-        bound[q + 1] = bound[q] + (int64_t)cnt * (ql + max_url + 56);
+        const double* sq = score + (int64_t)q * stride;
+        int64_t n_huge = 0;
+        for (int32_t r = 0; r < cnt; ++r) n_huge += fmt3_slow(sq[r]) ? 1 : 0;
+        bound[q + 1] = bound[q] + (int64_t)cnt * (ql + max_url + 56) + n_huge * HUGE_EXTRA;
     }
     const int64_t need = bound[n_queries];
     if (need > capacity) return -need;

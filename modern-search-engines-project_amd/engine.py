@@ -1153,8 +1153,9 @@ class DeviceEngine:
         out_doc, out_score, out_orig, out_chunk = mk(torch.int32), mk(torch.float64), mk(torch.float64), mk(torch.int32)
         out_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
         out_rows = torch.empty((Q,), dtype=torch.int32, device=self.device)
-        self._check(self.lib.msr_rerank_fuse(self.handle, Q, _ptr(cand), _ptr(bm), _ptr(cn), M, _ptr(cos.contiguous()),
-                                             _ptr(meta.contiguous()), C.byref(prm), _ptr(out_doc), _ptr(out_score),
+        cos, meta = cos.contiguous(), meta.contiguous()      # (named: a copy must outlive the call that reads it)
+        self._check(self.lib.msr_rerank_fuse(self.handle, Q, _ptr(cand), _ptr(bm), _ptr(cn), M, _ptr(cos),
+                                             _ptr(meta), C.byref(prm), _ptr(out_doc), _ptr(out_score),
                                              _ptr(out_orig), _ptr(out_chunk), _ptr(out_n), _ptr(out_rows),
                                              self._stream()))
         return out_doc, out_score, out_orig, out_chunk, out_n, out_rows
@@ -1170,13 +1171,15 @@ class DeviceEngine:
     def diversify(self, fused, top_k=100, relevance_threshold=0.8, diversification=True):
         """fused = (doc, score, orig, chunk, n, ...) of rerank / rerank_fuse -> (doc, score f64, orig f64, chunk, n): the final
         list of every query after reranker_api.py:178-236 (or, diversification=False, its first top_k accepted entries)."""
-        doc, score, orig, chunk, n = fused[:5]
+        # (named: the copy of a non-contiguous input must outlive the call -- as a temporary its block went back to the
+        # allocator at once and the next input's copy was written over it before the kernel ran)
+        doc, score, orig, chunk, n = (t.contiguous() for t in fused[:5])
         Q, M = int(doc.shape[0]), int(doc.shape[1])
         mk = lambda dt: torch.empty((Q, M), dtype=dt, device=self.device)
         o_doc, o_score, o_orig, o_chunk = mk(torch.int32), mk(torch.float64), mk(torch.float64), mk(torch.int32)
         o_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
-        self._check(self.lib.msr_diversify(self.handle, Q, _ptr(doc.contiguous()), _ptr(score.contiguous()), _ptr(orig.contiguous()),
-                                           _ptr(chunk.contiguous()), _ptr(n.contiguous()), M, int(top_k),
+        self._check(self.lib.msr_diversify(self.handle, Q, _ptr(doc), _ptr(score), _ptr(orig),
+                                           _ptr(chunk), _ptr(n), M, int(top_k),
                                            C.c_double(relevance_threshold), 1 if diversification else 0, _ptr(o_doc),
                                            _ptr(o_score), _ptr(o_orig), _ptr(o_chunk), _ptr(o_n), self._stream()))
         return o_doc, o_score, o_orig, o_chunk, o_n
@@ -1189,8 +1192,9 @@ class DeviceEngine:
         out_doc = torch.empty((Q, k), dtype=torch.int32, device=self.device)
         out_score = torch.empty((Q, k), dtype=scores.dtype, device=self.device)
         out_n = torch.empty((Q,), dtype=torch.int32, device=self.device)
-        self._check(self.lib.msr_merge_topk(self.handle, _ptr(docs.contiguous()), _ptr(scores.contiguous()),
-                                            _ptr(ns.contiguous()), G, Q, k, bits, _ptr(out_doc), _ptr(out_score),
+        docs, scores, ns = docs.contiguous(), scores.contiguous(), ns.contiguous()      # (named: see diversify)
+        self._check(self.lib.msr_merge_topk(self.handle, _ptr(docs), _ptr(scores),
+                                            _ptr(ns), G, Q, k, bits, _ptr(out_doc), _ptr(out_score),
                                             _ptr(out_n), self._stream()))
         return out_doc, out_score, out_n
 

@@ -239,3 +239,89 @@ def near_copies(n_groups, copies, length=120, edits=2, n_terms=5000, seed=3):
             streams.append(c)
             group.append(g)
     return streams, group
+
+
+# ---- planted tables: exact match counts (bound directly with msr_bind_signatures) ----------------------------------------------
+def planted_table(n_fill=1100):
+    """A signature table with the match count of every pair of rows known: every word is unique in the table unless planted.
+    -> (sig uint32 [N, 64], rows) with rows:
+      pairs[(m, "first")] / pairs[(m, "last")] = (a, b), m = 0 .. 64: rows that agree in exactly the FIRST / the LAST m words;
+      ones = (x, y, z): x holds one word of 0xFFFFFFFF (not EMPTY), y is x again (64 matches), z holds it in another word;
+      empty = two EMPTY rows;  chain = (a, b, c): a ~ b 61, b ~ c 61, a ~ c 58;  two = (a, e, d): d ~ a 60, d ~ e 60, a ~ e 56;
+      fill = n_fill rows that match nothing."""
+    rows, table = {"pairs": {}}, []
+
+    def fresh():
+        r = len(table)
+        table.append(np.arange(r * K + 1, r * K + K + 1, dtype=np.uint32))   # words r K + 1 .. r K + 64: unique, never 0xFFFFFFFF
+        return r
+
+    def copy_of(src, words):
+        r = fresh()
+        table[r][words] = table[src][words]
+        return r
+
+    for m in range(K + 1):
+        a = fresh()
+        rows["pairs"][(m, "first")] = (a, copy_of(a, slice(0, m)))
+        a = fresh()
+        rows["pairs"][(m, "last")] = (a, copy_of(a, slice(K - m, K)))
+    x = fresh()
+    table[x][0] = M32
+    y = copy_of(x, slice(0, K))
+    z = fresh()
+    table[z][K - 1] = M32
+    rows["ones"] = (x, y, z)
+    rows["empty"] = (fresh(), fresh())
+    for r in rows["empty"]:
+        table[r][:] = M32
+    a = fresh()
+    b = copy_of(a, slice(3, K))
+    c = copy_of(b, slice(0, K))
+    table[c][3:6] += np.uint32(1 << 30)
+    rows["chain"] = (a, b, c)
+    a = fresh()
+    d = copy_of(a, slice(0, 60))
+    e = copy_of(d, slice(0, K))
+    table[e][56:60] += np.uint32(1 << 30)
+    rows["two"] = (a, e, d)
+    rows["fill"] = [fresh() for _ in range(n_fill)]
+    return np.stack(table), rows
+
+
+def planted_pair_lists(rows, max_cand):
+    """Three lists over every planted pair -> doc int32 [3, max_cand], n: the pairs side by side (a0 b0 a1 b1 ..); every a, then
+    every b (a pair's rows in different tiles); and the first list behind one EMPTY row, so that pairs straddle the tile edges."""
+    pairs = [rows["pairs"][k] for k in sorted(rows["pairs"])]
+    flat = [r for p in pairs for r in p]
+    assert max_cand >= len(flat) + 1
+    doc = np.full((3, max_cand), -1, np.int32)
+    doc[0, :len(flat)] = flat
+    doc[1, :len(flat)] = [a for a, _ in pairs] + [b for _, b in pairs]
+    doc[2, :len(flat) + 1] = [rows["empty"][0]] + flat
+    return doc, np.array([len(flat), len(flat), len(flat) + 1], np.int32)
+
+
+def full_width_list(rows, n_sig):
+    """One list of 1024 slots of rows that match nothing, but: a leader at slot 600 whose copy stands at 1000 (the last tile);
+    the chain A ~ B ~ C at slots 10, 100, 700 (three tiles); a row at 990 that duplicates the leaders at 20 and 530 (the
+    smaller slot takes it); passive slots at 63, 64 (the two EMPTY rows) and 1023 (a document outside the table)."""
+    doc = np.array(rows["fill"][:1024], np.int32)
+    x, y, _ = rows["ones"]
+    doc[600], doc[1000] = x, y
+    doc[10], doc[100], doc[700] = rows["chain"]
+    doc[20], doc[530], doc[990] = rows["two"]
+    doc[63], doc[64] = rows["empty"]
+    doc[1023] = n_sig + 3
+    return doc
+
+
+def many_pair_queries(rows, n_queries):
+    """[n_queries, 2] lists of one planted pair each: query q holds pair (7 q + 3) mod 130."""
+    pairs = np.array([rows["pairs"][k] for k in sorted(rows["pairs"])], np.int32)
+    return pairs[(np.arange(n_queries, dtype=np.int64) * 7 + 3) % len(pairs)]
+
+
+def pair_matches(rows):
+    """The planted count of each pair, in the order of sorted(rows["pairs"])."""
+    return np.array([m for m, _ in sorted(rows["pairs"])], np.int32)

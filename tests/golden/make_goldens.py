@@ -20,7 +20,8 @@ and is therefore *not* pinned by executing the reference):
   * FLOAT[768] cells arrive in pandas as float32 ndarrays                  reranker_api.py:61
   * rows of the SQL result are ordered by (doc_id, chunk_id)
 
-Usage:  python tests/golden/make_goldens.py            (rewrites tests/golden/*.json|*.npz)
+Usage:  python tests/golden/make_goldens.py                          (rewrites tests/golden/*.json|*.npz)
+        python tests/golden/make_goldens.py diversification_edges    (rewrites diversification_edges.json alone)
 """
 import ast
 import asyncio
@@ -605,6 +606,29 @@ def diversification_fixture(ns):
                                        "extract_domain": [[u, ns["extract_domain"](u)] for u in doms]})
 
 
+def diversification_edges_fixture(ns):
+    """The reference's hybrid_diversification executed on the edge lists of tests/diversify_cases.py (ties across the tiers'
+    drops, scores at the threshold and one ulp below, the negative slice, the clamp at 0) at every threshold of
+    diversify_cases.THRESHOLDS.  Inputs and returned lists only: an entry's doc_id is its slot in the list."""
+    sys.path[:0] = [p for p in (os.path.dirname(OUT), os.path.dirname(os.path.dirname(OUT))) if p not in sys.path]
+    import diversify_cases as dc
+    DS, WS = ns["DocumentScore"], ns["WindowScore"]
+
+    def mk(i, url, s):
+        w = WS(text="t", similarity_score=s, doc_id=str(i), title="t", window_index=0)
+        return DS(doc_id=str(i), title="t", url=url, similarity_score=s, original_similarity=0.0, most_relevant_window=w)
+
+    cases = []
+    for c, top_k, thr in dc.fixture_inputs():
+        dom = dc.domains(c["doc"]).tolist()
+        score = [float(x) for x in c["score"]]
+        docs = [mk(i, f"https://h{g}.de/p{i}", s) for i, (g, s) in enumerate(zip(dom, score)) if g >= 0]      # rejected ones removed
+        res = ns["hybrid_diversification"](docs, relevance_threshold=thr, top_k=top_k)
+        cases.append({"name": c["name"], "doc": c["doc"].tolist(), "domain": dom, "score": score, "top_k": top_k, "threshold": thr,
+                      "expected": [[int(d.doc_id), d.similarity_score] for d in res]})
+    dump_json("diversification_edges.json", {"cases": cases})
+
+
 def windows_fixture(ns):
     out = []
     for n in (0, 10, 512, 513, 900, 962, 1000, 1412, 1413, 2000):
@@ -638,6 +662,11 @@ def main():
     if not os.path.isdir(REF):
         sys.exit("reference tree not present; goldens can only be regenerated in the build container")
     logging.disable(logging.CRITICAL)
+    if sys.argv[1:] == ["diversification_edges"]:               # this fixture alone: no other golden file is rewritten
+        diversification_edges_fixture(load_reranker_namespace())
+        return
+    if sys.argv[1:]:
+        sys.exit("usage: make_goldens.py [diversification_edges]")
     search_fn, stats_fn = load_bm25_methods()
     bm25_kat(search_fn, stats_fn)
     bm25_random(search_fn, stats_fn, "bm25_random_a", seed=101, N=600, V=400, mean_len=30, nq=14)
@@ -648,6 +677,7 @@ def main():
     cosine_unit_fixture(ns)
     rerank_fixtures(ns)
     diversification_fixture(ns)
+    diversification_edges_fixture(ns)
     windows_fixture(ns)
     search_api_fixture()
 

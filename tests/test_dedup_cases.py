@@ -215,3 +215,71 @@ def test_http_request_parsing_and_400s():
     for bad in (0, 1.5, -1):
         resp = client.post("/api/search", json={"query": "mensa", "collapse_duplicates": True, "duplicate_threshold": bad})
         assert resp.status_code == 400 and "duplicate_threshold" in resp.json()["error"], bad
+
+
+# ---- planted tables and lists (tests/test_gpu_collapse_edges.py runs them on the GPU) --------------------------------------------
+def test_planted_table_holds_the_counts_it_claims():
+    sig, rows = ref.planted_table()
+    assert sig.dtype == np.uint32 and sig.shape[1] == 64
+    count = lambda a, b: int((sig[a] == sig[b]).sum())
+    assert sorted(rows["pairs"]) == [(m, side) for m in range(65) for side in ("first", "last")]
+    for (m, side), (a, b) in rows["pairs"].items():
+        eq = sig[a] == sig[b]
+        assert eq.sum() == m and (eq[:m].all() if side == "first" else eq[64 - m:].all()), (m, side)
+        assert ref.matches(sig[a], sig[b]) == m
+    assert ref.pair_matches(rows).tolist() == [m for m in range(65) for _ in range(2)]
+    x, y, z = rows["ones"]
+    assert sig[x][0] == ref.M32 and sig[z][63] == ref.M32 and count(x, y) == 64 and count(x, z) == 0
+    assert not ref.is_empty(sig[x]) and not ref.is_empty(sig[z]) and all(ref.is_empty(sig[r]) for r in rows["empty"])
+    a, b, c = rows["chain"]
+    assert (count(a, b), count(b, c), count(a, c)) == (61, 61, 58)
+    a, e, d = rows["two"]
+    assert (count(d, a), count(d, e), count(a, e)) == (60, 60, 56)
+    # nothing else matches: every row pair outside the planted ones (the EMPTY rows apart) has count 0
+    m = (sig[:, None, :] == sig[None, :, :]).sum(axis=2)
+    np.fill_diagonal(m, 0)
+    planted = set(map(tuple, rows["pairs"].values())) | {(x, y), (a, d), (e, d), (a, e), rows["empty"]} | \
+        {(rows["chain"][i], rows["chain"][j]) for i in range(3) for j in range(i + 1, 3)}
+    for i, j in np.argwhere(np.triu(m) > 0).tolist():
+        if i not in rows["empty"] and j not in rows["empty"]:                 # (an EMPTY row equals the 0xFFFFFFFF words of `ones`)
+            assert (i, j) in planted or (j, i) in planted, (i, j, int(m[i, j]))
+    assert len(rows["fill"]) >= 1024
+
+
+def test_planted_pairs_drop_exactly_from_their_count_on():
+    sig, rows = ref.planted_table()
+    M = 272                                                  # 9 words per row: the last tile owns one word
+    doc, n = ref.planted_pair_lists(rows, M)
+    assert doc.shape == (3, M) and n.tolist() == [260, 260, 261] and (M + 31) // 32 % 2 == 1
+    want = ref.pair_matches(rows)
+    z = np.zeros((3, M))
+    for mm in (1, 2, 33, 64):
+        out = ref.collapse_lists(doc, z, z, doc, n, sig, mm)
+        for q in range(3):
+            dropped = {int(d): int(k) for d, k in zip(out[5][q, :out[8][q]], out[7][q, :out[8][q]])}
+            for (a, b), m in zip((rows["pairs"][k] for k in sorted(rows["pairs"])), want):
+                assert (b in dropped) == (m >= mm) and a not in dropped
+                if b in dropped:
+                    assert dropped[b] == m
+            assert out[8][q] == 2 * (65 - mm)
+    # the pairs of the second list stand in different tiles, some of the third straddle a tile edge
+    assert all(abs(int(np.nonzero(doc[1] == a)[0][0]) // 64 - int(np.nonzero(doc[1] == b)[0][0]) // 64) >= 2 for a, b in rows["pairs"].values())
+    assert any(int(np.nonzero(doc[2] == a)[0][0]) % 64 == 63 for a, _ in rows["pairs"].values())
+
+
+def test_full_width_list_and_the_many_queries():
+    sig, rows = ref.planted_table()
+    doc = ref.full_width_list(rows, len(sig))[None, :]
+    z = np.zeros((1, 1024))
+    out = ref.collapse_lists(doc, z, z, doc, [1024], sig, 60)
+    drops = [(int(np.nonzero(doc[0] == d)[0][0]), int(np.nonzero(doc[0] == l)[0][0]), int(m))
+             for d, l, m in zip(out[5][0, :out[8][0]], out[6][0, :out[8][0]], out[7][0, :out[8][0]])]
+    assert drops == [(100, 10, 61), (990, 20, 60), (1000, 600, 64)]          # (slot, leader slot, matches) in drop order
+    assert {s // 64 for s in (10, 100, 700)} == {0, 1, 10} and 1000 // 64 == 15 and 600 >= 512
+    assert all(int(doc[0, s]) in out[0][0, :out[4][0]] for s in (63, 64, 1023, 700, 530))      # passive slots and C stay
+    out58 = ref.collapse_lists(doc, z, z, doc, [1024], sig, 58)
+    assert out58[8][0] == 4 and int(doc[0, 700]) in out58[5][0, :4]          # at 58 the chain's C goes as well
+    q = ref.many_pair_queries(rows, 32770)
+    assert q.shape == (32770, 2) and len({tuple(r) for r in q[32767:32770].tolist()}) == 3
+    out = ref.collapse_lists(q[32766:], np.zeros((4, 2)), np.zeros((4, 2)), q[32766:], [2] * 4, sig, 32)
+    assert out[8].tolist() == [0, 0, 0, 1] and out[7][3, 0] == 33            # the rows on the slice's two sides differ in outcome

@@ -2,8 +2,13 @@
 every symbol of include/msretr.h exported by libmsretr.so, error behaviour without a device."""
 import ctypes as C
 import json
+import math
 import os
 import re
+import shutil
+import struct
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -437,6 +442,61 @@ def test_streaming_kernels_keep_their_row_rings_in_place():
     assert r.stdout.count("ok  ") == 12, r.stdout          # 10 instantiations of the 256-query kernel (2 with non-temporal row loads, 2 on the f16 image) + 2 of the 128-query kernel
 
 
+# scores on the formatter's slow path (1e12 and above, infinities, NaNs of both signs) and around its threshold, in the order
+# of tests/format_lines_check.cpp
+HUGE_SCORES = [1e12, -1e12, 1e12 - 0.0005, 1e36, 1e308, -1e308, sys.float_info.max, -sys.float_info.max, float("inf"),
+               -float("inf"), float("nan"), struct.unpack("<d", struct.pack("<Q", 0xFFF8000000000000))[0], 999999999999.9994,
+               4503599627370496.5, 9007199254740993.0]
+
+
+def test_python_prints_a_nan_without_its_sign():
+    """The decision msr_format_lines follows: format(x, ".3f") of a NaN is "nan" whatever its sign bit (C's printf prints
+    "-nan"), an infinity keeps its sign, and the longest line is -DBL_MAX's 314 characters."""
+    neg_nan = HUGE_SCORES[11]
+    assert math.isnan(neg_nan) and math.copysign(1.0, neg_nan) == -1.0
+    assert format(neg_nan, ".3f") == "nan" == format(float("nan"), ".3f")
+    assert format(-float("inf"), ".3f") == "-inf" and format(float("inf"), ".3f") == "inf"
+    assert len(format(1e36, ".3f")) == 41 and max(len(format(x, ".3f")) for x in HUGE_SCORES) == 314
+    assert 1e12 - 0.0005 < 1e12 and format(1e12 - 0.0005, ".3f") == "1000000000000.000"       # the fast path's longest number
+
+
+def test_line_formatter_on_huge_scores_under_the_host_sanitizers(tmp_path):
+    """tests/format_lines_check.cpp with csrc/msr_format.cpp under the address and undefined-behaviour sanitizers (a program
+    of its own: nothing is loaded into this process): every slow-path score as first and last result of the first and last
+    query, into a buffer of exactly the bytes the sizing call asked for.  A score of 1e12 and above used to advance the
+    output by what snprintf WOULD have written into its 40 bytes: 1e308 wrote 129 bytes past such a buffer, 1e36 left a
+    NUL and a cut line.  The printed lines equal Python's."""
+    from msretr.text import format_result_line
+    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
+    exe = str(tmp_path / "format_lines_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-static-libasan", "-pthread", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "format_lines_check.cpp"),
+           os.path.join(ROOT, "modern-search-engines-project_amd", "csrc", "msr_format.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, timeout=60)
+    out = r.stdout.decode("utf-8")
+    assert r.returncode == 0, out[-3000:] + r.stderr.decode("utf-8", "replace")[-6000:]
+    assert out.endswith("format lines ok\n") and "FAILED" not in out
+    urls = ["https://a.de/x", "", "http://b.org/a/long/path?q=1"]
+    url = lambda d: urls[d] if 0 <= d < 3 else ""
+    qn, doc, n = ["7", "Q-otto", "42"], [[0, 1, 2], [2, -1, 0], [1, 3, 0]], [3, 2, 3]
+    exp = []
+    for x in HUGE_SCORES:
+        exp.append("# %016x" % struct.unpack("<Q", struct.pack("<d", x))[0])
+        score = [[x, 0.5, x], [0.5, 0.5, x], [x, 0.5, x]]
+        exp += [format_result_line(qn[q], r + 1, url(doc[q][r]), score[q][r]) for q in range(3) for r in range(n[q])]
+    exp.append("# all")
+    NV = len(HUGE_SCORES)
+    exp += [format_result_line("7", i + 1, url(i % 4 - 1), HUGE_SCORES[i % NV]) for i in range(3 * NV)]
+    exp.append("format lines ok")
+    got = out.split("\n")
+    assert got[-1] == "" and len(got) - 1 == len(exp)
+    for g, e in zip(got, exp):
+        assert g == e
+    assert format_result_line("7", 1, "", HUGE_SCORES[4]).endswith("\t" + format(1e308, ".3f")) and len(format(1e308, ".3f")) == 313
+
+
 def test_native_line_formatter_equals_python_format():
     """msr_format_lines (host function of libmsretr: no GPU) writes byte for byte what the reference's f-string does
     (search_api.py:290 `f"{query_num}\\t{rank}\\t{url}\\t{score:.3f}"`), including the half-to-even rounding of the EXACT
@@ -450,6 +510,7 @@ def test_native_line_formatter_equals_python_format():
     vals = [0.0, -0.0, 0.0005, 0.0015, 0.0025, 0.5, 0.9995, 0.99949999999999994, 1.0, 0.1235, 0.1245, 2.675, 1e-9, 123456.7895,
             -0.0004, -1.2345, 0.3335, float(np.nextafter(0.0005, 1)), float(np.nextafter(0.0005, 0)), 5e-324, 1e11 + 0.0005,
             1e13, float("inf"), float("nan")]
+    vals += HUGE_SCORES                                        # (all inside the first query, whose 100 results are all formatted)
     vals += [rng.random() for _ in range(20000)] + [round(rng.random(), 3) + 0.0005 for _ in range(20000)]
     Q = len(vals) // 100
     doc = np.array([rng.randrange(-1, 52) for _ in range(Q * 100)], np.int32).reshape(Q, 100)
